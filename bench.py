@@ -53,6 +53,32 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_CAP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float32 (float64 for integer
+    tensors), DUMP_CAP_BYTES in all.  Over the cap, the largest tensors are replaced by <name>_sample.npy: a seeded sample
+    of their flattened elements, in ascending index order, that depends on nothing but the element count."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_CAP_BYTES - 128 * len(items)                        # (npy header)
+    total = 0
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        size = 4 if t.is_floating_point() else 8
+        share = left // (len(items) - i)
+        if t.numel() * size > share:
+            idx = torch.randint(0, t.numel(), (share // size,), generator=torch.Generator().manual_seed(t.numel()))
+            t, name = t.flatten().index_select(0, idx.sort().values.to(t.device)), name + "_sample"
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        total += a.nbytes
+    log(f"dumped {len(items)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 def host_cores():
     """Cores this process may really use: min(affinity mask, cgroup cpu quota)."""
     n = os.cpu_count() or 1
@@ -199,7 +225,12 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"], help="activation storage type (cfg 4 / 5)")
     ap.add_argument("--mode", default="train", choices=["train", "infer"], help="infer: eval-mode forward only (cfg 2)")
     ap.add_argument("--batch", type=int, default=1, help="per-GPU batch")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): the eval-mode output map(s); "
+                         "for a train step the loss terms and the parameters and buffers it left behind")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -294,11 +325,25 @@ def main():
         ops.TIMER = timer
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = None                                         # (an eager output is not kept alive across the next step)
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        # before the kernel-timer / comm-exposed steps below, which go on training the same parameters
+        if not train:
+            outs = last if isinstance(last, tuple) else (last,)
+            arrays = {"output" if len(outs) == 1 else f"output{i}": o for i, o in enumerate(outs)}
+        else:
+            terms = (gstep.values if mode == "hipgraph" else
+                     torch.tensor([v[-1] for v in holder.losses_and_metrics.values()]))
+            arrays = {"loss_terms": terms}                  # order: ce, dice terms, total (the handler's logged keys)
+            arrays.update(("param." + n, p) for n, p in net.named_parameters())
+            arrays.update(("buffer." + n, b) for n, b in net.named_buffers())
+        dump_outputs(args.dump_outputs, arrays)
     timer_steps = args.steps
     if rank == 0 and not args.no_kernel_timer and mode == "hipgraph":
         # Kernels inside a graph replay cannot be bracketed by events: time the SAME kernels (same launch shapes,

@@ -151,15 +151,42 @@ def test_skip_mode_state_dicts_match_reference_fixtures():
         assert got == {k: tuple(s) for k, s in want.items()}
 
 
-def test_ini_parser_matches_reference():
+_INI_DEFAULT_KEYS = ("train_flag", "test_flag", "name", "model_class", "problem_handler", "resume_model")
+
+
+def _write_ini(path, params):
+    """Writes `params` back as an ini file in the layout of the example configs: typed key prefixes (b_ i_ f_ s_),
+    integral floats written without a fraction, the run's identity under [DEFAULT] (configparser repeats those keys in
+    every section), the other keys spread over two named sections, comment lines and empty values."""
+    def line(k, v):
+        if isinstance(v, bool):
+            return f"b_{k} = {v}"
+        if isinstance(v, int):
+            return f"i_{k} = {v}"
+        if isinstance(v, float):
+            return f"f_{k} = {int(v) if v.is_integer() else repr(v)}"
+        return f"s_{k} = {v}"
+    rest = sorted(k for k in params if k not in _INI_DEFAULT_KEYS)
+    out = ["; written from tests/golden/ini_params.json", "", "[DEFAULT]"]
+    out += [line(k, params[k]) for k in _INI_DEFAULT_KEYS if k in params]
+    for sec, keys in (("TRAINING", rest[0::2]), ("MISC", rest[1::2])):
+        out += ["", f"[{sec}]", "; comment"] + [line(k, params[k]) for k in keys]
+    path.write_text("\n".join(out) + "\n")
+
+
+def test_ini_parser_matches_reference(tmp_path):
+    """ini_params.json holds the dict the reference's own parser made of each of its example configs; each is written
+    back as an ini file and must parse to exactly that dict (same keys, values and types)."""
     from ctunet_amd.utilities import load_params, set_cfg_params
     exp = load_json("ini_params.json")
-    ref_root = "/root/reference"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present (GPU box)")
-    for rel, params in exp.items():
-        got = set_cfg_params(os.path.join(ref_root, rel), {})
+    assert len(exp) == 6
+    for i, (rel, params) in enumerate(exp.items()):
+        p = tmp_path / f"cfg{i}.ini"
+        _write_ini(p, params)
+        got = set_cfg_params(str(p), {})
         assert json.loads(json.dumps(got)) == params, rel
+        assert {k: type(v) for k, v in got.items()} == {k: type(v) for k, v in params.items()}, rel
+        assert load_params(str(p)) == got, rel
         import ctunet_amd
         from ctunet_amd import ProblemHandler
         assert hasattr(ctunet_amd, got["model_class"])                 # s_model_class resolves to a drop-in

@@ -23,6 +23,17 @@ TINY = {
 }
 
 
+@pytest.fixture(autouse=True)
+def _recording_threads():
+    """The fixtures were recorded with 8 intra-op threads (make_golden.py).  ATen-CPU splits its reductions by the
+    thread count, so the summation order, and with it the near-zero gradients, follows the host's core count unless
+    the count is pinned to the recording one."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 def _loss_fn(name, rec):
     if "_sp" in name:
         t = (torch.from_numpy(rec["target_sk"]), torch.from_numpy(rec["target_fl"]))
