@@ -511,7 +511,11 @@ struct ScaleTable {
 };
 
 // nonfinite: optional device flag (float[1]) set to 1 when any scaled value is inf / NaN (the fp16 backward overflowed)
-__global__ void scale_tensors_kernel(ScaleTable tb, float s, float* __restrict__ nonfinite) {
+// DEV: the factor is the reciprocal of the device loss scale *dscale (dynamic loss scaling), formed the way
+// torch.amp.GradScaler forms it (scale.double().reciprocal().float()): one uniform scalar load per block
+template <bool DEV>
+__global__ void scale_tensors_kernel(ScaleTable tb, float s, const float* __restrict__ dscale, float* __restrict__ nonfinite) {
+    if (DEV) s = (float)(1.0 / (double)dscale[0]);
     const int t = blockIdx.y;
     float* __restrict__ p = tb.p[t];
     const int64_t n = tb.n[t];
@@ -522,6 +526,32 @@ __global__ void scale_tensors_kernel(ScaleTable tb, float s, float* __restrict__
         bad |= !(fabsf(v) <= 3.4028234e38f);            // inf or NaN
     }
     if (nonfinite && bad) nonfinite[0] = 1.f;          // (every writer stores the same value)
+}
+
+// ------------------------------------------------------------------ dynamic loss scale
+// torch._amp_update_scale_ on one thread: back off (and restart the growth count) after an overflowed step, grow after
+// `interval` clean steps in a row unless the grown scale would not be finite in float32.  Then count the skipped step and
+// clear found_inf: in dynamic mode this is the only place the flag is cleared, so every backward pass of a step (gradient
+// accumulation) and the ranks' combined flag of a distributed step reach this decision.
+__global__ void loss_scale_update_kernel(float* scale, int32_t* growth_tracker, float* found_inf, float* skipped,
+                                         float growth, float backoff, int interval) {
+    const float s = scale[0];
+    const bool inf = found_inf[0] != 0.f;
+    if (inf) {
+        scale[0] = (float)((double)s * (double)backoff);
+        growth_tracker[0] = 0;
+        skipped[0] += 1.f;
+    } else {
+        const int successful = growth_tracker[0] + 1;
+        if (successful == interval) {
+            const float grown = (float)((double)s * (double)growth);
+            if (isfinite(grown)) scale[0] = grown;
+            growth_tracker[0] = 0;
+        } else {
+            growth_tracker[0] = successful;
+        }
+    }
+    found_inf[0] = 0.f;
 }
 
 }  // namespace
@@ -834,8 +864,10 @@ extern "C" int ctu_adam_amsgrad(void* const* ptrs, const int64_t* sizes, int n, 
     return CTU_OK;
 }
 
-extern "C" int ctu_scale_tensors(void* const* ptrs, const int64_t* sizes, int n, float sc, float* nonfinite_flag, void* stream) {
-    CTU_REQUIRE(ptrs && sizes && n > 0, "scale_tensors: bad argument");
+namespace {
+template <bool DEV>
+int scale_tensors_impl(void* const* ptrs, const int64_t* sizes, int n, float sc, const float* dscale, float* nonfinite_flag,
+                       void* stream) {
     for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
         const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
         ScaleTable tb;
@@ -849,8 +881,30 @@ extern "C" int ctu_scale_tensors(void* const* ptrs, const int64_t* sizes, int n,
         int gx = (int)ceil_div64(mx, EW_BLOCK * 4);
         if (gx > 2048) gx = 2048;                                   // (dx of a 256^3 two-channel input is 134 MB)
         if (gx < 1) gx = 1;
-        scale_tensors_kernel<<<dim3(gx, nt), EW_BLOCK, 0, (hipStream_t)stream>>>(tb, sc, nonfinite_flag);
+        scale_tensors_kernel<DEV><<<dim3(gx, nt), EW_BLOCK, 0, (hipStream_t)stream>>>(tb, sc, dscale, nonfinite_flag);
         CTU_CHECK_LAUNCH("scale_tensors");
     }
+    return CTU_OK;
+}
+}  // namespace
+
+extern "C" int ctu_scale_tensors(void* const* ptrs, const int64_t* sizes, int n, float sc, float* nonfinite_flag, void* stream) {
+    CTU_REQUIRE(ptrs && sizes && n > 0, "scale_tensors: bad argument");
+    return scale_tensors_impl<false>(ptrs, sizes, n, sc, nullptr, nonfinite_flag, stream);
+}
+
+extern "C" int ctu_unscale_tensors(void* const* ptrs, const int64_t* sizes, int n, const float* scale, float* found_inf,
+                                   void* stream) {
+    CTU_REQUIRE(ptrs && sizes && n > 0 && scale && found_inf, "unscale_tensors: bad argument");
+    return scale_tensors_impl<true>(ptrs, sizes, n, 1.f, scale, found_inf, stream);
+}
+
+extern "C" int ctu_loss_scale_update(float* scale, int32_t* growth_tracker, float* found_inf, float* skipped, float growth,
+                                     float backoff, int interval, void* stream) {
+    CTU_REQUIRE(scale && growth_tracker && found_inf && skipped, "loss_scale_update: null pointer");
+    CTU_REQUIRE(growth > 1.f && backoff > 0.f && backoff < 1.f && interval >= 1,
+                "loss_scale_update: growth=%g backoff=%g interval=%d", (double)growth, (double)backoff, interval);
+    loss_scale_update_kernel<<<1, 1, 0, (hipStream_t)stream>>>(scale, growth_tracker, found_inf, skipped, growth, backoff, interval);
+    CTU_CHECK_LAUNCH("loss_scale_update");
     return CTU_OK;
 }

@@ -24,6 +24,7 @@ struct HeadP {
     int in_cs, in_relu, Ci, Co, act, head_mode, N;
     int64_t V;
     float gscale;            // backward: the incoming output gradients are multiplied by this (float16 loss scale), 1 otherwise
+    const float* gscale_dev; // backward, non-NULL: ... by this device float instead (dynamic loss scale, read once per block)
 };
 
 // activated input channels of one voxel -> logits -> y (post softmax/sigmoid)
@@ -133,6 +134,7 @@ __global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __
     __shared__ float sRed[HB / 64][MAXCO * CP + MAXCO + 2 * CP];
     head_load_weights<CP>(p, sWp, sB);
     const int qd = threadIdx.x % Q;
+    const float gscale = p.gscale_dev ? p.gscale_dev[0] : p.gscale;
     float wq[MAXCO][4], dw[MAXCO][4], db[MAXCO];
 #pragma unroll
     for (int co = 0; co < MAXCO; ++co) {
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __
             gy[0] = a0; gy[1] = a1 - b0 + b1; gy[2] = a1; gy[3] = 0.f;
         }
 #pragma unroll
-        for (int co = 0; co < MAXCO; ++co) gy[co] *= p.gscale;      // (everything downstream is linear in the output gradients)
+        for (int co = 0; co < MAXCO; ++co) gy[co] *= gscale;        // (everything downstream is linear in the output gradients)
         float gu[MAXCO], gl[MAXCO];
 #pragma unroll
         for (int co = 0; co < MAXCO; ++co) gu[co] = (p.act & 2) ? gy[co] * y[co] * (1.f - y[co]) : gy[co];
@@ -474,6 +476,7 @@ static int fill_head(HeadP& p, const void* in, int in_cs, int cin_p, const float
     CTU_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "%s: scale/shift must come together", name);
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.w = w; p.bias = bias; p.imap = imap;
     p.in_cs = in_cs; p.in_relu = in_relu; p.Ci = Ci; p.Co = Co; p.act = act; p.head_mode = head_mode; p.N = N; p.V = V; p.gscale = 1.f;
+    p.gscale_dev = nullptr;
     return CTU_OK;
 }
 
@@ -501,7 +504,8 @@ template <class T>
 int head_bwd_impl(const T* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift, int in_relu, const float* w,
                   const float* bias, const int32_t* imap, int Ci, int Co, int act, int head_mode, const float* g0, const float* g1,
                   T* gin, int gin_cs, float* dw, float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
-                  const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream, float gscale = 1.f) {
+                  const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream, float gscale = 1.f,
+                  const float* gscale_dev = nullptr) {
     CTU_REQUIRE(!tail || (bn_partials && tail->gamma && tail->invstd && tail->dgamma && tail->dbeta && tail->coef &&
                           tail->C > 0 && tail->C <= bn_cp && tail->count > 0 && (!tail->running_mean || (tail->mean && tail->running_var))),
                 "head_bwd: incomplete BatchNorm tail");
@@ -510,6 +514,7 @@ int head_bwd_impl(const T* in, int in_cs, int cin_p, const float* in_scale, cons
                        nvox_per_item, "head_bwd");
     if (rc != CTU_OK) return rc;
     p.gscale = gscale;
+    p.gscale_dev = gscale_dev;
     CTU_REQUIRE(g0 && (head_mode == 0 || g1) && gin && dw && db && ws, "head_bwd: null pointer");
     CTU_REQUIRE(gin_cs >= cin_p && gin_cs % 4 == 0, "head_bwd: bad gin stride");
     CTU_REQUIRE(!bn_partials || (bn_mean && bn_invstd && in_scale && in_relu && bn_cp > 0 && bn_cp % 4 == 0 && bn_cp <= cin_p),
@@ -580,6 +585,18 @@ extern "C" int ctu_lp_head_bwd_bn(int dtype, const void* in, int in_cs, int cin_
     CTU_DISPATCH_LP(dtype, return head_bwd_impl<T>((const T*)in, in_cs, cin_p, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act,
                                                    head_mode, g0, g1, (T*)gin, gin_cs, dw, db, ws, N, nvox_per_item, bn_mean,
                                                    bn_invstd, bn_cp, bn_partials, tail, stream, gscale));
+}
+
+extern "C" int ctu_lp_head_bwd_bn_dscale(int dtype, const void* in, int in_cs, int cin_p, const float* in_scale,
+                                         const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap,
+                                         int Ci, int Co, int act, int head_mode, const float* g0, const float* g1, void* gin,
+                                         int gin_cs, float* dw, float* db, float* ws, int N, int64_t nvox_per_item,
+                                         const float* bn_mean, const float* bn_invstd, int bn_cp, float* bn_partials,
+                                         const ctu_bn_bwd_tail* tail, const float* gscale, void* stream) {
+    CTU_REQUIRE(gscale, "lp_head_bwd_bn_dscale: null gscale");
+    CTU_DISPATCH_LP(dtype, return head_bwd_impl<T>((const T*)in, in_cs, cin_p, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act,
+                                                   head_mode, g0, g1, (T*)gin, gin_cs, dw, db, ws, N, nvox_per_item, bn_mean,
+                                                   bn_invstd, bn_cp, bn_partials, tail, stream, 1.f, gscale));
 }
 
 extern "C" size_t ctu_loss_ws_floats(int N, int64_t V) {

@@ -162,7 +162,10 @@ SIGNATURES = {
     "ctu_lp_channel_sum": (I, [I, P, I, I, L, P, P, I, P]),
     "ctu_lp_head_fwd": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, I, L, P]),
     "ctu_lp_head_bwd_bn": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P, P, I, P, P, F, P]),
+    "ctu_lp_head_bwd_bn_dscale": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P, P, I, P, P, P, P]),
     "ctu_scale_tensors": (I, [P, P, I, F, P, P]),
+    "ctu_unscale_tensors": (I, [P, P, I, P, P, P]),
+    "ctu_loss_scale_update": (I, [P, P, P, P, F, F, I, P]),
     "ctu_comm_available": (I, []),
     "ctu_comm_unique_id": (I, [P]),
     "ctu_comm_init": (I, [C.POINTER(C.c_void_p), I, I, P]),
@@ -174,7 +177,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 7          # CTU_ABI_VERSION of the csrc/ this file mirrors (bumped on any signature change)
+ABI_VERSION = 8          # CTU_ABI_VERSION of the csrc/ this file mirrors (bumped on any signature change)
 
 
 class CtuError(RuntimeError):

@@ -96,6 +96,9 @@ class UNetEngine:
         self.plan = plan
         self.dtype = dtype
         self.loss_scale = loss_scale
+        # dynamic loss scaling (float16): the model's loss_scale.LossScaler, set by the model before every use; None = the
+        # static loss_scale above
+        self.scaler = None
         self._pack_cache: Dict[Tuple, Tuple[int, torch.Tensor]] = {}
         self._replay_stats = False
         self._up_cache: Dict[str, Tuple] = {}
@@ -535,7 +538,14 @@ class UNetEngine:
         # every parameter gradient and dx on the way out; bf16 / fp32 need none
         gs = 1.0
         flag = None
-        if self.dtype == torch.float16:
+        dyn = self.scaler if self.dtype == torch.float16 else None
+        if dyn is not None:
+            # dynamic loss scaling: the scale is read from device memory by the launches below (a captured graph follows it),
+            # and the overflow flag is NOT cleared here -- every backward pass of a step adds to it, the optimizer step's
+            # loss-scale update reads and clears it
+            dyn.prepare(dev, n * d * h * w)
+            flag = dyn.found_inf
+        elif self.dtype == torch.float16:
             gs = self.loss_scale if self.loss_scale else float(2 ** max(0, (n * d * h * w).bit_length() - 5))
             # (the head backward multiplies g0 / g1 by gs as it reads them: no scaled copy of the output-sized maps)
             # overflow guard: the un-scaling launches below set this flag when a gradient came out inf / NaN (a static loss
@@ -551,7 +561,9 @@ class UNetEngine:
             scaling) and hand them to the gradient exchange."""
             new = [(nm, g) for nm, g in grads.items() if nm not in emitted and g is not None]
             emitted.update(nm for nm, _ in new)
-            if gs != 1.0 and new:
+            if dyn is not None and new:
+                ops.unscale_tensors([g for _, g in new], dyn.scale, flag)
+            elif gs != 1.0 and new:
                 ops.scale_tensors([g for _, g in new], 1.0 / gs, flag)
             if sync is not None:
                 sync.push(new)
@@ -584,6 +596,7 @@ class UNetEngine:
         gcat = [torch.empty_like(c) for c in cat]
         wl, bl = P[plan.head + ".weight"], P[plan.head + ".bias"]
         w2 = wl.detach().reshape(wl.shape[0], wl.shape[1])
+        gsd = None if dyn is None else dyn.scale
         def g_skip_target(level: int) -> CL:
             """Where the gradient w.r.t. the tensor a decoder level hands on (cat / sum / plain output) is written."""
             full = gcat[level].shape[-1]
@@ -604,12 +617,14 @@ class UNetEngine:
                 and head_in.c0 == r_last.y.c0 and head_in.buf is r_last.y.buf):
             fin = self._bwd_fin(P, r_last, head_in.buf.device)
             res = ops.head_bwd(head_in, w2, bl.detach(), ctx["imap_h"], plan.act, plan.head_mode, g0.contiguous(),
-                               None if g1 is None else g1.contiguous(), g_skip_target(0), (r_last.vec, part), fin, gscale=gs)
+                               None if g1 is None else g1.contiguous(), g_skip_target(0), (r_last.vec, part), fin, gscale=gs,
+                               gscale_dev=gsd)
             dwl, dbl, head_rows = res[:3]
             head_fin = res[3] if fin is not None else None
         else:
             dwl, dbl = ops.head_bwd(head_in, w2, bl.detach(), ctx["imap_h"], plan.act, plan.head_mode, g0.contiguous(),
-                                    None if g1 is None else g1.contiguous(), g_skip_target(0), gscale=gs)
+                                    None if g1 is None else g1.contiguous(), g_skip_target(0), gscale=gs,
+                                    gscale_dev=gsd)
         g_skip_fanout(0)
         grads[plan.head + ".weight"], grads[plan.head + ".bias"] = dwl.reshape(wl.shape), dbl
         emit()
@@ -702,7 +717,9 @@ class UNetEngine:
                 self._conv_bn_bwd(P, r1, g_d1, None, grads, ws, part)
             emit()
         emit()
-        if gs != 1.0 and dx is not None:
+        if dyn is not None and dx is not None:
+            ops.unscale_tensors([dx], dyn.scale, flag)
+        elif gs != 1.0 and dx is not None:
             ops.scale_tensors([dx], 1.0 / gs, flag)
         if sync is not None:
             if flag is not None:
@@ -718,7 +735,8 @@ class UNetEngine:
         """After a gradient exchange: the ranks' combined overflow flag (see backward) replaces this rank's own."""
         red = grads.pop("__overflow__", None)
         if red is not None:
-            self.overflow_flag(device).copy_(red.reshape(1))
+            (self.scaler.found_inf if self.scaler is not None and self.dtype == torch.float16
+             else self.overflow_flag(device)).copy_(red.reshape(1))
 
 
 # ----------------------------------------------------------------------------- autograd glue

@@ -74,8 +74,15 @@ class GraphedTrainStep:
                  input_requires_grad: bool = True, warmup: int = 3, distributed: bool = False, process_group=None,
                  bucket_bytes: Optional[int] = None):
         self.model, self.opt = model, optimizer
+        scaler = getattr(model, "loss_scaler", None)
+        if scaler is not None and not hasattr(optimizer, "guard"):
+            raise RuntimeError("GraphedTrainStep: a model with dynamic loss scaling needs an optimizer that reads the device "
+                               "overflow flag (ctunet_amd.optim.Adam / AdamW); loss_scaler.step(optimizer) would need a host "
+                               "sync inside the captured step")
         if hasattr(optimizer, "guard"):
             optimizer.guard(model)             # fp16: an overflowed step is skipped inside the replayed graph too
+        if scaler is not None:                 # (dynamic: its state must exist on the GPU before anything is captured)
+            scaler.prepare(example_input.device, example_input.shape[0] * example_input[0, 0].numel())
         self._params = [p for p in model.parameters()]
         self.distributed, self.group = distributed, process_group
         if distributed and model.__dict__.get("_grad_sync_cfg") is not None:

@@ -26,6 +26,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from .engine import BlockPlan, NetPlan, UNetEngine, run_network
+from .loss_scale import DynamicLossScale, LossScaler
 
 
 # ----------------------------------------------------------------------------- holders
@@ -122,6 +123,7 @@ class _HipNet(nn.Module):
         if eng is None or eng.dtype != dt:
             eng = UNetEngine(self._plan, dt, self.__dict__.get("_loss_scale"))
             self.__dict__["_eng"] = eng       # not a submodule / not in state_dict
+        eng.scaler = self.loss_scaler         # (the model owns the dynamic state: an engine rebuild keeps it)
         return eng
 
     def set_precision(self, dtype=torch.float32, loss_scale=None):
@@ -129,12 +131,31 @@ class _HipNet(nn.Module):
         1e-4 parity), ``torch.bfloat16`` or ``torch.float16`` (BASELINE configs 4 / 5: 16-bit tensors in HBM,
         v_mfma_f32_16x16x32 with fp32 accumulation, fp32 BatchNorm statistics, fp32 master weights / gradients /
         optimizer -- what ``torch.autocast`` would give the reference).  Inputs, outputs, parameters and their gradients
-        stay float32 either way.  ``loss_scale`` (float16 only): see ``UNetEngine``.  Accepts the strings
-        "fp32" / "bf16" / "fp16" too.  Returns self."""
+        stay float32 either way.  ``loss_scale`` (float16 only): a float or None is a static scale, see ``UNetEngine``;
+        "dynamic" or a ``DynamicLossScale`` turns on device-resident dynamic loss scaling (``model.loss_scaler``, the rule
+        of ``torch.amp.GradScaler``).  A model that already holds dynamic state keeps it (scale, growth tracker, skip
+        count) and takes the new hyper-parameters.  Accepts the strings "fp32" / "bf16" / "fp16" too.  Returns self."""
         names = {"fp32": torch.float32, "f32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16, "f16": torch.float16}
         dt = names.get(dtype, dtype) if isinstance(dtype, str) else dtype
         if dt not in (torch.float32, torch.bfloat16, torch.float16):
             raise ValueError(f"ctunet_amd: unsupported precision {dtype}")
+        dyn = None
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError(f"ctunet_amd: loss_scale must be a float, None, 'dynamic' or a DynamicLossScale, got {loss_scale!r}")
+            dyn = DynamicLossScale()
+        elif isinstance(loss_scale, DynamicLossScale):
+            dyn = loss_scale
+        if dyn is not None and dt != torch.float16:
+            raise ValueError(f"ctunet_amd: dynamic loss scaling is for float16 only (precision {dt})")
+        if dyn is not None:
+            sc = self.__dict__.get("_scaler")
+            if sc is None:
+                self.__dict__["_scaler"] = LossScaler(dyn, next(self.parameters()).device)
+            else:
+                sc.configure(dyn)
+            loss_scale = None
+        self.__dict__["_dynamic"] = dyn is not None
         self.__dict__["_act_dtype"] = dt
         self.__dict__["_loss_scale"] = loss_scale
         eng = self.__dict__.get("_eng")
@@ -142,11 +163,24 @@ class _HipNet(nn.Module):
             eng.loss_scale = loss_scale            # (the engine is only rebuilt when the storage type changes)
         return self
 
+    @property
+    def loss_scaler(self) -> Optional[LossScaler]:
+        """The device state of dynamic loss scaling (``set_precision("fp16", loss_scale="dynamic")``), None otherwise."""
+        if self.__dict__.get("_dynamic") and self.__dict__.get("_act_dtype") == torch.float16:
+            return self.__dict__.get("_scaler")
+        return None
+
     def overflow_flag(self) -> torch.Tensor:
         """float32[1] on the model's GPU: 1 after a float16 backward whose un-scaled parameter gradients contained inf / NaN
         (the static loss scale overflowed the 16-bit activation gradients), 0 otherwise; cleared at the start of every float16
         backward.  Hand it to the fused optimizer (``optim.Adam.guard(model)``): an overflowed step then changes nothing --
-        parameters, moments and step counter -- also inside a replayed HIP graph.  Call again after ``set_precision``."""
+        parameters, moments and step counter -- also inside a replayed HIP graph.  Call again after ``set_precision``.
+        Dynamic loss scaling: the scaler's ``found_inf``, which only ``loss_scaler.update()`` clears -- and a guarded fused
+        optimizer launches that update at the end of its step, so after a step ``loss_scaler.skipped_steps()`` is the
+        signal to watch."""
+        sc = self.loss_scaler
+        if sc is not None:
+            return sc.found_inf
         return self._engine().overflow_flag(next(self.parameters()).device)
 
     def overflowed(self) -> bool:

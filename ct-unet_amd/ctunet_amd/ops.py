@@ -793,15 +793,22 @@ def head_fwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
 
 
 def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int, g0: torch.Tensor,
-             g1: Optional[torch.Tensor], gin: CL, bn=None, fin=None, gscale: float = 1.0):
+             g1: Optional[torch.Tensor], gin: CL, bn=None, fin=None, gscale: float = 1.0,
+             gscale_dev: Optional[torch.Tensor] = None):
     """bn = (vec [4, bn_cp] of the BatchNorm whose activated output is x's first bn_cp channels, partials): also emit
     that BatchNorm's backward reduction rows; returns (dw, db, rows) then (rows -> bn_relu_bwd(pre_reduced=...)).
     fin = (gamma, c, replay) with bn: the launch pair also finalizes that reduction; returns (dw, db, rows, (dgb, coef)).
-    gscale (16-bit tensors): g0 / g1 are multiplied by it as they are read (float16 loss scale)."""
+    gscale (16-bit tensors): g0 / g1 are multiplied by it as they are read (float16 loss scale).
+    gscale_dev: float32[1] device tensor that replaces gscale (the dynamic loss scale, read by the kernel)."""
     assert gscale == 1.0 or x.lp, "gscale is the 16-bit path's loss scale"
+    assert gscale_dev is None or (x.lp and gscale_dev.is_cuda and gscale_dev.dtype == torch.float32), \
+        "gscale_dev is the 16-bit path's device loss scale"
 
     def call(*args):                                    # (the 16-bit entry carries gscale in front of the stream)
-        if x.lp:
+        if gscale_dev is not None:
+            _lib.check(_lib.load().ctu_lp_head_bwd_bn_dscale(x.lp, *args[:-1], gscale_dev.data_ptr(), args[-1]),
+                       "lp_head_bwd_bn_dscale")
+        elif x.lp:
             _lib.check(_lib.load().ctu_lp_head_bwd_bn(x.lp, *args[:-1], float(gscale), args[-1]), "lp_head_bwd_bn")
         else:
             _lib.check(_lib.load().ctu_head_bwd_bn(*args), "head_bwd_bn")
@@ -1201,3 +1208,21 @@ def scale_tensors(tensors, s: float, nonfinite: Optional[torch.Tensor] = None) -
     sa = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
     assert nonfinite is None or (nonfinite.is_cuda and nonfinite.dtype == torch.float32 and nonfinite.numel() == 1)
     _lib.check(_lib.load().ctu_scale_tensors(pa, sa, len(ts), float(s), _ptr(nonfinite), _stream()), "scale_tensors")
+
+
+def unscale_tensors(tensors, scale: torch.Tensor, found_inf: torch.Tensor) -> None:
+    """Every float32 CUDA tensor of the list multiplied in place by 1 / scale[0] (scale: the float32[1] device loss scale
+    of dynamic loss scaling), one launch; found_inf (float32[1] device flag) is set on inf / NaN and never cleared here."""
+    import ctypes as C
+    ts = [t for t in tensors if t is not None]
+    if not ts:
+        return
+    for t in ts:
+        _need_cuda(t, "tensor")
+        assert t.is_contiguous() and t.dtype == torch.float32
+    for f in (scale, found_inf):
+        assert f.is_cuda and f.dtype == torch.float32 and f.numel() == 1
+    pa = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    sa = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
+    _lib.check(_lib.load().ctu_unscale_tensors(pa, sa, len(ts), scale.data_ptr(), found_inf.data_ptr(), _stream()),
+               "unscale_tensors")

@@ -34,12 +34,21 @@ class Adam(torch.optim.Optimizer):
         # overflowed; a step that sees it set changes nothing (torch.amp.GradScaler.step's found_inf), also inside a replayed
         # HIP graph.  None: every step is applied.
         self.skip_flag = None
+        self._guarded = None
 
     def guard(self, model) -> "Adam":
-        """Skip every step whose float16 backward overflowed (``model.overflow_flag()``); no-op for fp32 / bf16 models."""
+        """Skip every step whose float16 backward overflowed (``model.overflow_flag()``); no-op for fp32 / bf16 models.
+        Dynamic loss scaling (``model.loss_scaler``): the flag is the scaler's ``found_inf``, and every ``step()`` also
+        launches ``loss_scaler.update()`` behind its own kernels.  The scaler is looked up on the model at each step, so
+        the guard survives a ``set_precision`` round trip of the model."""
         fp16 = model.__dict__.get("_act_dtype", torch.float32) == torch.float16
         self.skip_flag = model.overflow_flag() if fp16 and hasattr(model, "overflow_flag") else None
+        self._guarded = model if hasattr(model, "loss_scaler") else None
         return self
+
+    def guarded_scaler(self):
+        """The dynamic loss scaler of the guarded model (None: static scaling or none)."""
+        return None if self._guarded is None else self._guarded.loss_scaler
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -48,6 +57,9 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        scaler = self.guarded_scaler()
+        skip = scaler.found_inf if scaler is not None else self.skip_flag
+        stepped = False
         for group in self.param_groups:
             live: List[torch.Tensor] = [p for p in group["params"] if p.grad is not None]
             if not live:
@@ -79,11 +91,14 @@ class Adam(torch.optim.Optimizer):
             _lib.check(lib.ctu_adam_amsgrad(pa, sa, n, group["step_t"].data_ptr(), float(group["lr"]), float(b1),
                                             float(b2), float(group["eps"]), float(group["weight_decay"]),
                                             int(bool(group["decoupled_weight_decay"])),
-                                            None if self.skip_flag is None else self.skip_flag.data_ptr(),
+                                            None if skip is None else skip.data_ptr(),
                                             torch.cuda.current_stream().cuda_stream), "adam_amsgrad")
             # the kernel wrote the parameters through raw pointers: tell autograd / every (version-keyed) cache of
             # derived data -- the engine's MFMA-ordered weight copies -- that they changed
             torch.autograd.graph.increment_version(live)
+            stepped = True
+        if scaler is not None and stepped:
+            scaler.update()            # same stream, after every group's kernels have read found_inf: back off / grow, clear it
         return loss
 
 

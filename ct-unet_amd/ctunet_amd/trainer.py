@@ -91,7 +91,11 @@ class StepRunner:
                 self.comp_losses_metrics(self, model_out, target, batch_idx, len(data_loader))
                 if train:
                     self.pt_loss.backward()
-                    self.params["optimizer"].step()
+                    opt, scaler = self.params["optimizer"], getattr(net, "loss_scaler", None)
+                    if scaler is not None and not hasattr(opt, "guard"):
+                        scaler.step(opt)       # float16 dynamic loss scaling, torch.optim: skip an overflowed step (one sync)
+                    else:
+                        opt.step()
                     if self.params.get("scheduler") is not None:
                         self.params["scheduler"].step(self.pt_loss)
                     for param in net.parameters():

@@ -565,11 +565,31 @@ int ctu_lp_head_bwd_bn(int dtype, const void* in, int in_cs, int cin_p, const fl
                        float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
                        const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, float gscale,
                        void* stream);
+/* ctu_lp_head_bwd_bn with the loss scale read from DEVICE memory (gscale: float[1], the dynamic loss scale of
+ * ctu_loss_scale_update), so a captured graph multiplies by the scale current at replay time. */
+int ctu_lp_head_bwd_bn_dscale(int dtype, const void* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                              int in_relu, const float* w, const float* bias, const int32_t* imap, int Ci, int Co, int act,
+                              int head_mode, const float* g0, const float* g1, void* gin, int gin_cs, float* dw,
+                              float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
+                              const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail,
+                              const float* gscale, void* stream);
 /* Every tensor of a list scaled in place by s (one launch): un-scaling of loss-scaled fp16 gradients.
  * ptrs: HOST array of n DEVICE float pointers, sizes: HOST int64[n].  nonfinite_flag: NULL or a DEVICE float[1] that is set
  * to 1 when any scaled value is inf / NaN (the fp16 backward overflowed; the caller zeroes it per step and hands it to
  * ctu_adam_amsgrad as skip_flag, what torch.amp.GradScaler does with found_inf). */
 int ctu_scale_tensors(void* const* ptrs, const int64_t* sizes, int n, float s, float* nonfinite_flag, void* stream);
+/* Dynamic loss scaling (float16), the device-resident form of torch.amp.GradScaler; every operand is DEVICE memory, so
+ * the calls work unchanged inside a replayed graph.
+ *   ctu_unscale_tensors ... ctu_scale_tensors by 1 / scale[0] (formed as float(1.0 / (double)scale[0]), GradScaler's
+ *                           reciprocal); SETS found_inf (float[1]) on inf / NaN and never clears it, so several backward
+ *                           passes of one step accumulate into it
+ *   ctu_loss_scale_update . torch._amp_update_scale_ (one thread): found_inf != 0 -> scale *= backoff, growth_tracker = 0;
+ *                           else growth_tracker += 1, and when it reaches `interval`: scale *= growth if the product is
+ *                           finite in float32, growth_tracker = 0.  Then skipped[0] += 1 if found_inf was set, and
+ *                           found_inf = 0 (the only place it is cleared).  growth > 1, 0 < backoff < 1, interval >= 1. */
+int ctu_unscale_tensors(void* const* ptrs, const int64_t* sizes, int n, const float* scale, float* found_inf, void* stream);
+int ctu_loss_scale_update(float* scale, int32_t* growth_tracker, float* found_inf, float* skipped, float growth,
+                          float backoff, int interval, void* stream);
 
 /* --------------------------------------------------------------- gradient exchange (RCCL over xGMI) ---- */
 /* One process per GPU; the only cross-GPU step of the path is the mean of the parameter gradients before the optimizer
