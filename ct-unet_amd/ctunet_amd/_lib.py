@@ -117,6 +117,8 @@ SIGNATURES = {
     "ctu_hausdorff": (I, [P, P, I, I, I, I, I, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
+    "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),
+    "ctu_window_finalize": (I, [P, P, I, L, P, P, P]),
     "ctu_lp_upconv_fused_supported": (I, [I, I, I, I, I, I]),
     "ctu_lp_upconv_fused_packed_elems": (Z, [I]),
     "ctu_lp_upconv_fused_num_blocks": (I, [I, I, I, I]),

@@ -1194,6 +1194,44 @@ def stitch_patches(patches: torch.Tensor, coords: torch.Tensor, shape: Tuple[int
     return out
 
 
+def window_accumulate(patches: torch.Tensor, coords: torch.Tensor, valid: torch.Tensor, box: torch.Tensor,
+                      tables: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], wmin: float, extent: Tuple[int, int, int],
+                      num: torch.Tensor, wsum: Optional[torch.Tensor]) -> None:
+    """Blend one batch of patch predictions [B,K,pd,ph,pw] into num [K,D,H,W] (and wsum [D,H,W] unless None), in place:
+    w = max(wz[i]*wy[j]*wx[k], wmin) per patch-local voxel, num += w*y, wsum += w over the valid patches in order.
+    coords int32 [B,3], valid int32 [B], box int32 [3] (bounding-box origin, x a multiple of 4) live on the device;
+    extent = (bz, by, bx) the launch covers from that origin."""
+    for t, nm in ((patches, "patches"), (coords, "coordinates"), (valid, "valid flags"), (box, "box origin"), (num, "num")):
+        _need_cuda(t, nm)
+        assert t.is_contiguous(), nm
+    assert wsum is None or (wsum.is_cuda and wsum.dtype == torch.float32 and wsum.is_contiguous())
+    b, k, pd, ph, pw = patches.shape
+    _, d, h, w = num.shape
+    wz, wy, wx = tables
+    assert num.shape[0] == k and (wsum is None or wsum.shape == num.shape[1:]), "accumulator shapes"
+    assert coords.shape == (b, 3) and valid.numel() == b and box.numel() == 3 and coords.dtype == torch.int32
+    assert all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+               for t, n in zip(tables, (pd, ph, pw))), "weight tables"
+    _lib.check(_lib.load().ctu_window_accumulate(patches.data_ptr(), coords.data_ptr(), valid.data_ptr(), box.data_ptr(), b,
+                                                 k, d, h, w, pd, ph, pw, wz.data_ptr(), wy.data_ptr(), wx.data_ptr(),
+                                                 float(wmin), extent[0], extent[1], extent[2], num.data_ptr(), _ptr(wsum),
+                                                 _stream()), "window_accumulate")
+
+
+def window_finalize(num: torch.Tensor, wsum: torch.Tensor, probs: torch.Tensor,
+                    labels: Optional[torch.Tensor] = None) -> None:
+    """probs [K,D,H,W] = num / wsum (0 where wsum == 0; probs may be num), labels uint8 [D,H,W] = first argmax over K."""
+    _need_cuda(num, "num")
+    _need_cuda(wsum, "wsum")
+    _need_cuda(probs, "probs")
+    k = num.shape[0]
+    v = wsum.numel()
+    assert num.is_contiguous() and wsum.is_contiguous() and probs.is_contiguous() and num.numel() == k * v == probs.numel()
+    assert labels is None or (labels.is_cuda and labels.dtype == torch.uint8 and labels.numel() == v and labels.is_contiguous())
+    _lib.check(_lib.load().ctu_window_finalize(num.data_ptr(), wsum.data_ptr(), k, v, probs.data_ptr(), _ptr(labels),
+                                               _stream()), "window_finalize")
+
+
 def scale_tensors(tensors, s: float, nonfinite: Optional[torch.Tensor] = None) -> None:
     """Every float32 CUDA tensor of the list scaled in place by s, one launch (un-scaling of loss-scaled gradients).
     nonfinite: float32[1] device flag set to 1 when any scaled value is inf / NaN (fp16 overflow detection)."""

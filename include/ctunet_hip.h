@@ -429,6 +429,27 @@ int ctu_extract_patches(const float* vol, const int32_t* coords, int P, int C, i
 int ctu_stitch_patches(const float* patches, const int32_t* coords, int P, int C, int D, int H, int W, int pd, int ph,
                        int pw, float* out, void* stream);
 
+/* Sliding-window inference (whole-volume prediction from patch-sized forwards; the reference resizes whole volumes to the
+ * network size instead, ctunet/pytorch/datasets.py:89-112,195-235).  One batch of B patch predictions at a time is blended
+ * into whole-volume fp32 accumulators num [K,D,H,W] and wsum [D,H,W]:
+ *   for each valid patch p of the batch, in order, and each voxel v = (z0+i, y0+j, x0+k) it covers inside the volume:
+ *     w = max(wz[i] * wy[j] * wx[k], wmin);  num[c][v] += w * patches[p][c][i][j][k];  wsum[v] += w
+ *   (1-D tables of pd / ph / pw floats: Gaussian for the Gaussian blend, all ones for the plain mean).
+ *   coords: DEVICE int32 [B][3] = (z0, y0, x0); valid: DEVICE int32 [B], 0 = padding slot (skipped, coords still read).
+ *   box: DEVICE int32 [3] = origin of the batch's bounding box, box[2] a multiple of 4; bz/by/bx (bx a multiple of 4): the
+ *   extents the launch covers from that origin -- at least those of the batch's box.  Everything that changes between
+ *   batches is read from device memory, so one captured launch serves every batch of a volume.
+ *   Gather form (one thread per 4 x-consecutive voxels of the box), no atomics: bitwise reproducible.  wsum NULL: num only
+ *   (a second output head sharing the first head's weight sum).  B <= 64, K <= 4, pw a multiple of 4; patches, wx, num
+ *   and wsum 16-byte aligned.
+ * finalize: probs[c][v] = num[c][v] / wsum[v] (0 where wsum == 0) and, if labels is non-NULL, labels[v] = the first c of the
+ *   largest probability (the rule of ctu_hard_segm), uint8.  probs may be num itself (in place).  V = D*H*W. */
+int ctu_window_accumulate(const float* patches, const int32_t* coords, const int32_t* valid, const int32_t* box, int B,
+                          int K, int D, int H, int W, int pd, int ph, int pw, const float* wz, const float* wy,
+                          const float* wx, float wmin, int bz, int by, int bx, float* num, float* wsum, void* stream);
+int ctu_window_finalize(const float* num, const float* wsum, int K, int64_t V, float* probs, uint8_t* labels,
+                        void* stream);
+
 /* ------------------------------------------------ reduced precision (bf16 / fp16 activations) ---- */
 /* BASELINE configs 4 ("bf16, 192^3 patches") and 5 ("fp16 MFMA conv path, 256^3 patches").  Same operations, call sites
  * and argument meaning as the fp32 entry points above, with
