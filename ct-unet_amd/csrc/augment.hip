@@ -1,0 +1,401 @@
+// On-device flap-reconstruction augmentation, gfx950: the reference's SkullRandomHole (random hole in a binary skull) and
+// SaltAndPepper (random zeroed / set voxels) for a batch of N skulls, in three launches and without atomics or host syncs,
+// so the whole transform replays inside a captured graph and is bitwise reproducible:
+//   ctu_flap_count  bone voxels per (sample, chunk of CTU_FLAP_CHUNK voxels in C order)
+//   ctu_flap_draw   one block per sample: the per-sample scalars from Philox4x32-10 and the k-th bone voxel (the centre)
+//   ctu_flap_apply  one fused streaming pass: hole mask, noise, network input (+ atlas channel) and one-hot targets
+// The rules (shapes, RNG streams, record layout) are pinned in ctunet_amd/transforms.py and include/ctunet_hip.h.
+//
+// Replaces: ctunet/pytorch/transforms.py:13-95 (SaltAndPepper, SkullRandomHole) and ctunet/utilities.py:127-178 (shape_3d),
+//           ctunet/pytorch/transforms.py:241-300 (random_blank_patch), run per sample in NumPy on the host there.
+#include "common.h"
+
+namespace {
+
+constexpr int AB = 256;
+constexpr int REC = CTU_FLAP_RECORD;
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c, key k
+__device__ __forceinline__ uint4 philox(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+__device__ __forceinline__ uint4 philox_seq(uint32_t c0, uint32_t stream, int64_t seq, uint32_t k0, uint32_t k1) {
+    return philox(make_uint4(c0, stream, (uint32_t)(uint64_t)seq, (uint32_t)((uint64_t)seq >> 32)), k0, k1);
+}
+
+// u = (r >> 8) 2^-24 in [0, 1), exact in float32
+__device__ __forceinline__ float unif(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }
+// lo + floor(r (hi - lo) / 2^32): uniform integer in [lo, hi) for hi - lo <= 2^32
+__device__ __forceinline__ int64_t draw_int(uint32_t r, int64_t lo, uint64_t span) {
+    return lo + (int64_t)(((uint64_t)r * span) >> 32);
+}
+
+__device__ __forceinline__ bool bone_at(const void* skull, int u8, int64_t i) {
+    return u8 ? static_cast<const uint8_t*>(skull)[i] != 0 : static_cast<const float*>(skull)[i] >= 1.0f;
+}
+
+// --------------------------------------------------------------------------------------------------------------- count
+// grid (nchunks, N): block (c, n) counts the bone voxels of flat indices [c CH, min(V, (c+1) CH)) of sample n.
+// vec: the sample's bytes start 16-byte aligned (every chunk then does too), 16-byte loads of 4 floats / 16 bytes.
+__global__ void __launch_bounds__(AB) flap_count_kernel(const void* __restrict__ skull, int u8, int64_t V, int nchunks,
+                                                        int vec, int32_t* __restrict__ counts) {
+    const int c = blockIdx.x, n = blockIdx.y;
+    const int64_t s0 = (int64_t)c * CTU_FLAP_CHUNK, s1 = min(V, s0 + CTU_FLAP_CHUNK);
+    const int64_t base = (int64_t)n * V;
+    const int per = u8 ? 16 : 4;                      // voxels per 16 bytes
+    int cnt = 0;
+    for (int64_t s = s0 + (int64_t)threadIdx.x * per; s < s1; s += (int64_t)AB * per) {
+        if (vec && s + per <= s1) {
+            const uint4 q = *reinterpret_cast<const uint4*>(static_cast<const char*>(skull) + (base + s) * (u8 ? 1 : 4));
+            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (u8) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) cnt += ((w[j] >> (8 * b)) & 0xFFu) != 0;
+                } else {
+                    cnt += __uint_as_float(w[j]) >= 1.0f;
+                }
+            }
+        } else {
+            for (int64_t i = s; i < min(s1, s + per); ++i) cnt += bone_at(skull, u8, base + i);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    __shared__ int wsum[AB / 64];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < AB / 64; ++w) t += wsum[w];
+        counts[(int64_t)n * nchunks + c] = t;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- draw
+struct DrawArgs {
+    const void* skull;
+    int u8, N, D, H, W, nchunks, mode, decay, size_lo, size_hi, shapes;
+    const int32_t* counts;
+    const int64_t* hole_seq;
+    const int64_t* noise_seq;
+    const float* noise_nd;
+    uint32_t hk0, hk1, nk0, nk1;
+    float p_hole, p_noise, salt_ratio;
+    int32_t* params;
+};
+
+// one block per sample n; thread 0 draws the scalars, the block finds the centre (record layout: ctunet_hip.h)
+__global__ void __launch_bounds__(AB) flap_draw_kernel(DrawArgs a) {
+    const int n = blockIdx.x;
+    int32_t* rec = a.params + (int64_t)n * REC;
+    const int64_t V = (int64_t)a.D * a.H * a.W;
+    __shared__ int64_t tsum[AB];
+    __shared__ int64_t sh_chunk, sh_kloc, sh_idx;
+    if (a.mode & CTU_FLAP_HOLE) {
+        const int64_t seq = a.hole_seq[0] + n;
+        const int32_t* cn = a.counts + (int64_t)n * a.nchunks;
+        const int per = (a.nchunks + AB - 1) / AB;
+        const int c0 = threadIdx.x * per, c1 = min(a.nchunks, c0 + per);
+        int64_t s = 0;
+        for (int c = c0; c < c1; ++c) s += cn[c];
+        tsum[threadIdx.x] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint4 r = philox_seq(0, 0, seq, a.hk0, a.hk1);
+            const uint4 r2 = philox_seq(1, 0, seq, a.hk0, a.hk1);
+            int64_t total = 0;
+            for (int t = 0; t < AB; ++t) total += tsum[t];
+            const int64_t k = total > 0 ? draw_int(r.y, 0, (uint64_t)total) : 0;
+            int64_t chunk = -1, kloc = 0;
+            if (total > 0) {                          // the thread segment, then the chunk, that holds the k-th bone voxel
+                int64_t acc = 0;
+                int t = 0;
+                while (acc + tsum[t] <= k) acc += tsum[t++];
+                for (int c = t * per;; ++c) {
+                    if (acc + cn[c] > k) { chunk = c; kloc = k - acc; break; }
+                    acc += cn[c];
+                }
+            }
+            sh_chunk = chunk;
+            sh_kloc = kloc;
+            sh_idx = -1;
+            const int size = (int)draw_int(r.z, a.size_lo, (uint64_t)(a.size_hi - a.size_lo));
+            const int nsh = a.shapes & 3;
+            const int shape = (a.shapes >> (2 + 2 * (int)draw_int(r.w, 0, (uint64_t)nsh))) & 3;
+            // c_diam = U(0.25, 1) size / 4, every operation rounded separately (no contraction)
+            const float cd = __fmul_rn(__fmul_rn(__fadd_rn(0.25f, __fmul_rn(0.75f, unif(r2.x))), (float)size), 0.25f);
+            rec[0] = unif(r.x) < a.p_hole;
+            rec[1] = (int32_t)total;
+            rec[2] = (int32_t)k;
+            rec[6] = size;
+            rec[7] = shape;
+            rec[8] = __float_as_int(cd);
+            rec[9] = rec[0] && total > 0;
+        }
+        __syncthreads();
+        if (threadIdx.x < 64 && sh_chunk >= 0) {     // wave 0 rescans the chunk: 64 voxels per ballot
+            const int lane = threadIdx.x;
+            int64_t kl = sh_kloc;
+            const int64_t e = min(V, (sh_chunk + 1) * CTU_FLAP_CHUNK);
+            for (int64_t b = sh_chunk * CTU_FLAP_CHUNK; b < e; b += 64) {
+                const int64_t i = b + lane;
+                const bool bone = i < e && bone_at(a.skull, a.u8, (int64_t)n * V + i);
+                const uint64_t m = __ballot(bone);
+                const int pc = __popcll(m);
+                if (kl < pc) {
+                    if (bone && __popcll(m & ((1ull << lane) - 1ull)) == kl) sh_idx = i;
+                    break;
+                }
+                kl -= pc;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int64_t i = sh_idx;
+            const int64_t hw = (int64_t)a.H * a.W;
+            rec[3] = i < 0 ? -1 : (int32_t)(i / hw);
+            rec[4] = i < 0 ? -1 : (int32_t)((i / a.W) % a.H);
+            rec[5] = i < 0 ? -1 : (int32_t)(i % a.W);
+        }
+    } else if (threadIdx.x == 0) {
+        for (int j = 0; j < 10; ++j) rec[j] = 0;
+        rec[3] = rec[4] = rec[5] = -1;
+    }
+    if (threadIdx.x != 0) return;
+    if (a.mode & CTU_FLAP_NOISE) {
+        const int64_t s0 = a.noise_seq[0];
+        const int64_t seq = s0 + n;
+        const uint4 q = philox_seq(0, 0, seq, a.nk0, a.nk1);
+        float nd = a.noise_nd[0];
+        if (a.decay) {                                // nd_j = U_j nd_{j-1} over the samples before this one, in order
+            for (int j = 0; j <= n; ++j) nd = __fmul_rn(unif(philox_seq(0, 0, s0 + j, a.nk0, a.nk1).y), nd);
+        } else {
+            nd = __fmul_rn(unif(q.y), nd);
+        }
+        rec[10] = unif(q.x) < a.p_noise;
+        rec[11] = __float_as_int(nd);
+        rec[12] = __float_as_int(__fmul_rn(nd, __fsub_rn(1.0f, a.salt_ratio)));
+        rec[13] = __float_as_int(__fmul_rn(nd, a.salt_ratio));
+        rec[14] = (int32_t)(uint32_t)(uint64_t)seq;
+        rec[15] = (int32_t)(uint32_t)((uint64_t)seq >> 32);
+    } else {
+        for (int j = 10; j < REC; ++j) rec[j] = 0;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- apply
+struct ApplyArgs {
+    const void* skull;
+    const float* atlas;
+    const int32_t* params;
+    int64_t* hole_seq;
+    int64_t* noise_seq;
+    float* noise_nd;
+    float* x;
+    float* full;
+    float* flap;
+    int u8, N, D, H, W, C, mode, decay, vec;
+    uint32_t nk0, nk1;
+};
+
+// inside the hole shape of record rec at voxel (z, y, x); integer tests, the flap cylinders in doubled coordinates
+__device__ __forceinline__ bool inside(int shape, int size, float cd2, int dz, int dy, int dx, int y2c, int x2c1, int x2c2,
+                                       int y, int x) {
+    const int64_t lz = dz, ly = dy, lx = dx, s = size;
+    if (shape == CTU_FLAP_SPHERE) return s >= 0 && lz * lz + ly * ly + lx * lx <= s * s;
+    const int64_t az = lz < 0 ? -lz : lz, ay = ly < 0 ? -ly : ly, ax = lx < 0 ? -lx : lx;
+    if (shape == CTU_FLAP_BOX) return az <= s && ay <= s && ax <= s;
+    if (2 * az > s) return false;                     // cube and both cylinders: |z - cz| <= size / 2
+    if (2 * ay <= s && 2 * ax <= s) return true;
+    const int64_t ey = 2 * (int64_t)y - y2c, e1 = 2 * (int64_t)x - x2c1, e2 = 2 * (int64_t)x - x2c2;
+    return (double)(ey * ey + e1 * e1) <= (double)cd2 || (double)(ey * ey + e2 * e2) <= (double)cd2;
+}
+
+__global__ void __launch_bounds__(AB) flap_apply_kernel(ApplyArgs a) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {       // advance the instances' device state (nothing else reads it here)
+        if (a.mode & CTU_FLAP_HOLE) a.hole_seq[0] += a.N;
+        if (a.mode & CTU_FLAP_NOISE) {
+            a.noise_seq[0] += a.N;
+            if (a.decay) a.noise_nd[0] = __int_as_float(a.params[(int64_t)(a.N - 1) * REC + 11]);
+        }
+    }
+    const int Wq = (a.W + 3) >> 2;
+    const int64_t V = (int64_t)a.D * a.H * a.W;
+    const int64_t total = (int64_t)a.N * a.D * a.H * Wq;
+    for (int64_t g = (int64_t)blockIdx.x * AB + threadIdx.x; g < total; g += (int64_t)gridDim.x * AB) {
+        const int xq = (int)(g % Wq);
+        const int64_t row = g / Wq;
+        const int y = (int)(row % a.H);
+        const int z = (int)((row / a.H) % a.D);
+        const int n = (int)(row / ((int64_t)a.H * a.D));
+        const int x = 4 * xq;
+        const int64_t zyx = ((int64_t)z * a.H + y) * a.W + x;
+        const int64_t src = (int64_t)n * V + zyx;
+        const int32_t* rec = a.params + (int64_t)n * REC;
+        // the skull's 4 voxels: value = its uint8 cast (truncation on [0, 256)), bone = value != 0
+        float val[4];
+        if (a.vec) {
+            if (a.u8) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.skull) + src);
+#pragma unroll
+                for (int l = 0; l < 4; ++l) val[l] = (float)((w >> (8 * l)) & 0xFFu);
+            } else {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.skull) + src);
+#pragma unroll
+                for (int l = 0; l < 4; ++l) val[l] = truncf(v[l]);
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                val[l] = 0.f;
+                if (x + l < a.W)
+                    val[l] = a.u8 ? (float)static_cast<const uint8_t*>(a.skull)[src + l]
+                                  : truncf(static_cast<const float*>(a.skull)[src + l]);
+            }
+        }
+        float img[4], bone[4], fl[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            bone[l] = val[l] >= 1.0f ? 1.f : 0.f;
+            img[l] = val[l];
+            fl[l] = 0.f;
+        }
+        if ((a.mode & CTU_FLAP_HOLE) && rec[9]) {
+            const int cz = rec[3], cy = rec[4], cx = rec[5], size = rec[6], shape = rec[7];
+            const float cd = __int_as_float(rec[8]);
+            const float cd2 = __fmul_rn(2.f * cd, 2.f * cd);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                const bool in = inside(shape, size, cd2, z - cz, y - cy, x + l - cx, 2 * cy - size, 2 * cx - size,
+                                       2 * cx + size, y, x + l);
+                const bool b = bone[l] != 0.f;
+                img[l] = b && !in ? 1.f : 0.f;
+                fl[l] = b && in ? 1.f : 0.f;
+            }
+        }
+        if ((a.mode & CTU_FLAP_NOISE) && rec[10]) {
+            const int64_t seq = (int64_t)(((uint64_t)(uint32_t)rec[15] << 32) | (uint32_t)rec[14]);
+            const uint32_t c0 = (uint32_t)(((int64_t)z * a.H + y) * Wq + xq);
+            const uint4 r1 = philox_seq(c0, 1, seq, a.nk0, a.nk1);
+            const uint4 r2 = philox_seq(c0, 2, seq, a.nk0, a.nk1);
+            const float t0 = __int_as_float(rec[12]), t1 = __int_as_float(rec[13]);
+            const uint32_t w1[4] = {r1.x, r1.y, r1.z, r1.w}, w2[4] = {r2.x, r2.y, r2.z, r2.w};
+#pragma unroll
+            for (int l = 0; l < 4; ++l) img[l] = (img[l] != 0.f && !(unif(w1[l]) <= t0)) || unif(w2[l]) <= t1 ? 1.f : 0.f;
+        }
+        float* xo = a.x + (int64_t)n * a.C * V + zyx;
+        float* fo = a.full ? a.full + (int64_t)n * 2 * V + zyx : nullptr;
+        float* po = a.flap ? a.flap + (int64_t)n * 2 * V + zyx : nullptr;
+        if (a.vec) {
+            *reinterpret_cast<f32x4*>(xo) = f32x4{img[0], img[1], img[2], img[3]};
+            if (a.atlas && a.C > 1) *reinterpret_cast<f32x4*>(xo + V) = *reinterpret_cast<const f32x4*>(a.atlas + zyx);
+            if (fo) {
+                *reinterpret_cast<f32x4*>(fo) = f32x4{1.f - bone[0], 1.f - bone[1], 1.f - bone[2], 1.f - bone[3]};
+                *reinterpret_cast<f32x4*>(fo + V) = f32x4{bone[0], bone[1], bone[2], bone[3]};
+            }
+            if (po) {
+                *reinterpret_cast<f32x4*>(po) = f32x4{1.f - fl[0], 1.f - fl[1], 1.f - fl[2], 1.f - fl[3]};
+                *reinterpret_cast<f32x4*>(po + V) = f32x4{fl[0], fl[1], fl[2], fl[3]};
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                if (x + l >= a.W) break;
+                xo[l] = img[l];
+                if (a.atlas && a.C > 1) xo[V + l] = a.atlas[zyx + l];
+                if (fo) { fo[l] = 1.f - bone[l]; fo[V + l] = bone[l]; }
+                if (po) { po[l] = 1.f - fl[l]; po[V + l] = fl[l]; }
+            }
+        }
+    }
+}
+
+bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int check_shape(int N, int D, int H, int W) {
+    CTU_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "flap: bad shape %dx%dx%dx%d", N, D, H, W);
+    CTU_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "flap: %dx%dx%d voxels per sample (< 2^31 supported)", D, H, W);
+    CTU_REQUIRE((int64_t)D * H * ((W + 3) / 4) < ((int64_t)1 << 32), "flap: noise counter overflow");
+    return CTU_OK;
+}
+
+}  // namespace
+
+extern "C" int ctu_flap_count(const void* skull, int u8, int N, int64_t V, int32_t* counts, void* stream) {
+    CTU_REQUIRE(skull && counts, "flap_count: null pointer");
+    CTU_REQUIRE(N > 0 && N <= 65535 && V > 0 && V < ((int64_t)1 << 31), "flap_count: bad shape N=%d V=%lld", N, (long long)V);
+    const int nchunks = (int)ceil_div64(V, CTU_FLAP_CHUNK);
+    const int vec = aligned(skull, 16) && (V * (u8 ? 1 : 4)) % 16 == 0;
+    flap_count_kernel<<<dim3(nchunks, N), AB, 0, (hipStream_t)stream>>>(skull, u8 ? 1 : 0, V, nchunks, vec, counts);
+    CTU_CHECK_LAUNCH("flap_count");
+    return CTU_OK;
+}
+
+extern "C" int ctu_flap_draw(const void* skull, int u8, int N, int D, int H, int W, const int32_t* counts, int mode,
+                             const int64_t* hole_seq, uint64_t hole_seed, float p_hole, int size_lo, int size_hi,
+                             int shapes, const int64_t* noise_seq, const float* noise_nd, uint64_t noise_seed,
+                             float p_noise, float salt_ratio, int decay, int32_t* params, void* stream) {
+    if (int e = check_shape(N, D, H, W)) return e;
+    CTU_REQUIRE(params && mode >= 1 && mode <= 3, "flap_draw: null params or bad mode %d", mode);
+    CTU_REQUIRE(!(mode & CTU_FLAP_HOLE) || (skull && counts && hole_seq), "flap_draw: hole needs skull, counts, counter");
+    CTU_REQUIRE(!(mode & CTU_FLAP_NOISE) || (noise_seq && noise_nd), "flap_draw: noise needs counter and density");
+    CTU_REQUIRE(N <= 65535, "flap_draw: batch %d too large", N);
+    if (mode & CTU_FLAP_HOLE) {
+        const int nsh = shapes & 3;
+        CTU_REQUIRE(nsh >= 1, "flap_draw: empty shape list");
+        for (int i = 0; i < nsh; ++i) CTU_REQUIRE(((shapes >> (2 + 2 * i)) & 3) <= CTU_FLAP_FLAP, "flap_draw: bad shape code");
+        CTU_REQUIRE(size_hi > size_lo, "flap_draw: empty size range [%d, %d)", size_lo, size_hi);
+    }
+    DrawArgs a;
+    a.skull = skull;
+    a.u8 = u8 ? 1 : 0;
+    a.N = N; a.D = D; a.H = H; a.W = W;
+    a.nchunks = (int)ceil_div64((int64_t)D * H * W, CTU_FLAP_CHUNK);
+    a.mode = mode; a.decay = decay ? 1 : 0;
+    a.size_lo = size_lo; a.size_hi = size_hi; a.shapes = shapes;
+    a.counts = counts; a.hole_seq = hole_seq; a.noise_seq = noise_seq; a.noise_nd = noise_nd;
+    a.hk0 = (uint32_t)hole_seed; a.hk1 = (uint32_t)(hole_seed >> 32);
+    a.nk0 = (uint32_t)noise_seed; a.nk1 = (uint32_t)(noise_seed >> 32);
+    a.p_hole = p_hole; a.p_noise = p_noise; a.salt_ratio = salt_ratio;
+    a.params = params;
+    flap_draw_kernel<<<N, AB, 0, (hipStream_t)stream>>>(a);
+    CTU_CHECK_LAUNCH("flap_draw");
+    return CTU_OK;
+}
+
+extern "C" int ctu_flap_apply(const void* skull, int u8, const float* atlas, int N, int D, int H, int W,
+                              const int32_t* params, int mode, int64_t* hole_seq, int64_t* noise_seq, float* noise_nd,
+                              uint64_t noise_seed, int decay, float* x, int C, float* full, float* flap, void* stream) {
+    if (int e = check_shape(N, D, H, W)) return e;
+    CTU_REQUIRE(skull && params && x, "flap_apply: null pointer");
+    CTU_REQUIRE(mode >= 1 && mode <= 3, "flap_apply: bad mode %d", mode);
+    CTU_REQUIRE(!(mode & CTU_FLAP_HOLE) || hole_seq, "flap_apply: hole needs its counter");
+    CTU_REQUIRE(!(mode & CTU_FLAP_NOISE) || (noise_seq && noise_nd), "flap_apply: noise needs counter and density");
+    CTU_REQUIRE(C == 1 || C == 2, "flap_apply: %d input channels (1, or 2 with the atlas)", C);
+    CTU_REQUIRE((C == 2) == (atlas != nullptr), "flap_apply: the second input channel is the atlas");
+    ApplyArgs a;
+    a.skull = skull; a.atlas = atlas; a.params = params;
+    a.hole_seq = hole_seq; a.noise_seq = noise_seq; a.noise_nd = noise_nd;
+    a.x = x; a.full = full; a.flap = flap;
+    a.u8 = u8 ? 1 : 0;
+    a.N = N; a.D = D; a.H = H; a.W = W; a.C = C;
+    a.mode = mode; a.decay = decay ? 1 : 0;
+    a.vec = W % 4 == 0 && aligned(skull, u8 ? 4 : 16) && aligned(x, 16) && (!atlas || aligned(atlas, 16)) &&
+            (!full || aligned(full, 16)) && (!flap || aligned(flap, 16));
+    a.nk0 = (uint32_t)noise_seed; a.nk1 = (uint32_t)(noise_seed >> 32);
+    const int64_t quads = (int64_t)N * D * H * ((W + 3) / 4);
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(quads, AB), 2048));
+    flap_apply_kernel<<<grid, AB, 0, (hipStream_t)stream>>>(a);
+    CTU_CHECK_LAUNCH("flap_apply");
+    return CTU_OK;
+}

@@ -19,6 +19,7 @@ L = C.c_int64
 F = C.c_float
 D = C.c_double
 Z = C.c_size_t
+U = C.c_uint64
 
 class PackJob(C.Structure):
     """ctu_pack_job of include/ctunet_hip.h."""
@@ -119,6 +120,9 @@ SIGNATURES = {
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),
     "ctu_window_finalize": (I, [P, P, I, L, P, P, P]),
+    "ctu_flap_count": (I, [P, I, I, L, P, P]),
+    "ctu_flap_draw": (I, [P, I, I, I, I, I, P, I, P, U, F, I, I, I, P, P, U, F, F, I, P, P]),
+    "ctu_flap_apply": (I, [P, I, P, I, I, I, I, P, I, P, P, P, U, I, P, I, P, P, P]),
     "ctu_lp_upconv_fused_supported": (I, [I, I, I, I, I, I]),
     "ctu_lp_upconv_fused_packed_elems": (Z, [I]),
     "ctu_lp_upconv_fused_num_blocks": (I, [I, I, I, I]),

@@ -16,6 +16,9 @@ collate turns the target tuple into the list ``Model.forward_pass`` expects (Mod
 Inputs are binary masks cast to float like the reference's (datasets.py:92-94): a hollow ellipsoid shell ("skull"),
 a spherical bite out of it ("flap"); geometry is drawn from ``torch.Generator(seed + idx)`` so every rank / epoch can
 address its own deterministic items (rank r takes idx = r, r + world, ...).
+
+The in-memory training sets below (FlapRecWShapePrior2OTrainDataset, FlapRec2OTrainDataset) produce the same schema from
+real binary skulls through the on-device flap_rec_transform (transforms.py).
 """
 from __future__ import annotations
 
@@ -69,3 +72,70 @@ class SyntheticFlapDataset(Dataset):
             img = torch.cat((img, self._atlas.unsqueeze(0)), 0)
         target = (full, flap_oh) if self.double_out else flap_oh
         return {"image": img.contiguous(), "target": target, "filepath": f"synthetic://{self.seed}/{idx}"}
+
+
+class FlapRecWShapePrior2OTrainDataset(Dataset):
+    """In-memory binary skulls through the flap-reconstruction transform on the GPU (the reference's class of the same
+    name, ctunet/pytorch/datasets.py:152-235, minus its NIfTI I/O): item idx is
+
+        {"image":  float32 [2, D, H, W]  broken, noisy skull + atlas   ([1, D, H, W] without the atlas),
+         "target": (full skull one-hot [2, D, H, W], flap one-hot [2, D, H, W]),
+         "filepath": "memory://<idx>"}
+
+    skulls: a list of [D,H,W] tensors or one [M,D,H,W] tensor, float32 or uint8, on the host or the device (host items
+    are copied to the device per item); atlas: [D,H,W].  transform: a ``transforms.FlapRecTransform`` (default: the
+    module's ``flap_rec_transform``, with the reference's decaying noise density); its hole must be double-output.
+    The transform runs as ONE fused pass per item; every call advances its device sample counter."""
+
+    def __init__(self, skulls, atlas=None, transform=None, append_atlas: bool = True, device="cuda"):
+        from . import transforms as T
+        self.skulls = skulls
+        if len(skulls) == 0 or any(s.dim() != 3 for s in (skulls[i] for i in range(len(skulls)))):
+            raise ValueError("ctunet_amd: skulls must be a non-empty list of [D,H,W] tensors or an [M,D,H,W] tensor")
+        self.device = torch.device(device)
+        base = T.flap_rec_transform if transform is None else transform
+        if not isinstance(base, T.FlapRecTransform) or not base.hole.double_output:
+            raise ValueError("ctunet_amd: transform must be a FlapRecTransform with SkullRandomHole(double_output=True)")
+        self.append_atlas = bool(append_atlas)
+        if self.append_atlas and atlas is None:
+            raise ValueError("ctunet_amd: append_atlas needs an atlas [D,H,W]")
+        self.atlas = atlas.to(self.device, torch.float32).contiguous() if self.append_atlas else None
+        self.transform = T.FlapRecTransform(base.hole, base.noise, self.atlas)   # shares the hole / noise state
+
+    def __len__(self):
+        return len(self.skulls)
+
+    def __getitem__(self, idx: int):
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        s = self.skulls[idx]
+        s = s.to(self.device, non_blocking=True)
+        if s.dtype not in (torch.float32, torch.uint8):
+            s = s.float()
+        x, (full, flap) = self.transform.apply(s.contiguous().view(1, 1, *s.shape))
+        return {"image": x[0], "target": (full[0], flap[0]), "filepath": f"memory://{idx}"}
+
+
+class FlapRec2OTrainDataset(FlapRecWShapePrior2OTrainDataset):
+    """FlapRecDoubleOut's training set (datasets.py:238-250): the same without the atlas channel."""
+
+    def __init__(self, skulls, transform=None, device="cuda"):
+        super().__init__(skulls, None, transform, append_atlas=False, device=device)
+
+
+class FlapRecTrainDataset(Dataset):
+    """Not provided: in the reference (datasets.py:136-149 with 89-112) flap_rec_transform's (full skull, flap) tuple
+    target reaches ``sample['target'].long()`` (datasets.py:107-110) and raises, so this class cannot produce a sample."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("FlapRecTrainDataset crashes in the reference: flap_rec_transform's tuple target "
+                                  "reaches .long() (ctunet/pytorch/datasets.py:107-110); use FlapRec2OTrainDataset")
+
+
+class FlapRecWShapePriorTrainDataset(Dataset):
+    """Not provided: the reference's version (datasets.py:253-270) runs cranioplasty_transform, whose elastic and affine
+    steps come from torchio -- outside this package."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("FlapRecWShapePriorTrainDataset needs torchio's elastic and affine transforms "
+                                  "(cranioplasty_transform); use FlapRecWShapePrior2OTrainDataset")

@@ -1264,3 +1264,60 @@ def unscale_tensors(tensors, scale: torch.Tensor, found_inf: torch.Tensor) -> No
     sa = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
     _lib.check(_lib.load().ctu_unscale_tensors(pa, sa, len(ts), scale.data_ptr(), found_inf.data_ptr(), _stream()),
                "unscale_tensors")
+
+
+FLAP_CHUNK = 8192          # CTU_FLAP_CHUNK of ctunet_hip.h
+FLAP_RECORD = 16           # CTU_FLAP_RECORD
+FLAP_HOLE, FLAP_NOISE = 1, 2
+
+
+def _skull_kind(t: torch.Tensor, name: str) -> int:
+    if not t.is_cuda:
+        raise RuntimeError(f"ctunet_amd: {name} must live on the GPU (MI355X); this path has no CPU fallback")
+    if t.dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError(f"ctunet_amd: {name} must be float32 or uint8, got {t.dtype}")
+    assert t.is_contiguous(), name
+    return int(t.dtype == torch.uint8)
+
+
+def flap_count(skulls: torch.Tensor, counts: torch.Tensor) -> None:
+    """counts int32 [N, ceil(V / FLAP_CHUNK)] = bone voxels per chunk of each sample of skulls [N,1,D,H,W]."""
+    u8 = _skull_kind(skulls, "skulls")
+    n, v = skulls.shape[0], skulls[0].numel()
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == n * -(-v // FLAP_CHUNK)
+    _lib.check(_lib.load().ctu_flap_count(skulls.data_ptr(), u8, n, v, counts.data_ptr(), _stream()), "flap_count")
+
+
+def flap_draw(skulls: torch.Tensor, counts: Optional[torch.Tensor], mode: int, hole_seq: Optional[torch.Tensor],
+              hole_seed: int, p_hole: float, size_range: Tuple[int, int], shapes: int, noise_seq: Optional[torch.Tensor],
+              noise_nd: Optional[torch.Tensor], noise_seed: int, p_noise: float, salt_ratio: float, decay: bool,
+              params: torch.Tensor) -> None:
+    """params int32 [N, FLAP_RECORD] = the per-sample records (layout: ctunet_hip.h), drawn from the device counters."""
+    u8 = _skull_kind(skulls, "skulls")
+    n, _, d, h, w = skulls.shape
+    assert params.is_cuda and params.dtype == torch.int32 and params.numel() == n * FLAP_RECORD
+    _lib.check(_lib.load().ctu_flap_draw(skulls.data_ptr(), u8, n, d, h, w, _ptr(counts), mode, _ptr(hole_seq),
+                                         hole_seed, float(p_hole), size_range[0], size_range[1], shapes, _ptr(noise_seq),
+                                         _ptr(noise_nd), noise_seed, float(p_noise), float(salt_ratio), int(decay),
+                                         params.data_ptr(), _stream()), "flap_draw")
+
+
+def flap_apply(skulls: torch.Tensor, atlas: Optional[torch.Tensor], params: torch.Tensor, mode: int,
+               hole_seq: Optional[torch.Tensor], noise_seq: Optional[torch.Tensor], noise_nd: Optional[torch.Tensor],
+               noise_seed: int, decay: bool, x: torch.Tensor, full: Optional[torch.Tensor],
+               flap: Optional[torch.Tensor]) -> None:
+    """x [N,C,D,H,W] (image, + atlas channel), full / flap [N,2,D,H,W] one-hot targets, from the records; advances the
+    device counters (and the density with decay)."""
+    u8 = _skull_kind(skulls, "skulls")
+    n, _, d, h, w = skulls.shape
+    for t, nm, c in ((x, "x", x.shape[1]), (full, "full-skull target", 2), (flap, "flap target", 2)):
+        if t is None:
+            continue
+        _need_cuda(t, nm)
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, c, d, h, w), nm
+    if atlas is not None:
+        _need_cuda(atlas, "atlas")
+        assert atlas.is_contiguous() and atlas.numel() == d * h * w, "atlas [D,H,W]"
+    _lib.check(_lib.load().ctu_flap_apply(skulls.data_ptr(), u8, _ptr(atlas), n, d, h, w, params.data_ptr(), mode,
+                                          _ptr(hole_seq), _ptr(noise_seq), _ptr(noise_nd), noise_seed, int(decay),
+                                          x.data_ptr(), x.shape[1], _ptr(full), _ptr(flap), _stream()), "flap_apply")

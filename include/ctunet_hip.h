@@ -450,6 +450,38 @@ int ctu_window_accumulate(const float* patches, const int32_t* coords, const int
 int ctu_window_finalize(const float* num, const float* wsum, int K, int64_t V, float* probs, uint8_t* labels,
                         void* stream);
 
+/* Flap-reconstruction augmentation (SkullRandomHole + SaltAndPepper of ctunet/pytorch/transforms.py:13-95,131-134 and
+ * ctunet/utilities.py:127-178, on the device; rules pinned in ctunet_amd/transforms.py).  Batch of N skulls
+ * [N,1,D,H,W], float32 (u8 = 0) or uint8 (u8 = 1); a voxel's value is its uint8 cast (truncation, float values in
+ * [0, 256)) and it is bone iff that is nonzero.  Three launches, no atomics, no host sync:
+ *   count: counts [N][ceil(V / CTU_FLAP_CHUNK)] int32 = bone voxels per chunk of CTU_FLAP_CHUNK voxels in C order.
+ *   draw:  one block per sample: writes params [N][CTU_FLAP_RECORD] int32 from the DEVICE counters (int64 [1]) and
+ *          density (float32 [1]) of the hole / noise instances; sample n of the batch uses sequence number counter + n.
+ *          mode: CTU_FLAP_HOLE | CTU_FLAP_NOISE.  shapes = count | code_i << (2 + 2 i), codes CTU_FLAP_SPHERE / BOX / FLAP.
+ *          Hole sizes are drawn in [size_lo, size_hi).  counts may be NULL without CTU_FLAP_HOLE.
+ *   apply: one pass over the batch (4 x-consecutive voxels per thread): x [N,C,D,H,W] float32 gets the image in channel 0
+ *          and a copy of atlas [D,H,W] in channel 1 (C = 2 iff atlas); full / flap [N,2,D,H,W] float32 (either may be
+ *          NULL) get the one-hot full skull and flap.  Advances the device counters by N and, with decay, stores the
+ *          last sample's density.  skull may be x itself (C = 1, in place).
+ * record: 0 hole drawn (u < p_hole)  1 bone count  2 k  3-5 centre z, y, x (-1 without bone)  6 size  7 shape
+ *         8 c_diam (float bits)  9 hole cut (drawn and count > 0)  10 noise drawn  11 density nd' (float bits)
+ *         12 zero threshold nd' (1 - salt_ratio)  13 salt threshold nd' salt_ratio (float bits)  14-15 noise sequence lo, hi */
+#define CTU_FLAP_CHUNK 8192
+#define CTU_FLAP_RECORD 16
+#define CTU_FLAP_HOLE 1
+#define CTU_FLAP_NOISE 2
+#define CTU_FLAP_SPHERE 0
+#define CTU_FLAP_BOX 1
+#define CTU_FLAP_FLAP 2
+int ctu_flap_count(const void* skull, int u8, int N, int64_t V, int32_t* counts, void* stream);
+int ctu_flap_draw(const void* skull, int u8, int N, int D, int H, int W, const int32_t* counts, int mode,
+                  const int64_t* hole_seq, uint64_t hole_seed, float p_hole, int size_lo, int size_hi, int shapes,
+                  const int64_t* noise_seq, const float* noise_nd, uint64_t noise_seed, float p_noise, float salt_ratio,
+                  int decay, int32_t* params, void* stream);
+int ctu_flap_apply(const void* skull, int u8, const float* atlas, int N, int D, int H, int W, const int32_t* params,
+                   int mode, int64_t* hole_seq, int64_t* noise_seq, float* noise_nd, uint64_t noise_seed, int decay,
+                   float* x, int C, float* full, float* flap, void* stream);
+
 /* ------------------------------------------------ reduced precision (bf16 / fp16 activations) ---- */
 /* BASELINE configs 4 ("bf16, 192^3 patches") and 5 ("fp16 MFMA conv path, 256^3 patches").  Same operations, call sites
  * and argument meaning as the fp32 entry points above, with
