@@ -527,8 +527,9 @@ class UNetEngine:
 
     def backward(self, P: Dict[str, torch.Tensor], ctx, g0: torch.Tensor, g1: Optional[torch.Tensor],
                  need_dx: bool, sync=None):
-        """sync: optional parallel.GradSync -- receives each block's weight gradients as soon as their
-        kernels are enqueued (head, decoder top->bottom, centre, encoder bottom->top)."""
+        """sync: optional parallel.GradSync (or graph._Segmenter) -- receives each block's weight gradients as soon as their
+        kernels are enqueued (head, decoder top->bottom, centre, encoder bottom->top); its finish() hands back the
+        exchanged gradients, and the ranks' combined overflow flag then replaces this rank's own."""
         plan = self.plan
         recs = ctx["recs"]
         n, d, h, w = ctx["dims"]
@@ -724,19 +725,14 @@ class UNetEngine:
         if sync is not None:
             if flag is not None:
                 # N > 1: the overflow flag travels with the last gradient bucket, so that every rank skips the step when ANY
-                # rank overflowed (the mean of the ranks' 0 / 1 flags); the caller copies grads["__overflow__"] back into
-                # overflow_flag() once the exchange has completed (fold_overflow)
+                # rank overflowed (the mean of the ranks' 0 / 1 flags), copied back into the flag once the exchange is done
                 sync.push([("__overflow__", flag.clone())])
             grads.update(sync.finish())
+            red = grads.pop("__overflow__", None)
+            if red is not None:
+                flag.copy_(red.reshape(1))
         self._gy_bufs = {}
         return grads, dx
-
-    def fold_overflow(self, grads: Dict[str, torch.Tensor], device) -> None:
-        """After a gradient exchange: the ranks' combined overflow flag (see backward) replaces this rank's own."""
-        red = grads.pop("__overflow__", None)
-        if red is not None:
-            (self.scaler.found_inf if self.scaler is not None and self.dtype == torch.float16
-             else self.overflow_flag(device)).copy_(red.reshape(1))
 
 
 # ----------------------------------------------------------------------------- autograd glue
@@ -767,7 +763,6 @@ class _UNetFn(torch.autograd.Function):
         from .parallel import make_sync
         with torch.no_grad():
             grads, dx = fctx.engine.backward(P, ctx, g0, g1, fctx.x_req, make_sync(fctx.module))
-            fctx.engine.fold_overflow(grads, g0.device)        # (GradSync.finish has waited for every bucket)
         fctx.ctx = None
         # parameters the graph never touches (the dead centre block, models.py:241) get None,
         # exactly as torch autograd leaves them in the reference
@@ -786,7 +781,7 @@ def _tensor_dict(module) -> Dict[str, torch.Tensor]:
     return P
 
 
-def run_network(module, engine: UNetEngine, x: torch.Tensor):
+def check_input(module, x: torch.Tensor) -> None:
     if not isinstance(x, torch.Tensor) or x.dim() != 5:
         raise RuntimeError("ctunet_amd: expected a [N, C, D, H, W] tensor")
     if not x.is_cuda:
@@ -794,10 +789,14 @@ def run_network(module, engine: UNetEngine, x: torch.Tensor):
                            % x.device)
     if x.dtype != torch.float32:
         raise RuntimeError(f"ctunet_amd: fp32 input expected, got {x.dtype}")
-    names, params = zip(*module.named_parameters())
-    for p in params:
+    for p in module.parameters():
         if p.device != x.device:
             raise RuntimeError("ctunet_amd: module parameters and input must be on the same GPU (call .to(device))")
+
+
+def run_network(module, engine: UNetEngine, x: torch.Tensor):
+    check_input(module, x)
+    names, params = zip(*module.named_parameters())
     need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
     if not need_grad:
         with torch.no_grad():

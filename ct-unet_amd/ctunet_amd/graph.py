@@ -3,15 +3,16 @@ and replayed, so the ~270 kernel launches of a step cost one graph launch (MI355
 launch-bound inner loops in hipGraphs").
 
 The step is the reference's ``Model.forward_pass`` train branch (ctunet/pytorch/Model.py:343-374) minus its
-host round trips: the per-term ``float(loss)`` syncs become ONE device->host copy after the replay.
+host round trips: the per-term ``float(loss)`` syncs become ONE device->host copy after the replay.  It is captured by
+driving the engine directly on the capturing thread (forward, fused loss kernels, backward, optimizer): no autograd
+takes part, so an autograd graph that an earlier eager step left alive plays no role in the capture.
 
 With ``distributed`` set (one process per GPU) the step is a CHAIN of graph segments cut at the gradient-bucket
 boundaries of backward (head + upper decoder / deep decoder / deep encoder / rest, ``parallel.DEFAULT_BUCKET_BYTES``):
 segment k ends by flattening bucket k into a static buffer; its all-reduce (RCCL through the C ABI, never captured) is
 launched on a side stream behind an event and runs UNDER segment k+1; the last segment is the fused optimizer step,
-which waits for every bucket.  Only the last, smallest bucket's collective is exposed.  The segments are captured by
-driving the engine directly (forward, fused loss kernels, backward) on the capturing thread -- no autograd thread takes
-part, so a capture can be ended and the next begun at a bucket boundary in the middle of backward.
+which waits for every bucket.  Only the last, smallest bucket's collective is exposed.  Without it the same step body
+is one graph: the chain without bucket boundaries.
 """
 from __future__ import annotations
 
@@ -20,7 +21,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .losses import fused_ce_dice
+from .engine import _tensor_dict, check_input
+from .losses import _check_map, _total, select_terms
+from .parallel import DEFAULT_BUCKET_BYTES, get_communicator, make_sync
 
 
 class _Segmenter:
@@ -65,15 +68,16 @@ class _Segmenter:
 
 class GraphedTrainStep:
     """model: a ctunet_amd model on the GPU; optimizer: ctunet_amd.optim.Adam/AdamW (or torch.optim with capturable=True).
-    Build it before any eager backward of the same model, or drop every reference to that iteration's autograd graph (its
-    loss tensors) first: a live graph keeps its AccumulateGrad nodes on the default stream, and autograd's stream hand-over
-    to them inside the capture ends the capture with a fault in the HIP runtime (measured, torch 2.10 / ROCm 7.2)."""
+    ``x.grad`` is not filled: the input gradient kernels run (``input_requires_grad``), their result is not kept."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, example_input: torch.Tensor,
                  example_targets: Sequence[torch.Tensor], ce_lambda: float, dice_lambda: float,
                  input_requires_grad: bool = True, warmup: int = 3, distributed: bool = False, process_group=None,
                  bucket_bytes: Optional[int] = None):
         self.model, self.opt = model, optimizer
+        self.ce, self.dice = float(ce_lambda), float(dice_lambda)
+        if not self.ce and not self.dice:
+            raise ValueError("GraphedTrainStep: ce_lambda and dice_lambda are both 0: there is no loss to train on")
         scaler = getattr(model, "loss_scaler", None)
         if scaler is not None and not hasattr(optimizer, "guard"):
             raise RuntimeError("GraphedTrainStep: a model with dynamic loss scaling needs an optimizer that reads the device "
@@ -88,28 +92,25 @@ class GraphedTrainStep:
         if distributed and model.__dict__.get("_grad_sync_cfg") is not None:
             raise RuntimeError("GraphedTrainStep(distributed=True) does its own all-reduce: do not also call "
                                "parallel.distribute() on the model (use parallel.broadcast_parameters)")
-        self.ce, self.dice = float(ce_lambda), float(dice_lambda)
         self.x = example_input.detach().clone()
         self.targets = [t.detach().clone().contiguous() for t in example_targets]
         self.x_req = input_requires_grad
-        self.double = len(self.targets) == 2
         self.values: Optional[torch.Tensor] = None
+        self.keys: List[str] = []              # set by _step
         self.skip_comm = False                 # measurement only (bench.py's comm_ms_exposed): replay without the collectives
-        self.keys = self._keys()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         if not distributed:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.stream(side):
                 for _ in range(warmup):
-                    self._step()
+                    self._step(make_sync(model))
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             with torch.cuda.graph(self.graph):
-                self.values = self._step()
+                self.values = self._step(make_sync(model))
             return
         import torch.distributed as dist
-        from .parallel import DEFAULT_BUCKET_BYTES, get_communicator
         self.world = dist.get_world_size(process_group)
         self.bucket_bytes = DEFAULT_BUCKET_BYTES if bucket_bytes is None else int(bucket_bytes)
         self.comm = get_communicator(process_group)
@@ -118,110 +119,68 @@ class GraphedTrainStep:
         self.flats: List[torch.Tensor] = []
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):            # (the optimizer state must exist before its segment is captured)
-                self._segmented_step(capture=False)
+                self._step(_Segmenter(self.bucket_bytes, self._allreduce_now))
             torch.cuda.synchronize()
             # with a process group alive other threads of the process may issue HIP calls while this one captures (the
             # nccl backend's watchdog polls its events): thread-local capture mode, see DESIGN 6
-            self._segmented_step(capture=True)
+            self._capture_segments()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
 
-    def _keys(self) -> List[str]:
-        k: List[str] = []
-        if self.double:
-            if self.ce:
-                k += ["ce_sk", "ce_fl"]
-            if self.dice:
-                k += ["dice_loss_sk", "dice_loss_fl"]
-        else:
-            if self.ce:
-                k += ["ce"]
-            if self.dice:
-                k += ["dice_loss"]
-        return k + ["epoch_loss"]
-
-    # ------------------------------------------------------------------ single graph (one GPU): through autograd
-    def _step(self) -> torch.Tensor:
-        xi = self.x.requires_grad_(self.x_req)
-        xi.grad = None
-        out = self.model(xi)
-        terms: List[torch.Tensor] = []
-        if self.double:
-            ce_s, dc_s = fused_ce_dice(out[0], self.targets[0], self.ce, self.dice, True)
-            ce_f, dc_f = fused_ce_dice(out[1], self.targets[1], self.ce, self.dice, True)
-            if self.ce:
-                terms += [ce_s, ce_f]
-            if self.dice:
-                terms += [dc_s, dc_f]
-        else:
-            ce, dc = fused_ce_dice(out, self.targets[0], self.ce, self.dice, False)
-            if self.ce:
-                terms.append(ce)
-            if self.dice:
-                terms.append(dc)
-        loss = terms[0]
-        for t in terms[1:]:
-            loss = loss + t
-        loss.backward()
-        self.opt.step()
-        for p in self.model.parameters():
-            p.grad = None
-        return torch.stack([t.detach() for t in terms] + [loss.detach()])
-
-    # ------------------------------------------------------------------ segmented (N > 1): the engine driven directly
-    def _segmented_step(self, capture: bool) -> None:
-        from .engine import _tensor_dict
+    def _step(self, sync) -> torch.Tensor:
+        """One train step, the engine driven directly: forward, the fused loss kernels (each head's gradient seeded with
+        1, as autograd seeds it), backward pushing the gradients into ``sync``, optimizer.  Returns the loss terms and
+        their sum, order ``keys``.  The input / target checks of the eager path are host-side only."""
         model = self.model
+        check_input(model, self.x)
         eng = model._engine()
         P = _tensor_dict(model)
-        pool = None
-
-        def begin():
-            g = torch.cuda.CUDAGraph()
-            g.capture_begin(pool=pool, capture_error_mode="thread_local")
-            self.segments.append(g)
-            return g
-
-        def boundary(k: int, flat: torch.Tensor) -> None:
-            nonlocal pool
-            if capture:
-                self.flats.append(flat)
-                self.segments[-1].capture_end()
-                if pool is None:
-                    pool = self.segments[0].pool()
-                begin()
-            else:
-                self._launch_allreduce(flat)
-
-        if capture:
-            begin()
         with torch.no_grad():
-            out0, out1, ctx = eng.forward(P, self.x, True, True, bool(getattr(model, "chk", False)))
+            out0, out1, ctx = eng.forward(P, self.x, model.training, True, bool(getattr(model, "chk", False)))
             outs = [out0] if out1 is None else [out0, out1]
-            terms, gouts = [], []
+            if len(outs) != len(self.targets):
+                raise RuntimeError(f"GraphedTrainStep: {len(self.targets)} target(s) for {len(outs)} model output(s)")
+            two = out1 is not None
+            heads, gouts = [], []
             for o, t in zip(outs, self.targets):
-                tt, ws = ops.loss_fwd(o, t, self.ce, self.dice, self.double)
-                gouts.append(ops.loss_bwd(o, t, self.ce, self.dice, self.double, ws, None, None))
-                terms.append(tt)
-            # list order of the reference: ce terms first, then dice terms (ProblemHandler.py:252-273)
-            tl = ([t[0] for t in terms] if self.ce else []) + ([t[1] for t in terms] if self.dice else [])
-            loss = tl[0]
-            for t in tl[1:]:
-                loss = loss + t
-            values = torch.stack(tl + [loss])
-            seg = _Segmenter(self.bucket_bytes, boundary)
-            grads, _ = eng.backward(P, ctx, gouts[0], gouts[1] if len(gouts) == 2 else None, self.x_req, seg)
-            if not capture:
-                torch.cuda.current_stream().wait_stream(self.comm_stream)
-            eng.fold_overflow(grads, self.x.device)    # (capture: part of the last segment, replayed behind the last all-reduce)
+                _check_map(o, t)
+                terms, ws = ops.loss_fwd(o, t, self.ce, self.dice, two)
+                gouts.append(ops.loss_bwd(o, t, self.ce, self.dice, two, ws, None, None))
+                heads.append((terms[0], terms[1]))
+            keys, tl = select_terms(heads, self.ce != 0, self.dice != 0)
+            values = torch.stack(tl + [_total(tl)])
+            grads, _ = eng.backward(P, ctx, gouts[0], gouts[1] if two else None, self.x_req, sync)
             for name, p in model.named_parameters():
-                p.grad = grads.get(name)
+                p.grad = grads.get(name) if p.requires_grad else None
             self.opt.step()
             for p in self._params:
                 p.grad = None
-        if capture:
+        self.keys = keys + ["epoch_loss"]
+        return values
+
+    # ------------------------------------------------------------------ segmented (N > 1)
+    def _allreduce_now(self, k: int, flat: torch.Tensor) -> None:
+        """Bucket boundary of a warm-up step: the all-reduce, waited for at once (not timed; finish() then hands back
+        reduced gradients, as GradSync's does)."""
+        self._launch_allreduce(flat)
+        torch.cuda.current_stream().wait_stream(self.comm_stream)
+
+    def _capture_segments(self) -> None:
+        """Captures the step as a chain: every bucket boundary ends the segment being captured and begins the next one
+        in the same memory pool; the overflow fold and the optimizer step end up in the last segment."""
+        def begin():
+            g = torch.cuda.CUDAGraph()
+            g.capture_begin(pool=self.segments[0].pool() if self.segments else None, capture_error_mode="thread_local")
+            self.segments.append(g)
+
+        def boundary(k: int, flat: torch.Tensor) -> None:
+            self.flats.append(flat)
             self.segments[-1].capture_end()
-            self.values = values
+            begin()
+
+        begin()
+        self.values = self._step(_Segmenter(self.bucket_bytes, boundary))
+        self.segments[-1].capture_end()
 
     def _launch_allreduce(self, flat: torch.Tensor) -> None:
         """Mean over ranks of one bucket on the side stream, behind everything enqueued on the current stream so far."""

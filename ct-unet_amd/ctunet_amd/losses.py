@@ -71,6 +71,19 @@ def _total(terms: Sequence[torch.Tensor], like: torch.Tensor = None) -> torch.Te
     return total
 
 
+def select_terms(heads: Sequence[Tuple[torch.Tensor, torch.Tensor]], ce_on: bool,
+                 dice_on: bool) -> Tuple[List[str], List[torch.Tensor]]:
+    """Log keys and loss terms of one head [(ce, dice)] or two [(skull), (flap)] in the reference's list order: the CE
+    terms, then the Dice terms, suffixed _sk / _fl for two heads (ProblemHandler.py:88-91, 252-273)."""
+    sfx = ("_sk", "_fl") if len(heads) == 2 else ("",)
+    keys, terms = [], []
+    for on, name, i in ((ce_on, "ce", 0), (dice_on, "dice_loss", 1)):
+        if on:
+            keys += [name + s for s in sfx]
+            terms += [h[i] for h in heads]
+    return keys, terms
+
+
 def _append(lm: Dict[str, List], key: str, value) -> None:
     lm.setdefault(key, []).append(value)
 
@@ -100,12 +113,8 @@ def comp_losses_metrics_single(model, prediction, target, idx, n_imgs):
             raise RuntimeError(f"ctunet_amd: class-index target {tuple(target.shape)} does not match {tuple(prediction.shape)}")
         from . import ops
         target = ops.one_hot(target.float().contiguous(), prediction.shape[1])
-    ce, dc = fused_ce_dice(prediction, target, ce_l or 0.0, dc_l or 0.0, False)
-    keys, terms = [], []
-    if ce_l != 0:
-        keys.append("ce"); terms.append(ce)
-    if dc_l != 0:
-        keys.append("dice_loss"); terms.append(dc)
+    head = fused_ce_dice(prediction, target, ce_l or 0.0, dc_l or 0.0, False)
+    keys, terms = select_terms([head], ce_l != 0, dc_l != 0)
     model.pt_loss = _total(terms, prediction)
     _metrics(model, [("dice_coef", prediction, target)])
     _publish(model, keys, terms, idx, n_imgs, getattr(model, "verbose", True))
@@ -117,13 +126,8 @@ def comp_losses_metrics_double(model, prediction, target, idx, n_imgs):
     sk_p, fl_p = prediction
     sk_t, fl_t = target
     ce_l, dc_l = model.params["ce_lambda"], model.params["dice_lambda"]
-    ce_s, dc_s = fused_ce_dice(sk_p, sk_t, ce_l or 0.0, dc_l or 0.0, True)
-    ce_f, dc_f = fused_ce_dice(fl_p, fl_t, ce_l or 0.0, dc_l or 0.0, True)
-    keys, terms = [], []
-    if ce_l != 0:
-        keys += ["ce_sk", "ce_fl"]; terms += [ce_s, ce_f]
-    if dc_l != 0:
-        keys += ["dice_loss_sk", "dice_loss_fl"]; terms += [dc_s, dc_f]
+    heads = [fused_ce_dice(p, t, ce_l or 0.0, dc_l or 0.0, True) for p, t in ((sk_p, sk_t), (fl_p, fl_t))]
+    keys, terms = select_terms(heads, ce_l != 0, dc_l != 0)
     model.pt_loss = _total(terms, sk_p)
     _metrics(model, [("dice_coef_sk", sk_p, sk_t), ("dice_coef_fl", fl_p, fl_t)], hd=True)
     _publish(model, keys, terms, idx, n_imgs, getattr(model, "verbose", True))

@@ -71,6 +71,29 @@ def test_loss_total_adds_terms_without_an_int_zero():
     assert float(z) == 0.0 and z.dim() == 0
 
 
+def test_loss_terms_follow_the_reference_list_order():
+    """ProblemHandler.py:88-91, 252-273: the CE terms, then the Dice terms; suffixes _sk / _fl for two heads."""
+    from ctunet_amd import losses
+    sk, fl = (torch.tensor(1.0), torch.tensor(2.0)), (torch.tensor(3.0), torch.tensor(4.0))
+    keys, terms = losses.select_terms([sk, fl], True, True)
+    assert keys == ["ce_sk", "ce_fl", "dice_loss_sk", "dice_loss_fl"]
+    assert all(a is b for a, b in zip(terms, [sk[0], fl[0], sk[1], fl[1]])) and len(terms) == 4
+    keys, terms = losses.select_terms([sk], False, True)
+    assert keys == ["dice_loss"] and len(terms) == 1 and terms[0] is sk[1]
+    assert losses.select_terms([sk, fl], False, False) == ([], [])
+
+
+def test_graphed_step_refuses_a_step_without_loss():
+    """Both lambdas 0: a ValueError before any GPU work."""
+    import ctunet_amd
+    from ctunet_amd import optim
+    from ctunet_amd.graph import GraphedTrainStep
+    net = ctunet_amd.UNet(n_blocks=2, i_size=2)
+    with pytest.raises(ValueError, match="both 0"):
+        GraphedTrainStep(net, optim.Adam(net.parameters()), torch.zeros(1, 1, 8, 8, 8), [torch.zeros(1, 2, 8, 8, 8)],
+                         0.0, 0.0)
+
+
 def test_scheduler_is_built_whenever_the_key_exists(monkeypatch):
     """Model.py:544-546: ``if 'scheduler' in self.params`` -- b_scheduler = False still gets a ReduceLROnPlateau."""
     from ctunet_amd import trainer

@@ -577,9 +577,8 @@ def test_fp16_overflow_is_detected_and_the_step_skipped():
         assert torch.equal(p.detach(), b)                             # nothing moved
     for st in opt.state.values():
         assert float(st["step"]) == 0.0 and torch.isfinite(st["max_exp_avg_sq"]).all() and float(st["exp_avg"].abs().max()) == 0.0
-    # the same inside a captured graph, replayed twice (the eager loss tensors go first: an autograd graph of an earlier
-    # iteration that is still alive pins its AccumulateGrad nodes to the default stream, which breaks the capture)
-    del ce, dc
+    # the same inside a captured graph, replayed twice (built while the eager step's loss tensors are still alive, as in
+    # the reference's loop)
     for p in net.parameters():
         p.grad = None
     gstep = GraphedTrainStep(net, opt, x, [t], 1.0, 1.0, input_requires_grad=True)
