@@ -116,6 +116,8 @@ SIGNATURES = {
     "ctu_hard_dice_counts": (I, [P, P, I, I, L, P, P, P]),
     "ctu_hausdorff_ws_bytes": (Z, [I, I, I, I, I]),
     "ctu_hausdorff": (I, [P, P, I, I, I, I, I, P, P, P]),
+    "ctu_surface_ws_bytes": (Z, [I, I, I, I, I]),
+    "ctu_surface_metrics": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, P, P, D, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

@@ -420,6 +420,23 @@ size_t ctu_hausdorff_ws_bytes(int N, int C, int D, int H, int W);
 int ctu_hausdorff(const float* pred, const float* target, int N, int C, int D, int H, int W, float* out, void* ws,
                   void* stream);
 
+/* Surface-distance metrics with voxel spacing (no reference counterpart: ctunet/utilities.py:62-70 has only the voxel-unit
+ * maximum kept above; definitions pinned in ctunet_amd/metrics.py).  One (item n, class c) pair per scored class
+ * c = cls0 .. cls0+Cs-1 of each item; per side the mask is p[n][c] != 0 for a one-hot tensor [N,C,D,H,W] (onehot = 1) or
+ * p[n] == c for a label map [N,D,H,W] (onehot = 0); dtype CTU_U8, CTU_I64 or CTU_F32 per side.
+ * spacing: HOST float [N][3] (z, y, x spacing of each item; NULL = unit: exact int32 squared distances), tau: HOST double
+ * [Cs] surface-Dice tolerances (NULL: no NSD), percentile in [0, 100] (< 0: none).  out: DEVICE float [8][N*Cs], row r of
+ * pair n*Cs + (c-cls0): 0 hard Dice, 1 HD, 2 directed HD (P->G), 3 HD_p, 4 directed HD_p, 5 ASSD (symmetric),
+ * 6 directed ASD (mean P->G), 7 NSD.  NaN where undefined (empty surface, no percentile, no tau).
+ * ws: ctu_surface_ws_bytes() bytes (pairs processed in groups; about 5 bytes per voxel per plane).  Deterministic, no
+ * host sync, capture-safe.  Cs <= 16, every side <= 1024. */
+#define CTU_U8 3
+#define CTU_I64 4
+size_t ctu_surface_ws_bytes(int N, int Cs, int D, int H, int W);
+int ctu_surface_metrics(const void* pred, int pred_dtype, int pred_onehot, const void* target, int target_dtype,
+                        int target_onehot, int N, int C, int cls0, int Cs, int D, int H, int W, const float* spacing,
+                        const double* tau, double percentile, float* out, void* ws, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
