@@ -107,7 +107,7 @@ class GraphedTrainStep:
                     self._step(make_sync(model))
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
-            with torch.cuda.graph(self.graph):
+            with ops.gc_paused(), torch.cuda.graph(self.graph):
                 self.values = self._step(make_sync(model))
             return
         import torch.distributed as dist
@@ -178,9 +178,10 @@ class GraphedTrainStep:
             self.segments[-1].capture_end()
             begin()
 
-        begin()
-        self.values = self._step(_Segmenter(self.bucket_bytes, boundary))
-        self.segments[-1].capture_end()
+        with ops.gc_paused():
+            begin()
+            self.values = self._step(_Segmenter(self.bucket_bytes, boundary))
+            self.segments[-1].capture_end()
 
     def _launch_allreduce(self, flat: torch.Tensor) -> None:
         """Mean over ranks of one bucket on the side stream, behind everything enqueued on the current stream so far."""

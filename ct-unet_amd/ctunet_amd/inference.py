@@ -269,7 +269,7 @@ def _graphed(model, volume, patch, overlap, batch, blend, sigma_scale, dev) -> _
         win.step()
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with ops.gc_paused(), torch.cuda.graph(g):
             win.step()
         model.__dict__["_window_graph"] = (key, eng, win, g)
         first = 1

@@ -10,6 +10,8 @@ the slice, ``relu``): consumers see ``relu(raw * scale + shift)``.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 from dataclasses import dataclass
@@ -94,6 +96,22 @@ def lp(t_or_dtype) -> int:
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+@contextlib.contextmanager
+def gc_paused():
+    """Cyclic garbage collection off for the length of a graph capture.  A dead object cycle can hold an earlier capture
+    (a model keeps its sliding-window graph, whose window keeps the model); freed by the collector while another capture
+    is under way, that graph's teardown makes HIP calls a capture forbids and the process aborts.  So collect first,
+    outside the capture, and keep the collector off until the capture has ended."""
+    was = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class KernelTimer:

@@ -254,6 +254,25 @@ def test_no_side_effects_on_the_model(graph):
 
 
 # ------------------------------------------------------------------------------------------------ 7. memory
+def test_capture_runs_with_the_collector_paused(monkeypatch):
+    """predict_volume(graph=True) captures with cyclic garbage collection off -- a dead model cycle holding an earlier
+    capture must not be torn down inside this one -- and turns it back on afterwards."""
+    import gc
+    import ctunet_amd as A
+    seen = []
+
+    class Spy(torch.cuda.graph):
+        def __enter__(self):
+            seen.append(gc.isenabled())
+            return super().__enter__()
+
+    monkeypatch.setattr(torch.cuda, "graph", Spy)
+    net = A.UNet().cuda()
+    vol = torch.randn((1, 40, 40, 40), generator=gen(61)).cuda()
+    A.predict_volume(net, vol, patch=32, overlap=8, batch=2, graph=True)
+    assert seen == [False] and gc.isenabled()
+
+
 def test_peak_memory_is_one_batch_plus_the_volume_buffers():
     import ctunet_amd as A
     torch.manual_seed(61)
