@@ -118,6 +118,9 @@ SIGNATURES = {
     "ctu_hausdorff": (I, [P, P, I, I, I, I, I, P, P, P]),
     "ctu_surface_ws_bytes": (Z, [I, I, I, I, I]),
     "ctu_surface_metrics": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, P, P, D, P, P, P]),
+    "ctu_components_ws_bytes": (Z, [I, I, I, I]),
+    "ctu_label_components": (I, [P, I, I, I, I, I, I, P, I, P, P, P, P]),
+    "ctu_filter_components": (I, [P, I, I, I, I, I, I, P, I, I, I, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

@@ -437,6 +437,27 @@ int ctu_surface_metrics(const void* pred, int pred_dtype, int pred_onehot, const
                         int target_onehot, int N, int C, int cls0, int Cs, int D, int H, int W, const float* spacing,
                         const double* tau, double percentile, float* out, void* ws, void* stream);
 
+/* Connected components of label maps (no reference counterpart; definitions pinned in ctunet_amd/postprocess.py).
+ * in: DEVICE label map [N,D,H,W] of dtype CTU_U8 or CTU_I64.  A voxel is foreground if its label is nonzero and, when
+ * n_applied > 0, in the HOST list applied[n_applied] (1..16 distinct nonzero labels).  Two neighbours are connected iff
+ * both are foreground and carry the same label; connectivity 1 / 2 / 3 = 6 / 18 / 26 neighbours (scipy's rank), nothing
+ * across the border.  A component's root is its first voxel in C order.
+ *   label:  labels (DEVICE int32 [N,D,H,W], may be NULL) = 1 + rank of the component's root in C order per item, 0 for
+ *           background (scipy.ndimage.label's numbering); num: DEVICE int32 [N] = components per item.
+ *   filter: out (DEVICE, the input dtype, may alias in) = in, except foreground voxels of dropped components, which are 0.
+ *           mode CTU_CC_LARGEST: per (item, class) keep the param (1..8) largest components, ties to the earlier root;
+ *           the classes are the applied labels, or with n_applied = 0 the labels 1..255 (other labels are never dropped).
+ *           mode CTU_CC_MIN_SIZE: keep a component iff its voxel count >= param (>= 0).
+ * ws: ctu_components_ws_bytes() bytes (about 8 per voxel; 0 for invalid geometry).  Each item's D*H*W < 2^31, N <= 65535.
+ * Deterministic, no host sync, capture-safe. */
+#define CTU_CC_LARGEST 0
+#define CTU_CC_MIN_SIZE 1
+size_t ctu_components_ws_bytes(int N, int D, int H, int W);
+int ctu_label_components(const void* in, int dtype, int N, int D, int H, int W, int connectivity, const int64_t* applied,
+                         int n_applied, int32_t* labels, int32_t* num, void* ws, void* stream);
+int ctu_filter_components(const void* in, int dtype, int N, int D, int H, int W, int connectivity,
+                          const int64_t* applied, int n_applied, int mode, int param, void* out, void* ws, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
