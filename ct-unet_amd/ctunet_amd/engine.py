@@ -18,9 +18,8 @@ Data flow (DESIGN.md has the picture):
 """
 from __future__ import annotations
 
-import contextlib
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -50,8 +49,6 @@ LAZY_BN_LP = os.environ.get("CTUNET_LAZY_BN_LP", "0") != "0"
 # the launch that writes a BatchNorm's partial rows also finalizes them (its last block: ctu_bn_tail / ctu_bn_bwd_tail)
 # instead of a separate ctu_bn_finalize / ctu_bn_bwd_finalize launch (CTUNET_BN_TAIL=0: the separate launches)
 BN_TAIL = os.environ.get("CTUNET_BN_TAIL", "0") != "0"
-# the generic UNet's dead centre block (models.py:241) runs on a forked stream beside the decoder (CTUNET_CENTER_SIDE=0: in line)
-CENTER_SIDE = os.environ.get("CTUNET_CENTER_SIDE", "0") != "0"
 
 
 @dataclass
@@ -78,9 +75,21 @@ class NetPlan:
     skip: str = "cat"    # how a decoder level meets its encoder skip (models.py:247-253): "cat" | "add" | "none"
 
 
+@dataclass(slots=True)
 class _ConvRec:
     """What one conv+BN stage leaves behind for backward."""
-    __slots__ = ("x", "y", "vec", "stats", "nblk", "conv", "bn", "cin", "cout", "imap", "bias", "first")
+    x: Optional[CL]                    # the stage's activated input (None: not materialised -- first layer, fused up-convolution)
+    y: CL                              # its raw conv output
+    vec: torch.Tensor                  # [4, cp] scale, shift, mean, invstd of its BatchNorm
+    stats: Optional[torch.Tensor]
+    nblk: int
+    conv: str
+    bn: str
+    cin: int
+    cout: int
+    imap: Optional[torch.Tensor]
+    bias: bool
+    first: Optional[torch.Tensor] = None      # the NCDHW network input, when the direct C_in <= 2 kernels ran the stage
 
 
 class UNetEngine:
@@ -105,15 +114,16 @@ class UNetEngine:
         self._imaps: Dict[Tuple, torch.Tensor] = {}
         self._tail_words: Dict[str, torch.Tensor] = {}      # device -> int32 ticket counters, one per (layer, direction)
         self._tail_slots: Dict[Tuple[str, str], int] = {}
+        self._overflow: Dict[str, torch.Tensor] = {}        # device -> float32[1] overflow flag (overflow_flag)
+        self._gy_bufs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}     # per backward pass (_gy_like)
 
     # ------------------------------------------------------------------ small helpers
     def overflow_flag(self, device) -> torch.Tensor:
         """float32[1] on the device: 1 after a float16 backward whose (un-scaled) gradients contained inf / NaN, else 0.  One
         tensor per engine and device for its whole life (stable pointer: captured graphs and the optimizer keep it)."""
-        flags = self.__dict__.setdefault("_overflow", {})
-        f = flags.get(str(device))
+        f = self._overflow.get(str(device))
         if f is None:
-            f = flags[str(device)] = torch.zeros(1, dtype=torch.float32, device=device)
+            f = self._overflow[str(device)] = torch.zeros(1, dtype=torch.float32, device=device)
         return f
 
     def _counter(self, layer: str, direction: str, device) -> Optional[torch.Tensor]:
@@ -163,7 +173,7 @@ class UNetEngine:
         else:
             wp = hit[1] if hit is not None else torch.empty(ops.packed_floats(kind, w.shape[2], rin_p, nout_p, layout),
                                                             dtype=torch.float32, device=w.device)
-            ops.pack_batch([(kind, wd.contiguous(), wp, imap, rin_p, nout_p, mode, layout)])
+            ops.pack_batch([(kind, wd.contiguous(), wp, imap, rin_p, nout_p, mode, layout)], self.dtype)
         self._pack_cache[key] = (ver, wp, imap)
         return wp
 
@@ -186,10 +196,7 @@ class UNetEngine:
             if force or ent[0] != ver:
                 jobs.append((kind, w.detach().contiguous(), ent[1], ent[2], rin_p, nout_p, mode, layout))
                 self._pack_cache[key] = (ver, ent[1], ent[2])
-        if self.dtype != torch.float32:
-            ops.pack_batch_lp(jobs, self.dtype)
-        else:
-            ops.pack_batch(jobs)
+        ops.pack_batch(jobs, self.dtype)
 
     # ------------------------------------------------------------------ forward pieces
     def _fwd_tail(self, P, bn: str, c: int, nvox: int, n_upd: int, vec4: torch.Tensor, device):
@@ -199,6 +206,27 @@ class UNetEngine:
         return ops.make_bn_tail(c, nvox, P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"], P[bn + ".running_var"],
                                 BN_MOMENTUM, BN_EPS, n_upd, vec4, P.get(bn + ".num_batches_tracked") if n_upd else None,
                                 counter)
+
+    def _bn_stage(self, P, bn: str, out: CL, vec4: torch.Tensor, nvox: int, c: int, training: bool, n_upd: int, nblk: int,
+                  launch, tail_ok: bool = True) -> Tuple[CL, Optional[torch.Tensor]]:
+        """The BatchNorm half of a conv + BN stage, around the launch that writes the raw output ``out``.
+        Training: ``launch(stats, tail)`` fills the nblk partial rows of ``stats`` and -- given a tail (BN_TAIL, where the
+        kernel takes one: tail_ok) -- finalizes them into vec4 itself; otherwise a ctu_bn_finalize launch follows.
+        Eval: ``launch(None, None)``, then vec4's scale / shift from the running statistics.
+        Returns (out seen through the BatchNorm + ReLU, stats)."""
+        wb = (P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"], P[bn + ".running_var"])
+        if training:
+            stats = torch.empty((nblk, 2, out.cp), dtype=torch.float32, device=out.buf.device)
+            tail = self._fwd_tail(P, bn, c, nvox, n_upd, vec4, out.buf.device) if tail_ok else None
+            launch(stats, tail)
+            if tail is None:
+                ops.bn_finalize_into(stats, nblk, c, out.cp, nvox, *wb, BN_MOMENTUM, BN_EPS, n_upd, vec4,
+                                     P.get(bn + ".num_batches_tracked") if n_upd else None)
+        else:
+            stats = None
+            launch(None, None)
+            ops.bn_eval_affine_into(*wb, BN_EPS, c, out.cp, vec4)
+        return out.with_xf(vec4[0], vec4[1], True), stats
 
     def _conv_bn(self, P, x: CL, conv: str, bn: str, cin: int, cout: int, imap, out: CL, vec4: torch.Tensor,
                  training: bool, n_upd: int, save: bool) -> Tuple[CL, Optional[_ConvRec]]:
@@ -210,29 +238,10 @@ class UNetEngine:
             lay = 0                                  # (the 16-bit pair-layout kernel carries no bias)
         wp = self._packed(conv, w, "conv", imap, x.cp, out.cp, 0, lay)
         bias_p = None if bias is None else bias.detach()
-        dims = x.dims
-        c = cout
-        if training:
-            nblk = ops.conv_num_blocks(dims, out.cp, lay, k, self.dtype, x.cp)
-            stats = torch.empty((nblk, 2, out.cp), dtype=torch.float32, device=x.buf.device)
-            tail = self._fwd_tail(P, bn, c, x.nvox, n_upd, vec4, x.buf.device)
-            ops.conv3d_fwd(x, wp, bias_p, out, k, stats, (cin, cout), lay, tail)
-            if tail is None:
-                ops.bn_finalize_into(stats, nblk, c, out.cp, x.nvox, P[bn + ".weight"], P[bn + ".bias"],
-                                     P[bn + ".running_mean"], P[bn + ".running_var"], BN_MOMENTUM, BN_EPS, n_upd, vec4,
-                                     P.get(bn + ".num_batches_tracked") if n_upd else None)
-        else:
-            stats, nblk = None, 0
-            ops.conv3d_fwd(x, wp, bias_p, out, k, None, (cin, cout), lay)
-            ops.bn_eval_affine_into(P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
-                                    P[bn + ".running_var"], BN_EPS, c, out.cp, vec4)
-        y = out.with_xf(vec4[0], vec4[1], True)
-        rec = None
-        if save:
-            rec = _ConvRec()
-            rec.first = None
-            rec.x, rec.y, rec.vec, rec.stats, rec.nblk = x, out.raw(), vec4, stats, nblk
-            rec.conv, rec.bn, rec.cin, rec.cout, rec.imap, rec.bias = conv, bn, cin, cout, imap, bias is not None
+        nblk = ops.conv_num_blocks(x.dims, out.cp, lay, k, self.dtype, x.cp) if training else 0
+        y, stats = self._bn_stage(P, bn, out, vec4, x.nvox, cout, training, n_upd, nblk,
+                                  lambda stats, tail: ops.conv3d_fwd(x, wp, bias_p, out, k, stats, (cin, cout), lay, tail))
+        rec = _ConvRec(x, out.raw(), vec4, stats, nblk, conv, bn, cin, cout, imap, bias is not None) if save else None
         return y, rec
 
     def _fuse_up(self, x: CL, nout_p: int) -> bool:
@@ -263,34 +272,14 @@ class UNetEngine:
             self._up_cache[prefix] = (ver, wp, beff, (x.cp, out.cp, self.dtype), pws, wpd)
         else:
             wp, beff, wpd = hit[1], hit[2], hit[5]
-        nvox = 8 * x.nvox
-        if training:
-            nblk = ops.lp_upconv_fused_num_blocks(x.dims) if lp else ops.upconv_fused_num_blocks(x.dims, out.cp)
-            stats = torch.empty((nblk, 2, out.cp), dtype=torch.float32, device=x.buf.device)
-            tail = None if lp else self._fwd_tail(P, bn, cout, nvox, n_upd, vec4, x.buf.device)
-            if lp:
-                ops.lp_upconv_fused_fwd(x, wpd, beff, out, stats, (ct, cout))
-            else:
-                ops.upconv_fused_fwd(x, wp, beff, out, stats, (ct, cout), tail)
-            if tail is None:
-                ops.bn_finalize_into(stats, nblk, cout, out.cp, nvox, P[bn + ".weight"], P[bn + ".bias"],
-                                     P[bn + ".running_mean"], P[bn + ".running_var"], BN_MOMENTUM, BN_EPS, n_upd, vec4,
-                                     P.get(bn + ".num_batches_tracked") if n_upd else None)
+        if lp:                             # (the 16-bit fused kernel takes no BatchNorm tail: a ctu_bn_finalize launch follows)
+            nblk = ops.lp_upconv_fused_num_blocks(x.dims) if training else 0
+            launch = lambda stats, tail: ops.lp_upconv_fused_fwd(x, wpd, beff, out, stats, (ct, cout))
         else:
-            stats, nblk = None, 0
-            if lp:
-                ops.lp_upconv_fused_fwd(x, wpd, beff, out, None, (ct, cout))
-            else:
-                ops.upconv_fused_fwd(x, wp, beff, out, None, (ct, cout))
-            ops.bn_eval_affine_into(P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
-                                    P[bn + ".running_var"], BN_EPS, cout, out.cp, vec4)
-        y = out.with_xf(vec4[0], vec4[1], True)
-        rec = None
-        if save:
-            rec = _ConvRec()
-            rec.first = None
-            rec.x, rec.y, rec.vec, rec.stats, rec.nblk = None, out.raw(), vec4, stats, nblk
-            rec.conv, rec.bn, rec.cin, rec.cout, rec.imap, rec.bias = conv, bn, ct, cout, None, False
+            nblk = ops.upconv_fused_num_blocks(x.dims, out.cp) if training else 0
+            launch = lambda stats, tail: ops.upconv_fused_fwd(x, wp, beff, out, stats, (ct, cout), tail)
+        y, stats = self._bn_stage(P, bn, out, vec4, 8 * x.nvox, cout, training, n_upd, nblk, launch, tail_ok=not lp)
+        rec = _ConvRec(None, out.raw(), vec4, stats, nblk, conv, bn, ct, cout, None, False) if save else None
         return y, rec
 
     def _first_conv_bn(self, P, x: torch.Tensor, conv: str, bn: str, cin: int, cout: int, out: CL, vec4: torch.Tensor,
@@ -299,29 +288,10 @@ class UNetEngine:
         w = P[conv + ".weight"].detach()
         bias = P.get(conv + ".bias")
         bias_p = None if bias is None else bias.detach()
-        dims = out.dims
-        nvox = dims[0] * dims[1] * dims[2] * dims[3]
-        if training:
-            nblk = ops.conv_first_num_blocks(dims)
-            stats = torch.empty((nblk, 2, out.cp), dtype=torch.float32, device=x.device)
-            tail = self._fwd_tail(P, bn, cout, nvox, n_upd, vec4, x.device)
-            ops.conv_first_fwd(x, w, bias_p, out, stats, tail)
-            if tail is None:
-                ops.bn_finalize_into(stats, nblk, cout, out.cp, nvox, P[bn + ".weight"], P[bn + ".bias"],
-                                     P[bn + ".running_mean"], P[bn + ".running_var"], BN_MOMENTUM, BN_EPS, n_upd, vec4,
-                                     P.get(bn + ".num_batches_tracked") if n_upd else None)
-        else:
-            stats, nblk = None, 0
-            ops.conv_first_fwd(x, w, bias_p, out, None)
-            ops.bn_eval_affine_into(P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
-                                    P[bn + ".running_var"], BN_EPS, cout, out.cp, vec4)
-        y = out.with_xf(vec4[0], vec4[1], True)
-        rec = None
-        if save:
-            rec = _ConvRec()
-            rec.first = x
-            rec.x, rec.y, rec.vec, rec.stats, rec.nblk = None, out.raw(), vec4, stats, nblk
-            rec.conv, rec.bn, rec.cin, rec.cout, rec.imap, rec.bias = conv, bn, cin, cout, None, bias is not None
+        nblk = ops.conv_first_num_blocks(out.dims) if training else 0
+        y, stats = self._bn_stage(P, bn, out, vec4, out.nvox, cout, training, n_upd, nblk,
+                                  lambda stats, tail: ops.conv_first_fwd(x, w, bias_p, out, stats, tail))
+        rec = _ConvRec(None, out.raw(), vec4, stats, nblk, conv, bn, cin, cout, None, bias is not None, x) if save else None
         return y, rec
 
     def forward(self, P: Dict[str, torch.Tensor], x: torch.Tensor, training: bool, save: bool, chk: bool):
@@ -386,26 +356,18 @@ class UNetEngine:
         cb = plan.center
         cpc = pad8(cb.cout)
         center_out = None
-        side = None
         if plan.center_live or training:
             live = plan.center_live
             # The generic UNet drops the centre block's output (models.py:241): in train mode it runs only to move its
-            # BatchNorm buffers, two latency-bound 8^3 launches (~80 us) nothing downstream waits for -- on a forked
-            # stream beside the decoder, joined at the end of forward (inside a captured graph: a fork/join branch)
-            if not live and CENTER_SIDE:
-                side = self.__dict__.get("_side")
-                if side is None or side.device != dev:
-                    side = self.__dict__["_side"] = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                c1 = CL(torch.empty((n, dd, hh, ww, cpc), dtype=adt, device=dev), 0, cpc)
-                c2 = CL(torch.empty((n, dd, hh, ww, cpc), dtype=adt, device=dev), 0, cpc)
-                v1 = torch.empty((4, cpc), dtype=torch.float32, device=dev)
-                v2 = torch.empty((4, cpc), dtype=torch.float32, device=dev)
-                a1, r1 = self._conv_bn(P, cur, f"{cb.prefix}.{cb.first}", f"{cb.prefix}.{cb.first + 1}", cb.cin, cb.cout,
-                                       None, c1, v1, training, n_upd, save and live)
-                a2, r2 = self._conv_bn(P, a1, f"{cb.prefix}.{cb.first + 3}", f"{cb.prefix}.{cb.first + 4}", cb.cout, cb.cout,
-                                       None, c2, v2, training, n_upd, save and live)
+            # BatchNorm buffers, two latency-bound 8^3 launches (~80 us) nothing downstream waits for
+            c1 = CL(torch.empty((n, dd, hh, ww, cpc), dtype=adt, device=dev), 0, cpc)
+            c2 = CL(torch.empty((n, dd, hh, ww, cpc), dtype=adt, device=dev), 0, cpc)
+            v1 = torch.empty((4, cpc), dtype=torch.float32, device=dev)
+            v2 = torch.empty((4, cpc), dtype=torch.float32, device=dev)
+            a1, r1 = self._conv_bn(P, cur, f"{cb.prefix}.{cb.first}", f"{cb.prefix}.{cb.first + 1}", cb.cin, cb.cout,
+                                   None, c1, v1, training, n_upd, save and live)
+            a2, r2 = self._conv_bn(P, a1, f"{cb.prefix}.{cb.first + 3}", f"{cb.prefix}.{cb.first + 4}", cb.cout, cb.cout,
+                                   None, c2, v2, training, n_upd, save and live)
             if live:
                 recs[(cb.prefix, 1)], recs[(cb.prefix, 2)] = r1, r2
                 center_out = a2
@@ -454,8 +416,6 @@ class UNetEngine:
         wl, bl = P[plan.head + ".weight"], P[plan.head + ".bias"]
         w2 = wl.detach().reshape(wl.shape[0], wl.shape[1])
         out0, out1 = ops.head_fwd(cur, w2, bl.detach(), imap_h, plan.act, plan.head_mode)
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
         if save:
             ctx.update(recs=recs, x_cl=x_cl, cat=cat, xf=xf, pooled=pooled, dskip=dskip, dec_in=dec_in, ups=ups,
                        head_in=cur, imap_h=imap_h, center_out=center_out, dims=(n, d, h, w))
@@ -555,17 +515,21 @@ class UNetEngine:
             flag.zero_()
         grads: Dict[str, torch.Tensor] = {}
         emitted: set = set()
-        self._gy_bufs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._gy_bufs = {}
+
+        def unscale(tensors):
+            """Take the float16 loss scale out of finished gradients (one launch; sets the overflow flag on inf / NaN)."""
+            if dyn is not None:
+                ops.unscale_tensors(tensors, dyn.scale, flag)
+            elif gs != 1.0:
+                ops.scale_tensors(tensors, 1.0 / gs, flag)
 
         def emit():
             """Block boundary: the gradients produced since the last one are final -- un-scale them (float16 loss
             scaling) and hand them to the gradient exchange."""
             new = [(nm, g) for nm, g in grads.items() if nm not in emitted and g is not None]
             emitted.update(nm for nm, _ in new)
-            if dyn is not None and new:
-                ops.unscale_tensors([g for _, g in new], dyn.scale, flag)
-            elif gs != 1.0 and new:
-                ops.scale_tensors([g for _, g in new], 1.0 / gs, flag)
+            unscale([g for _, g in new])
             if sync is not None:
                 sync.push(new)
         k = plan.k
@@ -718,10 +682,7 @@ class UNetEngine:
                 self._conv_bn_bwd(P, r1, g_d1, None, grads, ws, part)
             emit()
         emit()
-        if dyn is not None and dx is not None:
-            ops.unscale_tensors([dx], dyn.scale, flag)
-        elif gs != 1.0 and dx is not None:
-            ops.scale_tensors([dx], 1.0 / gs, flag)
+        unscale([dx])
         if sync is not None:
             if flag is not None:
                 # N > 1: the overflow flag travels with the last gradient bucket, so that every rank skips the step when ANY

@@ -11,6 +11,7 @@ the slice, ``relu``): consumers see ``relu(raw * scale + shift)``.
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import gc
 import os
 
@@ -45,17 +46,32 @@ def _ptr(t: Optional[torch.Tensor], off_elems: int = 0):
 
 def _dual(code: int, name: str, *args) -> None:
     """ctu_<name>(args) for fp32 tensors, ctu_lp_<name>(dtype code, args) for 16-bit ones (same argument lists)."""
-    lib = _lib.load()
-    if code:
-        _lib.check(getattr(lib, "ctu_lp_" + name)(code, *args), "lp_" + name)
-    else:
-        _lib.check(getattr(lib, "ctu_" + name)(*args), name)
+    entries = _LP_ENTRIES if code else _ENTRIES
+    fn = entries.get(name)
+    if fn is None:
+        fn = entries[name] = getattr(_lib.load(), ("ctu_lp_" if code else "ctu_") + name)
+    status = fn(code, *args) if code else fn(*args)
+    if status:
+        _lib.check(status, ("lp_" if code else "") + name)
+
+
+# entry points _dual has resolved, by name (every launch of a step passes through it: one dict look-up per call)
+_ENTRIES: dict = {}
+_LP_ENTRIES: dict = {}
+
+
+def _query(code: int, name: str, *args):
+    """Value of ctu_<name>(args) / ctu_lp_<name>(args): the geometry queries (*_ws_floats, *_supported) take no dtype code."""
+    return getattr(_lib.load(), ("ctu_lp_" if code else "ctu_") + name)(*args)
 
 
 def _tail_arg(tail):
     """ctypes argument of an optional ctu_bn_tail / ctu_bn_bwd_tail."""
-    import ctypes
     return None if tail is None else ctypes.byref(tail)
+
+
+def _lp_name(code: int) -> str:
+    return "bf16" if code == 1 else "f16"
 
 
 def make_bn_tail(c: int, count, gamma, beta, rmean, rvar, momentum: float, eps: float, n_updates: int, vec4, nbt, counter):
@@ -73,11 +89,17 @@ def make_bn_tail(c: int, count, gamma, beta, rmean, rvar, momentum: float, eps: 
     return t
 
 
+def _replay_args(replay):
+    """(running_mean, running_var, momentum, eps, num_batches_tracked) of a replay= tuple as in bn_relu_bwd (None: no update)."""
+    rm, rv, mom, eps, nbt = (tuple(replay) + (None,))[:5] if replay is not None else (None, None, 0.0, 0.0, None)
+    assert nbt is None or (nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1)
+    return rm, rv, mom, eps, nbt
+
+
 def make_bn_bwd_tail(c: int, count, gamma, vec4, dgb, coef, replay, counter):
     """ctu_bn_bwd_tail (replaces the ctu_bn_bwd_finalize launch); replay as in bn_relu_bwd."""
     assert counter is None or (counter.dtype == torch.int32 and counter.is_cuda and counter.numel() == 1)
-    rm, rv, mom, eps, nbt = (tuple(replay) + (None,))[:5] if replay is not None else (None, None, 0.0, 0.0, None)
-    assert nbt is None or (nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1)
+    rm, rv, mom, eps, nbt = _replay_args(replay)
     t = _lib.BnBwdTail()
     t.gamma, t.invstd, t.mean = gamma.data_ptr(), vec4[3].data_ptr(), vec4[2].data_ptr()
     t.dgamma, t.dbeta, t.coef = dgb[0].data_ptr(), dgb[1].data_ptr(), coef.data_ptr()
@@ -86,6 +108,14 @@ def make_bn_bwd_tail(c: int, count, gamma, vec4, dgb, coef, replay, counter):
     t.counter = None if counter is None else counter.data_ptr()
     t.count, t.momentum, t.eps, t.C = float(count), mom, eps, c
     return t
+
+
+def _bn_bwd_outputs(c: int, cp: int, count, gamma, vec4, replay, counter, device, tail: bool = True):
+    """(ctu_bn_bwd_tail | None, (dgb [2, c], coef [5, cp])): what a BatchNorm backward finalize writes, freshly allocated,
+    and (tail=True) the struct that makes the launch writing the reduction rows finalize them into it."""
+    dgb = torch.empty((2, c), dtype=torch.float32, device=device)
+    coef = torch.empty((5, cp), dtype=torch.float32, device=device)
+    return (make_bn_bwd_tail(c, count, gamma, vec4, dgb, coef, replay, counter) if tail else None), (dgb, coef)
 
 
 def lp(t_or_dtype) -> int:
@@ -189,13 +219,22 @@ TIMER: Optional[KernelTimer] = None      # set by bench.py; None in normal opera
 FIRST_WGRAD_MFMA_MIN_VOX = int(os.environ.get("CTUNET_FIRST_WGRAD_MFMA_MIN_VOX", "4000000"))
 
 
-def _tile_tag(w: int) -> str:
-    return "4_4_16" if w >= 16 else ("4_8_8" if w >= 8 else "4_4_4")
+class _timed:
+    """``with _timed(record):`` around a launch site -- one TIMER record when TIMER is set, nothing otherwise.
+    record() -> (tag, algorithmic flops, algorithmic bytes, detail) of what the bracket encloses; it is called only when
+    timing, after the launch (so a ctu_*_kernel_name look-up or an f-string costs the normal path nothing)."""
+    __slots__ = ("record", "t0")
 
+    def __init__(self, record):
+        self.record = record
 
-def _nt(nout_p: int) -> int:
-    n16 = (nout_p + 15) // 16
-    return 1 if n16 == 1 else (2 if n16 == 2 else 4)
+    def __enter__(self):
+        self.t0 = TIMER.begin() if TIMER is not None else None
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.t0 is not None and exc_type is None:
+            tag, flops, nbytes, detail = self.record()
+            TIMER.end(tag, flops, nbytes, self.t0, detail)
 
 
 @dataclass
@@ -304,38 +343,25 @@ def packed_floats(kind: str, k: int, rin_p: int, nout_p: int, layout: int) -> in
         lib.ctu_convt_packed_floats(rin_p, nout_p)
 
 
-def pack_batch(jobs) -> None:
-    """jobs: list of (kind 'conv'|'convt', w, wp, cinv, rin_p, nout_p, mode, layout): every job in ONE launch."""
+def pack_batch(jobs, dtype: torch.dtype = torch.float32) -> None:
+    """jobs: list of (kind 'conv'|'convt', w, wp, cinv, rin_p, nout_p, mode, layout): every job in ONE launch.
+    dtype: element type of the packed copies wp (16-bit: the fragment-ordered copies of the fp32 masters)."""
     if not jobs:
         return
+    code = 0 if dtype == torch.float32 else LP_CODE[dtype]
     arr = (_lib.PackJob * len(jobs))()
     for a, (kind, w, wp, cinv, rin_p, nout_p, mode, layout) in zip(arr, jobs):
         _need_cuda(w, "weight")
-        assert w.is_contiguous()
+        assert w.is_contiguous() and (not code or wp.dtype == dtype)
         a.w, a.wp, a.cinv = w.data_ptr(), wp.data_ptr(), (None if cinv is None else cinv.data_ptr())
         if kind == "conv":
             a.kind, a.Co, a.Ci, a.k = 0, w.shape[0], w.shape[1], w.shape[2]
         else:
             a.kind, a.Ci, a.Co, a.k = 1, w.shape[0], w.shape[1], 2
+            if code:
+                layout = 0              # (the 16-bit transposed-conv copy has one layout)
         a.rin_p, a.nout_p, a.mode, a.layout = rin_p, nout_p, mode, layout
-    _lib.check(_lib.load().ctu_pack_batch(arr, len(jobs), _stream()), "pack_batch")
-
-
-def pack_batch_lp(jobs, dtype: torch.dtype) -> None:
-    """jobs as in pack_batch: every 16-bit weight copy in ONE launch."""
-    if not jobs:
-        return
-    arr = (_lib.PackJob * len(jobs))()
-    for a, (kind, w, wp, cinv, rin_p, nout_p, mode, layout) in zip(arr, jobs):
-        _need_cuda(w, "weight")
-        assert w.is_contiguous() and wp.dtype == dtype
-        a.w, a.wp, a.cinv = w.data_ptr(), wp.data_ptr(), (None if cinv is None else cinv.data_ptr())
-        if kind == "conv":
-            a.kind, a.Co, a.Ci, a.k = 0, w.shape[0], w.shape[1], w.shape[2]
-        else:
-            a.kind, a.Ci, a.Co, a.k = 1, w.shape[0], w.shape[1], 2
-        a.rin_p, a.nout_p, a.mode, a.layout = rin_p, nout_p, mode, (layout if kind == "conv" else 0)
-    _lib.check(_lib.load().ctu_lp_pack_batch(LP_CODE[dtype], arr, len(jobs), _stream()), "lp_pack_batch")
+    _dual(code, "pack_batch", arr, len(jobs), _stream())
 
 
 def conv_num_blocks(dims, nout_p: int, layout: int = 0, k: int = 3, dtype=torch.float32, rin_p: int = 32) -> int:
@@ -354,71 +380,63 @@ def conv3d_fwd(x: CL, wp: torch.Tensor, bias: Optional[torch.Tensor], out: CL, k
     tail: make_bn_tail(...) -- the launch finalizes the BatchNorm of its output itself."""
     n, d, h, w = x.dims
     assert out.dims == x.dims
-    lib = _lib.load()
-    if x.lp:
-        assert out.dtype == x.dtype and wp.dtype == x.dtype, (x.dtype, out.dtype, wp.dtype)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.check(lib.ctu_lp_conv3d_fwd(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(),
-                                         _ptr(bias), 0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp,
-                                         _ptr(stats), n, d, h, w, k, layout, _tail_arg(tail), _stream()), "lp_conv3d_fwd")
-        if t0 is not None:
-            ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
-            vox = n * d * h * w
-            name = lib.ctu_lp_conv3d_fwd_kernel_name(n, d, h, w, k, x.cp, out.cp, layout).decode()
-            TIMER.end(f"{name}<{'bf16' if x.lp == 1 else 'f16'}, {k}>", 2.0 * ci * co * k ** 3 * vox, 2.0 * vox * (ci + co), t0,
-                      (w, x.cp, out.cp))
-        return
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_conv3d_fwd(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(),
-                                  _ptr(bias), 0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp, _ptr(stats),
-                                  n, d, h, w, k, layout, _tail_arg(tail), _stream()), "conv3d_fwd")
-    if t0 is not None:
+    code = x.lp
+    assert not code or (out.dtype == x.dtype and wp.dtype == x.dtype), (x.dtype, out.dtype, wp.dtype)
+
+    def record():
         ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
         vox = n * d * h * w
-        TIMER.end(lib.ctu_conv3d_fwd_kernel_name(n, d, h, w, k, out.cp, layout).decode(), 2.0 * ci * co * k ** 3 * vox,
-                  4.0 * vox * (ci + co), t0, (w, x.cp, out.cp))
+        if code:
+            name = _lib.load().ctu_lp_conv3d_fwd_kernel_name(n, d, h, w, k, x.cp, out.cp, layout).decode()
+            tag = f"{name}<{_lp_name(code)}, {k}>"
+        else:
+            tag = _lib.load().ctu_conv3d_fwd_kernel_name(n, d, h, w, k, out.cp, layout).decode()
+        return tag, 2.0 * ci * co * k ** 3 * vox, (2.0 if code else 4.0) * vox * (ci + co), (w, x.cp, out.cp)
+    with _timed(record):
+        _dual(code, "conv3d_fwd", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(), _ptr(bias),
+              0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp, _ptr(stats), n, d, h, w, k, layout,
+              _tail_arg(tail), _stream())
+
+
+def _wgrad_setup(x: CL, g: CL, co: int, ci: int, k: int, ws: torch.Tensor):
+    """What conv3d_wgrad and conv3d_wgrad_bn share around their launch: the workspace check, dw and the timing bracket."""
+    n, d, h, w = x.dims
+    code = x.lp
+    assert not code or g.dtype == x.dtype
+    need = _query(code, "conv3d_wgrad_ws_floats", n, d, h, w, k, x.cp, g.cp)
+    assert ws.numel() >= need, (ws.numel(), need)
+    dw = torch.empty((co, ci, k, k, k), dtype=torch.float32, device=x.buf.device)
+
+    def record():
+        vox = n * d * h * w
+        if code:
+            name = _lib.load().ctu_lp_conv3d_wgrad_kernel_name(d, h, w, k, x.cp, g.cp).decode()
+            tag = f"{name}<{_lp_name(code)}, {k}> (+slab reduce)"
+        else:
+            tag = _lib.load().ctu_conv3d_wgrad_kernel_name(w, k, x.cp, g.cp).decode() + " (+slab reduce)"
+        return tag, 2.0 * ci * co * k ** 3 * vox, (2.0 if code else 4.0) * vox * (ci + co), (w, x.cp, g.cp)
+    return dw, _timed(record)
 
 
 def conv3d_wgrad(x: CL, g: CL, co: int, ci: int, k: int, cinv: Optional[torch.Tensor], ws: torch.Tensor,
                  want_bias: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     n, d, h, w = x.dims
-    lib = _lib.load()
-    if x.lp:
-        assert g.dtype == x.dtype
-        need = lib.ctu_lp_conv3d_wgrad_ws_floats(n, d, h, w, k, x.cp, g.cp)
-        assert ws.numel() >= need, (ws.numel(), need)
-        dw = torch.empty((co, ci, k, k, k), dtype=torch.float32, device=x.buf.device)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.check(lib.ctu_lp_conv3d_wgrad(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs,
-                                           g.cp, dw.data_ptr(), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, _stream()),
-                   "lp_conv3d_wgrad")
-        if t0 is not None:
-            vox = n * d * h * w
-            name = lib.ctu_lp_conv3d_wgrad_kernel_name(d, h, w, k, x.cp, g.cp).decode()
-            TIMER.end(f"{name}<{'bf16' if x.lp == 1 else 'f16'}, {k}> (+slab reduce)",
-                      2.0 * ci * co * k ** 3 * vox, 2.0 * vox * (ci + co), t0, (w, x.cp, g.cp))
-        return dw, (channel_sum(g, co) if want_bias else None)
-    need = lib.ctu_conv3d_wgrad_ws_floats(n, d, h, w, k, x.cp, g.cp)
-    assert ws.numel() >= need, (ws.numel(), need)
-    dw = torch.empty((co, ci, k, k, k), dtype=torch.float32, device=x.buf.device)
-    db = torch.empty(co, dtype=torch.float32, device=x.buf.device) if want_bias else None
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_conv3d_wgrad(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
-                                    dw.data_ptr(), _ptr(db), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k,
-                                    _stream()), "conv3d_wgrad")
-    if t0 is not None:
-        vox = n * d * h * w
-        TIMER.end(lib.ctu_conv3d_wgrad_kernel_name(w, k, x.cp, g.cp).decode() + " (+slab reduce)",
-                  2.0 * ci * co * k ** 3 * vox, 4.0 * vox * (ci + co), t0, (w, x.cp, g.cp))
+    code = x.lp
+    dw, timed = _wgrad_setup(x, g, co, ci, k, ws)
+    # the fp32 kernel's reduction writes the bias gradient too; the 16-bit one leaves it to a channel_sum launch
+    db = torch.empty(co, dtype=torch.float32, device=x.buf.device) if want_bias and not code else None
+    with timed:
+        _dual(code, "conv3d_wgrad", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
+              dw.data_ptr(), *(() if code else (_ptr(db),)), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, _stream())
+    if want_bias and code:
+        db = channel_sum(g, co)
     return dw, db
 
 
 def conv3d_wgrad_bn_supported(dims, k: int, cin_p: int, cout_p: int, dtype=torch.float32) -> bool:
     """Can conv3d_wgrad_bn take this layer (k = 3, full boxes [and channel tiles for fp32])?"""
     n, d, h, w = dims
-    if lp(dtype):
-        return bool(_lib.load().ctu_lp_conv3d_wgrad_bn_supported(n, d, h, w, k, cin_p, cout_p))
-    return bool(_lib.load().ctu_conv3d_wgrad_bn_supported(n, d, h, w, k, cin_p, cout_p))
+    return bool(_query(lp(dtype), "conv3d_wgrad_bn_supported", n, d, h, w, k, cin_p, cout_p))
 
 
 def conv3d_wgrad_bn(x: CL, ga: CL, y: CL, vec: torch.Tensor, coef: torch.Tensor, gy: CL, co: int, ci: int, k: int,
@@ -427,44 +445,19 @@ def conv3d_wgrad_bn(x: CL, ga: CL, y: CL, vec: torch.Tensor, coef: torch.Tensor,
     the raw conv output, vec = its [4, cp] BatchNorm vectors, coef = bn_relu_bwd(lazy=True)'s rows; gy (same buffer shape
     and channel offset as ga) receives the raw-output gradient for the data-gradient kernel."""
     n, d, h, w = x.dims
-    lib = _lib.load()
     assert ga.dims == x.dims and y.dims == x.dims and gy.dims == x.dims and ga.dtype == x.dtype == y.dtype == gy.dtype
     assert y.cs == ga.cs == gy.cs and y.cp == ga.cp == gy.cp and gy.buf.data_ptr() != ga.buf.data_ptr()
-    if x.lp:
-        need = lib.ctu_lp_conv3d_wgrad_ws_floats(n, d, h, w, k, x.cp, ga.cp)
-        assert ws.numel() >= need, (ws.numel(), need)
-        dw = torch.empty((co, ci, k, k, k), dtype=torch.float32, device=x.buf.device)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.check(lib.ctu_lp_conv3d_wgrad_bn(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), ga.ptr, ga.cs,
-                                              ga.cp, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
-                                              dw.data_ptr(), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, _stream()),
-                   "lp_conv3d_wgrad_bn")
-        if t0 is not None:
-            vox = n * d * h * w
-            name = lib.ctu_lp_conv3d_wgrad_kernel_name(d, h, w, k, x.cp, ga.cp).decode()
-            TIMER.end(f"{name}<{'bf16' if x.lp == 1 else 'f16'}, {k}> (+slab reduce)",
-                      2.0 * ci * co * k ** 3 * vox, 2.0 * vox * (ci + co), t0, (w, x.cp, ga.cp))
-        return dw
-    need = lib.ctu_conv3d_wgrad_ws_floats(n, d, h, w, k, x.cp, ga.cp)
-    assert ws.numel() >= need, (ws.numel(), need)
-    dw = torch.empty((co, ci, k, k, k), dtype=torch.float32, device=x.buf.device)
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_conv3d_wgrad_bn(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), ga.ptr, ga.cs, ga.cp,
-                                       y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
-                                       dw.data_ptr(), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, _stream()),
-               "conv3d_wgrad_bn")
-    if t0 is not None:
-        vox = n * d * h * w
-        TIMER.end(lib.ctu_conv3d_wgrad_kernel_name(w, k, x.cp, ga.cp).decode() + " (+slab reduce)",
-                  2.0 * ci * co * k ** 3 * vox, 4.0 * vox * (ci + co), t0, (w, x.cp, ga.cp))
+    dw, timed = _wgrad_setup(x, ga, co, ci, k, ws)
+    with timed:
+        _dual(x.lp, "conv3d_wgrad_bn", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), ga.ptr, ga.cs, ga.cp,
+              y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ci, _ptr(cinv),
+              ws.data_ptr(), n, d, h, w, k, _stream())
     return dw
 
 
 def conv3d_wgrad_ws(dims, k, cin_p, cout_p, dtype=torch.float32) -> int:
     n, d, h, w = dims
-    if lp(dtype):
-        return _lib.load().ctu_lp_conv3d_wgrad_ws_floats(n, d, h, w, k, cin_p, cout_p)
-    return _lib.load().ctu_conv3d_wgrad_ws_floats(n, d, h, w, k, cin_p, cout_p)
+    return _query(lp(dtype), "conv3d_wgrad_ws_floats", n, d, h, w, k, cin_p, cout_p)
 
 
 def pack_conv_w_lp(w: torch.Tensor, cinv: Optional[torch.Tensor], rin_p: int, nout_p: int, mode: int, dtype: torch.dtype,
@@ -497,13 +490,10 @@ def conv_first_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
     """x: NCDHW float32 on the GPU (read in place); w: torch Conv3d weight [Co, cin, 3, 3, 3]."""
     _need_cuda(x, "input")
     n, cin, d, h, w_ = x.shape
-    lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
-    _dual(out.lp, "conv3d_first_fwd", x.data_ptr(), cin, w.data_ptr(), _ptr(bias), 0 if bias is None else bias.numel(),
-          out.ptr, out.cs, w.shape[0], _ptr(stats), n, d, h, w_, _tail_arg(tail), _stream())
-    if t0 is not None:
-        vox = n * d * h * w_
-        TIMER.end(f"first_fwd_kernel<{cin}>", 2.0 * cin * w.shape[0] * 27 * vox, 4.0 * vox * (cin + w.shape[0]), t0)
+    vox = n * d * h * w_
+    with _timed(lambda: (f"first_fwd_kernel<{cin}>", 2.0 * cin * w.shape[0] * 27 * vox, 4.0 * vox * (cin + w.shape[0]), None)):
+        _dual(out.lp, "conv3d_first_fwd", x.data_ptr(), cin, w.data_ptr(), _ptr(bias), 0 if bias is None else bias.numel(),
+              out.ptr, out.cs, w.shape[0], _ptr(stats), n, d, h, w_, _tail_arg(tail), _stream())
 
 
 def conv_first_bwd_data(g: CL, w: torch.Tensor, cin: int) -> torch.Tensor:
@@ -513,18 +503,19 @@ def conv_first_bwd_data(g: CL, w: torch.Tensor, cin: int) -> torch.Tensor:
     n, d, h, w_ = g.dims
     dx = torch.empty((n, cin, d, h, w_), dtype=torch.float32, device=g.buf.device)
     lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
     pair = bool(g.lp and g.cp == 8 and lib.ctu_lp_conv3d_first_bwd_data_pair_supported(cin, w_))
-    if pair:
-        wp = pack_conv_w_lp(w, None, 8, 8, 1, g.dtype, None, 1)
-        _lib.check(lib.ctu_lp_conv3d_first_bwd_data_pair(g.lp, g.ptr, g.cs, wp.data_ptr(), cin, dx.data_ptr(), n, d, h, w_,
-                                                         _stream()), "lp_conv3d_first_bwd_data_pair")
-    else:
-        _dual(g.lp, "conv3d_first_bwd_data", g.ptr, g.cs, w.data_ptr(), cin, w.shape[0], dx.data_ptr(), n, d, h, w_, _stream())
-    if t0 is not None:
+
+    def record():
+        tag = f"lp_conv_fwd_pair_kernel<{_lp_name(g.lp)}, dx of the first layer>" if pair else f"first_bwd_data_kernel<{cin}>"
         vox = n * d * h * w_
-        tag = f"lp_conv_fwd_pair_kernel<{'bf16' if g.lp == 1 else 'f16'}, dx of the first layer>" if pair else f"first_bwd_data_kernel<{cin}>"
-        TIMER.end(tag, 2.0 * cin * w.shape[0] * 27 * vox, (2.0 * w.shape[0] if g.lp else 4.0 * w.shape[0]) * vox + 4.0 * vox * cin, t0)
+        return tag, 2.0 * cin * w.shape[0] * 27 * vox, (2.0 * w.shape[0] if g.lp else 4.0 * w.shape[0]) * vox + 4.0 * vox * cin, None
+    with _timed(record):
+        if pair:                                     # (the bracket takes the small pack launch with the pair kernel)
+            wp = pack_conv_w_lp(w, None, 8, 8, 1, g.dtype, None, 1)
+            _lib.check(lib.ctu_lp_conv3d_first_bwd_data_pair(g.lp, g.ptr, g.cs, wp.data_ptr(), cin, dx.data_ptr(), n, d, h, w_,
+                                                             _stream()), "lp_conv3d_first_bwd_data_pair")
+        else:
+            _dual(g.lp, "conv3d_first_bwd_data", g.ptr, g.cs, w.data_ptr(), cin, w.shape[0], dx.data_ptr(), n, d, h, w_, _stream())
     return dx
 
 
@@ -541,12 +532,13 @@ def conv_first_wgrad(x: torch.Tensor, g: CL, co: int, ws: torch.Tensor) -> torch
         return conv3d_wgrad(x8, g, co, cin, 3, None, ws if ws.numel() >= need else torch.empty(need, device=x.device), False)[0]
     assert ws.numel() >= lib.ctu_conv3d_first_wgrad_ws_floats(n, d, h, w_, cin)
     dw = torch.empty((co, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    t0 = TIMER.begin() if TIMER is not None else None
-    _dual(g.lp, "conv3d_first_wgrad", x.data_ptr(), cin, g.ptr, g.cs, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream())
-    if t0 is not None:
-        vox = n * d * h * w_
-        TIMER.end(f"first_wgrad_kernel<{cin}> (+slab reduce)", 2.0 * cin * co * 27 * vox, 4.0 * vox * (cin + co), t0)
+    with _timed_first_wgrad(cin, co, n * d * h * w_):
+        _dual(g.lp, "conv3d_first_wgrad", x.data_ptr(), cin, g.ptr, g.cs, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream())
     return dw
+
+
+def _timed_first_wgrad(cin: int, co: int, vox: int) -> _timed:
+    return _timed(lambda: (f"first_wgrad_kernel<{cin}> (+slab reduce)", 2.0 * cin * co * 27 * vox, 4.0 * vox * (cin + co), None))
 
 
 def conv_first_wgrad_bn(x: torch.Tensor, ga: CL, y: CL, vec: torch.Tensor, coef: torch.Tensor, gy: CL, co: int,
@@ -557,13 +549,10 @@ def conv_first_wgrad_bn(x: torch.Tensor, ga: CL, y: CL, vec: torch.Tensor, coef:
     assert not ga.lp and y.cs == ga.cs == gy.cs and ga.cp == 8 and gy.buf.data_ptr() != ga.buf.data_ptr()
     assert ws.numel() >= lib.ctu_conv3d_first_wgrad_ws_floats(n, d, h, w_, cin)
     dw = torch.empty((co, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_conv3d_first_wgrad_bn(x.data_ptr(), cin, ga.ptr, ga.cs, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(),
-                                             coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream()),
-               "conv3d_first_wgrad_bn")
-    if t0 is not None:
-        vox = n * d * h * w_
-        TIMER.end(f"first_wgrad_kernel<{cin}> (+slab reduce)", 2.0 * cin * co * 27 * vox, 4.0 * vox * (cin + co), t0)
+    with _timed_first_wgrad(cin, co, n * d * h * w_):
+        _lib.check(lib.ctu_conv3d_first_wgrad_bn(x.data_ptr(), cin, ga.ptr, ga.cs, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(),
+                                                 coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream()),
+                   "conv3d_first_wgrad_bn")
     return dw
 
 
@@ -625,16 +614,14 @@ def bn_relu_bwd(y: CL, ga: CL, vec: torch.Tensor, gamma: torch.Tensor, c: int, p
         return dgb[0], dgb[1]
     nb = lib.ctu_bn_bwd_num_blocks(nvox) if pre_reduced is None else pre_reduced
     assert partials.numel() >= nb * 2 * cp
-    dgb = torch.empty((2, c), dtype=torch.float32, device=y.buf.device)
-    coef = torch.empty((5, cp), dtype=torch.float32, device=y.buf.device)
-    tail = make_bn_bwd_tail(c, nvox, gamma, vec, dgb, coef, replay, counter) if (counter is not None and pre_reduced is None) else None
+    tail, (dgb, coef) = _bn_bwd_outputs(c, cp, nvox, gamma, vec, replay, counter, y.buf.device,
+                                        tail=counter is not None and pre_reduced is None)
     if pre_reduced is None:       # (else: the kernel that produced ga wrote the nb reduction rows, maxpool_bwd(bn=...))
         assert ga.dtype == y.dtype
         _dual(y.lp, "bn_relu_bwd_reduce", y.ptr, y.cs, ga.ptr, ga.cs, cp, sc, sh, mu, istd, nvox, partials.data_ptr(),
               _tail_arg(tail), st)
     if tail is None:
-        rm, rv, mom, eps, nbt = (tuple(replay) + (None,))[:5] if replay is not None else (None, None, 0.0, 0.0, None)
-        assert nbt is None or (nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1)
+        rm, rv, mom, eps, nbt = _replay_args(replay)
         _lib.check(lib.ctu_bn_bwd_finalize(partials.data_ptr(), nb, c, cp, float(nvox), gamma.data_ptr(), istd,
                                            dgb[0].data_ptr(), dgb[1].data_ptr(), coef.data_ptr(), mu, _ptr(rm), _ptr(rv),
                                            mom, eps, None if nbt is None else nbt.data_ptr(), st), "bn_bwd_finalize")
@@ -651,7 +638,6 @@ def bn_bwd_partials_floats(nvox: int, cp: int) -> int:
 # ---------------------------------------------------------------------------- pool
 def maxpool_fwd(x: CL, out: CL) -> None:
     n, d, h, w = x.dims
-    lib = _lib.load()
     assert out.dtype == x.dtype
     _dual(x.lp, "maxpool2_fwd", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), out.ptr, out.cs, n, d, h, w,
           _stream())
@@ -668,18 +654,15 @@ def maxpool_bwd(x: CL, gout: CL, gin: CL, accumulate: bool, bn=None, fin=None):
     fin = (gamma, c, replay, counter) with bn: the launch also finalizes that reduction (ctu_bn_bwd_tail); returns
     (rows, (dgb, coef)) -- pass the pair to bn_relu_bwd(finalized=...)."""
     n, d, h, w = x.dims
-    lib = _lib.load()
     if bn is not None:
         vec, partials = bn
-        nb = lib.ctu_maxpool2_bwd_bn_num_blocks(n, d, h, w, x.cp)
+        nb = maxpool_bwd_bn_blocks(x.dims, x.cp)
         assert x.scale is not None and x.relu and partials.numel() >= nb * 2 * x.cp
         assert vec[0].data_ptr() == x.scale.data_ptr() and vec[1].data_ptr() == x.shift.data_ptr()
         tail, done = None, None
         if fin is not None:
             gamma, c, replay, counter = fin
-            dgb = torch.empty((2, c), dtype=torch.float32, device=x.buf.device)
-            coef = torch.empty((5, x.cp), dtype=torch.float32, device=x.buf.device)
-            tail, done = make_bn_bwd_tail(c, x.nvox, gamma, vec, dgb, coef, replay, counter), (dgb, coef)
+            tail, done = _bn_bwd_outputs(c, x.cp, x.nvox, gamma, vec, replay, counter, x.buf.device)
         _dual(x.lp, "maxpool2_bwd_bn", x.ptr, x.cs, x.cp, vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
               vec[3].data_ptr(), gout.ptr, gout.cs, gin.ptr, gin.cs, int(accumulate), n, d, h, w, partials.data_ptr(),
               _tail_arg(tail), _stream())
@@ -713,83 +696,48 @@ def pack_convt_w_lp(w: torch.Tensor, cinv, rin_p: int, nout_p: int, mode: int, d
     return wp
 
 
-def _timed_convt(tag: str, x_cp: int, o_cp: int, vox: int, w: int, elem: int):
-    """Context for the ConvTranspose launches of the stage table: algorithmic 2*8*C*C FLOP and (C + 8C) elements per coarse voxel."""
-    class _T:
-        def __enter__(self_):
-            self_.t0 = TIMER.begin() if TIMER is not None else None
-        def __exit__(self_, *exc):
-            if self_.t0 is not None and exc[0] is None:
-                TIMER.end(tag, 16.0 * x_cp * o_cp * vox, float(elem) * vox * (x_cp + 8 * o_cp), self_.t0, (w, x_cp, o_cp))
-    return _T()
+def _convt_bracket(name: str, x: CL, x_cp: int, o_cp: int, dims) -> _timed:
+    """Bracket of the ConvTranspose launches of the stage table: algorithmic 2*8*C*C FLOP and (C + 8C) elements per coarse voxel."""
+    n, d, h, w = dims
+    vox = n * d * h * w
+    return _timed(lambda: (name + ("_lp" if x.lp else ""), 16.0 * x_cp * o_cp * vox,
+                           float(x.buf.element_size()) * vox * (x_cp + 8 * o_cp), (w, x_cp, o_cp)))
 
 
 def convt_fwd(x: CL, wp: torch.Tensor, bias: Optional[torch.Tensor], out: CL) -> None:
     n, d, h, w = x.dims
-    lib = _lib.load()
-    with _timed_convt("convt2_fwd" + ("_lp" if x.lp else ""), x.cp, out.cp, n * d * h * w, w, x.buf.element_size()):
-        _convt_fwd(x, wp, bias, out, lib, n, d, h, w)
-
-
-def _convt_fwd(x, wp, bias, out, lib, n, d, h, w) -> None:
-    if x.lp:
-        assert out.dtype == x.dtype and wp.dtype == x.dtype
-        _lib.check(lib.ctu_lp_convt2_fwd(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(),
-                                         _ptr(bias), 0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp, n, d, h, w,
-                                         _stream()), "lp_convt2_fwd")
-        return
-    _lib.check(lib.ctu_convt2_fwd(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(),
-                                  _ptr(bias), 0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp, n, d, h, w,
-                                  _stream()), "convt2_fwd")
+    with _convt_bracket("convt2_fwd", x, x.cp, out.cp, x.dims):
+        assert not x.lp or (out.dtype == x.dtype and wp.dtype == x.dtype)
+        _dual(x.lp, "convt2_fwd", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(), _ptr(bias),
+              0 if bias is None else bias.numel(), out.ptr, out.cs, out.cp, n, d, h, w, _stream())
 
 
 def convt_bwd_data(gout: CL, wp: torch.Tensor, gin: CL) -> None:
     n, d, h, w = gin.dims
-    lib = _lib.load()
-    with _timed_convt("convt2_bwd_data" + ("_lp" if gout.lp else ""), gin.cp, gout.cp, n * d * h * w, w, gout.buf.element_size()):
-        _convt_bwd_data(gout, wp, gin, lib, n, d, h, w)
-
-
-def _convt_bwd_data(gout, wp, gin, lib, n, d, h, w) -> None:
-    if gout.lp:
-        assert gin.dtype == gout.dtype and wp.dtype == gout.dtype
-        _lib.check(lib.ctu_lp_convt2_bwd_data(gout.lp, gout.ptr, gout.cs, gout.cp, wp.data_ptr(), gin.ptr, gin.cs, gin.cp, n, d,
-                                              h, w, _stream()), "lp_convt2_bwd_data")
-        return
-    _lib.check(lib.ctu_convt2_bwd_data(gout.ptr, gout.cs, gout.cp, wp.data_ptr(), gin.ptr, gin.cs, gin.cp, n, d, h, w,
-                                       _stream()), "convt2_bwd_data")
+    with _convt_bracket("convt2_bwd_data", gout, gin.cp, gout.cp, gin.dims):
+        assert not gout.lp or (gin.dtype == gout.dtype and wp.dtype == gout.dtype)
+        _dual(gout.lp, "convt2_bwd_data", gout.ptr, gout.cs, gout.cp, wp.data_ptr(), gin.ptr, gin.cs, gin.cp, n, d, h, w,
+              _stream())
 
 
 def convt_wgrad(x: CL, g: CL, ci: int, co: int, imap, ws: torch.Tensor):
     n, d, h, w = x.dims
-    lib = _lib.load()
-    with _timed_convt("convt2_wgrad" + ("_lp" if x.lp else ""), x.cp, g.cp, n * d * h * w, w, x.buf.element_size()):
-        return _convt_wgrad(x, g, ci, co, imap, ws, lib, n, d, h, w)
-
-
-def _convt_wgrad(x, g, ci, co, imap, ws, lib, n, d, h, w):
-    if x.lp:
-        assert g.dtype == x.dtype
-        assert ws.numel() >= lib.ctu_lp_convt2_wgrad_ws_floats(n, d, h, w, x.cp, g.cp)
+    with _convt_bracket("convt2_wgrad", x, x.cp, g.cp, x.dims):
+        assert not x.lp or g.dtype == x.dtype
+        assert ws.numel() >= convt_wgrad_ws(x.dims, x.cp, g.cp, x.dtype)
         dw = torch.empty((ci, co, 2, 2, 2), dtype=torch.float32, device=x.buf.device)
-        _lib.check(lib.ctu_lp_convt2_wgrad(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs,
-                                           g.cp, dw.data_ptr(), ci, co, _ptr(imap), ws.data_ptr(), n, d, h, w, _stream()),
-                   "lp_convt2_wgrad")
-        return dw, channel_sum(g, co)
-    assert ws.numel() >= lib.ctu_convt2_wgrad_ws_floats(n, d, h, w, x.cp, g.cp)
-    dw = torch.empty((ci, co, 2, 2, 2), dtype=torch.float32, device=x.buf.device)
-    db = torch.empty(co, dtype=torch.float32, device=x.buf.device)
-    _lib.check(lib.ctu_convt2_wgrad(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
-                                    dw.data_ptr(), db.data_ptr(), ci, co, _ptr(imap), ws.data_ptr(), n, d, h, w,
-                                    _stream()), "convt2_wgrad")
+        # the fp32 kernel's reduction writes the bias gradient too; the 16-bit one leaves it to a channel_sum launch
+        db = None if x.lp else torch.empty(co, dtype=torch.float32, device=x.buf.device)
+        _dual(x.lp, "convt2_wgrad", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
+              dw.data_ptr(), *(() if x.lp else (db.data_ptr(),)), ci, co, _ptr(imap), ws.data_ptr(), n, d, h, w, _stream())
+        if x.lp:
+            db = channel_sum(g, co)
     return dw, db
 
 
 def convt_wgrad_ws(dims, cin_p, cout_p, dtype=torch.float32) -> int:
     n, d, h, w = dims
-    if lp(dtype):
-        return _lib.load().ctu_lp_convt2_wgrad_ws_floats(n, d, h, w, cin_p, cout_p)
-    return _lib.load().ctu_convt2_wgrad_ws_floats(n, d, h, w, cin_p, cout_p)
+    return _query(lp(dtype), "convt2_wgrad_ws_floats", n, d, h, w, cin_p, cout_p)
 
 
 # ---------------------------------------------------------------------------- head
@@ -798,7 +746,6 @@ def head_fwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
     co, ci = w.shape[0], w.shape[1]
     v = d * h * w_
     dev = x.buf.device
-    lib = _lib.load()
     if head_mode == 0:
         out0 = torch.empty((n, co, d, h, w_), dtype=torch.float32, device=dev)
         out1 = None
@@ -821,15 +768,6 @@ def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
     assert gscale == 1.0 or x.lp, "gscale is the 16-bit path's loss scale"
     assert gscale_dev is None or (x.lp and gscale_dev.is_cuda and gscale_dev.dtype == torch.float32), \
         "gscale_dev is the 16-bit path's device loss scale"
-
-    def call(*args):                                    # (the 16-bit entry carries gscale in front of the stream)
-        if gscale_dev is not None:
-            _lib.check(_lib.load().ctu_lp_head_bwd_bn_dscale(x.lp, *args[:-1], gscale_dev.data_ptr(), args[-1]),
-                       "lp_head_bwd_bn_dscale")
-        elif x.lp:
-            _lib.check(_lib.load().ctu_lp_head_bwd_bn(x.lp, *args[:-1], float(gscale), args[-1]), "lp_head_bwd_bn")
-        else:
-            _lib.check(_lib.load().ctu_head_bwd_bn(*args), "head_bwd_bn")
     n, d, h, w_ = x.dims
     co, ci = w.shape[0], w.shape[1]
     v = d * h * w_
@@ -838,25 +776,26 @@ def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
     ws = torch.empty(lib.ctu_head_bwd_ws_floats(n, v, x.cp, co), dtype=torch.float32, device=dev)
     dw = torch.empty_like(w)
     db = torch.empty_like(b)
+    bn_args, tail, done = (None, None, 0, None), None, None
     if bn is not None:
         vec, partials = bn
         bn_cp = vec.shape[1]
         rows = lib.ctu_head_bwd_num_blocks(n, v)
         assert x.scale is not None and x.relu and vec[0].data_ptr() == x.scale.data_ptr() and partials.numel() >= rows * 2 * bn_cp
-        tail, done = None, None
+        bn_args = (vec[2].data_ptr(), vec[3].data_ptr(), bn_cp, partials.data_ptr())
         if fin is not None:
             gamma, c, replay = fin[:3]
-            dgb = torch.empty((2, c), dtype=torch.float32, device=dev)
-            coef = torch.empty((5, bn_cp), dtype=torch.float32, device=dev)
-            tail, done = make_bn_bwd_tail(c, n * v, gamma, vec, dgb, coef, replay, None), (dgb, coef)
-        call(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(),
-             _ptr(imap), ci, co, act, head_mode, g0.data_ptr(), _ptr(g1), gin.ptr, gin.cs, dw.data_ptr(), db.data_ptr(),
-              ws.data_ptr(), n, v, vec[2].data_ptr(), vec[3].data_ptr(), bn_cp, partials.data_ptr(), _tail_arg(tail), _stream())
-        return (dw, db, rows) if fin is None else (dw, db, rows, done)
-    call(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(),
-          _ptr(imap), ci, co, act, head_mode, g0.data_ptr(), _ptr(g1), gin.ptr, gin.cs, dw.data_ptr(), db.data_ptr(),
-          ws.data_ptr(), n, v, None, None, 0, None, None, _stream())
-    return dw, db
+            tail, done = _bn_bwd_outputs(c, bn_cp, n * v, gamma, vec, replay, None, dev)
+    # the 16-bit entries carry the loss scale in front of the stream: a float, or (_dscale) a pointer to the device scale
+    entry, scale = "head_bwd_bn", ((float(gscale),) if x.lp else ())
+    if gscale_dev is not None:
+        entry, scale = "head_bwd_bn_dscale", (gscale_dev.data_ptr(),)
+    _dual(x.lp, entry, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(), _ptr(imap),
+          ci, co, act, head_mode, g0.data_ptr(), _ptr(g1), gin.ptr, gin.cs, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, v,
+          *bn_args, _tail_arg(tail), *scale, _stream())
+    if bn is None:
+        return dw, db
+    return (dw, db, rows) if fin is None else (dw, db, rows, done)
 
 
 def head_bwd_blocks(dims) -> int:
@@ -951,18 +890,14 @@ def upconv_fused_fwd(x: CL, wp: torch.Tensor, beff: torch.Tensor, out: CL, stats
     """out (fine grid, raw) = conv3(convT(act(x))) in one kernel; x is the COARSE input."""
     n, d, h, w = x.dims
     assert out.dims == (n, 2 * d, 2 * h, 2 * w)
-    lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_upconv_fused_fwd(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp.data_ptr(),
-                                        beff.data_ptr(), out.ptr, out.cs, out.cp, _ptr(stats), n, d, h, w, _tail_arg(tail),
-                                        _stream()),
-               "upconv_fused_fwd")
-    if t0 is not None:
-        ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
-        vox = n * d * h * w
-        # algorithmic work of the two layers it replaces: convT 2*ci*ci*8 per coarse voxel + conv 2*27*ci*co per fine voxel
-        TIMER.end(f"upconv_fused_fwd_kernel<{out.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co), 4.0 * vox * (ci + 8 * co),
-                  t0, (w, x.cp, out.cp))
+    ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
+    vox = n * d * h * w
+    # algorithmic work of the two layers it replaces: convT 2*ci*ci*8 per coarse voxel + conv 2*27*ci*co per fine voxel
+    with _timed(lambda: (f"upconv_fused_fwd_kernel<{out.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
+                         4.0 * vox * (ci + 8 * co), (w, x.cp, out.cp))):
+        _lib.check(_lib.load().ctu_upconv_fused_fwd(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu),
+                                                    wp.data_ptr(), beff.data_ptr(), out.ptr, out.cs, out.cp, _ptr(stats),
+                                                    n, d, h, w, _tail_arg(tail), _stream()), "upconv_fused_fwd")
 
 
 def upconv_fused_wgrad_bn_supported(dims, cin_p: int, nout_p: int, dtype=torch.float32) -> bool:
@@ -978,35 +913,42 @@ def upconv_fused_wgrad(x: CL, g: CL, c: int, co: int, bt: torch.Tensor, pack_ws:
     the weight-gradient kernel stages it and the raw-output gradient lands in gy (read by the projections here and by
     upconv_fused_bwd_data afterwards) -- see conv3d_wgrad_bn."""
     n, d, h, w = x.dims
-    assert g.dims == (n, 2 * d, 2 * h, 2 * w)
-    lib = _lib.load()
+    assert g.dims == (n, 2 * d, 2 * h, 2 * w) and not x.lp
+    return _upconv_wgrad(x, g, c, co, bt, pack_ws, imap, lazy,
+                         lambda: (f"upconv_fused_wgrad_kernel<{g.cp}> (+slab reduce)", 4.0 * (n * d * h * w) * (c + 8 * co)))
+
+
+def _upconv_wgrad(x: CL, g: CL, c: int, co: int, bt, pack_ws, imap, lazy, tag_bytes):
+    """Body of upconv_fused_wgrad / lp_upconv_fused_wgrad: composite-weight gradient (with the lazy BatchNorm backward or
+    without), then its projection onto the two layers' parameters.  The 16-bit weight-gradient entries carry no g.cp (it is 8).
+    tag_bytes() -> (tag, algorithmic bytes) of the timer record."""
+    n, d, h, w = x.dims
     dev = x.buf.device
+    gcp = () if x.lp else (g.cp,)
     dweff = torch.empty((8, 8, x.cp, g.cp), dtype=torch.float32, device=dev)
-    ws = torch.empty(lib.ctu_upconv_fused_wgrad_ws_floats(n, d, h, w, x.cp, g.cp), dtype=torch.float32, device=dev)
-    t0 = TIMER.begin() if TIMER is not None else None
-    if lazy is not None:
-        y, vec, coef, gy = lazy
-        assert y.dims == g.dims and gy.dims == g.dims and y.cs == g.cs == gy.cs and y.cp == g.cp == gy.cp
-        assert gy.buf.data_ptr() != g.buf.data_ptr()
-        _lib.check(lib.ctu_upconv_fused_wgrad_bn(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs,
-                                                 g.cp, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
-                                                 dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream()),
-                   "upconv_fused_wgrad_bn")
-        g = gy
-    else:
-        _lib.check(lib.ctu_upconv_fused_wgrad(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
-                                              dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream()), "upconv_fused_wgrad")
-    if t0 is not None:
-        vox = n * d * h * w
-        TIMER.end(f"upconv_fused_wgrad_kernel<{g.cp}> (+slab reduce)", vox * (16.0 * c * c + 8 * 54.0 * c * co),
-                  4.0 * vox * (c + 8 * co), t0, (w, x.cp, g.cp))
+    ws = torch.empty(_query(x.lp, "upconv_fused_wgrad_ws_floats", n, d, h, w, x.cp, *gcp), dtype=torch.float32, device=dev)
+    act = (x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, *gcp)
+    detail = (w, x.cp, g.cp)
+
+    def record():
+        tag, nbytes = tag_bytes()
+        return tag, (n * d * h * w) * (16.0 * c * c + 8 * 54.0 * c * co), nbytes, detail
+    with _timed(record):
+        if lazy is not None:
+            y, vec, coef, gy = lazy
+            assert y.dims == g.dims and gy.dims == g.dims and y.cs == g.cs == gy.cs and y.cp == g.cp == gy.cp
+            assert gy.buf.data_ptr() != g.buf.data_ptr()
+            _dual(x.lp, "upconv_fused_wgrad_bn", *act, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
+                  dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream())
+            g = gy
+        else:
+            _dual(x.lp, "upconv_fused_wgrad", *act, dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream())
     dwt = torch.empty((c, c, 2, 2, 2), dtype=torch.float32, device=dev)
     dbt = torch.empty(c, dtype=torch.float32, device=dev)
     dw3 = torch.empty((co, c, 3, 3, 3), dtype=torch.float32, device=dev)
-    ws2 = torch.empty(lib.ctu_upconv_fused_project_ws_floats(g.cp, g.nvox), dtype=torch.float32, device=dev)
-    _lib.check(lib.ctu_upconv_fused_project(dweff.data_ptr(), g.ptr, g.cs, g.cp, n, d, h, w, bt.detach().data_ptr(),
-                                            pack_ws.data_ptr(), _ptr(imap), c, co, x.cp, dwt.data_ptr(), dbt.data_ptr(),
-                                            dw3.data_ptr(), ws2.data_ptr(), _stream()), "upconv_fused_project")
+    ws2 = torch.empty(_lib.load().ctu_upconv_fused_project_ws_floats(g.cp, g.nvox), dtype=torch.float32, device=dev)
+    _dual(x.lp, "upconv_fused_project", dweff.data_ptr(), g.ptr, g.cs, g.cp, n, d, h, w, bt.detach().data_ptr(),
+          pack_ws.data_ptr(), _ptr(imap), c, co, x.cp, dwt.data_ptr(), dbt.data_ptr(), dw3.data_ptr(), ws2.data_ptr(), _stream())
     return dwt, dbt, dw3
 
 
@@ -1036,16 +978,13 @@ def lp_upconv_fused_fwd(x: CL, wp16: torch.Tensor, beff: torch.Tensor, out: CL, 
     """out (fine grid, 16-bit, raw) = conv3(convT(act(x))) in one kernel; x = the COARSE 16-bit input."""
     n, d, h, w = x.dims
     assert out.dims == (n, 2 * d, 2 * h, 2 * w) and x.lp and out.dtype == x.dtype and wp16.dtype == x.dtype and out.cp == 8
-    lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_lp_upconv_fused_fwd(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), wp16.data_ptr(),
-                                           beff.data_ptr(), out.ptr, out.cs, _ptr(stats), n, d, h, w, _stream()),
-               "lp_upconv_fused_fwd")
-    if t0 is not None:
-        ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
-        vox = n * d * h * w
-        TIMER.end(f"lp_upconv_fwd_kernel<{'bf16' if x.lp == 1 else 'f16'}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
-                  2.0 * vox * (x.cp + 8 * out.cp), t0, (w, x.cp, out.cp))
+    ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
+    vox = n * d * h * w
+    with _timed(lambda: (f"lp_upconv_fwd_kernel<{_lp_name(x.lp)}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
+                         2.0 * vox * (x.cp + 8 * out.cp), (w, x.cp, out.cp))):
+        _lib.check(_lib.load().ctu_lp_upconv_fused_fwd(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu),
+                                                       wp16.data_ptr(), beff.data_ptr(), out.ptr, out.cs, _ptr(stats),
+                                                       n, d, h, w, _stream()), "lp_upconv_fused_fwd")
 
 
 def lp_upconv_fused_wgrad_bn_supported(dims, cin_p: int) -> bool:
@@ -1058,48 +997,20 @@ def lp_upconv_fused_wgrad(x: CL, g: CL, c: int, co: int, bt: torch.Tensor, pack_
     lazy = (y, vec, coef, gy) as in upconv_fused_wgrad."""
     n, d, h, w = x.dims
     assert g.dims == (n, 2 * d, 2 * h, 2 * w) and x.lp and g.dtype == x.dtype and g.cp == 8 and g.cs == 8
-    lib = _lib.load()
-    dev = x.buf.device
-    dweff = torch.empty((8, 8, x.cp, 8), dtype=torch.float32, device=dev)
-    ws = torch.empty(lib.ctu_lp_upconv_fused_wgrad_ws_floats(n, d, h, w, x.cp), dtype=torch.float32, device=dev)
-    t0 = TIMER.begin() if TIMER is not None else None
-    if lazy is not None:
-        y, vec, coef, gy = lazy
-        assert y.dims == g.dims and gy.dims == g.dims and y.cs == g.cs == gy.cs and gy.buf.data_ptr() != g.buf.data_ptr()
-        _lib.check(lib.ctu_lp_upconv_fused_wgrad_bn(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs,
-                                                    y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
-                                                    dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream()), "lp_upconv_fused_wgrad_bn")
-        g = gy
-    else:
-        _lib.check(lib.ctu_lp_upconv_fused_wgrad(x.lp, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs,
-                                                 dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream()), "lp_upconv_fused_wgrad")
-    if t0 is not None:
-        vox = n * d * h * w
-        TIMER.end(f"lp_upconv_wgrad_kernel<{'bf16' if x.lp == 1 else 'f16'}> (+slab reduce)", vox * (16.0 * c * c + 8 * 54.0 * c * co),
-                  2.0 * vox * (x.cp + 8 * g.cp), t0, (w, x.cp, g.cp))
-    dwt = torch.empty((c, c, 2, 2, 2), dtype=torch.float32, device=dev)
-    dbt = torch.empty(c, dtype=torch.float32, device=dev)
-    dw3 = torch.empty((co, c, 3, 3, 3), dtype=torch.float32, device=dev)
-    ws2 = torch.empty(lib.ctu_upconv_fused_project_ws_floats(g.cp, g.nvox), dtype=torch.float32, device=dev)
-    _lib.check(lib.ctu_lp_upconv_fused_project(x.lp, dweff.data_ptr(), g.ptr, g.cs, g.cp, n, d, h, w, bt.detach().data_ptr(),
-                                               pack_ws.data_ptr(), _ptr(imap), c, co, x.cp, dwt.data_ptr(), dbt.data_ptr(),
-                                               dw3.data_ptr(), ws2.data_ptr(), _stream()), "lp_upconv_fused_project")
-    return dwt, dbt, dw3
+    return _upconv_wgrad(x, g, c, co, bt, pack_ws, imap, lazy,
+                         lambda: (f"lp_upconv_wgrad_kernel<{_lp_name(x.lp)}> (+slab reduce)", 2.0 * (n * d * h * w) * (x.cp + 8 * g.cp)))
 
 
 def lp_upconv_fused_bwd_data(g: CL, wp16: torch.Tensor, gin: CL, algo_ch: Optional[Tuple[int, int]] = None) -> None:
     """gin (coarse, 16-bit) <- gradient of the fused pair w.r.t. its activated input, from the fine-grid gradient g."""
     n, d, h, w = gin.dims
     assert g.dims == (n, 2 * d, 2 * h, 2 * w) and g.lp and gin.dtype == g.dtype and wp16.dtype == g.dtype and g.cp == 8
-    lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_lp_upconv_fused_bwd_data(g.lp, g.ptr, g.cs, wp16.data_ptr(), gin.ptr, gin.cs, gin.cp, n, d, h, w, _stream()),
-               "lp_upconv_fused_bwd_data")
-    if t0 is not None:
-        ci, co = algo_ch if algo_ch is not None else (gin.cp, g.cp)
-        vox = n * d * h * w
-        TIMER.end(f"lp_upconv_bwd_data_kernel<{'bf16' if g.lp == 1 else 'f16'}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
-                  2.0 * vox * (gin.cp + 8 * g.cp), t0, (w, gin.cp, g.cp))
+    ci, co = algo_ch if algo_ch is not None else (gin.cp, g.cp)
+    vox = n * d * h * w
+    with _timed(lambda: (f"lp_upconv_bwd_data_kernel<{_lp_name(g.lp)}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
+                         2.0 * vox * (gin.cp + 8 * g.cp), (w, gin.cp, g.cp))):
+        _lib.check(_lib.load().ctu_lp_upconv_fused_bwd_data(g.lp, g.ptr, g.cs, wp16.data_ptr(), gin.ptr, gin.cs, gin.cp,
+                                                            n, d, h, w, _stream()), "lp_upconv_fused_bwd_data")
 
 
 def upconv_fused_pack_bwd(wp: torch.Tensor, cin_p: int, nout_p: int, into: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1114,15 +1025,12 @@ def upconv_fused_bwd_data(g: CL, wpd: torch.Tensor, gin: CL, algo_ch: Optional[T
     """gin (coarse) <- gradient of the fused ConvTranspose3d -> Conv3d pair w.r.t. its (activated) input."""
     n, d, h, w = gin.dims
     assert g.dims == (n, 2 * d, 2 * h, 2 * w)
-    lib = _lib.load()
-    t0 = TIMER.begin() if TIMER is not None else None
-    _lib.check(lib.ctu_upconv_fused_bwd_data(g.ptr, g.cs, g.cp, wpd.data_ptr(), gin.ptr, gin.cs, gin.cp, n, d, h, w, _stream()),
-               "upconv_fused_bwd_data")
-    if t0 is not None:
-        ci, co = algo_ch if algo_ch is not None else (gin.cp, g.cp)
-        vox = n * d * h * w
-        TIMER.end(f"upconv_fused_bwd_data_kernel<{g.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co), 4.0 * vox * (ci + 8 * co),
-                  t0, (w, gin.cp, g.cp))
+    ci, co = algo_ch if algo_ch is not None else (gin.cp, g.cp)
+    vox = n * d * h * w
+    with _timed(lambda: (f"upconv_fused_bwd_data_kernel<{g.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
+                         4.0 * vox * (ci + 8 * co), (w, gin.cp, g.cp))):
+        _lib.check(_lib.load().ctu_upconv_fused_bwd_data(g.ptr, g.cs, g.cp, wpd.data_ptr(), gin.ptr, gin.cs, gin.cp,
+                                                         n, d, h, w, _stream()), "upconv_fused_bwd_data")
 
 
 # ---------------------------------------------------------------------------- inference tail / sample schema
@@ -1250,37 +1158,36 @@ def window_finalize(num: torch.Tensor, wsum: torch.Tensor, probs: torch.Tensor,
                                                _stream()), "window_finalize")
 
 
-def scale_tensors(tensors, s: float, nonfinite: Optional[torch.Tensor] = None) -> None:
-    """Every float32 CUDA tensor of the list scaled in place by s, one launch (un-scaling of loss-scaled gradients).
-    nonfinite: float32[1] device flag set to 1 when any scaled value is inf / NaN (fp16 overflow detection)."""
-    import ctypes as C
+def _tensor_table(tensors):
+    """(pointer array, element-count array, length) over the tensors of a list that are not None: the first three arguments
+    of ctu_scale_tensors / ctu_unscale_tensors."""
     ts = [t for t in tensors if t is not None]
-    if not ts:
-        return
     for t in ts:
         _need_cuda(t, "tensor")
         assert t.is_contiguous() and t.dtype == torch.float32
-    pa = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    sa = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
+    return ((ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts]),
+            len(ts))
+
+
+def scale_tensors(tensors, s: float, nonfinite: Optional[torch.Tensor] = None) -> None:
+    """Every float32 CUDA tensor of the list scaled in place by s, one launch (un-scaling of loss-scaled gradients).
+    nonfinite: float32[1] device flag set to 1 when any scaled value is inf / NaN (fp16 overflow detection)."""
+    pa, sa, n = _tensor_table(tensors)
+    if not n:
+        return
     assert nonfinite is None or (nonfinite.is_cuda and nonfinite.dtype == torch.float32 and nonfinite.numel() == 1)
-    _lib.check(_lib.load().ctu_scale_tensors(pa, sa, len(ts), float(s), _ptr(nonfinite), _stream()), "scale_tensors")
+    _lib.check(_lib.load().ctu_scale_tensors(pa, sa, n, float(s), _ptr(nonfinite), _stream()), "scale_tensors")
 
 
 def unscale_tensors(tensors, scale: torch.Tensor, found_inf: torch.Tensor) -> None:
     """Every float32 CUDA tensor of the list multiplied in place by 1 / scale[0] (scale: the float32[1] device loss scale
     of dynamic loss scaling), one launch; found_inf (float32[1] device flag) is set on inf / NaN and never cleared here."""
-    import ctypes as C
-    ts = [t for t in tensors if t is not None]
-    if not ts:
+    pa, sa, n = _tensor_table(tensors)
+    if not n:
         return
-    for t in ts:
-        _need_cuda(t, "tensor")
-        assert t.is_contiguous() and t.dtype == torch.float32
     for f in (scale, found_inf):
         assert f.is_cuda and f.dtype == torch.float32 and f.numel() == 1
-    pa = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    sa = (C.c_int64 * len(ts))(*[t.numel() for t in ts])
-    _lib.check(_lib.load().ctu_unscale_tensors(pa, sa, len(ts), scale.data_ptr(), found_inf.data_ptr(), _stream()),
+    _lib.check(_lib.load().ctu_unscale_tensors(pa, sa, n, scale.data_ptr(), found_inf.data_ptr(), _stream()),
                "unscale_tensors")
 
 
