@@ -60,6 +60,27 @@ void ctu_set_error(const char* fmt, ...);
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// grid of a persistent kernel (a block loops over tpb boxes): at most `cap` blocks, the boxes spread evenly over them.  The
+// cap is what differs between kernels (resident blocks per CU x 256 CUs, divided by the grid's other axes).
+struct Grid { int gx, tpb; };
+inline Grid persist_grid(int ntiles, int cap) {
+    const int g = cap < 1 ? 1 : (cap > ntiles ? ntiles : cap);
+    const int tpb = ceil_div(ntiles, g);
+    return {ceil_div(ntiles, tpb), tpb};
+}
+
+// the dynamic-LDS limit of a kernel is raised only for launches that need more than was raised before (64 KB by default),
+// and only to what they need.  `raised` belongs to one kernel instantiation: a function-local static of the launching template.
+template <class K>
+int raise_lds(K kernel, size_t lds, size_t* raised, const char* what) {
+    if (lds > *raised) {
+        CTU_REQUIRE(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+                    "%s: cannot raise the dynamic LDS limit", what);
+        *raised = lds;
+    }
+    return CTU_OK;
+}
+
 // lazy-BN input transform on 4 consecutive channels: 2 packed FMAs + 4 max (the clamp bound is -inf without ReLU,
 // so there is no branch; __builtin_elementwise_max avoids the extra canonicalising max of fmaxf)
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -1707,49 +1707,11 @@ __global__ __launch_bounds__(1024) void conv3d_wgrad_k3s_reduce_kernel(const flo
     if (ok && ci >= 0 && co < Co) dw[((size_t)co * Ci + ci) * 27 + r * 3 + kw] = tot;
 }
 
-// geometry of the persistent k = 3 kernel for a layer: tile shape (SM, SN), box width, boxes, channel-tile pairs, grid
-struct K3sGeom { int sm, sn, tw, ntiles, n_ci_g, pairs, gx, tpb, nmf; };
-static K3sGeom k3s_geom(int N, int D, int H, int W, int cin_p, int cout_p) {
-    K3sGeom g;
-    g.sm = cin_p == 8 ? 2 : 1; g.sn = cout_p == 8 ? 2 : 1;
-    g.tw = (g.sm == 2 && g.sn == 2) ? 16 : 8;
-    g.nmf = (g.sm == 2 && g.sn == 2) ? 9 : ((g.sm == 1 && g.sn == 1) ? 27 : 18);
-    g.ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, g.tw);
-    g.n_ci_g = ceil_div(cin_p, 16 / g.sm);
-    g.pairs = g.n_ci_g * ceil_div(cout_p, 16 / g.sn);
-    g.gx = wgrad_gx(g.ntiles, g.pairs);
-    // small layers: with fewer than 4 boxes per block the 27-tap slab a block writes (and the reduce kernel re-reads)
-    // outweighs its MFMA work -- one block per CU instead of two (64->64 @16^3: 28.4 -> 23.8 us, 32->32 @32^3: 34.4 -> 30.4)
-    if (g.ntiles / g.gx < 4) {
-        g.gx = (CTU_WG_BLOCKS / 2) / g.pairs;
-        if (g.gx < 1) g.gx = 1;
-        if (g.gx > g.ntiles) g.gx = g.ntiles;
-    }
-    g.tpb = ceil_div(g.ntiles, g.gx);
-    g.gx = ceil_div(g.ntiles, g.tpb);
-    return g;
-}
-
 // lazy BatchNorm backward inside the k = 3 weight-gradient kernel: full boxes and full channel tiles only
 static bool k3s_lazy_ok(int D, int H, int W, int k, int cin_p, int cout_p) {
     if (!use_k3s(k, W, cin_p, cout_p)) return false;
     const int sm = cin_p == 8 ? 2 : 1, sn = cout_p == 8 ? 2 : 1, tw = (sm == 2 && sn == 2) ? 16 : 8;
     return D % 4 == 0 && H % 4 == 0 && W % tw == 0 && cin_p % (16 / sm) == 0 && cout_p % (16 / sn) == 0;
-}
-
-template <int SM, int SN>
-static int launch_wgrad_k3s(WgP p, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
-    const K3sGeom g = k3s_geom(p.N, p.D, p.H, p.W, p.cin_p, p.cout_p);
-    p.tiles_d = ceil_div(p.D, 4); p.tiles_h = ceil_div(p.H, 4); p.tiles_w = ceil_div(p.W, g.tw);
-    p.ntiles = g.ntiles;
-    p.n_ci_t = g.n_ci_g;
-    if (p.lz_y) conv3d_wgrad_k3s_kernel<SM, SN, 0, true><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
-    else conv3d_wgrad_k3s_kernel<SM, SN><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
-    CTU_CHECK_LAUNCH("conv3d_wgrad_k3s");
-    conv3d_wgrad_k3s_reduce_kernel<SM, SN><<<dim3(ceil_div(g.nmf * 256, 64), g.pairs), 64 * RPARTS, 0, st>>>(
-        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, g.gx);
-    CTU_CHECK_LAUNCH("conv3d_wgrad_k3s_reduce");
-    return CTU_OK;
 }
 
 // ------------------------------------------------------------------ weight gradient, narrow layers (k = 5: the legacy nets)
@@ -2118,34 +2080,6 @@ __global__ __launch_bounds__(1024) void conv3d_wgrad_k5s_reduce_kernel(const flo
 // k = 5 layers with an 8-channel side (W >= 16) take the (w-shift, channel) tiles too
 inline bool use_k5s(int k, int W, int cin_p, int cout_p) { return k == 5 && W >= 16 && (cin_p == 8 || cout_p == 8); }
 
-static K3sGeom k5s_geom(int N, int D, int H, int W, int cin_p, int cout_p) {
-    K3sGeom g;
-    g.sm = cin_p == 8 ? 2 : 1; g.sn = cout_p == 8 ? 2 : 1;
-    g.tw = (g.sm == 2 && g.sn == 2) ? 16 : 8;
-    g.nmf = 5 * ((g.sm == 2 && g.sn == 2) ? 2 : ((g.sm == 1 && g.sn == 1) ? 5 : (g.sn == 2 ? 4 : 3)));
-    g.ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, g.tw);
-    g.n_ci_g = ceil_div(cin_p, 16 / g.sm);
-    g.pairs = g.n_ci_g * ceil_div(cout_p, 16 / g.sn);
-    g.gx = wgrad_gx(g.ntiles, g.pairs * 5);
-    g.tpb = ceil_div(g.ntiles, g.gx);
-    g.gx = ceil_div(g.ntiles, g.tpb);
-    return g;
-}
-
-template <int SM, int SN>
-static int launch_wgrad_k5s(WgP p, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
-    const K3sGeom g = k5s_geom(p.N, p.D, p.H, p.W, p.cin_p, p.cout_p);
-    p.tiles_d = ceil_div(p.D, 4); p.tiles_h = ceil_div(p.H, 4); p.tiles_w = ceil_div(p.W, g.tw);
-    p.ntiles = g.ntiles;
-    p.n_ci_t = g.n_ci_g;
-    conv3d_wgrad_k5s_kernel<SM, SN><<<dim3(g.gx, g.pairs, 5), 256, 0, st>>>(p, g.tpb);
-    CTU_CHECK_LAUNCH("conv3d_wgrad_k5s");
-    conv3d_wgrad_k5s_reduce_kernel<SM, SN><<<dim3(ceil_div(g.nmf * 256, 64), g.pairs, 5), 64 * RPARTS, 0, st>>>(
-        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, g.gx);
-    CTU_CHECK_LAUNCH("conv3d_wgrad_k5s_reduce");
-    return CTU_OK;
-}
-
 // dW_eff[parity 8][tap 8][cin_p][nout_p] from the slabs of the UP kernel (fixed-order parallel reduction)
 __global__ __launch_bounds__(1024) void upconv_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dweff,
                                                                   int cin_p, int nout_p, int n_ci_g, int n_co_g, int gx) {
@@ -2187,40 +2121,99 @@ __global__ __launch_bounds__(1024) void upconv_wgrad_reduce_pw_kernel(const floa
         dweff[((size_t)((par4 * 2 + px) * 8 + (t / 3) * 2 + jx) * cin_p + rp) * 8 + co] = tot;
 }
 
-struct UpWgGeom { int ntiles, n_ci_g, n_co_g, pairs, gx, tpb, nmf; };
-static UpWgGeom upwg_geom(int N, int D, int H, int W, int cin_p, int nout_p, bool pw) {
-    UpWgGeom g;
-    if (pw) {
-        g.ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 8);
-        g.n_ci_g = ceil_div(cin_p, 16); g.n_co_g = 1; g.pairs = 4 * g.n_ci_g; g.nmf = 12;
-        g.gx = wgrad_gx(g.ntiles, g.pairs);
-        g.tpb = ceil_div(g.ntiles, g.gx);
-        g.gx = ceil_div(g.ntiles, g.tpb);
-        return g;
+// grid of the persistent k = 3 weight-gradient kernel: CTU_WG_BLOCKS blocks (two per CU) over the (pair) axis.  Small layers:
+// with fewer than 4 boxes per block the 27-tap slab a block writes (and the reduce kernel re-reads) outweighs its MFMA
+// work -- one block per CU instead of two (64->64 @16^3: 28.4 -> 23.8 us, 32->32 @32^3: 34.4 -> 30.4)
+static Grid k3s_grid(int ntiles, int pairs) {
+    const bool few = ntiles / wgrad_gx(ntiles, pairs) < 4;
+    return persist_grid(ntiles, (few ? CTU_WG_BLOCKS / 2 : CTU_WG_BLOCKS) / pairs);
+}
+
+// The route of an fp32 weight-gradient launch: ctu_conv3d_wgrad_ws_floats, ctu_conv3d_wgrad_kernel_name and the launch read
+// this one plan.  (sm, sn): (w-shift, channel) tiles of the 8-channel sides; boxes td x th x tw; nmf 16 x 16 tiles per slab;
+// grid (gx, pairs, planes).  n_co_t is read by the generic kernel only.
+enum WgKind { WG_K3S, WG_K5S, WG_GENERIC };
+struct WgPlan {
+    WgKind kind;
+    int sm, sn, td, th, tw, tiles_d, tiles_h, tiles_w, ntiles, n_ci_g, n_co_t, pairs, planes, nmf;
+    Grid grid;
+    size_t slabs;
+};
+
+static WgPlan wgrad_plan(int N, int D, int H, int W, int k, int cin_p, int cout_p) {
+    WgPlan r;
+    r.kind = use_k3s(k, W, cin_p, cout_p) ? WG_K3S : (use_k5s(k, W, cin_p, cout_p) ? WG_K5S : WG_GENERIC);
+    r.sm = (r.kind != WG_GENERIC && cin_p == 8) ? 2 : 1; r.sn = (r.kind != WG_GENERIC && cout_p == 8) ? 2 : 1;
+    if (r.kind == WG_GENERIC) pick_tile(W, &r.td, &r.th, &r.tw);
+    else { r.td = 4; r.th = 4; r.tw = (r.sm == 2 && r.sn == 2) ? 16 : 8; }
+    r.tiles_d = ceil_div(D, r.td); r.tiles_h = ceil_div(H, r.th); r.tiles_w = ceil_div(W, r.tw);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    r.n_ci_g = ceil_div(cin_p, 16 / r.sm); r.n_co_t = ceil_div(cout_p, 16);
+    r.pairs = r.n_ci_g * ceil_div(cout_p, 16 / r.sn);
+    r.planes = k == 3 ? 1 : 5;
+    const int both = r.sm == 2 && r.sn == 2, none = r.sm == 1 && r.sn == 1;
+    if (r.kind == WG_K3S) {
+        r.nmf = both ? 9 : (none ? 27 : 18);
+        r.grid = k3s_grid(r.ntiles, r.pairs);
+    } else if (r.kind == WG_K5S) {
+        r.nmf = 5 * (both ? 2 : (none ? 5 : (r.sn == 2 ? 4 : 3)));
+        r.grid = persist_grid(r.ntiles, CTU_WG_BLOCKS / (r.pairs * 5));
+    } else {
+        r.nmf = k == 3 ? 27 : 25;
+        r.grid = {wgrad_gx(r.ntiles, r.pairs * r.planes), 0};        // (blocks stride over the boxes)
     }
-    g.nmf = 8;
-    g.ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 8);
-    g.n_ci_g = ceil_div(cin_p, 16);
-    g.n_co_g = ceil_div(nout_p, 16);
-    g.pairs = 8 * g.n_ci_g * g.n_co_g;
-    g.gx = wgrad_gx(g.ntiles, g.pairs);
-    // small layers: with fewer than 4 boxes per block the 27-tap slab a block writes (and the reduce kernel re-reads)
-    // outweighs its MFMA work -- one block per CU instead of two (64->64 @16^3: 28.4 -> 23.8 us, 32->32 @32^3: 34.4 -> 30.4)
-    if (g.ntiles / g.gx < 4) {
-        g.gx = (CTU_WG_BLOCKS / 2) / g.pairs;
-        if (g.gx < 1) g.gx = 1;
-        if (g.gx > g.ntiles) g.gx = g.ntiles;
-    }
-    g.tpb = ceil_div(g.ntiles, g.gx);
-    g.gx = ceil_div(g.ntiles, g.tpb);
-    return g;
+    r.slabs = (size_t)r.planes * r.pairs * r.grid.gx * r.nmf * 256;
+    return r;
+}
+
+// The fused up-convolution's weight gradient (COARSE dims, 4 x 4 x 8 boxes of conv3d_wgrad_k3s_kernel<1, 1, UP>): pw = the
+// (w-parity, c_out) tile of 8-output layers (UP = 2, 12 tiles per slab), else one pair per (parity, ci tile, co tile).
+struct UpWgPlan { int ntiles, n_ci_g, n_co_g, pairs, nmf; Grid grid; size_t slabs; };
+static UpWgPlan upwg_plan(int N, int D, int H, int W, int cin_p, int nout_p, bool pw) {
+    UpWgPlan r;
+    r.ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 8);
+    r.n_ci_g = ceil_div(cin_p, 16); r.n_co_g = pw ? 1 : ceil_div(nout_p, 16);
+    r.pairs = (pw ? 4 : 8) * r.n_ci_g * r.n_co_g; r.nmf = pw ? 12 : 8;
+    r.grid = pw ? persist_grid(r.ntiles, CTU_WG_BLOCKS / r.pairs) : k3s_grid(r.ntiles, r.pairs);
+    r.slabs = (size_t)r.pairs * r.grid.gx * r.nmf * 256;
+    return r;
 }
 
 }  // namespace
 
-// k == 5: the same boxes, one block per CU -- when the boxes fill the chip (a block owns one whole box per stage)
-static bool use_persist5(int k, int nt, int tw, int N, int D, int H, int W) {
-    return k == 5 && tw == 16 && nt <= 2 && (long)N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 16) >= 256;
+// The route of an fp32 forward / data-gradient launch: ctu_conv3d_num_blocks, ctu_conv3d_fwd_kernel_name and ctu_conv3d_fwd
+// read this one plan.  nt = N-tiles (16 output channels) per block, ny = blocks in y, boxes td x th x tw voxels.
+enum FwdKind { FWD_PAIR_K3, FWD_PAIR_K5, FWD_PERSIST_K3, FWD_PERSIST_K5, FWD_BOX };
+struct FwdPlan { FwdKind kind; int nt, td, th, tw, tiles_d, tiles_h, tiles_w, ntiles, n16, ny; Grid grid; };
+
+static FwdPlan fwd_plan(int N, int D, int H, int W, int k, int nout_p, int layout) {
+    FwdPlan r;
+    if (layout == 1) {                                   // 8 outputs: (w-parity, channel) tiles
+        r.nt = 1; r.td = 4; r.th = 4; r.tw = 32;
+        r.n16 = 1;
+    } else {
+        pick_launch(N, D, H, W, k, nout_p, &r.nt, &r.td, &r.th, &r.tw);
+        r.n16 = ceil_div(nout_p, 16);
+    }
+    r.tiles_d = ceil_div(D, r.td); r.tiles_h = ceil_div(H, r.th); r.tiles_w = ceil_div(W, r.tw);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    r.ny = ceil_div(r.n16, r.nt);
+    int per_cu = 0;                                      // resident blocks per CU of the persistent kernels
+    if (layout == 1) {                                   // (k = 5: 123 KB of LDS)
+        r.kind = k == 3 ? FWD_PAIR_K3 : FWD_PAIR_K5;
+        per_cu = k == 3 ? 2 : 1;
+    } else if (k == 5 && r.tw == 16 && r.nt <= 2 && r.ntiles >= 256) {
+        // k == 5: the same boxes, one block per CU -- when the boxes fill the chip (a block owns one whole box per stage)
+        r.kind = FWD_PERSIST_K5;
+        per_cu = 1;
+    } else if (k == 3 && r.tw == 16 && r.nt <= 2) {
+        // k == 3 volumes wide enough for the 4x4x16 box with at most 2 N-tiles per block: the persistent, register-prefetching kernel
+        r.kind = FWD_PERSIST_K3;
+        per_cu = r.nt == 1 ? CTU_FWD_OCC1 : 2;
+    } else r.kind = FWD_BOX;
+    // the persistent kernels write ONE stats row per block
+    r.grid = per_cu ? persist_grid(r.ntiles, 256 * per_cu / r.ny) : Grid{r.ntiles, 1};
+    return r;
 }
 
 // =================================================================== C ABI
@@ -2230,26 +2223,17 @@ extern "C" int ctu_conv3d_layout(int k, int nout_p, int W) {
 
 extern "C" const char* ctu_conv3d_fwd_kernel_name(int N, int D, int H, int W, int k, int nout_p, int layout) {
     static thread_local char buf[64];
-    if (layout == 1) return k == 3 ? "conv3d_fwd_k3_persist<1, true>" : "conv3d_fwd_k5_persist<1, true>";
-    int nt, td, th, tw;
-    pick_launch(N, D, H, W, k, nout_p, &nt, &td, &th, &tw);
-    if (use_persist5(k, nt, tw, N, D, H, W)) snprintf(buf, sizeof(buf), "conv3d_fwd_k5_persist<%d, false>", nt);
-    else if (k == 3 && tw == 16 && nt <= 2) snprintf(buf, sizeof(buf), "conv3d_fwd_k3_persist<%d, false>", nt);
-    else snprintf(buf, sizeof(buf), "conv3d_fwd_kernel<%d, %d, %d, %d, %d>", k, nt, td, th, tw);
+    const FwdPlan r = fwd_plan(N, D, H, W, k, nout_p, layout);
+    if (r.kind == FWD_BOX) snprintf(buf, sizeof(buf), "conv3d_fwd_kernel<%d, %d, %d, %d, %d>", k, r.nt, r.td, r.th, r.tw);
+    else snprintf(buf, sizeof(buf), "conv3d_fwd_k%d_persist<%d, %s>", k, r.nt, layout == 1 ? "true" : "false");
     return buf;
 }
 
 extern "C" const char* ctu_conv3d_wgrad_kernel_name(int W, int k, int cin_p, int cout_p) {
     static thread_local char buf[64];
-    if (use_k3s(k, W, cin_p, cout_p))
-        snprintf(buf, sizeof(buf), "conv3d_wgrad_k3s_kernel<%d, %d>", cin_p == 8 ? 2 : 1, cout_p == 8 ? 2 : 1);
-    else if (use_k5s(k, W, cin_p, cout_p))
-        snprintf(buf, sizeof(buf), "conv3d_wgrad_k5s_kernel<%d, %d>", cin_p == 8 ? 2 : 1, cout_p == 8 ? 2 : 1);
-    else {
-        int td, th, tw;
-        pick_tile(W, &td, &th, &tw);
-        snprintf(buf, sizeof(buf), "conv3d_wgrad_kernel<%d, %d, %d, %d, %d>", k, k == 3 ? 3 : 1, td, th, tw);
-    }
+    const WgPlan r = wgrad_plan(1, 1, 1, W, k, cin_p, cout_p);
+    if (r.kind == WG_GENERIC) snprintf(buf, sizeof(buf), "conv3d_wgrad_kernel<%d, %d, %d, %d, %d>", k, k == 3 ? 3 : 1, r.td, r.th, r.tw);
+    else snprintf(buf, sizeof(buf), "conv3d_wgrad_k%ds_kernel<%d, %d>", k, r.sm, r.sn);
     return buf;
 }
 
@@ -2259,36 +2243,8 @@ extern "C" size_t ctu_conv3d_packed_floats(int k, int rin_p, int nout_p, int lay
     return (size_t)(rin_p / 8) * k * k * k * ceil_div(nout_p, 16) * 128;
 }
 
-// grid of the persistent kernels: boxes per block and blocks in x
-static void persist_grid(int ntiles, int ny, int blocks_per_cu, int* gx, int* tpb) {
-    int g = (256 * blocks_per_cu) / ny;
-    if (g < 1) g = 1;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
-// k == 3 volumes wide enough for the 4x4x16 box with at most 2 N-tiles per block use the persistent kernel
-static bool use_persist(int k, int nt, int tw) { return k == 3 && tw == 16 && nt <= 2; }
-
 extern "C" int ctu_conv3d_num_blocks(int N, int D, int H, int W, int k, int nout_p, int layout) {
-    int gx, tpb;
-    if (layout == 1) {
-        persist_grid(N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 32), 1, k == 3 ? 2 : 1, &gx, &tpb);
-        return gx;                                   // the persistent kernels write ONE stats row per block
-    }
-    int nt, td, th, tw;
-    pick_launch(N, D, H, W, k, nout_p, &nt, &td, &th, &tw);
-    const int ntiles = N * ceil_div(D, td) * ceil_div(H, th) * ceil_div(W, tw);
-    if (use_persist5(k, nt, tw, N, D, H, W)) {
-        persist_grid(ntiles, ceil_div(ceil_div(nout_p, 16), nt), 1, &gx, &tpb);
-        return gx;
-    }
-    if (use_persist(k, nt, tw)) {
-        persist_grid(ntiles, ceil_div(ceil_div(nout_p, 16), nt), nt == 1 ? CTU_FWD_OCC1 : 2, &gx, &tpb);
-        return gx;
-    }
-    return ntiles;
+    return fwd_plan(N, D, H, W, k, nout_p, layout).grid.gx;
 }
 
 extern "C" int ctu_pack_conv3d_weight(const float* w, float* wp, int Co, int Ci, int k, const int32_t* cinv,
@@ -2345,18 +2301,24 @@ extern "C" int ctu_pack_batch(const ctu_pack_job* jobs, int n, void* stream) {
 }
 
 template <int KS, int NT>
-static int launch_fwd(const ConvP& p0, int td, int th, int tw, hipStream_t st) {
-    ConvP p = p0;
-    p.n16 = ceil_div(p.nout_p, 16);
-    p.tiles_d = ceil_div(p.D, td); p.tiles_h = ceil_div(p.H, th); p.tiles_w = ceil_div(p.W, tw);
-    dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, ceil_div(p.nout_p, 16 * NT));
-    if (tw == 16) conv3d_fwd_kernel<KS, NT, 4, 4, 16><<<grid, 256, 0, st>>>(p);
-    else if (tw == 8) conv3d_fwd_kernel<KS, NT, 4, 8, 8><<<grid, 256, 0, st>>>(p);
+static int launch_fwd(const ConvP& p, const FwdPlan& r, hipStream_t st) {
+    const dim3 grid(r.grid.gx, r.ny);
+    if (r.tw == 16) conv3d_fwd_kernel<KS, NT, 4, 4, 16><<<grid, 256, 0, st>>>(p);
+    else if (r.tw == 8) conv3d_fwd_kernel<KS, NT, 4, 8, 8><<<grid, 256, 0, st>>>(p);
     else if (KS == 3 && NT == 1 && p.rin_p % 32 == 0) {
         // small deep-level volumes: 32 channels per barrier pair (4x fewer exposed staging latencies)
         if constexpr (KS == 3 && NT == 1) conv3d_fwd_kernel<3, 1, 4, 4, 4, 4><<<grid, 256, 0, st>>>(p);
     } else conv3d_fwd_kernel<KS, NT, 4, 4, 4><<<grid, 256, 0, st>>>(p);
     CTU_CHECK_LAUNCH("conv3d_fwd");
+    return CTU_OK;
+}
+
+// conv3d_fwd_k5_persist with its dynamic-LDS limit raised
+template <int NT, bool PAIR>
+static int launch_fwd_k5(const ConvP& p, const FwdPlan& r, hipStream_t st) {
+    CTU_REQUIRE((k5_attr<NT, PAIR>()) == hipSuccess, "conv3d_fwd: cannot raise the dynamic LDS limit of the k=5 kernel");
+    conv3d_fwd_k5_persist<NT, PAIR><<<dim3(r.grid.gx, r.ny), 256, k5_persist_lds<NT, PAIR>(), st>>>(p, r.ntiles, r.grid.tpb);
+    CTU_CHECK_LAUNCH(PAIR ? "conv3d_fwd_k5_persist<1, pair>" : "conv3d_fwd_k5_persist");
     return CTU_OK;
 }
 
@@ -2383,112 +2345,75 @@ extern "C" int ctu_conv3d_fwd(const float* in, int in_cs, int rin_p, const float
     p.nbias = bias ? nbias : 0;
     p.N = N; p.D = D; p.H = H; p.W = W;
     hipStream_t st = (hipStream_t)stream;
-    if (layout == 1) {
-        CTU_REQUIRE(nout_p == 8, "conv3d_fwd: layout 1 needs nout_p=8");
-        p.n16 = 1;
-        p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 32);
-        const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        int gx, tpb;
-        if (k == 5) {
-            persist_grid(ntiles, 1, 1, &gx, &tpb);     // 1 resident block per CU (123 KB of LDS)
-            { const hipError_t arc = k5_attr<1, true>(); CTU_REQUIRE(arc == hipSuccess, "conv3d_fwd: cannot raise the dynamic LDS limit of the k=5 kernel"); }
-            conv3d_fwd_k5_persist<1, true><<<gx, 256, k5_persist_lds<1, true>(), st>>>(p, ntiles, tpb);
-            CTU_CHECK_LAUNCH("conv3d_fwd_k5_persist<1, pair>");
-            return CTU_OK;
-        }
-        persist_grid(ntiles, 1, 2, &gx, &tpb);         // 2 resident blocks per CU (LDS)
-        conv3d_fwd_k3_persist<1, true><<<gx, 256, 0, st>>>(p, ntiles, tpb);
+    CTU_REQUIRE(layout != 1 || nout_p == 8, "conv3d_fwd: layout 1 needs nout_p=8");
+    CTU_REQUIRE(layout == 0 || layout == 1, "conv3d_fwd: unknown layout %d", layout);
+    const FwdPlan r = fwd_plan(N, D, H, W, k, nout_p, layout);
+    p.n16 = r.n16;
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
+    const dim3 grid(r.grid.gx, r.ny);
+    switch (r.kind) {
+    case FWD_PAIR_K5: return launch_fwd_k5<1, true>(p, r, st);
+    case FWD_PERSIST_K5: return r.nt == 1 ? launch_fwd_k5<1, false>(p, r, st) : launch_fwd_k5<2, false>(p, r, st);
+    case FWD_PAIR_K3:
+        conv3d_fwd_k3_persist<1, true><<<grid, 256, 0, st>>>(p, r.ntiles, r.grid.tpb);
         CTU_CHECK_LAUNCH("conv3d_fwd_k3_persist<1, pair>");
         return CTU_OK;
-    }
-    CTU_REQUIRE(layout == 0, "conv3d_fwd: unknown layout %d", layout);
-    int NT, td, th, tw;
-    pick_launch(N, D, H, W, k, nout_p, &NT, &td, &th, &tw);
-    if (use_persist5(k, NT, tw, N, D, H, W)) {
-        p.n16 = ceil_div(p.nout_p, 16);
-        p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
-        const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        const int ny = ceil_div(p.n16, NT);
-        int gx, tpb;
-        persist_grid(ntiles, ny, 1, &gx, &tpb);
-        if (NT == 1) {
-            { const hipError_t arc = k5_attr<1, false>(); CTU_REQUIRE(arc == hipSuccess, "conv3d_fwd: cannot raise the dynamic LDS limit of the k=5 kernel"); }
-            conv3d_fwd_k5_persist<1, false><<<dim3(gx, ny), 256, k5_persist_lds<1, false>(), st>>>(p, ntiles, tpb);
-        } else {
-            { const hipError_t arc = k5_attr<2, false>(); CTU_REQUIRE(arc == hipSuccess, "conv3d_fwd: cannot raise the dynamic LDS limit of the k=5 kernel"); }
-            conv3d_fwd_k5_persist<2, false><<<dim3(gx, ny), 256, k5_persist_lds<2, false>(), st>>>(p, ntiles, tpb);
-        }
-        CTU_CHECK_LAUNCH("conv3d_fwd_k5_persist");
-        return CTU_OK;
-    }
-    if (use_persist(k, NT, tw)) {
-        // large layers: persistent, register-prefetching kernel
-        p.n16 = ceil_div(p.nout_p, 16);
-        p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
-        const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        const int ny = ceil_div(p.n16, NT);
-        int gx, tpb;
-        persist_grid(ntiles, ny, NT == 1 ? CTU_FWD_OCC1 : 2, &gx, &tpb);
-        if (NT == 1) conv3d_fwd_k3_persist<1, false><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
-        else conv3d_fwd_k3_persist<2, false><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
+    case FWD_PERSIST_K3:
+        if (r.nt == 1) conv3d_fwd_k3_persist<1, false><<<grid, 256, 0, st>>>(p, r.ntiles, r.grid.tpb);
+        else conv3d_fwd_k3_persist<2, false><<<grid, 256, 0, st>>>(p, r.ntiles, r.grid.tpb);
         CTU_CHECK_LAUNCH("conv3d_fwd_k3_persist");
         return CTU_OK;
+    case FWD_BOX: break;
     }
     if (k == 3) {
-        if (NT == 1) return launch_fwd<3, 1>(p, td, th, tw, st);
-        if (NT == 2) return launch_fwd<3, 2>(p, td, th, tw, st);
-        return launch_fwd<3, 4>(p, td, th, tw, st);
+        if (r.nt == 1) return launch_fwd<3, 1>(p, r, st);
+        if (r.nt == 2) return launch_fwd<3, 2>(p, r, st);
+        return launch_fwd<3, 4>(p, r, st);
     }
-    if (NT == 1) return launch_fwd<5, 1>(p, td, th, tw, st);
-    if (NT == 2) return launch_fwd<5, 2>(p, td, th, tw, st);
-    return launch_fwd<5, 4>(p, td, th, tw, st);
-}
-
-static void wgrad_geom(int N, int D, int H, int W, int k, int cin_p, int cout_p, int* ntiles, int* n_ci_t,
-                       int* n_co_t, int* gz, int* gx, int* bt) {
-    int td, th, tw;
-    pick_tile(W, &td, &th, &tw);
-    *ntiles = N * ceil_div(D, td) * ceil_div(H, th) * ceil_div(W, tw);
-    *n_ci_t = ceil_div(cin_p, 16);
-    *n_co_t = ceil_div(cout_p, 16);
-    *gz = (k == 3) ? 1 : 5;
-    *bt = (k == 3) ? 27 : 25;
-    *gx = wgrad_gx(*ntiles, (*n_ci_t) * (*n_co_t) * (*gz));
+    if (r.nt == 1) return launch_fwd<5, 1>(p, r, st);
+    if (r.nt == 2) return launch_fwd<5, 2>(p, r, st);
+    return launch_fwd<5, 4>(p, r, st);
 }
 
 extern "C" int ctu_channel_sum_num_blocks(int64_t nvox);
 
 extern "C" size_t ctu_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int k, int cin_p, int cout_p) {
     if (k != 3 && k != 5) return 0;
-    int ntiles, nci, nco, gz, gx, bt;
-    wgrad_geom(N, D, H, W, k, cin_p, cout_p, &ntiles, &nci, &nco, &gz, &gx, &bt);
-    size_t slabs = (size_t)gz * nci * nco * gx * bt * 256;
-    if (use_k3s(k, W, cin_p, cout_p)) {
-        const K3sGeom g = k3s_geom(N, D, H, W, cin_p, cout_p);
-        slabs = (size_t)g.pairs * g.gx * g.nmf * 256;
-    }
-    if (use_k5s(k, W, cin_p, cout_p)) {
-        const K3sGeom g = k5s_geom(N, D, H, W, cin_p, cout_p);
-        slabs = (size_t)5 * g.pairs * g.gx * g.nmf * 256;
-    }
+    const size_t slabs = wgrad_plan(N, D, H, W, k, cin_p, cout_p).slabs;
     const size_t bsum = (size_t)ctu_channel_sum_num_blocks((int64_t)N * D * H * W) * cout_p;
     return slabs > bsum ? slabs : bsum;
 }
 
+template <int SM, int SN>
+static int launch_wgrad_k3s(const WgP& p, const WgPlan& r, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
+    if (p.lz_y) conv3d_wgrad_k3s_kernel<SM, SN, 0, true><<<dim3(r.grid.gx, r.pairs), 256, 0, st>>>(p, r.grid.tpb);
+    else conv3d_wgrad_k3s_kernel<SM, SN><<<dim3(r.grid.gx, r.pairs), 256, 0, st>>>(p, r.grid.tpb);
+    CTU_CHECK_LAUNCH("conv3d_wgrad_k3s");
+    conv3d_wgrad_k3s_reduce_kernel<SM, SN><<<dim3(ceil_div(r.nmf * 256, 64), r.pairs), 64 * RPARTS, 0, st>>>(
+        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, r.grid.gx);
+    CTU_CHECK_LAUNCH("conv3d_wgrad_k3s_reduce");
+    return CTU_OK;
+}
+
+template <int SM, int SN>
+static int launch_wgrad_k5s(const WgP& p, const WgPlan& r, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
+    conv3d_wgrad_k5s_kernel<SM, SN><<<dim3(r.grid.gx, r.pairs, 5), 256, 0, st>>>(p, r.grid.tpb);
+    CTU_CHECK_LAUNCH("conv3d_wgrad_k5s");
+    conv3d_wgrad_k5s_reduce_kernel<SM, SN><<<dim3(ceil_div(r.nmf * 256, 64), r.pairs, 5), 64 * RPARTS, 0, st>>>(
+        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, r.grid.gx);
+    CTU_CHECK_LAUNCH("conv3d_wgrad_k5s_reduce");
+    return CTU_OK;
+}
+
 template <int KS, int KDS>
-static int launch_wgrad(WgP p, float* dw, int Co, int Ci, const int32_t* cinv, int gz, int gx, hipStream_t st) {
-    int td, th, tw;
-    pick_tile(p.W, &td, &th, &tw);
-    p.tiles_d = ceil_div(p.D, td); p.tiles_h = ceil_div(p.H, th); p.tiles_w = ceil_div(p.W, tw);
-    dim3 grid(gx, p.n_ci_t * p.n_co_t, gz);
-    if (tw == 16) conv3d_wgrad_kernel<KS, KDS, 4, 4, 16><<<grid, 256, 0, st>>>(p);
-    else if (tw == 8) conv3d_wgrad_kernel<KS, KDS, 4, 8, 8><<<grid, 256, 0, st>>>(p);
+static int launch_wgrad(const WgP& p, const WgPlan& r, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
+    const dim3 grid(r.grid.gx, r.pairs, r.planes);
+    if (r.tw == 16) conv3d_wgrad_kernel<KS, KDS, 4, 4, 16><<<grid, 256, 0, st>>>(p);
+    else if (r.tw == 8) conv3d_wgrad_kernel<KS, KDS, 4, 8, 8><<<grid, 256, 0, st>>>(p);
     else conv3d_wgrad_kernel<KS, KDS, 4, 4, 4><<<grid, 256, 0, st>>>(p);
     CTU_CHECK_LAUNCH("conv3d_wgrad");
-    constexpr int BT = KDS * KS * KS;
-    const int n_pairs = p.n_ci_t * p.n_co_t;
-    conv3d_wgrad_reduce_kernel<KS, KDS><<<dim3(ceil_div(BT * 256, 64), gz * n_pairs), 64 * RPARTS, 0, st>>>(
-        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, gx);
+    conv3d_wgrad_reduce_kernel<KS, KDS><<<dim3(ceil_div(r.nmf * 256, 64), r.planes * r.pairs), 64 * RPARTS, 0, st>>>(
+        p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, r.grid.gx);
     CTU_CHECK_LAUNCH("conv3d_wgrad_reduce");
     return CTU_OK;
 }
@@ -2542,32 +2467,22 @@ static int conv3d_wgrad_impl(const float* in, int in_cs, int cin_p, const float*
     p.N = N; p.D = D; p.H = H; p.W = W;
     p.lz_y = nullptr; p.lz_out = nullptr; p.lz_scale = nullptr; p.lz_shift = nullptr; p.lz_coef = nullptr; p.lz_cp = 0;
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; p.lz_cp = lz->cp; }
-    int gz, gx, bt;
-    wgrad_geom(N, D, H, W, k, cin_p, cout_p, &p.ntiles, &p.n_ci_t, &p.n_co_t, &gz, &gx, &bt);
-    if (use_k3s(k, W, cin_p, cout_p)) {
-        // persistent, software-pipelined kernel; 8-channel sides use (shift, channel) MFMA tiles.
-        // Workspace need is at most the generic bound.
-        int rc2;
-        if (cin_p == 8 && cout_p == 8) rc2 = launch_wgrad_k3s<2, 2>(p, dw, Co, Ci, cinv, st);
-        else if (cout_p == 8) rc2 = launch_wgrad_k3s<1, 2>(p, dw, Co, Ci, cinv, st);
-        else if (cin_p == 8) rc2 = launch_wgrad_k3s<2, 1>(p, dw, Co, Ci, cinv, st);
-        else rc2 = launch_wgrad_k3s<1, 1>(p, dw, Co, Ci, cinv, st);
-        if (rc2 != CTU_OK) return rc2;
-        if (dbias) return ctu_channel_sum(gout, g_cs, cout_p, (int64_t)N * D * H * W, ws, dbias, Co, stream);
-        return CTU_OK;
-    }
-    if (use_k5s(k, W, cin_p, cout_p)) {
+    const WgPlan r = wgrad_plan(N, D, H, W, k, cin_p, cout_p);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
+    p.ntiles = r.ntiles; p.n_ci_t = r.n_ci_g; p.n_co_t = r.n_co_t;
+    int rc;
+    if (r.kind == WG_K3S) {
+        // persistent, software-pipelined kernel; 8-channel sides use (shift, channel) MFMA tiles
+        if (r.sm == 2 && r.sn == 2) rc = launch_wgrad_k3s<2, 2>(p, r, dw, Co, Ci, cinv, st);
+        else if (r.sn == 2) rc = launch_wgrad_k3s<1, 2>(p, r, dw, Co, Ci, cinv, st);
+        else if (r.sm == 2) rc = launch_wgrad_k3s<2, 1>(p, r, dw, Co, Ci, cinv, st);
+        else rc = launch_wgrad_k3s<1, 1>(p, r, dw, Co, Ci, cinv, st);
+    } else if (r.kind == WG_K5S) {
         CTU_REQUIRE((int64_t)((4 + 2 * 2) * H + 8) * W * in_cs * 4 < (int64_t)1 << 31, "conv3d_wgrad: volume too large for 32-bit offsets");
-        int rc2;
-        if (cin_p == 8 && cout_p == 8) rc2 = launch_wgrad_k5s<2, 2>(p, dw, Co, Ci, cinv, st);
-        else if (cout_p == 8) rc2 = launch_wgrad_k5s<1, 2>(p, dw, Co, Ci, cinv, st);
-        else rc2 = launch_wgrad_k5s<2, 1>(p, dw, Co, Ci, cinv, st);
-        if (rc2 != CTU_OK) return rc2;
-        if (dbias) return ctu_channel_sum(gout, g_cs, cout_p, (int64_t)N * D * H * W, ws, dbias, Co, stream);
-        return CTU_OK;
-    }
-    int rc = (k == 3) ? launch_wgrad<3, 3>(p, dw, Co, Ci, cinv, gz, gx, st)
-                      : launch_wgrad<5, 1>(p, dw, Co, Ci, cinv, gz, gx, st);
+        if (r.sm == 2 && r.sn == 2) rc = launch_wgrad_k5s<2, 2>(p, r, dw, Co, Ci, cinv, st);
+        else if (r.sn == 2) rc = launch_wgrad_k5s<1, 2>(p, r, dw, Co, Ci, cinv, st);
+        else rc = launch_wgrad_k5s<2, 1>(p, r, dw, Co, Ci, cinv, st);
+    } else rc = (k == 3) ? launch_wgrad<3, 3>(p, r, dw, Co, Ci, cinv, st) : launch_wgrad<5, 1>(p, r, dw, Co, Ci, cinv, st);
     if (rc != CTU_OK) return rc;
     if (dbias) return ctu_channel_sum(gout, g_cs, cout_p, (int64_t)N * D * H * W, ws, dbias, Co, stream);
     return CTU_OK;
@@ -2575,8 +2490,7 @@ static int conv3d_wgrad_impl(const float* in, int in_cs, int cin_p, const float*
 
 // ---- fused decoder up-convolution: weight gradient w.r.t. the composite weights (see upconv_fused.hip)
 extern "C" size_t ctu_upconv_fused_wgrad_ws_floats(int N, int D, int H, int W, int cin_p, int nout_p) {
-    const UpWgGeom a = upwg_geom(N, D, H, W, cin_p, nout_p, false), b = upwg_geom(N, D, H, W, cin_p, nout_p, true);
-    const size_t na = (size_t)a.pairs * a.gx * a.nmf * 256, nb = (size_t)b.pairs * b.gx * b.nmf * 256;
+    const size_t na = upwg_plan(N, D, H, W, cin_p, nout_p, false).slabs, nb = upwg_plan(N, D, H, W, cin_p, nout_p, true).slabs;
     return na > nb ? na : nb;                            // either tiling (the w-parity tile needs nout_p = 8 = g_cs)
 }
 
@@ -2619,7 +2533,7 @@ static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const 
                 "upconv_fused_wgrad: volume too large for 32-bit offsets");
     hipStream_t st = (hipStream_t)stream;
     const bool pw = nout_p == 8 && g_cs == 8;             // (w-parity, c_out) tile: the two fine voxels are 16 contiguous floats
-    const UpWgGeom g = upwg_geom(N, D, H, W, cin_p, nout_p, pw);
+    const UpWgPlan g = upwg_plan(N, D, H, W, cin_p, nout_p, pw);
     WgP p;
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.g = gout; p.ws = ws;
     p.in_cs = in_cs; p.cin_p = cin_p; p.in_relu = in_relu; p.g_cs = g_cs; p.cout_p = nout_p;
@@ -2630,17 +2544,17 @@ static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const 
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; p.lz_cp = lz->cp; }
     if (pw) {
         p.cout_p = 16;                                   // all 4 channel quads of the (w-parity, c_out) tile are real
-        if (lz) conv3d_wgrad_k3s_kernel<1, 1, 2, true><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
-        else conv3d_wgrad_k3s_kernel<1, 1, 2><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
+        if (lz) conv3d_wgrad_k3s_kernel<1, 1, 2, true><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
+        else conv3d_wgrad_k3s_kernel<1, 1, 2><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
         CTU_CHECK_LAUNCH("upconv_fused_wgrad(pw)");
-        upconv_wgrad_reduce_pw_kernel<<<dim3(12 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, g.n_ci_g, g.gx);
+        upconv_wgrad_reduce_pw_kernel<<<dim3(12 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, g.n_ci_g, g.grid.gx);
         CTU_CHECK_LAUNCH("upconv_fused_wgrad_reduce(pw)");
         return CTU_OK;
     }
-    if (lz) conv3d_wgrad_k3s_kernel<1, 1, 1, true><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
-    else conv3d_wgrad_k3s_kernel<1, 1, 1><<<dim3(g.gx, g.pairs), 256, 0, st>>>(p, g.tpb);
+    if (lz) conv3d_wgrad_k3s_kernel<1, 1, 1, true><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
+    else conv3d_wgrad_k3s_kernel<1, 1, 1><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
     CTU_CHECK_LAUNCH("upconv_fused_wgrad");
-    upconv_wgrad_reduce_kernel<<<dim3(8 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, nout_p, g.n_ci_g, g.n_co_g, g.gx);
+    upconv_wgrad_reduce_kernel<<<dim3(8 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, nout_p, g.n_ci_g, g.n_co_g, g.grid.gx);
     CTU_CHECK_LAUNCH("upconv_fused_wgrad_reduce");
     return CTU_OK;
 }

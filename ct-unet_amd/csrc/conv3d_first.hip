@@ -396,18 +396,15 @@ __global__ __launch_bounds__(1024) void first_wgrad_reduce_kernel(const float* _
     if (r < 27 * CIN && co < Co) dw[((size_t)co * CIN + ci) * 27 + tap] = tot;
 }
 
-void grid_for(int ntiles, int per_cu, int* gx, int* tpb) {
-    int g = 256 * per_cu;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
+// resident blocks per CU of the three kernels (x 256 CUs: the cap of their persistent grids)
+constexpr int FWD_PER_CU = 4, DGRAD_PER_CU = 3, WGRAD_PER_CU = 5;
 
-int fill(FirstP& p, int N, int D, int H, int W, int TW) {
+// the 4 x 4 x 32 boxes of a volume and the grid of a kernel over them
+Grid fill(FirstP& p, int N, int D, int H, int W, int per_cu) {
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, TD); p.tiles_h = ceil_div(H, TH); p.tiles_w = ceil_div(W, TW);
+    p.tiles_d = ceil_div(D, TD); p.tiles_h = ceil_div(H, TH); p.tiles_w = ceil_div(W, 32);
     p.ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-    return p.ntiles;
+    return persist_grid(p.ntiles, 256 * per_cu);
 }
 
 }  // namespace
@@ -419,9 +416,7 @@ extern "C" int ctu_conv3d_first_supported(int k, int cin, int nout_p, int W) {
 
 extern "C" int ctu_conv3d_first_num_blocks(int N, int D, int H, int W) {
     FirstP p;
-    int gx, tpb;
-    grid_for(fill(p, N, D, H, W, 32), 4, &gx, &tpb);
-    return gx;
+    return fill(p, N, D, H, W, FWD_PER_CU).gx;
 }
 
 namespace {
@@ -437,8 +432,7 @@ int first_fwd_impl(const float* x, int cin, const float* w, const float* bias, i
     CTU_REQUIRE(out_cs >= 8 && out_cs % 4 == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0, "conv3d_first_fwd: output slice alignment");
     FirstP p{};
     p.x = x; p.w = w; p.bias = bias; p.nbias = bias ? nbias : 0; p.out = out; p.out_cs = out_cs; p.Co = Co; p.stats = stats;
-    int gx, tpb;
-    grid_for(fill(p, N, D, H, W, 32), 4, &gx, &tpb);
+    const auto [gx, tpb] = fill(p, N, D, H, W, FWD_PER_CU);
     if (cin == 1) first_fwd_kernel<1, T><<<gx, 256, 0, (hipStream_t)stream>>>(p, tpb, tail_or_off(tail));
     else first_fwd_kernel<2, T><<<gx, 256, 0, (hipStream_t)stream>>>(p, tpb, tail_or_off(tail));
     CTU_CHECK_LAUNCH("conv3d_first_fwd");
@@ -452,8 +446,7 @@ int first_bwd_data_impl(const T* g, int g_cs, const float* w, int cin, int Co, f
                 "conv3d_first_bwd_data: bad argument");
     FirstP p{};
     p.g = g; p.g_cs = g_cs; p.w = w; p.out = dx; p.Co = Co;
-    int gx, tpb;
-    grid_for(fill(p, N, D, H, W, 32), 3, &gx, &tpb);
+    const auto [gx, tpb] = fill(p, N, D, H, W, DGRAD_PER_CU);
     if (cin == 1) first_bwd_data_kernel<1, T><<<gx, 256, 0, (hipStream_t)stream>>>(p, tpb);
     else first_bwd_data_kernel<2, T><<<gx, 256, 0, (hipStream_t)stream>>>(p, tpb);
     CTU_CHECK_LAUNCH("conv3d_first_bwd_data");
@@ -471,8 +464,7 @@ int first_wgrad_impl(const float* x, int cin, const T* g, int g_cs, float* dw, i
     FirstP p{};
     p.x = x; p.g = g; p.g_cs = g_cs; p.ws = ws; p.Co = Co;
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; }
-    int gx, tpb;
-    grid_for(fill(p, N, D, H, W, 32), 5, &gx, &tpb);
+    const auto [gx, tpb] = fill(p, N, D, H, W, WGRAD_PER_CU);
     hipStream_t st = (hipStream_t)stream;
     if (cin == 1) {
         if constexpr (std::is_same<T, float>::value) {
@@ -513,9 +505,7 @@ extern "C" int ctu_lp_conv3d_first_bwd_data(int dtype, const void* g, int g_cs, 
 
 extern "C" size_t ctu_conv3d_first_wgrad_ws_floats(int N, int D, int H, int W, int cin) {
     FirstP p;
-    int gx, tpb;
-    grid_for(fill(p, N, D, H, W, 32), 5, &gx, &tpb);
-    return (size_t)gx * ((27 * cin + 15) / 16) * 256;
+    return (size_t)fill(p, N, D, H, W, WGRAD_PER_CU).gx * ((27 * cin + 15) / 16) * 256;
 }
 
 extern "C" int ctu_conv3d_first_wgrad(const float* x, int cin, const float* g, int g_cs, float* dw, int Co, float* ws, int N,

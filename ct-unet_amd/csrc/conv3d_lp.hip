@@ -1165,14 +1165,6 @@ __global__ __launch_bounds__(256, 3) void lp_conv_fwd_pair_kernel(LpConvP p, int
 }
 
 inline bool lp_use_pair(int k, int rin_p, int nout_p, int W) { return k == 3 && rin_p == 8 && nout_p == 8 && W >= 32; }
-inline int lp_pair_ntiles(int N, int D, int H, int W) { return N * ceil_div(D, 4) * ceil_div(H, LPP_TH) * ceil_div(W, LPP_BW); }
-inline void lp_pair_grid(int ntiles, int* gx, int* tpb) {
-    int g = 768;                                                    // 3 blocks per CU
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
 struct LpBox { int th, bw; };
 
 // box of a forward / data-gradient launch: bigger boxes for thin voxels (see lp_conv_fwd_kernel)
@@ -1188,27 +1180,47 @@ LpBox lp_box(int W, int rin_p, int64_t nvox) {
     return {4, 16};
 }
 
-int lp_fill(LpConvP& p, int N, int D, int H, int W, int rin_p) {
-    const LpBox bx = lp_box(W, rin_p, (int64_t)N * D * H * W);
-    p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, bx.th); p.tiles_w = ceil_div(W, bx.bw);
-    return N * p.tiles_d * p.tiles_h * p.tiles_w;
-}
+// The route of a 16-bit forward / data-gradient launch: ctu_lp_conv3d_num_blocks, ctu_lp_conv3d_fwd_kernel_name and the
+// launches all read this one plan.  Boxes are 4 x th x bw voxels; nt = out tiles per block, ny = blocks in y.
+enum LpFwdKind { LP_FWD_PAIR, LP_FWD_PERSIST, LP_FWD_SMALL, LP_FWD_BOX };
+struct LpFwdPlan {
+    LpFwdKind kind;
+    int th, bw, tiles_d, tiles_h, tiles_w, ntiles, nt, ny;
+    Grid grid;
+    const char* name;
+};
 
-// persistent single-stage kernel: k = 3, one stage, enough boxes to give every CU a few
-bool lp_use_persist(int k, int rin_p, int ntiles) { return k == 3 && rin_p <= LP_SC && ntiles >= 1024; }
-
-void lp_persist_grid(int ntiles, int* gx, int* tpb) {
-    int g = 512;                                                    // 2 blocks per CU
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
+LpFwdPlan lp_fwd_plan(int N, int D, int H, int W, int k, int rin_p, int nout_p, int layout) {
+    LpFwdPlan r;
+    const LpBox bx = layout == 1 ? LpBox{LPP_TH, LPP_BW} : lp_box(W, rin_p, (int64_t)N * D * H * W);
+    r.th = bx.th; r.bw = bx.bw;
+    r.tiles_d = ceil_div(D, 4); r.tiles_h = ceil_div(H, bx.th); r.tiles_w = ceil_div(W, bx.bw);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    // two out tiles per block share one staged box -- unless that leaves CUs idle (small volumes: one tile per block)
+    r.nt = (layout == 0 && nout_p > 16 && (int64_t)r.ntiles * ceil_div((nout_p + 15) >> 4, 2) >= 256) ? 2 : 1;
+    r.ny = layout == 1 ? 1 : ceil_div((nout_p + 15) >> 4, r.nt);
+    if (layout == 1) {
+        r.kind = LP_FWD_PAIR;
+        r.name = "lp_conv_fwd_pair_kernel";
+        r.grid = persist_grid(r.ntiles, 768);                       // 3 blocks per CU
+    } else if (k == 3 && rin_p <= LP_SC && r.ntiles >= 1024 && bx.bw == 16) {
+        // persistent single-stage kernel: k = 3, one stage, enough boxes to give every CU a few
+        r.kind = LP_FWD_PERSIST;
+        r.name = "lp_conv_fwd_p1_kernel";
+        r.grid = persist_grid(r.ntiles, 512);                       // 2 blocks per CU
+    } else {
+        const bool small = k == 3 && bx.th == 4 && bx.bw == 8;      // the deep levels
+        r.kind = small ? LP_FWD_SMALL : LP_FWD_BOX;
+        r.name = small ? "lp_conv_fwd_small_kernel" : "lp_conv_fwd_kernel";
+        r.grid = {r.ntiles, 1};
+    }
+    return r;
 }
 
 int lp_voxel_stride(int rin_p) { return rin_p >= 16 ? (rin_p >= LP_SC ? LP_SC : rin_p) * 2 + 16 : 16; }
 
 template <class T, int KS, int NT, int TH, int BW, bool WG>
-int lp_conv_launch_box_wg(LpConvP& p, int ntiles, hipStream_t st) {
+int lp_conv_launch_box_wg(LpConvP& p, const LpFwdPlan& r, hipStream_t st) {
     constexpr int PK = (KS - 1) / 2;
     const int hv = (4 + 2 * PK) * (TH + 2 * PK) * (BW + 2 * PK);
     const int nch_max = (p.rin_p >= LP_SC ? LP_SC : p.rin_p) >> 3;
@@ -1217,16 +1229,10 @@ int lp_conv_launch_box_wg(LpConvP& p, int ntiles, hipStream_t st) {
     const size_t wlds = WG ? (size_t)(KS == 3 ? ks_max : (ks_max < 25 ? ks_max : 25)) * NT * 1024 : 0;
     const size_t lds = 2048 + 256 + 4 * NT * 32 * 4 + (size_t)hv * p.S + wlds;
     CTU_REQUIRE(lds <= 160 * 1024, "lp_conv3d_fwd: LDS box of %zu bytes", lds);
-    const int n16 = (p.nout_p + 15) >> 4;
-    const dim3 grid(ntiles, ceil_div(n16, NT));
-    // the dynamic-LDS limit is raised only for launches that need more than the default 64 KB, and only to what they need
     static size_t raised = 64 * 1024;
-    if (lds > raised) {
-        CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_conv_fwd_kernel<T, KS, NT, TH, BW, WG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                    "lp_conv3d_fwd: cannot raise the dynamic LDS limit");
-        raised = lds;
-    }
-    lp_conv_fwd_kernel<T, KS, NT, TH, BW, WG><<<grid, 256, lds, st>>>(p);
+    const int rc = raise_lds(lp_conv_fwd_kernel<T, KS, NT, TH, BW, WG>, lds, &raised, "lp_conv3d_fwd");
+    if (rc != CTU_OK) return rc;
+    lp_conv_fwd_kernel<T, KS, NT, TH, BW, WG><<<dim3(r.grid.gx, r.ny), 256, lds, st>>>(p);
     CTU_CHECK_LAUNCH("lp_conv3d_fwd");
     return CTU_OK;
 }
@@ -1234,64 +1240,49 @@ int lp_conv_launch_box_wg(LpConvP& p, int ntiles, hipStream_t st) {
 // k = 3: the stage's weights always sit in LDS.  k = 5: weight groups through LDS when a K-step carries few MFMAs and the box
 // already limits the block to one or two per CU (one out tile per block, >= 2 chunks per voxel); the register ring otherwise.
 template <class T, int KS, int NT, int TH, int BW>
-int lp_conv_launch_box(LpConvP& p, int ntiles, hipStream_t st) {
-    if constexpr (KS == 3) return lp_conv_launch_box_wg<T, KS, NT, TH, BW, true>(p, ntiles, st);
+int lp_conv_launch_box(LpConvP& p, const LpFwdPlan& r, hipStream_t st) {
+    if constexpr (KS == 3) return lp_conv_launch_box_wg<T, KS, NT, TH, BW, true>(p, r, st);
     else {
         const int nch_max = (p.rin_p >= LP_SC ? LP_SC : p.rin_p) >> 3;
-        if (NT == 1 && nch_max >= 2) return lp_conv_launch_box_wg<T, KS, NT, TH, BW, true>(p, ntiles, st);
-        return lp_conv_launch_box_wg<T, KS, NT, TH, BW, false>(p, ntiles, st);
+        if (NT == 1 && nch_max >= 2) return lp_conv_launch_box_wg<T, KS, NT, TH, BW, true>(p, r, st);
+        return lp_conv_launch_box_wg<T, KS, NT, TH, BW, false>(p, r, st);
     }
 }
 
 template <class T, int NT, int TH, int BW>
-int lp_conv_launch_persist(LpConvP& p, int ntiles, hipStream_t st) {
+int lp_conv_launch_persist(LpConvP& p, const LpFwdPlan& r, hipStream_t st) {
     const int hv = 6 * (TH + 2) * (BW + 2);
     const size_t lds = 2048 + 256 + 4 * NT * 32 * 4 + (size_t)hv * p.S + (size_t)lp_ksteps(27, p.rin_p >> 3) * NT * 1024;
     CTU_REQUIRE(lds <= 160 * 1024, "lp_conv3d_fwd: LDS box of %zu bytes", lds);
-    int gx, tpb;
-    lp_persist_grid(ntiles, &gx, &tpb);
-    const int n16 = (p.nout_p + 15) >> 4;
     static size_t raised = 64 * 1024;
-    if (lds > raised) {
-        CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_conv_fwd_p1_kernel<T, NT, TH, BW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds) == hipSuccess, "lp_conv3d_fwd: cannot raise the dynamic LDS limit");
-        raised = lds;
-    }
-    lp_conv_fwd_p1_kernel<T, NT, TH, BW><<<dim3(gx, ceil_div(n16, NT)), 256, lds, st>>>(p, ntiles, tpb);
+    const int rc = raise_lds(lp_conv_fwd_p1_kernel<T, NT, TH, BW>, lds, &raised, "lp_conv3d_fwd");
+    if (rc != CTU_OK) return rc;
+    lp_conv_fwd_p1_kernel<T, NT, TH, BW><<<dim3(r.grid.gx, r.ny), 256, lds, st>>>(p, r.ntiles, r.grid.tpb);
     CTU_CHECK_LAUNCH("lp_conv3d_fwd (persistent)");
     return CTU_OK;
 }
 
+template <class T, int NT>
+int lp_conv_launch_small(LpConvP& p, const LpFwdPlan& r, hipStream_t st) {
+    const size_t lds = 2048 + 256 + 4 * NT * 32 * 4 + (size_t)(6 * 6 * 10) * p.S + (size_t)27 * NT * 1024;
+    static size_t raised = 64 * 1024;
+    const int rc = raise_lds(lp_conv_fwd_small_kernel<T, NT>, lds, &raised, "lp_conv3d_fwd");
+    if (rc != CTU_OK) return rc;
+    lp_conv_fwd_small_kernel<T, NT><<<dim3(r.grid.gx, r.ny), 256, lds, st>>>(p);
+    CTU_CHECK_LAUNCH("lp_conv3d_fwd (deep level)");
+    return CTU_OK;
+}
+
+// the template instantiation of a layout-0 plan (lp_box never returns a 32-wide box: tests/test_routes_cpu.py)
 template <class T, int KS, int NT>
-int lp_conv_launch(LpConvP& p, int ntiles, hipStream_t st) {
-    const LpBox bx = lp_box(p.W, p.rin_p, (int64_t)p.N * p.D * p.H * p.W);
+int lp_conv_launch(LpConvP& p, const LpFwdPlan& r, hipStream_t st) {
     if constexpr (KS == 3) {
-        if (lp_use_persist(3, p.rin_p, ntiles)) {
-            if (bx.bw == 32) return lp_conv_launch_persist<T, NT, 8, 32>(p, ntiles, st);
-            if (bx.th == 8 && bx.bw == 16) return lp_conv_launch_persist<T, NT, 8, 16>(p, ntiles, st);
-            if (bx.bw == 16) return lp_conv_launch_persist<T, NT, 4, 16>(p, ntiles, st);
-        }
+        if (r.kind == LP_FWD_PERSIST)
+            return r.th == 8 ? lp_conv_launch_persist<T, NT, 8, 16>(p, r, st) : lp_conv_launch_persist<T, NT, 4, 16>(p, r, st);
+        if (r.kind == LP_FWD_SMALL) return lp_conv_launch_small<T, NT>(p, r, st);
     }
-    if (bx.bw == 32) return lp_conv_launch_box<T, KS, NT, 8, 32>(p, ntiles, st);
-    if (bx.bw == 8 && bx.th == 4) {
-        if constexpr (KS == 3) {
-            const size_t lds = 2048 + 256 + 4 * NT * 32 * 4 + (size_t)(6 * 6 * 10) * p.S + (size_t)27 * NT * 1024;
-            const int n16 = (p.nout_p + 15) >> 4;
-            static size_t raised = 64 * 1024;
-            if (lds > raised) {
-                CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_conv_fwd_small_kernel<T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)lds) == hipSuccess, "lp_conv3d_fwd: cannot raise the dynamic LDS limit");
-                raised = lds;
-            }
-            lp_conv_fwd_small_kernel<T, NT><<<dim3(ntiles, ceil_div(n16, NT)), 256, lds, st>>>(p);
-            CTU_CHECK_LAUNCH("lp_conv3d_fwd (deep level)");
-            return CTU_OK;
-        }
-        return lp_conv_launch_box<T, KS, NT, 4, 8>(p, ntiles, st);
-    }
-    if (bx.bw == 8) return lp_conv_launch_box<T, KS, NT, 8, 8>(p, ntiles, st);
-    if (bx.th == 8) return lp_conv_launch_box<T, KS, NT, 8, 16>(p, ntiles, st);
-    return lp_conv_launch_box<T, KS, NT, 4, 16>(p, ntiles, st);
+    if (r.bw == 8) return r.th == 4 ? lp_conv_launch_box<T, KS, NT, 4, 8>(p, r, st) : lp_conv_launch_box<T, KS, NT, 8, 8>(p, r, st);
+    return r.th == 8 ? lp_conv_launch_box<T, KS, NT, 8, 16>(p, r, st) : lp_conv_launch_box<T, KS, NT, 4, 16>(p, r, st);
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradient
@@ -2042,24 +2033,10 @@ __global__ __launch_bounds__(256, 1) void lp_wgrad16_kernel(LpWgP p, int tiles_p
 inline bool lp_wg16_ok(int D, int H, int W, int k, int cin_p, int cout_p) {
     return k == 3 && cin_p >= 16 && cout_p >= 16 && D % 4 == 0 && H % 8 == 0 && W >= 32 && W % 8 == 0;     // (last w box may be partial)
 }
-inline void lp_wg16_grid(int ntiles, int pairs, int* gx, int* tpb) {
-    int g = 256 / pairs;
-    if (g < 8) g = 8;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
 // the geometries lp_wgrad8_kernel takes
 inline bool lp_wg8_ok(int D, int H, int W, int k, int cin_p, int cout_p) {
     return k == 3 && cin_p == 8 && cout_p == 8 && D % 4 == 0 && H % 8 == 0 && W % 32 == 0;
 }
-inline void lp_wg8_grid(int ntiles, int* gx, int* tpb) {
-    int g = ntiles < 512 ? ntiles : 512;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
 // dw[co][ci][tap] (torch layout) = sum over the gx slabs of (pair, plane); 16 slab groups x 64 elements per block
 template <int KS, int SM, int SN>
 __global__ __launch_bounds__(1024) void lp_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Co, int Ci,
@@ -2106,14 +2083,6 @@ __global__ __launch_bounds__(1024) void lp_wgrad_reduce_kernel(const float* __re
 
 int lp_wg_box_w(int W) { return W >= 32 ? 32 : (W >= 16 ? 16 : 8); }
 
-int lp_wg_fill(LpWgP& p, int N, int D, int H, int W) {
-    const int bw = lp_wg_box_w(W), th = 4 * (32 / bw);
-    p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, th); p.tiles_w = ceil_div(W, bw);
-    p.ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-    return p.ntiles;
-}
-
 // persistent blocks per (pair, plane): about 768 blocks in all (3 per CU), at least 1 box each -- and at least LP_WG_MINBOX
 // boxes each while that still leaves one block per CU: a block's fixed costs (the first box's exposed loads, the cross-wave
 // reduction and its slab, which the reduce kernel reads back) are those of several boxes' MFMAs
@@ -2129,47 +2098,82 @@ int lp_wg_fill(LpWgP& p, int N, int D, int H, int W) {
 #ifndef LP_WG8
 #define LP_WG8 1               // 8 -> 8 padded channels, k = 3, box-multiple volumes: lp_wgrad8_kernel (0: the generic kernel)
 #endif
-void lp_wg_grid(int ntiles, int groups, int* gx, int* tpb) {
+int lp_wg_cap(int ntiles, int groups) {
     int g = 768 / groups;
     if (g < 16) g = 16;
     if (g * LP_WG_MINBOX > ntiles && ntiles / LP_WG_MINBOX * groups >= 256) g = ntiles / LP_WG_MINBOX;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
+    return g;
+}
+
+// The route of a 16-bit weight-gradient launch: ctu_lp_conv3d_wgrad_ws_floats, ctu_lp_conv3d_wgrad_kernel_name and the launch
+// read this one plan.  Boxes are 4 x th x bw voxels; ntap 16 x 16 tiles per (pair, plane) slab; the reduce kernel is
+// lp_wgrad_reduce_kernel<k, sm, sn> for every route.
+enum LpWgKind { LP_WG_K8, LP_WG_K16, LP_WG_GENERIC };
+struct LpWgPlan {
+    LpWgKind kind;
+    int bw, sm, sn, tiles_d, tiles_h, tiles_w, ntiles, pairs, planes, ntap;
+    Grid grid;
+    size_t ws_floats;
+    const char* name;
+};
+
+LpWgKind lp_wg_kind(int D, int H, int W, int k, int cin_p, int cout_p) {
+    if (LP_WG8 && lp_wg8_ok(D, H, W, k, cin_p, cout_p)) return LP_WG_K8;
+    return (LP_WG16 && lp_wg16_ok(D, H, W, k, cin_p, cout_p)) ? LP_WG_K16 : LP_WG_GENERIC;
+}
+
+LpWgPlan lp_wg_plan(LpWgKind kind, int N, int D, int H, int W, int k, int cin_p, int cout_p) {
+    LpWgPlan r;
+    r.kind = kind;
+    r.bw = kind == LP_WG_GENERIC ? lp_wg_box_w(W) : 32;
+    const int th = kind == LP_WG_GENERIC ? 4 * (32 / r.bw) : 8;
+    r.tiles_d = ceil_div(D, 4); r.tiles_h = ceil_div(H, th); r.tiles_w = ceil_div(W, r.bw);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    r.pairs = ((cin_p + 15) >> 4) * ((cout_p + 15) >> 4); r.planes = k == 3 ? 1 : k;
+    // 8-channel sides of volumes at least 16 wide take the (w-shift, channel) tiles
+    r.sm = kind == LP_WG_K8 || (kind == LP_WG_GENERIC && W >= 16 && cin_p == 8) ? 2 : 1;
+    r.sn = kind == LP_WG_K8 || (kind == LP_WG_GENERIC && W >= 16 && cout_p == 8) ? 2 : 1;
+    r.ntap = (k == 3 ? 9 : k) * lp_wg_qn(k, r.sm, r.sn);
+    if (kind == LP_WG_K8) {
+        r.grid = persist_grid(r.ntiles, 512);
+        r.name = "lp_wgrad8_kernel";
+    } else if (kind == LP_WG_K16) {
+        r.grid = persist_grid(r.ntiles, 256 / r.pairs < 8 ? 8 : 256 / r.pairs);
+        r.name = "lp_wgrad16_kernel";
+    } else {
+        r.grid = persist_grid(r.ntiles, lp_wg_cap(r.ntiles, r.pairs * r.planes));
+        r.name = "lp_conv_wgrad_kernel";
+    }
+    // (lp_wgrad8_kernel's workspace is sized for its grid cap, not for the grid of the volume)
+    r.ws_floats = (size_t)(kind == LP_WG_K8 ? 512 : r.grid.gx) * r.pairs * r.planes * r.ntap * 256;
+    return r;
 }
 
 template <class T, int KS, int BW, int SM, int SN, bool LZ = false>
-int lp_wgrad_launch(LpWgP& p, int gx, int tpb, int pairs, hipStream_t st) {
+int lp_wgrad_launch(LpWgP& p, const LpWgPlan& r, hipStream_t st) {
     constexpr int PK = (KS - 1) / 2, RPK = 32 / BW, TH = 4 * RPK;
     constexpr int HD = (KS == 3) ? 6 : 4, HV = HD * (TH + 2 * PK) * (BW + 2 * PK), NV = 4 * TH * BW;
     constexpr int NTAP = ((KS == 3) ? 9 : KS) * lp_wg_qn(KS, SM, SN);
     size_t lds = 128 + (size_t)(HV + NV) * WG_SX;
     if (lds < 128 + (size_t)NTAP * 1024) lds = 128 + (size_t)NTAP * 1024;
-    // the dynamic-LDS limit is raised only for launches that need more than the default 64 KB, and only to what they need
     static size_t raised = 64 * 1024;
-    if (lds > raised) {
-        CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_conv_wgrad_kernel<T, KS, BW, SM, SN, 0, LZ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                    "lp_conv3d_wgrad: cannot raise the dynamic LDS limit");
-        raised = lds;
-    }
-    lp_conv_wgrad_kernel<T, KS, BW, SM, SN, 0, LZ><<<dim3(gx, pairs, KS == 3 ? 1 : KS), 256, lds, st>>>(p, tpb);
+    const int rc = raise_lds(lp_conv_wgrad_kernel<T, KS, BW, SM, SN, 0, LZ>, lds, &raised, "lp_conv3d_wgrad");
+    if (rc != CTU_OK) return rc;
+    lp_conv_wgrad_kernel<T, KS, BW, SM, SN, 0, LZ><<<dim3(r.grid.gx, r.pairs, r.planes), 256, lds, st>>>(p, r.grid.tpb);
     CTU_CHECK_LAUNCH("lp_conv3d_wgrad");
     return CTU_OK;
 }
 
 // fused up-convolution (UP = 2): COARSE boxes 4 x TH x BW, blockIdx.y = (p_d, p_h) parity x input-channel tile
 template <class T, int BW, bool LZ = false>
-int lp_upwg_launch(LpWgP& p, int gx, int tpb, hipStream_t st) {
+int lp_upwg_launch(LpWgP& p, Grid grid, hipStream_t st) {
     constexpr int RPK = 32 / BW, TH = 4 * RPK, HV = 6 * (TH + 2) * (BW + 2), NV = 4 * TH * BW;
     size_t lds = 128 + (size_t)(HV + NV) * WG_SX;
     if (lds < 128 + (size_t)12 * 1024) lds = 128 + (size_t)12 * 1024;
     static size_t raised = 64 * 1024;
-    if (lds > raised) {
-        CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_conv_wgrad_kernel<T, 3, BW, 1, 1, 2, LZ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                    "lp_upconv_fused_wgrad: cannot raise the dynamic LDS limit");
-        raised = lds;
-    }
-    lp_conv_wgrad_kernel<T, 3, BW, 1, 1, 2, LZ><<<dim3(gx, 4 * (p.cin_p >> 4)), 256, lds, st>>>(p, tpb);
+    const int rc = raise_lds(lp_conv_wgrad_kernel<T, 3, BW, 1, 1, 2, LZ>, lds, &raised, "lp_upconv_fused_wgrad");
+    if (rc != CTU_OK) return rc;
+    lp_conv_wgrad_kernel<T, 3, BW, 1, 1, 2, LZ><<<dim3(grid.gx, 4 * (p.cin_p >> 4)), 256, lds, st>>>(p, grid.tpb);
     CTU_CHECK_LAUNCH("lp_upconv_fused_wgrad");
     return CTU_OK;
 }
@@ -2343,13 +2347,6 @@ __global__ __launch_bounds__(256, 1) void lp_upwg4_kernel(LpWgP p, int tiles_per
     }
 }
 
-inline bool lp_upwg4_ok(int D, int H, int W, int cin_p) { return cin_p % 32 == 0 && D % 4 == 0 && H % 4 == 0 && W % 32 == 0; }
-inline void lp_upwg4_grid(int ntiles, int* gx, int* tpb) {
-    int g = ntiles < 256 ? ntiles : 256;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
 // dW_eff[(pz,py,px)][(dz,dy,dxx-px)][cin_p][8] from the slabs [12 taps][16 ci][16 = (px, co)] (= conv3d.hip's
 // upconv_wgrad_reduce_pw_kernel for the 16-bit kernel's slabs)
 __global__ __launch_bounds__(1024) void lp_upwg_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dweff, int cin_p, int n_ci_g,
@@ -2374,33 +2371,27 @@ __global__ __launch_bounds__(1024) void lp_upwg_reduce_kernel(const float* __res
         dweff[((size_t)((par4 * 2 + px) * 8 + (t / 3) * 2 + jx) * cin_p + rp) * 8 + co] = tot;
 }
 
-// 8-channel sides of volumes at least 16 wide take the (w-shift, channel) tiles
-inline int lp_wg_sm(int W, int cin_p) { return (W >= 16 && cin_p == 8) ? 2 : 1; }
-inline int lp_wg_sn(int W, int cout_p) { return (W >= 16 && cout_p == 8) ? 2 : 1; }
-
 template <class T, int KS, int BW, bool LZ = false>
-int lp_wgrad_launch_s(LpWgP& p, int gx, int tpb, int pairs, hipStream_t st) {
+int lp_wgrad_launch_s(LpWgP& p, const LpWgPlan& r, hipStream_t st) {
     if constexpr (BW >= 16) {
-        const int sm = lp_wg_sm(p.W, p.cin_p), sn = lp_wg_sn(p.W, p.cout_p);
-        if (sm == 2 && sn == 2) return lp_wgrad_launch<T, KS, BW, 2, 2, LZ>(p, gx, tpb, pairs, st);
-        if (sm == 2) return lp_wgrad_launch<T, KS, BW, 2, 1, LZ>(p, gx, tpb, pairs, st);
-        if (sn == 2) return lp_wgrad_launch<T, KS, BW, 1, 2, LZ>(p, gx, tpb, pairs, st);
+        if (r.sm == 2 && r.sn == 2) return lp_wgrad_launch<T, KS, BW, 2, 2, LZ>(p, r, st);
+        if (r.sm == 2) return lp_wgrad_launch<T, KS, BW, 2, 1, LZ>(p, r, st);
+        if (r.sn == 2) return lp_wgrad_launch<T, KS, BW, 1, 2, LZ>(p, r, st);
     }
-    return lp_wgrad_launch<T, KS, BW, 1, 1, LZ>(p, gx, tpb, pairs, st);
+    return lp_wgrad_launch<T, KS, BW, 1, 1, LZ>(p, r, st);
 }
 
 template <class T, int KS>
-int lp_wgrad_dispatch(LpWgP& p, int gx, int tpb, int pairs, hipStream_t st) {
-    const int bw = lp_wg_box_w(p.W);
+int lp_wgrad_dispatch(LpWgP& p, const LpWgPlan& r, hipStream_t st) {
     if constexpr (KS == 3) {
         if (p.lz_y) {                                               // lazy BatchNorm backward (16-wide boxes and wider)
-            if (bw == 32) return lp_wgrad_launch_s<T, 3, 32, true>(p, gx, tpb, pairs, st);
-            return lp_wgrad_launch_s<T, 3, 16, true>(p, gx, tpb, pairs, st);
+            if (r.bw == 32) return lp_wgrad_launch_s<T, 3, 32, true>(p, r, st);
+            return lp_wgrad_launch_s<T, 3, 16, true>(p, r, st);
         }
     }
-    if (bw == 32) return lp_wgrad_launch_s<T, KS, 32>(p, gx, tpb, pairs, st);
-    if (bw == 16) return lp_wgrad_launch_s<T, KS, 16>(p, gx, tpb, pairs, st);
-    return lp_wgrad_launch_s<T, KS, 8>(p, gx, tpb, pairs, st);
+    if (r.bw == 32) return lp_wgrad_launch_s<T, KS, 32>(p, r, st);
+    if (r.bw == 16) return lp_wgrad_launch_s<T, KS, 16>(p, r, st);
+    return lp_wgrad_launch_s<T, KS, 8>(p, r, st);
 }
 
 // lazy BatchNorm backward inside the 16-bit weight-gradient kernel: k = 3, volumes at least 16 wide that are multiples of the box
@@ -2408,6 +2399,24 @@ inline bool lp_wg_lazy_ok(int D, int H, int W, int k) {
     if (k != 3 || W < 16) return false;
     const int bw = lp_wg_box_w(W), th = 4 * (32 / bw);
     return D % 4 == 0 && H % th == 0 && W % bw == 0;
+}
+
+// The route of the fused up-convolution's weight gradient (COARSE dims): lp_upwg4_kernel on box-multiple volumes without the
+// lazy BatchNorm backward, else lp_conv_wgrad_kernel<.., UP = 2>.  Both walk 4 x th x bw boxes with th x bw = 4 x 32 where
+// lp_upwg4_kernel applies; the workspace holds either route's slabs (lp_upwg4_kernel's: sized for its grid cap).
+struct LpUpWgPlan { bool four; int bw, tiles_d, tiles_h, tiles_w, ntiles; Grid grid; size_t ws_floats; };
+
+LpUpWgPlan lp_upwg_plan(int N, int D, int H, int W, int cin_p, bool lazy) {
+    LpUpWgPlan r;
+    const bool four_ok = cin_p % 32 == 0 && D % 4 == 0 && H % 4 == 0 && W % 32 == 0;
+    r.four = LP_UPWG4 && !lazy && four_ok;
+    r.bw = lp_wg_box_w(W);
+    r.tiles_d = ceil_div(D, 4); r.tiles_h = ceil_div(H, 4 * (32 / r.bw)); r.tiles_w = ceil_div(W, r.bw);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    const Grid up2 = persist_grid(r.ntiles, lp_wg_cap(r.ntiles, 4 * (cin_p >> 4)));
+    r.grid = r.four ? persist_grid(r.ntiles, 256) : up2;          // lp_upwg4_kernel: one block per CU (144 KB of LDS)
+    r.ws_floats = (size_t)(four_ok && up2.gx < 256 ? 256 : up2.gx) * 4 * (cin_p >> 4) * 12 * 256;
+    return r;
 }
 
 }  // namespace
@@ -2425,20 +2434,7 @@ extern "C" size_t ctu_lp_conv3d_packed_elems(int k, int rin_p, int nout_p) {
 }
 
 extern "C" int ctu_lp_conv3d_num_blocks(int N, int D, int H, int W, int k, int rin_p, int nout_p, int layout) {
-    if (layout == 1) {
-        int gx, tpb;
-        lp_pair_grid(lp_pair_ntiles(N, D, H, W), &gx, &tpb);
-        return gx;
-    }
-    (void)nout_p;
-    LpConvP p;
-    const int ntiles = lp_fill(p, N, D, H, W, rin_p);
-    if (lp_use_persist(k, rin_p, ntiles) && lp_box(W, rin_p, (int64_t)N * D * H * W).bw >= 16) {
-        int gx, tpb;
-        lp_persist_grid(ntiles, &gx, &tpb);
-        return gx;
-    }
-    return ntiles;
+    return lp_fwd_plan(N, D, H, W, k, rin_p, nout_p, layout).grid.gx;
 }
 
 extern "C" int ctu_lp_pack_conv3d_weight(int dtype, const float* w, void* wp, int Co, int Ci, int k, const int32_t* cinv,
@@ -2484,24 +2480,19 @@ extern "C" int ctu_lp_conv3d_fwd(int dtype, const void* in, int in_cs, int rin_p
     p.in_cs = in_cs; p.rin_p = rin_p; p.relu = in_relu; p.out_cs = out_cs; p.nout_p = nout_p; p.nbias = bias ? nbias : 0;
     p.S = lp_voxel_stride(rin_p);
     hipStream_t st = (hipStream_t)stream;
-    if (layout == 1) {
-        p.N = N; p.D = D; p.H = H; p.W = W;
-        p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, LPP_TH); p.tiles_w = ceil_div(W, LPP_BW);
-        const int nt_ = lp_pair_ntiles(N, D, H, W);
-        int gx, tpb;
-        lp_pair_grid(nt_, &gx, &tpb);
+    const LpFwdPlan r = lp_fwd_plan(N, D, H, W, k, rin_p, nout_p, layout);
+    p.N = N; p.D = D; p.H = H; p.W = W;
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
+    if (r.kind == LP_FWD_PAIR) {
         CTU_REQUIRE((int64_t)(6 * H + 6) * W * in_cs * 2 < (int64_t)1 << 31, "lp_conv3d_fwd: volume too large for 32-bit offsets");
-        CTU_DISPATCH_LP(dtype, lp_conv_fwd_pair_kernel<T><<<gx, 256, LPP_LDS, st>>>(p, nt_, tpb));
+        CTU_DISPATCH_LP(dtype, lp_conv_fwd_pair_kernel<T><<<r.grid.gx, 256, LPP_LDS, st>>>(p, r.ntiles, r.grid.tpb));
         CTU_CHECK_LAUNCH("lp_conv3d_fwd (pair)");
         return CTU_OK;
     }
-    const int ntiles = lp_fill(p, N, D, H, W, rin_p);
-    // two out tiles per block share one staged box -- unless that leaves CUs idle (small volumes: one tile per block)
-    const bool two = nout_p > 16 && (int64_t)ntiles * ceil_div((nout_p + 15) >> 4, 2) >= 256;
     int rc = CTU_OK;
     CTU_DISPATCH_LP(dtype, {
-        if (k == 3) rc = two ? lp_conv_launch<T, 3, 2>(p, ntiles, st) : lp_conv_launch<T, 3, 1>(p, ntiles, st);
-        else rc = two ? lp_conv_launch<T, 5, 2>(p, ntiles, st) : lp_conv_launch<T, 5, 1>(p, ntiles, st);
+        if (k == 3) rc = r.nt == 2 ? lp_conv_launch<T, 3, 2>(p, r, st) : lp_conv_launch<T, 3, 1>(p, r, st);
+        else rc = r.nt == 2 ? lp_conv_launch<T, 5, 2>(p, r, st) : lp_conv_launch<T, 5, 1>(p, r, st);
     });
     return rc;
 }
@@ -2525,13 +2516,11 @@ extern "C" int ctu_lp_conv3d_first_bwd_data_pair(int dtype, const void* g, int g
     p.in = g; p.wp = wp; p.out = dx;
     p.tail = tail_or_off(nullptr);
     p.in_cs = g_cs; p.rin_p = 8; p.relu = 0; p.out_cs = 0; p.nout_p = 8; p.nbias = cin;
+    const LpFwdPlan r = lp_fwd_plan(N, D, H, W, 3, 8, 8, 1);
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, LPP_TH); p.tiles_w = ceil_div(W, LPP_BW);
-    const int nt_ = lp_pair_ntiles(N, D, H, W);
-    int gx, tpb;
-    lp_pair_grid(nt_, &gx, &tpb);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     hipStream_t st = (hipStream_t)stream;
-    CTU_DISPATCH_LP(dtype, (lp_conv_fwd_pair_kernel<T, true><<<gx, 256, LPP_LDS, st>>>(p, nt_, tpb)));
+    CTU_DISPATCH_LP(dtype, (lp_conv_fwd_pair_kernel<T, true><<<r.grid.gx, 256, LPP_LDS, st>>>(p, r.ntiles, r.grid.tpb)));
     CTU_CHECK_LAUNCH("lp_conv3d_first_bwd_data_pair");
     return CTU_OK;
 }
@@ -2539,37 +2528,19 @@ extern "C" int ctu_lp_conv3d_first_bwd_data_pair(int dtype, const void* g, int g
 // kernel symbols the launches above pick for a geometry (measurement only: bench.py's per-kernel roofline leg and
 // scripts/stage_table.py tag their event pairs with them)
 extern "C" const char* ctu_lp_conv3d_fwd_kernel_name(int N, int D, int H, int W, int k, int rin_p, int nout_p, int layout) {
-    (void)nout_p;
-    if (layout == 1) return "lp_conv_fwd_pair_kernel";
-    LpConvP p;
-    const int ntiles = lp_fill(p, N, D, H, W, rin_p);
-    const LpBox bx = lp_box(W, rin_p, (int64_t)N * D * H * W);
-    if (k == 3 && lp_use_persist(3, rin_p, ntiles) && bx.bw >= 16) return "lp_conv_fwd_p1_kernel";
-    if (k == 3 && bx.bw == 8 && bx.th == 4) return "lp_conv_fwd_small_kernel";
-    return "lp_conv_fwd_kernel";
+    return lp_fwd_plan(N, D, H, W, k, rin_p, nout_p, layout).name;
 }
 extern "C" const char* ctu_lp_conv3d_wgrad_kernel_name(int D, int H, int W, int k, int cin_p, int cout_p) {
-    if (LP_WG8 && lp_wg8_ok(D, H, W, k, cin_p, cout_p)) return "lp_wgrad8_kernel";
-    return (LP_WG16 && lp_wg16_ok(D, H, W, k, cin_p, cout_p)) ? "lp_wgrad16_kernel" : "lp_conv_wgrad_kernel";
+    return lp_wg_plan(lp_wg_kind(D, H, W, k, cin_p, cout_p), 1, D, H, W, k, cin_p, cout_p).name;
 }
 
+// the workspace holds the slabs of every route the geometry could take, whichever the build-time switches select
 extern "C" size_t ctu_lp_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int k, int cin_p, int cout_p) {
     if ((k != 3 && k != 5) || cin_p <= 0 || cout_p <= 0) return 0;
-    LpWgP p;
-    const int ntiles = lp_wg_fill(p, N, D, H, W);
-    const int pairs = ((cin_p + 15) >> 4) * ((cout_p + 15) >> 4), planes = k == 3 ? 1 : k;
-    int gx, tpb;
-    lp_wg_grid(ntiles, pairs * planes, &gx, &tpb);
-    const int ntap = (k == 3 ? 9 : k) * lp_wg_qn(k, lp_wg_sm(W, cin_p), lp_wg_sn(W, cout_p));
-    size_t n = (size_t)gx * pairs * planes * ntap * 256;
-    if (lp_wg8_ok(D, H, W, k, cin_p, cout_p) && n < (size_t)512 * 9 * 256) n = (size_t)512 * 9 * 256;     // lp_wgrad8_kernel's slabs
-    if (lp_wg16_ok(D, H, W, k, cin_p, cout_p)) {                                                         // lp_wgrad16_kernel's
-        int gx16, tpb16;
-        lp_wg16_grid(N * (D / 4) * (H / 8) * ceil_div(W, 32), pairs, &gx16, &tpb16);
-        const size_t n16 = (size_t)gx16 * pairs * 27 * 256;
-        if (n < n16) n = n16;
-    }
-    return n;
+    const size_t n = lp_wg_plan(LP_WG_GENERIC, N, D, H, W, k, cin_p, cout_p).ws_floats;
+    const size_t n8 = lp_wg8_ok(D, H, W, k, cin_p, cout_p) ? lp_wg_plan(LP_WG_K8, N, D, H, W, k, cin_p, cout_p).ws_floats : 0;
+    const size_t n16 = lp_wg16_ok(D, H, W, k, cin_p, cout_p) ? lp_wg_plan(LP_WG_K16, N, D, H, W, k, cin_p, cout_p).ws_floats : 0;
+    return n > n8 ? (n > n16 ? n : n16) : (n8 > n16 ? n8 : n16);
 }
 
 struct LpLazy { const void* y; const float* scale; const float* shift; const float* coef; void* out; int cp; };
@@ -2617,28 +2588,17 @@ static int lp_conv3d_wgrad_impl(int dtype, const void* in, int in_cs, int cin_p,
     p.x_cs = in_cs; p.cin_p = cin_p; p.relu = in_relu; p.g_cs = g_cs; p.cout_p = cout_p;
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; p.lz_cp = lz->cp; }
     hipStream_t st = (hipStream_t)stream;
-    if (LP_WG8 && lp_wg8_ok(D, H, W, k, cin_p, cout_p)) {
-        p.N = N; p.D = D; p.H = H; p.W = W;
-        p.tiles_d = D / 4; p.tiles_h = H / 8; p.tiles_w = W / 32;
-        p.ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        int gx8, tpb8;
-        lp_wg8_grid(p.ntiles, &gx8, &tpb8);
+    const LpWgPlan r = lp_wg_plan(lp_wg_kind(D, H, W, k, cin_p, cout_p), N, D, H, W, k, cin_p, cout_p);
+    p.N = N; p.D = D; p.H = H; p.W = W;
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w; p.ntiles = r.ntiles;
+    int rc = CTU_OK;
+    if (r.kind == LP_WG_K8) {
         CTU_DISPATCH_LP(dtype, {
-            if (lz) lp_wgrad8_kernel<T, true><<<gx8, 256, W8_LDS, st>>>(p, tpb8);
-            else lp_wgrad8_kernel<T, false><<<gx8, 256, W8_LDS, st>>>(p, tpb8);
+            if (lz) lp_wgrad8_kernel<T, true><<<r.grid.gx, 256, W8_LDS, st>>>(p, r.grid.tpb);
+            else lp_wgrad8_kernel<T, false><<<r.grid.gx, 256, W8_LDS, st>>>(p, r.grid.tpb);
         });
         CTU_CHECK_LAUNCH("lp_conv3d_wgrad (8 -> 8)");
-        lp_wgrad_reduce_kernel<3, 2, 2><<<dim3(ceil_div(9 * 256, 64)), 1024, 0, st>>>(ws, dw, Co, Ci, cinv, cin_p, cout_p, gx8);
-        CTU_CHECK_LAUNCH("lp_conv3d_wgrad reduce");
-        return CTU_OK;
-    }
-    if (LP_WG16 && lp_wg16_ok(D, H, W, k, cin_p, cout_p)) {
-        p.N = N; p.D = D; p.H = H; p.W = W;
-        p.tiles_d = D / 4; p.tiles_h = H / 8; p.tiles_w = ceil_div(W, 32);
-        p.ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        const int pairs16 = ((cin_p + 15) >> 4) * ((cout_p + 15) >> 4);
-        int gx16, tpb16;
-        lp_wg16_grid(p.ntiles, pairs16, &gx16, &tpb16);
+    } else if (r.kind == LP_WG_K16) {
         static bool raised = false;
         if (!raised) {
             CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_wgrad16_kernel<bf16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, W16_LDS) == hipSuccess &&
@@ -2651,34 +2611,25 @@ static int lp_conv3d_wgrad_impl(int dtype, const void* in, int in_cs, int cin_p,
         // (lazy BatchNorm backward: only the output-channel tile's FIRST input-channel tile forms and stores the raw-output
         //  gradient -- every (ci tile, co tile) block of a co tile would write the same values)
         CTU_DISPATCH_LP(dtype, {
-            if (lz) lp_wgrad16_kernel<T, true><<<dim3(gx16, pairs16), 256, W16_LDS, st>>>(p, tpb16);
-            else lp_wgrad16_kernel<T, false><<<dim3(gx16, pairs16), 256, W16_LDS, st>>>(p, tpb16);
+            if (lz) lp_wgrad16_kernel<T, true><<<dim3(r.grid.gx, r.pairs), 256, W16_LDS, st>>>(p, r.grid.tpb);
+            else lp_wgrad16_kernel<T, false><<<dim3(r.grid.gx, r.pairs), 256, W16_LDS, st>>>(p, r.grid.tpb);
         });
         CTU_CHECK_LAUNCH("lp_conv3d_wgrad (16-channel tiles)");
-        lp_wgrad_reduce_kernel<3, 1, 1><<<dim3(ceil_div(pairs16 * 27 * 256, 64)), 1024, 0, st>>>(ws, dw, Co, Ci, cinv, cin_p, cout_p, gx16);
-        CTU_CHECK_LAUNCH("lp_conv3d_wgrad reduce");
-        return CTU_OK;
-    }
-    const int ntiles = lp_wg_fill(p, N, D, H, W);
-    const int nci = (cin_p + 15) >> 4, nco = (cout_p + 15) >> 4, pairs = nci * nco, planes = k == 3 ? 1 : k;
-    int gx, tpb;
-    lp_wg_grid(ntiles, pairs * planes, &gx, &tpb);
-    int rc = CTU_OK;
-    CTU_DISPATCH_LP(dtype, {
-        if (k == 3) rc = lp_wgrad_dispatch<T, 3>(p, gx, tpb, pairs, st);
-        else rc = lp_wgrad_dispatch<T, 5>(p, gx, tpb, pairs, st);
-    });
-    if (rc != CTU_OK) return rc;
-    const int sm = lp_wg_box_w(W) >= 16 ? lp_wg_sm(W, cin_p) : 1, sn = lp_wg_box_w(W) >= 16 ? lp_wg_sn(W, cout_p) : 1;
-    const int total = planes * pairs * (k == 3 ? 9 : k) * lp_wg_qn(k, sm, sn) * 256;
-    const dim3 rg(ceil_div(total, 64));
-#define CTU_LP_WG_REDUCE(K_, SM_, SN_) lp_wgrad_reduce_kernel<K_, SM_, SN_><<<rg, 1024, 0, st>>>(ws, dw, Co, Ci, cinv, cin_p, cout_p, gx)
-    if (k == 3) {
-        if (sm == 2 && sn == 2) CTU_LP_WG_REDUCE(3, 2, 2); else if (sm == 2) CTU_LP_WG_REDUCE(3, 2, 1);
-        else if (sn == 2) CTU_LP_WG_REDUCE(3, 1, 2); else CTU_LP_WG_REDUCE(3, 1, 1);
     } else {
-        if (sm == 2 && sn == 2) CTU_LP_WG_REDUCE(5, 2, 2); else if (sm == 2) CTU_LP_WG_REDUCE(5, 2, 1);
-        else if (sn == 2) CTU_LP_WG_REDUCE(5, 1, 2); else CTU_LP_WG_REDUCE(5, 1, 1);
+        CTU_DISPATCH_LP(dtype, {
+            if (k == 3) rc = lp_wgrad_dispatch<T, 3>(p, r, st);
+            else rc = lp_wgrad_dispatch<T, 5>(p, r, st);
+        });
+        if (rc != CTU_OK) return rc;
+    }
+    const dim3 rg(ceil_div(r.planes * r.pairs * r.ntap * 256, 64));
+#define CTU_LP_WG_REDUCE(K_, SM_, SN_) lp_wgrad_reduce_kernel<K_, SM_, SN_><<<rg, 1024, 0, st>>>(ws, dw, Co, Ci, cinv, cin_p, cout_p, r.grid.gx)
+    if (k == 3) {
+        if (r.sm == 2 && r.sn == 2) CTU_LP_WG_REDUCE(3, 2, 2); else if (r.sm == 2) CTU_LP_WG_REDUCE(3, 2, 1);
+        else if (r.sn == 2) CTU_LP_WG_REDUCE(3, 1, 2); else CTU_LP_WG_REDUCE(3, 1, 1);
+    } else {
+        if (r.sm == 2 && r.sn == 2) CTU_LP_WG_REDUCE(5, 2, 2); else if (r.sm == 2) CTU_LP_WG_REDUCE(5, 2, 1);
+        else if (r.sn == 2) CTU_LP_WG_REDUCE(5, 1, 2); else CTU_LP_WG_REDUCE(5, 1, 1);
     }
 #undef CTU_LP_WG_REDUCE
     CTU_CHECK_LAUNCH("lp_conv3d_wgrad reduce");
@@ -2688,16 +2639,8 @@ static int lp_conv3d_wgrad_impl(int dtype, const void* in, int in_cs, int cin_p,
 // ---- 16-bit fused decoder up-convolution (upconv_lp.hip): weight gradient w.r.t. the composite weights.  in = COARSE
 // activations (lazy transform), gout = fine-grid gradient of the fused op's raw output (8 padded channels, channel stride 8),
 // dweff fp32 [8][8][cin_p][8] for ctu_lp_upconv_fused_project.  N, D, H, W: COARSE dims; cin_p a multiple of 16.
-static void lp_upwg_geom(int N, int D, int H, int W, int cin_p, int* gx, int* tpb) {
-    LpWgP p;
-    const int ntiles = lp_wg_fill(p, N, D, H, W);
-    lp_wg_grid(ntiles, 4 * (cin_p >> 4), gx, tpb);
-}
 extern "C" size_t ctu_lp_upconv_fused_wgrad_ws_floats(int N, int D, int H, int W, int cin_p) {
-    int gx, tpb;
-    lp_upwg_geom(N, D, H, W, cin_p, &gx, &tpb);
-    if (lp_upwg4_ok(D, H, W, cin_p) && gx < 256) gx = 256;        // lp_upwg4_kernel's slabs
-    return (size_t)gx * 4 * (cin_p >> 4) * 12 * 256;
+    return lp_upwg_plan(N, D, H, W, cin_p, false).ws_floats;
 }
 static int lp_upconv_fused_wgrad_impl(int dtype, const void* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                                       int in_relu, const void* gout, int g_cs, float* dweff, float* ws, int N, int D, int H,
@@ -2732,12 +2675,10 @@ static int lp_upconv_fused_wgrad_impl(int dtype, const void* in, int in_cs, int 
     p.x_cs = in_cs; p.cin_p = cin_p; p.relu = in_relu; p.g_cs = g_cs; p.cout_p = 16;
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; p.lz_cp = lz->cp; }
     hipStream_t st = (hipStream_t)stream;
-    if (LP_UPWG4 && !lz && lp_upwg4_ok(D, H, W, cin_p)) {
-        p.N = N; p.D = D; p.H = H; p.W = W;
-        p.tiles_d = D / 4; p.tiles_h = H / 4; p.tiles_w = W / 32;
-        p.ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-        int gx4, tpb4;
-        lp_upwg4_grid(p.ntiles, &gx4, &tpb4);
+    const LpUpWgPlan r = lp_upwg_plan(N, D, H, W, cin_p, lz != nullptr);
+    p.N = N; p.D = D; p.H = H; p.W = W;
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w; p.ntiles = r.ntiles;
+    if (r.four) {
         static bool raised = false;
         if (!raised) {
             CTU_REQUIRE(hipFuncSetAttribute((const void*)lp_upwg4_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, U4_LDS) == hipSuccess &&
@@ -2745,25 +2686,19 @@ static int lp_upconv_fused_wgrad_impl(int dtype, const void* in, int in_cs, int 
                         "lp_upconv_fused_wgrad: cannot raise the dynamic LDS limit");
             raised = true;
         }
-        CTU_DISPATCH_LP(dtype, (lp_upwg4_kernel<T><<<dim3(gx4, cin_p >> 5), 256, U4_LDS, st>>>(p, tpb4)));
+        CTU_DISPATCH_LP(dtype, (lp_upwg4_kernel<T><<<dim3(r.grid.gx, cin_p >> 5), 256, U4_LDS, st>>>(p, r.grid.tpb)));
         CTU_CHECK_LAUNCH("lp_upconv_fused_wgrad (4 parities)");
-        lp_upwg_reduce_kernel<<<dim3(12 * 256 / 64, 4 * (cin_p >> 4)), 1024, 0, st>>>(ws, dweff, cin_p, cin_p >> 4, gx4);
-        CTU_CHECK_LAUNCH("lp_upconv_fused_wgrad reduce");
-        return CTU_OK;
+    } else {
+        int rc = CTU_OK;
+        CTU_DISPATCH_LP(dtype, {
+            if (lz) rc = r.bw == 32 ? lp_upwg_launch<T, 32, true>(p, r.grid, st) : lp_upwg_launch<T, 16, true>(p, r.grid, st);
+            else if (r.bw == 32) rc = lp_upwg_launch<T, 32>(p, r.grid, st);
+            else if (r.bw == 16) rc = lp_upwg_launch<T, 16>(p, r.grid, st);
+            else rc = lp_upwg_launch<T, 8>(p, r.grid, st);
+        });
+        if (rc != CTU_OK) return rc;
     }
-    lp_wg_fill(p, N, D, H, W);
-    int gx, tpb;
-    lp_upwg_geom(N, D, H, W, cin_p, &gx, &tpb);
-    const int bw = lp_wg_box_w(W);
-    int rc = CTU_OK;
-    CTU_DISPATCH_LP(dtype, {
-        if (lz) rc = bw == 32 ? lp_upwg_launch<T, 32, true>(p, gx, tpb, st) : lp_upwg_launch<T, 16, true>(p, gx, tpb, st);
-        else if (bw == 32) rc = lp_upwg_launch<T, 32>(p, gx, tpb, st);
-        else if (bw == 16) rc = lp_upwg_launch<T, 16>(p, gx, tpb, st);
-        else rc = lp_upwg_launch<T, 8>(p, gx, tpb, st);
-    });
-    if (rc != CTU_OK) return rc;
-    lp_upwg_reduce_kernel<<<dim3(12 * 256 / 64, 4 * (cin_p >> 4)), 1024, 0, st>>>(ws, dweff, cin_p, cin_p >> 4, gx);
+    lp_upwg_reduce_kernel<<<dim3(12 * 256 / 64, 4 * (cin_p >> 4)), 1024, 0, st>>>(ws, dweff, cin_p, cin_p >> 4, r.grid.gx);
     CTU_CHECK_LAUNCH("lp_upconv_fused_wgrad reduce");
     return CTU_OK;
 }

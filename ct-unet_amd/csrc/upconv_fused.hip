@@ -893,19 +893,25 @@ __global__ void upconv_project_kernel(const float* __restrict__ dweff, const flo
     if (sub == 0) *dst = v;
 }
 
-static void up_grid(int ntiles, int ny, int* gx, int* tpb) {
-    int g = 512 / ny;                                   // 2 resident blocks per CU
-    if (g < 1) g = 1;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
-// parity groups (blockIdx.y) of the forward kernel: all 8 parities in one block for <= 16 output channels, unless the
-// coarse volume has fewer than 256 boxes -- then 16-channel layers split the parities over two blocks so every CU gets one
-static int up_ny(int nout_p, int ntiles) {
-    if (nout_p == 16 && ntiles < 256) return 2;
-    return nout_p <= 16 ? 1 : (nout_p <= 32 ? 2 : 4);
+// The grid of the fused forward / data-gradient kernels over the COARSE 4 x 4 x 16 boxes: ny blocks in y (parity groups of the
+// forward, input-channel tile groups of the data gradient: nt tiles per block), 2 resident blocks per CU.
+struct UpPlan { int tiles_d, tiles_h, tiles_w, ntiles, nt, ny; Grid grid; };
+static UpPlan up_plan(int N, int D, int H, int W, int nout_p, int bwd_n16) {
+    UpPlan r;
+    r.tiles_d = ceil_div(D, 4); r.tiles_h = ceil_div(H, 4); r.tiles_w = ceil_div(W, 16);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    if (bwd_n16) {
+        r.nt = bwd_n16 >= 4 ? 4 : (bwd_n16 >= 2 ? 2 : 1);
+        while (r.nt > 1 && (long)r.ntiles * ceil_div(bwd_n16, r.nt) < 256) r.nt >>= 1;     // few boxes: narrower blocks so every CU gets one
+        r.ny = ceil_div(bwd_n16, r.nt);
+    } else {
+        // all 8 parities in one block for <= 16 output channels, unless the coarse volume has fewer than 256 boxes -- then
+        // 16-channel layers split the parities over two blocks so every CU gets one
+        r.nt = 0;
+        r.ny = (nout_p == 16 && r.ntiles < 256) ? 2 : (nout_p <= 16 ? 1 : (nout_p <= 32 ? 2 : 4));
+    }
+    r.grid = persist_grid(r.ntiles, 512 / r.ny);
+    return r;
 }
 
 }  // namespace
@@ -925,11 +931,8 @@ extern "C" size_t ctu_upconv_fused_packed_floats(int cin_p, int nout_p) {
 }
 
 extern "C" int ctu_upconv_fused_num_blocks(int N, int D, int H, int W, int nout_p) {
-    int gx, tpb;
-    const int ntiles = N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 16);
-    const int ny = up_ny(nout_p, ntiles);
-    up_grid(ntiles, ny, &gx, &tpb);
-    return gx * ny;
+    const UpPlan r = up_plan(N, D, H, W, nout_p, 0);
+    return r.grid.gx * r.ny;
 }
 
 extern "C" size_t ctu_upconv_fused_pack_ws_floats(int C, int nout_p) { return (size_t)27 * C * nout_p + (size_t)8 * C * C; }
@@ -980,11 +983,9 @@ extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const
     p.tail = tail_or_off(tail);
     p.in_cs = in_cs; p.rin_p = cin_p; p.in_relu = in_relu; p.out_cs = out_cs; p.nout_p = nout_p;
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
-    const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-    const int ny = up_ny(nout_p, ntiles);
-    int gx, tpb;
-    up_grid(ntiles, ny, &gx, &tpb);
+    const UpPlan r = up_plan(N, D, H, W, nout_p, 0);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
+    const int ny = r.ny, gx = r.grid.gx, tpb = r.grid.tpb, ntiles = r.ntiles;
     hipStream_t st = (hipStream_t)stream;
     if (nout_p == 16 && ny == 2) {
         upconv_fused_fwd_kernel<4, 1><<<dim3(gx, 2), 256, 0, st>>>(p, ntiles, tpb);
@@ -1080,14 +1081,10 @@ extern "C" int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p
     UpDP p;
     p.g = gout; p.wp = wpd; p.out = gin; p.g_cs = g_cs; p.nout_p = nout_p; p.out_cs = gin_cs; p.cin_p = cin_p;
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
     p.n16 = ceil_div(cin_p, 16);
-    const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-    int NT = p.n16 >= 4 ? 4 : (p.n16 >= 2 ? 2 : 1);
-    while (NT > 1 && (long)ntiles * ceil_div(p.n16, NT) < 256) NT >>= 1;      // few boxes: narrower blocks so every CU gets one
-    const int ny = ceil_div(p.n16, NT);
-    int gx, tpb;
-    up_grid(ntiles, ny, &gx, &tpb);
+    const UpPlan r = up_plan(N, D, H, W, nout_p, p.n16);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
+    const int NT = r.nt, ny = r.ny, gx = r.grid.gx, tpb = r.grid.tpb, ntiles = r.ntiles;
     hipStream_t st = (hipStream_t)stream;
     if (NT == 4) upconv_fused_bwd_data_kernel<4><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
     else if (NT == 2) upconv_fused_bwd_data_kernel<2><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);

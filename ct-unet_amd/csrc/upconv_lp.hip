@@ -456,21 +456,14 @@ __global__ __launch_bounds__(256, 1) void lp_upconv_bwd_data_kernel(UlBwdP p, in
     }
 }
 
-void ul_grid(int ntiles, int* gx, int* tpb) {                      // one persistent block per CU
-    int g = 256;
-    if (g > ntiles) g = ntiles;
-    *tpb = ceil_div(ntiles, g);
-    *gx = ceil_div(ntiles, *tpb);
-}
-
-template <class K>
-int ul_raise_lds(K kernel, size_t lds, size_t* raised, const char* what) {
-    if (lds > *raised) {
-        CTU_REQUIRE(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                    "%s: cannot raise the dynamic LDS limit", what);
-        *raised = lds;
-    }
-    return CTU_OK;
+// the COARSE 4 x 4 x 16 boxes of a volume and the grid of the forward / data-gradient kernels over them
+struct UlPlan { int tiles_d, tiles_h, tiles_w, ntiles; Grid grid; };
+UlPlan ul_plan(int N, int D, int H, int W) {
+    UlPlan r;
+    r.tiles_d = ceil_div(D, 4); r.tiles_h = ceil_div(H, 4); r.tiles_w = ceil_div(W, 16);
+    r.ntiles = N * r.tiles_d * r.tiles_h * r.tiles_w;
+    r.grid = persist_grid(r.ntiles, 256);                           // one persistent block per CU
+    return r;
 }
 
 }  // namespace
@@ -488,9 +481,7 @@ extern "C" size_t ctu_lp_upconv_fused_packed_elems(int cin_p) {       // forward
 }
 
 extern "C" int ctu_lp_upconv_fused_num_blocks(int N, int D, int H, int W) {
-    int gx, tpb;
-    ul_grid(N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 16), &gx, &tpb);
-    return gx;
+    return ul_plan(N, D, H, W).grid.gx;
 }
 
 // wp32: ctu_upconv_fused_pack's fp32 packing for (cin_p, nout_p = 8); wp16: ctu_lp_upconv_fused_packed_elems(cin_p) elements
@@ -521,17 +512,15 @@ extern "C" int ctu_lp_upconv_fused_fwd(int dtype, const void* in, int in_cs, int
     p.in = in; p.wf = wp16; p.out = out; p.scale = in_scale; p.shift = in_shift; p.beff = beff; p.stats = stats;
     p.in_cs = in_cs; p.cin_p = cin_p; p.relu = in_relu; p.out_cs = out_cs;
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
-    const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
-    int gx, tpb;
-    ul_grid(ntiles, &gx, &tpb);
+    const UlPlan r = ul_plan(N, D, H, W);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     hipStream_t st = (hipStream_t)stream;
     static size_t raised[2] = {64 * 1024, 64 * 1024};
     int rc = CTU_OK;
     CTU_DISPATCH_LP(dtype, {
-        rc = ul_raise_lds(lp_upconv_fwd_kernel<T>, UL_FWD_LDS, &raised[dtype == CTU_BF16 ? 0 : 1], "lp_upconv_fused_fwd");
+        rc = raise_lds(lp_upconv_fwd_kernel<T>, UL_FWD_LDS, &raised[dtype == CTU_BF16 ? 0 : 1], "lp_upconv_fused_fwd");
         if (rc != CTU_OK) return rc;
-        lp_upconv_fwd_kernel<T><<<gx, 256, UL_FWD_LDS, st>>>(p, ntiles, tpb);
+        lp_upconv_fwd_kernel<T><<<r.grid.gx, 256, UL_FWD_LDS, st>>>(p, r.ntiles, r.grid.tpb);
     });
     CTU_CHECK_LAUNCH("lp_upconv_fused_fwd");
     return CTU_OK;
@@ -547,27 +536,25 @@ extern "C" int ctu_lp_upconv_fused_bwd_data(int dtype, const void* gout, int g_c
     UlBwdP p{};
     p.g = gout; p.out = gin; p.g_cs = g_cs; p.out_cs = gin_cs; p.cin_p = cin_p;
     p.N = N; p.D = D; p.H = H; p.W = W;
-    p.tiles_d = ceil_div(D, 4); p.tiles_h = ceil_div(H, 4); p.tiles_w = ceil_div(W, 16);
-    const int ntiles = N * p.tiles_d * p.tiles_h * p.tiles_w;
+    const UlPlan r = ul_plan(N, D, H, W);
+    p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     const int n16 = cin_p >> 4;
     const int NT = n16 >= 4 ? 4 : 2;                                // cin_p is a multiple of 32: at least two tiles
-    int gx, tpb;
-    ul_grid(ntiles, &gx, &tpb);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)UL_FV * 16 + (size_t)16 * NT * 1024;
     static size_t raised[4] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
-    const dim3 grid(gx, ceil_div(n16, NT));
+    const dim3 grid(r.grid.gx, ceil_div(n16, NT));
     int rc = CTU_OK;
     CTU_DISPATCH_LP(dtype, {
         p.wb = (const T*)wp16 + (size_t)(cin_p >> 5) * 48 * 512;
         if (NT == 4) {
-            rc = ul_raise_lds(lp_upconv_bwd_data_kernel<T, 4>, lds, &raised[(dtype == CTU_BF16 ? 0 : 1) * 2 + 1], "lp_upconv_fused_bwd_data");
+            rc = raise_lds(lp_upconv_bwd_data_kernel<T, 4>, lds, &raised[(dtype == CTU_BF16 ? 0 : 1) * 2 + 1], "lp_upconv_fused_bwd_data");
             if (rc != CTU_OK) return rc;
-            lp_upconv_bwd_data_kernel<T, 4><<<grid, 256, lds, st>>>(p, ntiles, tpb);
+            lp_upconv_bwd_data_kernel<T, 4><<<grid, 256, lds, st>>>(p, r.ntiles, r.grid.tpb);
         } else {
-            rc = ul_raise_lds(lp_upconv_bwd_data_kernel<T, 2>, lds, &raised[(dtype == CTU_BF16 ? 0 : 1) * 2], "lp_upconv_fused_bwd_data");
+            rc = raise_lds(lp_upconv_bwd_data_kernel<T, 2>, lds, &raised[(dtype == CTU_BF16 ? 0 : 1) * 2], "lp_upconv_fused_bwd_data");
             if (rc != CTU_OK) return rc;
-            lp_upconv_bwd_data_kernel<T, 2><<<grid, 256, lds, st>>>(p, ntiles, tpb);
+            lp_upconv_bwd_data_kernel<T, 2><<<grid, 256, lds, st>>>(p, r.ntiles, r.grid.tpb);
         }
     });
     CTU_CHECK_LAUNCH("lp_upconv_fused_bwd_data");

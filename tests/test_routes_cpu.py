@@ -30,16 +30,16 @@ def pad8(c):
 
 
 # ------------------------------------------------------------------ grid caps (each mirrors one line of the C++)
-WG_BLOCKS = 512          # conv3d.hip: CTU_WG_BLOCKS, `int gx = CTU_WG_BLOCKS / pairs_z;` in wgrad_gx
-LP_WG8_CAP = 512         # conv3d_lp.hip: `int g = ntiles < 512 ? ntiles : 512;` in lp_wg8_grid
-LP_WG16_CAP = 256        # conv3d_lp.hip: `int g = 256 / pairs;` in lp_wg16_grid (at least 8)
-LP_WG_CAP = 768          # conv3d_lp.hip: `int g = 768 / groups;` in lp_wg_grid (at least 16)
-LP_PAIR_CAP = 768        # conv3d_lp.hip: `int g = 768;` in lp_pair_grid
-LP_P1_CAP = 512          # conv3d_lp.hip: `int g = 512;` in lp_persist_grid
-LP_UPWG4_CAP = 256       # conv3d_lp.hip: `int g = ntiles < 256 ? ntiles : 256;` in lp_upwg4_grid
-UP_CAP = 512             # upconv_fused.hip: `int g = 512 / ny;` in up_grid
-UL_CAP = 256             # upconv_lp.hip: `int g = 256;` in ul_grid
-FIRST_PER_CU = {"fwd": 4, "dgrad": 3, "wgrad": 5}    # conv3d_first.hip: grid_for(..., 4 | 3 | 5, ...) = 256 * per_cu blocks
+WG_BLOCKS = 512          # conv3d.hip: CTU_WG_BLOCKS, the cap `CTU_WG_BLOCKS / (pairs * planes)` in wgrad_plan / k3s_grid / upwg_plan
+LP_WG8_CAP = 512         # conv3d_lp.hip: `persist_grid(r.ntiles, 512)` in lp_wg_plan (LP_WG_K8)
+LP_WG16_CAP = 256        # conv3d_lp.hip: the cap `256 / r.pairs` in lp_wg_plan (LP_WG_K16; at least 8)
+LP_WG_CAP = 768          # conv3d_lp.hip: `int g = 768 / groups;` in lp_wg_cap (at least 16)
+LP_PAIR_CAP = 768        # conv3d_lp.hip: `persist_grid(r.ntiles, 768)` in lp_fwd_plan (LP_FWD_PAIR)
+LP_P1_CAP = 512          # conv3d_lp.hip: `persist_grid(r.ntiles, 512)` in lp_fwd_plan (LP_FWD_PERSIST)
+LP_UPWG4_CAP = 256       # conv3d_lp.hip: `persist_grid(r.ntiles, 256)` in lp_upwg_plan (lp_upwg4_kernel)
+UP_CAP = 512             # upconv_fused.hip: `persist_grid(r.ntiles, 512 / r.ny)` in up_plan
+UL_CAP = 256             # upconv_lp.hip: `persist_grid(r.ntiles, 256)` in ul_plan
+FIRST_PER_CU = {"fwd": 4, "dgrad": 3, "wgrad": 5}    # conv3d_first.hip: FWD_PER_CU, DGRAD_PER_CU, WGRAD_PER_CU (x 256 blocks)
 LP_SC = 32               # conv3d_lp.hip: input channels per stage
 
 
@@ -67,14 +67,14 @@ def lp_wg_box_w(W):
 
 
 def up_ny(nout_p, ntiles):
-    """upconv_fused.hip up_ny: parity groups (blockIdx.y) of the fp32 fused up-convolution forward."""
+    """upconv_fused.hip up_plan: parity groups (blockIdx.y) of the fp32 fused up-convolution forward."""
     if nout_p == 16 and ntiles < 256:
         return 2
     return 1 if nout_p <= 16 else (2 if nout_p <= 32 else 4)
 
 
 def up_bwd_nt(cin_p, ntiles):
-    """upconv_fused.hip ctu_upconv_fused_bwd_data: the NT loop (input-channel tiles per block)."""
+    """upconv_fused.hip up_plan: the nt loop of the data gradient (input-channel tiles per block)."""
     n16 = cdiv(cin_p, 16)
     nt = 4 if n16 >= 4 else (2 if n16 >= 2 else 1)
     while nt > 1 and ntiles * cdiv(n16, nt) < 256:
@@ -171,7 +171,7 @@ def route(c):
                 return _capped("lp_upwg4_kernel", N, D, H, W, (4, 4, 32), LP_UPWG4_CAP)
             bw = lp_wg_box_w(W)
             return _capped(f"lp_upwg_kernel<{bw}>", N, D, H, W, (4, 4 * (32 // bw), bw), max(16, LP_WG_CAP // (4 * (cip // 16))), lz)
-        if cop == 8:      # upwg_geom(pw): the (w-parity, c_out) tile
+        if cop == 8:      # upwg_plan(pw): the (w-parity, c_out) tile
             return _capped("conv3d_wgrad_k3s_kernel<1, 1, 2>", N, D, H, W, (4, 4, 8), max(1, WG_BLOCKS // (4 * cdiv(cip, 16))), lz)
         return _capped("conv3d_wgrad_k3s_kernel<1, 1, 1>", N, D, H, W, (4, 4, 8),
                        max(1, WG_BLOCKS // (8 * cdiv(cip, 16) * cdiv(cop, 16))), lz)
