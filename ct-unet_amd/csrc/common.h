@@ -59,6 +59,12 @@ void ctu_set_error(const char* fmt, ...);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// limits of the label-map entry points (components, morphology): grid.y carries N, item-local voxel indices are int32
+static inline bool geometry_ok(int N, int D, int H, int W) {
+    return N > 0 && N <= 65535 && D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < ((int64_t)1 << 31);
+}
 
 // grid of a persistent kernel (a block loops over tpb boxes): at most `cap` blocks, the boxes spread evenly over them.  The
 // cap is what differs between kernels (resident blocks per CU x 256 CUs, divided by the grid's other axes).

@@ -22,6 +22,10 @@
 // Everything is integer and every order is fixed: two calls are bit-equal.  Workspace: 8 bytes per voxel (parent, size)
 // plus per-tile / per-chunk tables.
 //
+// Fill holes (ctu_fill_holes): phases 1-3 on the complement mask (one byte per voxel, written first), the size array as a
+// per-root flag (init zeroes it at every root): the background voxels of the six faces set their root's flag, the apply pass
+// writes in OR (background AND root not flagged).
+//
 // Replaces: nothing in the reference; users would copy the label map to the host for scipy.ndimage.label.
 #include "common.h"
 
@@ -550,12 +554,6 @@ struct Layout {
     int ntz, nty, ntx, ntiles, nch;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-bool geometry_ok(int N, int D, int H, int W) {
-    return N > 0 && N <= 65535 && D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < ((int64_t)1 << 31);
-}
-
 Layout layout(int N, int D, int H, int W) {
     Layout l;
     const int64_t V = (int64_t)D * H * W;
@@ -638,6 +636,108 @@ int run_filter(const CcArgs& a, int N, const Layout& l, uint8_t* w, int mode, in
     return CTU_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ fill holes
+constexpr int FB = 256;                                     // 16 C-order voxels per thread
+
+// comp[v] = 1 where the input is background (the union-find then runs on the complement)
+template <class T>
+__global__ void __launch_bounds__(FB) fh_complement_kernel(const T* __restrict__ in, int64_t V, int has_label, long long label,
+                                                           uint8_t* __restrict__ comp) {
+    const int n = blockIdx.y;
+    const int64_t v0 = ((int64_t)blockIdx.x * FB + threadIdx.x) * 16;
+    if (v0 >= V) return;
+    const T* src = in + n * V + v0;
+    uint8_t* dst = comp + n * V + v0;
+    const int nv = (int)(V - v0 < 16 ? V - v0 : 16);
+    long long c[16];
+    load8(src, nv < VPT ? nv : VPT, c);
+    load8(src + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
+#pragma unroll
+    for (int u = 0; u < 16; ++u) c[u] = (has_label ? c[u] == label : c[u] != 0) ? 0 : 1;
+    store8(dst, nv < VPT ? nv : VPT, c);
+    store8(dst + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
+}
+
+// flag[root] = 1 for every background voxel on one of the six faces (flag: the size array, 0 at every root after init)
+__global__ void __launch_bounds__(FB) fh_faces_kernel(const int* __restrict__ parent, int* __restrict__ flag, int64_t V, int D,
+                                                      int H, int W) {
+    const int n = blockIdx.y;
+    const int64_t fz = (int64_t)H * W, fy = (int64_t)D * W, fx = (int64_t)D * H;
+    int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= 2 * (fz + fy + fx)) return;
+    int z, y, x;
+    if (i < 2 * fz) {
+        z = i < fz ? 0 : D - 1;
+        i %= fz;
+        y = (int)(i / W); x = (int)(i % W);
+    } else if (i < 2 * (fz + fy)) {
+        i -= 2 * fz;
+        y = i < fy ? 0 : H - 1;
+        i %= fy;
+        z = (int)(i / W); x = (int)(i % W);
+    } else {
+        i -= 2 * (fz + fy);
+        x = i < fx ? 0 : W - 1;
+        i %= fx;
+        z = (int)(i / H); y = (int)(i % H);
+    }
+    const int p = parent[n * V + ((int64_t)z * H + y) * W + x];
+    if (p >= 0) flag[n * V + p] = 1;
+}
+
+// out = in OR (background whose component touches no face)
+__global__ void __launch_bounds__(FB) fh_apply_kernel(const uint8_t* __restrict__ comp, const int* __restrict__ parent,
+                                                      const int* __restrict__ flag, int64_t V, uint8_t* __restrict__ out) {
+    const int n = blockIdx.y;
+    const int64_t v0 = ((int64_t)blockIdx.x * FB + threadIdx.x) * 16;
+    if (v0 >= V) return;
+    const int nv = (int)(V - v0 < 16 ? V - v0 : 16);
+    const int* P = parent + n * V;
+    const int* F = flag + n * V;
+    long long c[16];
+    load8(comp + n * V + v0, nv < VPT ? nv : VPT, c);
+    load8(comp + n * V + v0 + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        long long o = 1;
+        if (u < nv && c[u]) o = F[P[v0 + u]] ? 0 : 1;
+        c[u] = o;
+    }
+    uint8_t* dst = out + n * V + v0;
+    store8(dst, nv < VPT ? nv : VPT, c);
+    store8(dst + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
+}
+
+template <class T>
+int run_fill_holes(const void* in, int N, int D, int H, int W, int conn, int has_label, long long label, uint8_t* out,
+                   uint8_t* w, hipStream_t st) {
+    const Layout l = layout(N, D, H, W);
+    const int64_t V = (int64_t)D * H * W;
+    uint8_t* comp = w + align256(l.total);
+    CcArgs a;
+    const int rc = make_args(a, comp, CTU_U8, N, D, H, W, conn, nullptr, 0, w, "fill_holes");
+    if (rc != CTU_OK) return rc;
+    const dim3 flat((unsigned)ceil_div64(V, FB * 16), (unsigned)N);
+    fh_complement_kernel<T><<<flat, FB, 0, st>>>((const T*)in, V, has_label, label, comp);
+    CTU_CHECK_LAUNCH("fill_holes complement");
+    int* parent = (int*)(w + l.parent);
+    int* flag = (int*)(w + l.size);
+    int* tflag = (int*)(w + l.tflag);
+    const dim3 grid((unsigned)l.ntiles, (unsigned)N);
+    cc_init_kernel<uint8_t><<<grid, TB, 0, st>>>(a, parent, flag, tflag);      // flag[root] = 0
+    CTU_CHECK_LAUNCH("fill_holes init");
+    cc_merge_kernel<uint8_t><<<grid, TB, 0, st>>>(a, parent, tflag);
+    CTU_CHECK_LAUNCH("fill_holes merge");
+    cc_flatten_kernel<false><<<grid, TB, 0, st>>>(a, parent, flag, tflag);
+    CTU_CHECK_LAUNCH("fill_holes flatten");
+    const int64_t faces = 2 * ((int64_t)H * W + (int64_t)D * W + (int64_t)D * H);
+    fh_faces_kernel<<<dim3((unsigned)ceil_div64(faces, FB), (unsigned)N), FB, 0, st>>>(parent, flag, V, D, H, W);
+    CTU_CHECK_LAUNCH("fill_holes faces");
+    fh_apply_kernel<<<flat, FB, 0, st>>>(comp, parent, flag, V, out);
+    CTU_CHECK_LAUNCH("fill_holes apply");
+    return CTU_OK;
+}
+
 }  // namespace
 
 extern "C" size_t ctu_components_ws_bytes(int N, int D, int H, int W) {
@@ -691,4 +791,16 @@ extern "C" int ctu_filter_components(const void* in, int dtype, int N, int D, in
     uint8_t* w = (uint8_t*)ws;
     return dtype == CTU_U8 ? run_filter<uint8_t>(a, N, l, w, mode, param, out, st)
                            : run_filter<long long>(a, N, l, w, mode, param, out, st);
+}
+
+extern "C" int ctu_fill_holes(const void* in, int dtype, int N, int D, int H, int W, int connectivity, int has_label,
+                              int64_t label, uint8_t* out, void* ws, void* stream) {
+    CTU_REQUIRE(in && out && ws, "fill_holes: null pointer");
+    CTU_REQUIRE(dtype == CTU_U8 || dtype == CTU_I64, "fill_holes: unsupported dtype %d (uint8 or int64)", dtype);
+    CTU_REQUIRE(geometry_ok(N, D, H, W), "fill_holes: bad shape N=%d D=%d H=%d W=%d (every side >= 1, D*H*W < 2^31)", N, D, H,
+                W);
+    CTU_REQUIRE(connectivity >= 1 && connectivity <= 3, "fill_holes: connectivity must be 1, 2 or 3, got %d", connectivity);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == CTU_U8 ? run_fill_holes<uint8_t>(in, N, D, H, W, connectivity, has_label != 0, label, out, (uint8_t*)ws, st)
+                           : run_fill_holes<long long>(in, N, D, H, W, connectivity, has_label != 0, label, out, (uint8_t*)ws, st);
 }

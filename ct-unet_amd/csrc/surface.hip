@@ -481,7 +481,6 @@ __global__ void surf_final_kernel(GroupArgs g, const unsigned long long* __restr
 
 // ------------------------------------------------------------------------------------------------ host side
 int64_t pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int group_pairs(int pairs, int64_t Vp) {
     const int64_t per_pair = 2 * Vp * 5;                              // two planes: edge byte + 4-byte distance

@@ -121,6 +121,10 @@ SIGNATURES = {
     "ctu_components_ws_bytes": (Z, [I, I, I, I]),
     "ctu_label_components": (I, [P, I, I, I, I, I, I, P, I, P, P, P, P]),
     "ctu_filter_components": (I, [P, I, I, I, I, I, I, P, I, I, I, P, P, P]),
+    "ctu_morphology_ws_bytes": (Z, [I, I, I, I, I]),
+    "ctu_binary_morphology": (I, [P, I, I, I, I, I, I, C.c_uint32, I, I, I, L, P, P, P]),
+    "ctu_fill_holes": (I, [P, I, I, I, I, I, I, I, L, P, P, P]),
+    "ctu_implant_mask": (I, [P, I, P, I, I, I, I, I, C.c_uint32, I, I, I, I, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

@@ -21,6 +21,33 @@ Definitions (the tests restate them on scipy / numpy):
 - Foreground voxels of dropped components become 0; every other voxel keeps its label.
 
 Results are deterministic: every value is an integer and every order is fixed.
+
+Binary morphology (``binary_erosion`` / ``binary_dilation`` / ``binary_opening`` / ``binary_closing`` /
+``binary_fill_holes`` / ``extract_implant``; ``ctu_binary_morphology``, ``ctu_fill_holes``, ``ctu_implant_mask`` of
+``csrc/morphology.hip`` and ``csrc/components.hip``) follows ``scipy.ndimage`` in 3-D, bit for bit:
+
+- **Foreground**: a nonzero voxel of a bool, uint8 or int64 tensor; with ``label=k`` a voxel equal to ``k`` (tested in the
+  kernel that reads the map).  The result is bool for bool input, otherwise uint8 holding 0 / 1.
+- **Structure**: an int 1 / 2 / 3 is ``scipy.ndimage.generate_binary_structure(3, c)`` (6 / 18 / 26 neighbours plus the
+  centre); any 3x3x3 bool array or tensor with at least one true entry is taken as it is (with or without its centre,
+  symmetric or not).  It travels as a 27-bit code, bit ``(i*3+j)*3+k`` for ``structure[i, j, k]``.
+- **Offsets**: with ``S`` the offsets ``s = (i-1, j-1, k-1)`` of the true entries, every voxel outside the volume reads as
+  ``border_value`` (0 or 1).
+- **Erosion**: ``out[v] = AND_{s in S} in[v+s]``.  **Dilation**: ``out[v] = OR_{s in S} in[v-s]`` (the reflection).
+- **Iterations**: ``iterations=k`` (1..64) is k successive applications.  scipy's ``iterations < 1`` (repeat until nothing
+  changes) is refused: it needs a decision on the host per step.  ``mask=`` and ``origin=`` are not offered.
+- **Opening**: ``dilation(erosion(x, k), k)``.  **Closing**: ``erosion(dilation(x, k), k)``.  Both with border value 0, as
+  scipy does, so closing erodes at the volume border.
+- **Fill holes**: ``x OR (background voxels whose background component, at the given connectivity, touches no face of the
+  volume)``; ``connectivity=1`` is scipy's default structure.
+- **Implant extraction**, in order: ``m = (full_skull != 0) AND (defective_skull == 0)``; ``opening_iterations > 0``:
+  ``binary_opening(m, structure, opening_iterations)``; ``fill_holes``: ``binary_fill_holes(., 1)``;
+  ``keep_largest_connected_component(., connectivity=connectivity, num_components=num_components)``; a uint8 0 / 1 mask.
+
+Each item of a batch is processed on its own.  The morphology calls use no atomics and no host synchronisation, so a
+call can be captured into a graph.  The output and the workspace are ``torch.empty`` tensors, which a capture draws from
+the graph's private pool.  Under capture give ``structure`` as an int or a host array: a structure tensor on the device
+is copied to the host to form its 27-bit code, which synchronises and is refused during capture.
 """
 from __future__ import annotations
 
@@ -33,6 +60,10 @@ from . import _lib
 
 MAX_APPLIED = 16
 MAX_COMPONENTS = 8
+MAX_ITERATIONS = 64
+_ERODE, _DILATE, _OPEN, _CLOSE = 0, 1, 2, 3
+_WS_MORPH, _WS_FILL, _WS_IMPLANT = 0, 1, 2
+_MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
 CTU_U8, CTU_I64 = 3, 4
 _LARGEST, _MIN_SIZE = 0, 1
 
@@ -160,3 +191,161 @@ def remove_small_objects(labels: torch.Tensor, min_size: int, applied_labels: Op
 def workspace_bytes(n: int, shape) -> int:
     """Device workspace of one call (bytes) for n items of a (D, H, W) volume."""
     return int(_lib.load().ctu_components_ws_bytes(n, *shape))
+
+
+# ------------------------------------------------------------------------------------------------ binary morphology
+def _structure_code(structure) -> int:
+    """27-bit code of a structure: bit (i*3+j)*3+k for structure[i, j, k] (a device tensor is read back to the host)."""
+    if isinstance(structure, Integral) and not isinstance(structure, bool):
+        if structure not in (1, 2, 3):
+            raise ValueError(f"postprocess: an integer structure must be 1, 2 or 3, got {structure!r}")
+        return sum(1 << ((i * 3 + j) * 3 + k) for i in range(3) for j in range(3) for k in range(3)
+                   if abs(i - 1) + abs(j - 1) + abs(k - 1) <= structure)
+    try:
+        st = torch.as_tensor(structure)
+    except Exception as e:
+        raise ValueError(f"postprocess: structure must be 1, 2, 3 or a 3x3x3 bool array, got {structure!r}") from e
+    if tuple(st.shape) != (3, 3, 3):
+        raise ValueError(f"postprocess: structure must be 1, 2, 3 or a 3x3x3 bool array, got shape {tuple(st.shape)}")
+    bits = (st != 0).flatten().tolist()
+    code = sum(1 << i for i, b in enumerate(bits) if b)
+    if code == 0:
+        raise ValueError("postprocess: structure has no true entry")
+    return code
+
+
+def _iterations(iterations, lo: int = 1, what: str = "iterations") -> int:
+    if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not lo <= iterations <= MAX_ITERATIONS:
+        raise ValueError(f"postprocess: {what} must be an integer in {lo}..{MAX_ITERATIONS} (repeat-until-stable is not "
+                         f"offered), got {iterations!r}")
+    return int(iterations)
+
+
+def _border(border_value) -> int:
+    if isinstance(border_value, bool):
+        return int(border_value)
+    if not isinstance(border_value, Integral) or border_value not in (0, 1):
+        raise ValueError(f"postprocess: border_value must be 0 or 1, got {border_value!r}")
+    return int(border_value)
+
+
+def _label_arg(label):
+    if label is None:
+        return 0, 0
+    if isinstance(label, bool) or not isinstance(label, Integral) or not -(1 << 63) <= label < (1 << 63):
+        raise ValueError(f"postprocess: label must be an integer of the map's range, got {label!r}")
+    return 1, int(label)
+
+
+def _as_bytes(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """The contiguous tensor the kernels read (bool viewed as uint8) and its dtype code."""
+    t = t.contiguous()
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    return t, (CTU_I64 if t.dtype == torch.int64 else CTU_U8)
+
+
+def _mask_out(src: torch.Tensor) -> torch.Tensor:
+    return torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+
+
+def _finish(out: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return out.view(torch.bool) if like.dtype == torch.bool else out
+
+
+def _morphology(mask, mode: int, structure, iterations, border_value, label) -> torch.Tensor:
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    code = _structure_code(structure)
+    it = _iterations(iterations)
+    border = _border(border_value)
+    has_label, lab = _label_arg(label)
+    _check_device(mask)
+    lib = _lib.load()
+    src, dt = _as_bytes(mask)
+    out = _mask_out(mask)
+    ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_MORPH), dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_binary_morphology(src.data_ptr(), dt, n, *shape, mode, code, it, border, has_label, lab,
+                                             out.data_ptr(), ws.data_ptr(), stream), "binary_morphology")
+    return _finish(out, mask)
+
+
+def binary_erosion(mask: torch.Tensor, structure=1, iterations: int = 1, border_value: int = 0,
+                   label: Optional[int] = None) -> torch.Tensor:
+    """``scipy.ndimage.binary_erosion`` of a bool / uint8 / int64 mask [D,H,W] or [N,D,H,W] (each item on its own)."""
+    return _morphology(mask, _ERODE, structure, iterations, border_value, label)
+
+
+def binary_dilation(mask: torch.Tensor, structure=1, iterations: int = 1, border_value: int = 0,
+                    label: Optional[int] = None) -> torch.Tensor:
+    """``scipy.ndimage.binary_dilation`` of a bool / uint8 / int64 mask [D,H,W] or [N,D,H,W]."""
+    return _morphology(mask, _DILATE, structure, iterations, border_value, label)
+
+
+def binary_opening(mask: torch.Tensor, structure=1, iterations: int = 1, label: Optional[int] = None) -> torch.Tensor:
+    """``scipy.ndimage.binary_opening``: ``iterations`` erosions, then as many dilations, border value 0."""
+    return _morphology(mask, _OPEN, structure, iterations, 0, label)
+
+
+def binary_closing(mask: torch.Tensor, structure=1, iterations: int = 1, label: Optional[int] = None) -> torch.Tensor:
+    """``scipy.ndimage.binary_closing``: ``iterations`` dilations, then as many erosions, border value 0."""
+    return _morphology(mask, _CLOSE, structure, iterations, 0, label)
+
+
+def binary_fill_holes(mask: torch.Tensor, connectivity: int = 1, label: Optional[int] = None) -> torch.Tensor:
+    """``scipy.ndimage.binary_fill_holes`` with ``generate_binary_structure(3, connectivity)``: the background components
+    that touch no face of the volume become foreground."""
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    conn = _connectivity(connectivity)
+    has_label, lab = _label_arg(label)
+    _check_device(mask)
+    lib = _lib.load()
+    src, dt = _as_bytes(mask)
+    out = _mask_out(mask)
+    ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_FILL), dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_fill_holes(src.data_ptr(), dt, n, *shape, conn, has_label, lab, out.data_ptr(), ws.data_ptr(),
+                                      stream), "fill_holes")
+    return _finish(out, mask)
+
+
+def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, opening_iterations: int = 1, structure=1,
+                    connectivity: int = 3, num_components: int = 1, fill_holes: bool = False) -> torch.Tensor:
+    """The implant of a (full skull, defective skull) prediction pair: ``full AND NOT defective``, opened, optionally
+    hole-filled, reduced to its ``num_components`` largest components (module docstring); a uint8 0 / 1 mask."""
+    n, shape = _volume(full_skull, "full_skull", _MASK_DTYPES)
+    n2, shape2 = _volume(defective_skull, "defective_skull", _MASK_DTYPES)
+    if tuple(full_skull.shape) != tuple(defective_skull.shape):
+        raise ValueError(f"postprocess: full_skull and defective_skull must have the same shape, got "
+                         f"{tuple(full_skull.shape)} and {tuple(defective_skull.shape)}")
+    it = _iterations(opening_iterations, 0, "opening_iterations")
+    code = _structure_code(structure)
+    conn = _connectivity(connectivity)
+    if (isinstance(num_components, bool) or not isinstance(num_components, Integral)
+            or not 1 <= num_components <= MAX_COMPONENTS):
+        raise ValueError(f"postprocess: num_components must lie in 1..{MAX_COMPONENTS}, got {num_components!r}")
+    if not isinstance(fill_holes, (bool, Integral)):
+        raise ValueError(f"postprocess: fill_holes must be a bool, got {fill_holes!r}")
+    _check_device(full_skull)
+    _check_device(defective_skull)
+    if full_skull.device != defective_skull.device:
+        raise ValueError("postprocess: full_skull and defective_skull must live on the same GPU")
+    lib = _lib.load()
+    a, da = _as_bytes(full_skull)
+    b, db = _as_bytes(defective_skull)
+    out = _mask_out(full_skull)
+    ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_IMPLANT), dtype=torch.uint8, device=full_skull.device)
+    with torch.cuda.device(full_skull.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_implant_mask(a.data_ptr(), da, b.data_ptr(), db, n, *shape, code, it, int(bool(fill_holes)), conn,
+                                        int(num_components), out.data_ptr(), ws.data_ptr(), stream), "implant_mask")
+    return out
+
+
+def morphology_workspace_bytes(n: int, shape, iterations: int = 1) -> int:
+    """Device workspace (bytes) of one erosion / dilation / opening / closing call on n items of a (D, H, W) volume: two
+    bit images, whatever ``iterations`` is (``ctu_morphology_ws_bytes`` also sizes fill-holes and implant calls)."""
+    _iterations(iterations)
+    return int(_lib.load().ctu_morphology_ws_bytes(n, *shape, _WS_MORPH))

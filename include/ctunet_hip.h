@@ -458,6 +458,40 @@ int ctu_label_components(const void* in, int dtype, int N, int D, int H, int W, 
 int ctu_filter_components(const void* in, int dtype, int N, int D, int H, int W, int connectivity,
                           const int64_t* applied, int n_applied, int mode, int param, void* out, void* ws, void* stream);
 
+/* Binary morphology of masks on bit images, hole filling and the implant mask (reference: erode / dilate / ErodeDilate of
+ * ctunet/pytorch/transforms.py:97-127,356-377 through SimpleITK; pinned here on scipy.ndimage, definitions in
+ * ctunet_amd/postprocess.py).  in: DEVICE [N,D,H,W] of dtype CTU_U8 or CTU_I64; a voxel is foreground if it is nonzero or,
+ * with has_label != 0, equal to label.  out: DEVICE uint8 [N,D,H,W] of 0 / 1, a buffer of its own unless stated.
+ * structure: 27-bit code, bit (i*3+j)*3+k set iff structure[i][j][k] (z, y, x; nonzero).  With S the offsets
+ * (i-1, j-1, k-1) of the set bits and every voxel outside the volume reading as the border value (0 / 1):
+ *   CTU_MORPH_ERODE:  out[v] = AND_{s in S} in[v+s], `iterations` (1..64) times;  CTU_MORPH_DILATE: out[v] = OR in[v-s];
+ *   CTU_MORPH_OPEN:   `iterations` erosions, then as many dilations;  CTU_MORPH_CLOSE: dilations, then erosions (pass
+ *                     border 0 for scipy's binary_opening / binary_closing).
+ *   fill_holes:   out (may alias in) = in OR the background voxels whose background component (connectivity 1 / 2 / 3)
+ *                 touches no face of the volume.
+ *   implant_mask: m = (full != 0) AND (defective == 0); opening_iterations (0..64) > 0: opened with structure, border 0;
+ *                 fill_holes != 0: holes filled at connectivity 1; then the num_components (1..8) largest components at
+ *                 `connectivity` are kept (ctu_filter_components).
+ * ws: ctu_morphology_ws_bytes(kind) bytes, 0 for invalid geometry: CTU_MORPH_WS_MORPH (binary_morphology) two bit
+ * images, 1/8 byte per voxel each, rows padded to 64 voxels; CTU_MORPH_WS_FILL (fill_holes) the components workspace
+ * plus one byte per voxel; CTU_MORPH_WS_IMPLANT (implant_mask) both.  Each item's D*H*W < 2^31, N <= 65535.
+ * Deterministic, no atomics in the morphology kernels, no host sync, capture-safe. */
+#define CTU_MORPH_ERODE 0
+#define CTU_MORPH_DILATE 1
+#define CTU_MORPH_OPEN 2
+#define CTU_MORPH_CLOSE 3
+#define CTU_MORPH_WS_MORPH 0
+#define CTU_MORPH_WS_FILL 1
+#define CTU_MORPH_WS_IMPLANT 2
+size_t ctu_morphology_ws_bytes(int N, int D, int H, int W, int kind);
+int ctu_binary_morphology(const void* in, int dtype, int N, int D, int H, int W, int mode, uint32_t structure,
+                          int iterations, int border, int has_label, int64_t label, uint8_t* out, void* ws, void* stream);
+int ctu_fill_holes(const void* in, int dtype, int N, int D, int H, int W, int connectivity, int has_label, int64_t label,
+                   uint8_t* out, void* ws, void* stream);
+int ctu_implant_mask(const void* full, int full_dtype, const void* defective, int defective_dtype, int N, int D, int H,
+                     int W, uint32_t structure, int opening_iterations, int fill_holes, int connectivity,
+                     int num_components, uint8_t* out, void* ws, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
