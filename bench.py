@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: voxels/sec, forward+backward, 128^3 fp32 patch (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" is what ``Model.forward_pass`` does per batch in the reference
@@ -9,6 +9,12 @@ One "step" is what ``Model.forward_pass`` does per batch in the reference
 Dice + cross-entropy loss (lambda 1, 1), backward, gradient mean over ranks (N > 1),
 Adam(amsgrad) step, grads -> None.  Per-GPU batch 1 of a synthetic 128^3 fp32 patch (the example inis
 use i_batch_size = 1); weak scaling.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  ``--full`` adds every leg that takes steps or runs of its own after the timed region: the per-kernel table and the
+roofline kernel of a graph-replayed run (eagerly launched steps bracketed by HIP events), ``comm_ms_exposed`` (N > 1: the
+timed steps replayed without the collectives) and ``cpu_baseline`` (the oracle timed on the host cores, and the Dice /
+output-error check of the measured path against it).  Without it those keys are absent or null.
 """
 import argparse
 import json
@@ -200,25 +206,25 @@ ALGO = {"UNet": (129.6e3, 694), "UNetSP": (100.6e3, 617), "UNetDO": (99.5e3, 613
 PEAK_16BIT_MFMA_TFLOPS = 2500.0    # dense bf16 / fp16 (MI355X_MICROARCH.md)
 
 
-def main():
-    # Libraries (RCCL's version banner, ...) write to fd 1; the contract is ONE JSON line on stdout.  Route fd 1 to
-    # stderr for the whole run and keep the real stdout for the final line.
-    sys.stdout.flush()
-    real_stdout = os.fdopen(os.dup(1), "w")
-    os.dup2(2, 1)
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take steps of their own after the timed region: per-kernel table and roofline "
+                         "kernel of a graph-replayed run, comm_ms_exposed (N > 1), cpu_baseline (default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline leg")
     ap.add_argument("--cpu-check-only", action="store_true",
                     help="cpu_baseline leg: ONE oracle step (its time is reported as the bounded sample) plus the Dice / "
                          "output-error check against the CPU reference -- for the large cfg 4 / 5 legs")
     ap.add_argument("--allow-torch-comm", action="store_true",
                     help="N > 1: accept torch.distributed's RCCL group if the C ABI's communicator (ctu_comm_*) cannot be "
                          "brought up on every rank (default: exit non-zero -- the measured path is the C-ABI one)")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="no HIP events around the launches: neither in --full's eager steps after a graph-replayed timed "
+                         "region nor, with --eager, inside the timed region")
     ap.add_argument("--eager", action="store_true", help="do not replay the step from a HIP graph (default: graph)")
     # secondary legs (the defaults above ARE the headline: UNet(), 128^3, fp32, batch 1, train step)
     ap.add_argument("--model", default="UNet", choices=sorted(ALGO), help="drop-in class to run")
@@ -228,9 +234,19 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (rank 0): the eval-mode output map(s); "
                          "for a train step the loss terms and the parameters and buffers it left behind")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    # Libraries (RCCL's version banner, ...) write to fd 1; the contract is ONE JSON line on stdout.  Route fd 1 to
+    # stderr for the whole run and keep the real stdout for the final line.
+    sys.stdout.flush()
+    real_stdout = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -345,7 +361,7 @@ def main():
             arrays.update(("buffer." + n, b) for n, b in net.named_buffers())
         dump_outputs(args.dump_outputs, arrays)
     timer_steps = args.steps
-    if rank == 0 and not args.no_kernel_timer and mode == "hipgraph":
+    if args.full and rank == 0 and not args.no_kernel_timer and mode == "hipgraph":
         # Kernels inside a graph replay cannot be bracketed by events: time the SAME kernels (same launch shapes,
         # same buffers' sizes) in a few eagerly launched steps right after the timed region.
         timer_steps = min(5, args.steps)
@@ -361,7 +377,7 @@ def main():
         torch.cuda.synchronize()
         ops.TIMER = None
     comm_ms_exposed = None
-    if distributed and mode == "hipgraph" and train:
+    if args.full and distributed and mode == "hipgraph" and train:
         # exposed communication = step time with the bucket all-reduces minus the same graph segments replayed without
         # them (after the timed region; those steps skip the averaging and are not part of any reported number)
         gstep.skip_comm = True
@@ -455,7 +471,7 @@ def main():
                                           "the MFMA peak; the roofline kernel is chosen among the unfused convolutions"},
             "roofline": roofline, "kernels": kernels,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.size, args.model, precision, args.mode, args.batch, check_only=args.cpu_check_only)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()

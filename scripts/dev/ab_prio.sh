@@ -12,7 +12,7 @@ done
 done
 cat $O/layers.txt
 for LIB in scripts/build/lib_p0.so $MAIN scripts/build/lib_p3.so scripts/build/lib_p0.so $MAIN scripts/build/lib_p3.so; do
-  CTUNET_HIP_LIB=$PWD/$LIB timeout -k 10 200 python bench.py --no-cpu-baseline > $O/one.json 2>$O/one.err || { tail -5 $O/one.err; exit 1; }
+  CTUNET_HIP_LIB=$PWD/$LIB timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/one.json 2>$O/one.err || { tail -5 $O/one.err; exit 1; }
   python - "$LIB" <<'PY' | tee -a $O/bench.txt
 import json,sys
 d=json.loads(open('gpurun_out/ab_prio/one.json').read().strip().splitlines()[-1])

@@ -4,11 +4,11 @@ set -e
 O=gpurun_out/final2
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python bench.py"
+B="python bench.py --full"
 echo "[1] default bench (headline, with cpu_baseline)"
 timeout -k 10 600 $B > $O/r02_bench_default.json 2> $O/bench_default.err
 echo "[2] torchrun 1 rank (segmented graph + RCCL path)"
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/r02_bench_torchrun1.json 2> $O/bench_torchrun1.err
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/r02_bench_torchrun1.json 2> $O/bench_torchrun1.err
 echo "[3] rocprof kernel stats of the default command"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err
 cp $O/prof/r_kernel_stats.csv $O/r02_kernel_stats.csv

@@ -5,7 +5,7 @@ set -e
 O=gpurun_out/final3
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python bench.py"
+B="python bench.py --full"
 PART=${1:-a}
 pmc3() {   # pmc3 <tag> <command...>: FETCH_SIZE, WRITE_SIZE, SQ_VALU_MFMA_BUSY_CYCLES passes (separate, kernel trace only)
   T=$1; shift
@@ -17,7 +17,7 @@ if [ $PART = a ]; then
 echo "[1] default bench (headline, with cpu_baseline)"
 timeout -k 10 600 $B > $O/r03_bench_default.json 2> $O/bench_default.err
 echo "[2] torchrun 1 rank (segmented graph + RCCL path)"
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/r03_bench_torchrun1.json 2> $O/r03_bench_torchrun1.stderr.txt
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/r03_bench_torchrun1.json 2> $O/r03_bench_torchrun1.stderr.txt
 echo "[3] rocprof kernel stats of the default command, and of the 16-bit leg"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err
 cp $O/prof/r_kernel_stats.csv $O/r03_kernel_stats.csv
