@@ -125,6 +125,7 @@ SIGNATURES = {
     "ctu_binary_morphology": (I, [P, I, I, I, I, I, I, C.c_uint32, I, I, I, L, P, P, P]),
     "ctu_fill_holes": (I, [P, I, I, I, I, I, I, I, L, P, P, P]),
     "ctu_implant_mask": (I, [P, I, P, I, I, I, I, I, C.c_uint32, I, I, I, I, P, P, P]),
+    "ctu_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

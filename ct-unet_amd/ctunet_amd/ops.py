@@ -1246,3 +1246,26 @@ def flap_apply(skulls: torch.Tensor, atlas: Optional[torch.Tensor], params: torc
     _lib.check(_lib.load().ctu_flap_apply(skulls.data_ptr(), u8, _ptr(atlas), n, d, h, w, params.data_ptr(), mode,
                                           _ptr(hole_seq), _ptr(noise_seq), _ptr(noise_nd), noise_seed, int(decay),
                                           x.data_ptr(), x.shape[1], _ptr(full), _ptr(flap), _stream()), "flap_apply")
+
+
+RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_LABEL_LINEAR = 0, 1, 2          # CTU_RESAMPLE_* of ctunet_hip.h
+# dtype codes of ctu_resample (CTU_F32 / CTU_U8 / CTU_I64 / CTU_I16 / CTU_I32); bool travels as uint8
+RESAMPLE_CODE = {torch.float32: 0, torch.uint8: 3, torch.bool: 3, torch.int64: 4, torch.int16: 5, torch.int32: 6}
+
+
+def resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n: int, in_shape: Tuple[int, int, int],
+             out_shape: Tuple[int, int, int], tables: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]) -> None:
+    """out [n, d, h, w] = x [n, D, H, W] resampled through the device tables (i0 int32, wt float32, near int32, each the
+    z, y and x table of the output grid one after the other; rule: ctunet_amd/resample.py).  One launch, nothing allocated."""
+    for t, nm in ((x, "input"), (out, "output")):
+        if not t.is_cuda:
+            raise RuntimeError(f"ctunet_amd: resample {nm} must live on the GPU (MI355X); this path has no CPU fallback")
+        assert t.is_contiguous(), nm
+    (d0, h0, w0), (d1, h1, w1) = in_shape, out_shape
+    assert x.numel() == n * d0 * h0 * w0 and out.numel() == n * d1 * h1 * w1, "resample shapes"
+    i0, wt, near = tables
+    assert all(t.is_cuda and t.is_contiguous() and t.numel() == d1 + h1 + w1 for t in tables), "resample tables"
+    assert i0.dtype == torch.int32 and near.dtype == torch.int32 and wt.dtype == torch.float32, "resample tables"
+    _lib.check(_lib.load().ctu_resample(x.data_ptr(), RESAMPLE_CODE[x.dtype], mode, num_classes, n, d0, h0, w0, d1, h1, w1,
+                                        i0.data_ptr(), wt.data_ptr(), near.data_ptr(), out.data_ptr(), _stream()),
+               "resample")

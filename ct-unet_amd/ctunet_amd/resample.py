@@ -1,0 +1,238 @@
+"""Resampling of volumes between voxel grids and spacings on the GPU: the step between a scanner's grid and the
+network's, in both directions.  A deterministic, separable, axis-aligned change of grid (``ctu_resample`` of
+``csrc/resample.hip``); no CPU fallback.
+
+    y = resample(x, size=(179, 230, 230))                              # to a grid
+    y = resample(x, spacing=(0.8, 0.45, 0.45), new_spacing=1.0)        # to a spacing
+    r = Resampler(x.shape[-3:], in_spacing=(0.8, 0.45, 0.45), out_spacing=1.0).to(x.device)
+    y = r(x)                                                           # in grid -> out grid (r.out_shape, r.out_spacing)
+    back = r.inverse(labels, mode="label_linear", num_classes=2)       # out grid -> in grid, exactly in_shape
+
+``x`` has at least three dimensions; the last three are (D, H, W) and all leading ones are a batch.
+
+The pinned rule (``tests/resample_ref.py`` restates it; it is ``scipy.ndimage.zoom(order=1, mode="nearest",
+grid_mode=True)`` and torch's ``trilinear, align_corners=False`` up to float32 rounding, and its ``near`` table is torch's
+``nearest-exact``, bit for bit).
+
+Geometry, per axis, with ``n`` input and ``m`` output voxels, in float64:
+
+- ``size`` alone: ``a = n / m``.
+- ``spacing`` and ``new_spacing`` (a number or a (D, H, W) triple each): ``a = s_new / s`` and
+  ``m = max(1, floor(n * s / s_new + 0.5))`` unless ``size`` is given as well.
+- The inverse of a ``Resampler`` maps the out grid to ``in_shape`` with ``m / n`` in size mode, ``s / s_new`` in spacing mode.
+
+Tables, per axis, of length ``m``, formed on the host in float64 and then rounded::
+
+    src_j  = clip((j + 0.5) * a - 0.5, 0, n - 1)
+    i0_j   = min(floor(src_j), max(n - 2, 0))     int32
+    i1_j   = min(i0_j + 1, n - 1)
+    w_j    = float32(src_j - i0_j)
+    near_j = min(floor((j + 0.5) * a), n - 1)     int32
+
+Modes:
+
+- ``"nearest"``: ``out[k,j,i] = in[near_z[k], near_y[j], near_x[i]]``; bool, uint8, int16, int32, int64 or float32, the same
+  dtype out.
+- ``"linear"``: with ``lerp(p, q, w) = p + w * (q - p)``, every float32 subtraction, multiplication and addition rounded
+  separately (no fused multiply-add), four lerps along x, then two along y, then one along z:
+  ``c00 = lerp(in[z0,y0,x0], in[z0,y0,x1], wx)``, likewise ``c01`` (z0, y1), ``c10`` (z1, y0), ``c11`` (z1, y1); the result
+  is ``lerp(lerp(c00, c01, wy), lerp(c10, c11, wy), wz)``.  float32, int16 (raw CT) or uint8 in, converted in the kernel;
+  float32 out.
+- ``"label_linear"``: for each class ``c`` in increasing order the linear rule runs on the 0/1 indicator ``in == c``; the
+  output is the smallest ``c`` with the largest score.  bool, uint8 or int64 label maps with values in
+  ``[0, num_classes)``, ``2 <= num_classes <= 16``; a voxel ``>= num_classes`` belongs to no class.  The same dtype out.  No
+  one-hot or score volume is written to memory.
+
+A call is one launch: no host synchronisation, no atomics, and with ``out=`` and a contiguous input no allocation, so it
+can be captured into a graph; two calls are bit-equal.  A ``Resampler`` uploads its tables once (``.to(device)``, or the
+first call on a device: do that before a capture); ``resample`` keeps the tables of its recent geometries.  D*H*W is
+below 2^31 on either grid; offsets across the batch are 64-bit.
+"""
+from __future__ import annotations
+
+import functools
+import math
+from numbers import Integral, Real
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+MODES = ("nearest", "linear", "label_linear")
+MAX_CLASSES = 16
+_IN_DTYPES = {
+    "nearest": (torch.bool, torch.uint8, torch.int16, torch.int32, torch.int64, torch.float32),
+    "linear": (torch.float32, torch.int16, torch.uint8),
+    "label_linear": (torch.bool, torch.uint8, torch.int64),
+}
+_MODE_CODE = {"nearest": ops.RESAMPLE_NEAREST, "linear": ops.RESAMPLE_LINEAR, "label_linear": ops.RESAMPLE_LABEL_LINEAR}
+
+
+def _triple_int(v, what: str, who: str) -> Tuple[int, int, int]:
+    try:
+        vals = tuple(v)
+    except TypeError:
+        raise TypeError(f"{who}: {what} must be a (D, H, W) triple of positive integers, got {v!r}") from None
+    if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Integral) for s in vals):
+        raise TypeError(f"{who}: {what} must be a (D, H, W) triple of positive integers, got {v!r}")
+    if any(s < 1 for s in vals):
+        raise ValueError(f"{who}: every side of {what} must be >= 1, got {v!r}")
+    if vals[0] * vals[1] * vals[2] >= 1 << 31:
+        raise ValueError(f"{who}: {what} must hold fewer than 2^31 voxels, got {v!r}")
+    return tuple(int(s) for s in vals)
+
+
+def _triple_spacing(v, what: str, who: str) -> Tuple[float, float, float]:
+    if isinstance(v, Real) and not isinstance(v, bool):
+        vals = (v, v, v)
+    else:
+        try:
+            vals = tuple(v)
+        except TypeError:
+            raise TypeError(f"{who}: {what} must be a positive number or a (D, H, W) triple, got {v!r}") from None
+        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
+            raise TypeError(f"{who}: {what} must be a positive number or a (D, H, W) triple, got {v!r}")
+    if any(not math.isfinite(s) or s <= 0 for s in vals):
+        raise ValueError(f"{who}: {what} must be positive and finite, got {v!r}")
+    return tuple(float(s) for s in vals)
+
+
+def geometry(in_shape, size=None, spacing=None, new_spacing=None, who: str = "resample"):
+    """``(in_shape, out_shape, a)`` of the module docstring's geometry: ``a`` the per-axis float64 scale of the tables."""
+    n = _triple_int(in_shape, "the input grid", who)
+    if (spacing is None) != (new_spacing is None):
+        raise ValueError(f"{who}: spacing and new_spacing go together (with or without size); got only one of them")
+    if size is None and spacing is None:
+        raise ValueError(f"{who}: give size, or spacing and new_spacing")
+    m = None if size is None else _triple_int(size, "size", who)
+    if spacing is not None:
+        s = _triple_spacing(spacing, "spacing", who)
+        t = _triple_spacing(new_spacing, "new_spacing", who)
+        a = tuple(tj / sj for sj, tj in zip(s, t))
+        if m is None:
+            m = _triple_int(tuple(max(1, int(math.floor(nj * sj / tj + 0.5))) for nj, sj, tj in zip(n, s, t)),
+                            "the output grid", who)
+    else:
+        a = tuple(nj / mj for nj, mj in zip(n, m))
+    return n, m, a
+
+
+def axis_tables(n: int, m: int, a: float):
+    """``(i0 int32, w float32, near int32)`` of one axis: the tables of the module docstring."""
+    j = np.arange(m, dtype=np.float64)
+    src = np.clip((j + 0.5) * np.float64(a) - 0.5, 0.0, float(n - 1))
+    i0 = np.minimum(np.floor(src), float(max(n - 2, 0)))
+    near = np.minimum(np.floor((j + 0.5) * np.float64(a)), float(n - 1))
+    return i0.astype(np.int32), (src - i0).astype(np.float32), near.astype(np.int32)
+
+
+def _check_call(x, mode, num_classes, who: str):
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"{who}: mode must be one of {', '.join(MODES)}, got {mode!r}")
+    if mode == "label_linear":
+        if isinstance(num_classes, bool) or not isinstance(num_classes, Integral):
+            raise TypeError(f"{who}: label_linear needs num_classes, an integer in 2..{MAX_CLASSES}, got {num_classes!r}")
+        if not 2 <= num_classes <= MAX_CLASSES:
+            raise ValueError(f"{who}: num_classes must lie in 2..{MAX_CLASSES}, got {num_classes!r}")
+    elif num_classes is not None:
+        raise ValueError(f"{who}: num_classes belongs to mode 'label_linear' only, got {num_classes!r} with mode {mode!r}")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}: the input must be a tensor, got {type(x).__name__}")
+    if x.dim() < 3:
+        raise ValueError(f"{who}: the input needs at least the three dimensions (D, H, W), got shape {tuple(x.shape)}")
+    if x.dtype not in _IN_DTYPES[mode]:
+        raise TypeError(f"{who}: mode {mode!r} takes {', '.join(str(d) for d in _IN_DTYPES[mode])}, got {x.dtype}")
+
+
+class Resampler:
+    """The tables of one change of grid, ``in_shape -> out_shape``, and of its inverse; uploaded once per device.
+
+    ``out_shape`` alone, or ``in_spacing`` and ``out_spacing`` (with or without ``out_shape``).  ``r(x)`` maps the in grid
+    to the out grid, ``r.inverse(y)`` the out grid to exactly ``in_shape``.  ``r.out_shape`` and ``r.out_spacing`` (None in
+    size mode) say what the grid became."""
+
+    def __init__(self, in_shape, out_shape=None, in_spacing=None, out_spacing=None, _who: str = "Resampler"):
+        self.in_shape, self.out_shape, a = geometry(in_shape, out_shape, in_spacing, out_spacing, _who)
+        spaced = in_spacing is not None
+        self.in_spacing = _triple_spacing(in_spacing, "spacing", _who) if spaced else None
+        self.out_spacing = _triple_spacing(out_spacing, "new_spacing", _who) if spaced else None
+        if spaced:
+            inv = tuple(s / t for s, t in zip(self.in_spacing, self.out_spacing))
+        else:
+            inv = tuple(m / n for n, m in zip(self.in_shape, self.out_shape))
+        self.scale, self.inverse_scale = a, inv
+        # host tables per direction: (i0, w, near), each the z, y and x table one after the other
+        self._host = tuple(
+            tuple(np.concatenate(t) for t in zip(*(axis_tables(n, m, s) for n, m, s in zip(src, dst, sc))))
+            for src, dst, sc in ((self.in_shape, self.out_shape, a), (self.out_shape, self.in_shape, inv)))
+        self._device = {}
+
+    def to(self, device) -> "Resampler":
+        """Upload the tables of both directions to ``device`` (once); returns self."""
+        self._tables(torch.device(device))
+        return self
+
+    def _tables(self, device: torch.device):
+        if device.type != "cuda":
+            raise ValueError("Resampler: the tables live on the GPU; this path has no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._device.get(device)
+        if t is None:
+            t = self._device[device] = tuple(tuple(torch.from_numpy(h).to(device) for h in d) for d in self._host)
+        return t
+
+    def _run(self, x, direction: int, mode, num_classes, out, who: str):
+        _check_call(x, mode, num_classes, who)
+        src, dst = (self.in_shape, self.out_shape) if direction == 0 else (self.out_shape, self.in_shape)
+        if tuple(x.shape[-3:]) != src:
+            raise ValueError(f"{who}: the input's grid is {tuple(x.shape[-3:])}, this Resampler maps {src} -> {dst}")
+        lead = tuple(x.shape[:-3])
+        n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        if n < 1:
+            raise ValueError(f"{who}: the batch is empty, got shape {tuple(x.shape)}")
+        out_dtype = torch.float32 if mode == "linear" else x.dtype
+        if out is not None:
+            if not isinstance(out, torch.Tensor):
+                raise TypeError(f"{who}: out must be a tensor, got {type(out).__name__}")
+            if tuple(out.shape) != lead + dst or out.dtype != out_dtype or out.device != x.device or not out.is_contiguous():
+                raise ValueError(f"{who}: out must be a contiguous {out_dtype} tensor of shape {lead + dst} on {x.device}, "
+                                 f"got {out.dtype} {tuple(out.shape)} on {out.device}"
+                                 f"{'' if out.is_contiguous() else ', not contiguous'}")
+        if not x.is_cuda:
+            raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
+        tables = self._tables(x.device)[direction]
+        if out is None:
+            out = torch.empty(lead + dst, dtype=out_dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            ops.resample(x.contiguous(), out, _MODE_CODE[mode], int(num_classes or 0), n, src, dst, tables)
+        return out
+
+    def __call__(self, x, mode: str = "linear", num_classes: Optional[int] = None, out=None) -> torch.Tensor:
+        """``x [..., *in_shape]`` on the out grid."""
+        return self._run(x, 0, mode, num_classes, out, "Resampler")
+
+    def inverse(self, y, mode: str = "linear", num_classes: Optional[int] = None, out=None) -> torch.Tensor:
+        """``y [..., *out_shape]`` back on the in grid: exactly ``in_shape``."""
+        return self._run(y, 1, mode, num_classes, out, "Resampler.inverse")
+
+
+@functools.lru_cache(maxsize=16)
+def _cached(in_shape, size, spacing, new_spacing) -> Resampler:
+    return Resampler(in_shape, size, spacing, new_spacing, _who="resample")
+
+
+def _key(v):
+    return v if v is None or isinstance(v, Real) else tuple(v)
+
+
+def resample(x, size=None, *, spacing=None, new_spacing=None, mode: str = "linear", num_classes: Optional[int] = None,
+             out=None) -> torch.Tensor:
+    """``x [..., D, H, W]`` on the grid ``size``, or on the grid that ``spacing -> new_spacing`` gives (module docstring)."""
+    _check_call(x, mode, num_classes, "resample")
+    in_shape = tuple(int(s) for s in x.shape[-3:])
+    geometry(in_shape, size, spacing, new_spacing, "resample")           # raises before the cache sees an unhashable value
+    r = _cached(in_shape, _key(size), _key(spacing), _key(new_spacing))
+    return r._run(x, 0, mode, num_classes, out, "resample")

@@ -492,6 +492,30 @@ int ctu_implant_mask(const void* full, int full_dtype, const void* defective, in
                      int W, uint32_t structure, int opening_iterations, int fill_holes, int connectivity,
                      int num_components, uint8_t* out, void* ws, void* stream);
 
+/* Resampling of volumes between voxel grids (no reference counterpart: the reference resizes on the host in its datasets,
+ * ctunet/pytorch/datasets.py:89-112; rule and tables pinned in ctunet_amd/resample.py).  in: DEVICE [N,D,H,W], out: DEVICE
+ * [N,d,h,w], both contiguous, a buffer each.  Tables: DEVICE arrays of d + h + w entries each, the z, y and x tables one
+ * after the other, every entry an input index of its axis (non-decreasing along an axis):
+ *   i0 (int32) and wt (float32): lower neighbour and weight of the upper one (the upper neighbour is min(i0 + 1, n - 1));
+ *   near (int32): the nearest-exact source index.
+ *   CTU_RESAMPLE_NEAREST:      out[k,j,i] = in[near_z[k], near_y[j], near_x[i]]; dtype CTU_U8 (bool too), CTU_I16, CTU_I32,
+ *                              CTU_I64 or CTU_F32, the same dtype out.
+ *   CTU_RESAMPLE_LINEAR:       lerp(p, q, w) = p + w (q - p), each float32 operation rounded on its own; four lerps along
+ *                              x, two along y, one along z; dtype CTU_F32, CTU_I16 or CTU_U8 (converted in the kernel),
+ *                              float32 out.
+ *   CTU_RESAMPLE_LABEL_LINEAR: the linear rule on the indicator in == c of every class c < num_classes (2..16); out = the
+ *                              smallest c of the largest score; a voxel >= num_classes belongs to no class; dtype CTU_U8 or
+ *                              CTU_I64, the same dtype out.
+ * One launch per 65535 items, no workspace, no atomics, no host sync, capture-safe, bitwise reproducible.  D*H*W < 2^31
+ * on either grid; offsets across the batch are 64-bit. */
+#define CTU_I16 5
+#define CTU_I32 6
+#define CTU_RESAMPLE_NEAREST 0
+#define CTU_RESAMPLE_LINEAR 1
+#define CTU_RESAMPLE_LABEL_LINEAR 2
+int ctu_resample(const void* in, int dtype, int mode, int num_classes, int64_t N, int D, int H, int W, int d, int h, int w,
+                 const int32_t* i0, const float* wt, const int32_t* near, void* out, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
