@@ -373,7 +373,7 @@ def test_convtranspose(case):
     assert rel_err(db.cpu(), b.grad) < 1e-4
 
 
-@pytest.mark.parametrize("co,act,mode", [(2, 2, 0), (2, 1, 0), (3, 2, 1), (3, 2, 2), (3, 3, 0), (1, 0, 0)])
+@pytest.mark.parametrize("co,act,mode", [(2, 2, 0), (2, 1, 0), (3, 2, 1), (3, 2, 2), (3, 3, 0), (1, 0, 0), (4, 1, 0), (4, 3, 0)])
 def test_head_fwd_bwd(co, act, mode):
     ops = _ops()
     n, d, h, w = 2, 4, 6, 10
@@ -458,15 +458,12 @@ def test_loss_fwd_bwd(ce, dice, sm):
     p = torch.rand(2, 2, 6, 8, 10, generator=g(1)).requires_grad_(True)
     m = (torch.rand(2, 6, 8, 10, generator=g(2)) < 0.3).long()
     t = F.one_hot(m, 2).movedim(4, 1).float().contiguous()
-    terms = []
-    if ce:
-        terms.append(ce * O.cross_entropy(p, t))
-    if dice:
-        terms.append(dice * O.dice_loss(F.softmax(p, 1) if sm else p, t))
-    total = sum(terms)
-    total.backward()
+    terms = [ce * O.cross_entropy(p, t) if ce else torch.zeros(()),
+             dice * O.dice_loss(F.softmax(p, 1) if sm else p, t) if dice else torch.zeros(())]
+    sum(terms).backward()
     tg, ws = ops.loss_fwd(p.detach().cuda(), t.cuda(), ce, dice, sm)
-    assert abs(tg.sum().item() - total.item()) < 1e-5 * max(1.0, abs(total.item()))
+    for got, want in zip(tg.tolist(), terms):                   # (ce term, dice term), each on its own
+        assert abs(got - want.item()) < 1e-5 * max(1.0, abs(want.item()))
     gp = ops.loss_bwd(p.detach().cuda(), t.cuda(), ce, dice, sm, ws, None, None)
     assert rel_err(gp.cpu(), p.grad) < 1e-4
     gp2 = ops.loss_bwd(p.detach().cuda(), t.cuda(), ce, dice, sm, ws, torch.tensor(2.0).cuda(), torch.tensor(2.0).cuda(), gp.clone(), True)
