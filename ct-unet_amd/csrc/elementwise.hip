@@ -410,6 +410,190 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ in, int in_cs, int cp,
     }
 }
 
+// ---- MaxPool3d(2,2) with lanes along the FINE row (cp / 4 a power of two <= 32; the kernels above serve every other width).
+// A coarse row is one (n, do, ho); its flat positions are (w, quad) of the fine grid, W * nq of them, and a thread owns one
+// position for the row's four (d, h) planes -- so every load or store instruction of a wave covers one contiguous run of a
+// fine row (the kernels above touch every second voxel per instruction).  The two w of a window sit nq lanes apart in one
+// wave (W is even and 2 nq divides 64): each lane reduces its own w over (d, h) with strict >, then the pair exchanges
+// {maximum, its (d, h) index} once.  Grid-stride over positions (the backward with reduction rows: two trips per block, one
+// block per row): every stride is a multiple of nq, so a thread keeps its channel quad and that quad's constants stay in
+// registers.
+struct PoolRows { unsigned total, rowlen; int lg_nq, Do, Ho; };      // positions overall / per coarse row, log2(nq)
+
+__device__ __forceinline__ void pool_row_decode(const PoolRows& g, unsigned f, int D, int H, int W, size_t& vox,
+                                                size_t& ovox) {
+    const unsigned r = f / g.rowlen, w = (f - r * g.rowlen) >> g.lg_nq;
+    const unsigned ho = r % (unsigned)g.Ho, nd = r / (unsigned)g.Ho;                  // nd = n * Do + do
+    const unsigned dd = nd % (unsigned)g.Do, n = nd / (unsigned)g.Do;
+    vox = (((size_t)n * D + dd * 2) * H + ho * 2) * W + w;                            // plane (d, h) = (0, 0) of the window
+    ovox = (size_t)r * (W >> 1) + (w >> 1);
+}
+
+template <class T>
+__global__ __launch_bounds__(EW_BLOCK) void maxpool2_fwd_row_kernel(const T* __restrict__ in, int in_cs,
+                                                                     const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift, int relu,
+                                                                     T* __restrict__ out, int out_cs, int D, int H, int W,
+                                                                     PoolRows g) {
+    const int nq = 1 << g.lg_nq, qd = threadIdx.x & (nq - 1);
+    const bool xf = scale != nullptr;
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xf) {
+        sc = *reinterpret_cast<const float4*>(scale + qd * 4);
+        sh = *reinterpret_cast<const float4*>(shift + qd * 4);
+    }
+    const bool upper = (threadIdx.x & nq) != 0;                                       // this lane holds the odd w of its window
+    for (unsigned f = blockIdx.x * EW_BLOCK + threadIdx.x; f < g.total; f += gridDim.x * EW_BLOCK) {
+        size_t vox, ovox;
+        pool_row_decode(g, f, D, H, W, vox, ovox);
+        float4 v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            v[t] = ld4<T>(in + (vox + ((size_t)(t >> 1) * H + (t & 1)) * W) * in_cs + qd * 4);
+        float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float4 a = xf ? xform4(v[t], sc, sh, relu) : v[t];
+            best.x = fmaxf(best.x, a.x); best.y = fmaxf(best.y, a.y);
+            best.z = fmaxf(best.z, a.z); best.w = fmaxf(best.w, a.w);
+        }
+        best.x = fmaxf(best.x, __shfl_xor(best.x, nq)); best.y = fmaxf(best.y, __shfl_xor(best.y, nq));
+        best.z = fmaxf(best.z, __shfl_xor(best.z, nq)); best.w = fmaxf(best.w, __shfl_xor(best.w, nq));
+        if (!upper) st4<T>(out + ovox * out_cs + qd * 4, best);
+    }
+}
+
+template <bool RED, class T>
+__global__ __launch_bounds__(EW_BLOCK) void maxpool2_bwd_row_kernel(const T* __restrict__ in, int in_cs, int cp,
+                                                                     const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift, int relu,
+                                                                     const T* __restrict__ gout, int gout_cs,
+                                                                     T* __restrict__ gin, int gin_cs, int accumulate, int D,
+                                                                     int H, int W, PoolRows g, const float* __restrict__ mean,
+                                                                     const float* __restrict__ invstd,
+                                                                     float* __restrict__ partials, ctu_bn_bwd_tail tail) {
+    const int nq = 1 << g.lg_nq, qd = threadIdx.x & (nq - 1);
+    const bool xf = scale != nullptr;
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xf) {
+        sc = *reinterpret_cast<const float4*>(scale + qd * 4);
+        sh = *reinterpret_cast<const float4*>(shift + qd * 4);
+    }
+    float4 mu = make_float4(0.f, 0.f, 0.f, 0.f), is = mu;
+    if constexpr (RED) {
+        mu = *reinterpret_cast<const float4*>(mean + qd * 4);
+        is = *reinterpret_cast<const float4*>(invstd + qd * 4);
+    }
+    const bool upper = (threadIdx.x & nq) != 0;
+    // RED: a block owns 2 * EW_BLOCK consecutive positions = the EW_BLOCK (pooled voxel, quad) items of one partial row of
+    // the kernel above, and sums them in that kernel's order, so the rows are the same bit for bit (what is trained from
+    // them does not depend on which kernel ran); red holds the items' sums.
+    __shared__ float red[RED ? EW_BLOCK * 8 : 1];
+    if constexpr (RED) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = 0.f;
+        __syncthreads();
+    }
+    constexpr unsigned PER = RED ? 2 * EW_BLOCK : EW_BLOCK;
+    const unsigned stride = RED ? EW_BLOCK : gridDim.x * EW_BLOCK;
+    const unsigned stop = RED ? min(g.total, (blockIdx.x + 1) * PER) : g.total;
+    unsigned slot = threadIdx.x;                                                      // position inside the block's row (RED)
+    for (unsigned f = blockIdx.x * PER + threadIdx.x; f < stop; f += stride, slot += EW_BLOCK) {
+        size_t vox, ovox;
+        pool_row_decode(g, f, D, H, W, vox, ovox);
+        float4 raw[4], r[4], gz[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            raw[t] = ld4<T>(in + (vox + ((size_t)(t >> 1) * H + (t & 1)) * W) * in_cs + qd * 4);
+        const float4 go = ld4<T>(gout + ovox * gout_cs + qd * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            r[t] = accumulate ? ld4<T>(gin + (vox + ((size_t)(t >> 1) * H + (t & 1)) * W) * gin_cs + qd * 4)
+                              : make_float4(0.f, 0.f, 0.f, 0.f);
+        // first maximum in (d, h, w) scan order wins, as ATen's max_pool3d does: strict > over this lane's (d, h) ...
+        float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        int bx = 0, by = 0, bz = 0, bw = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float4 a = xf ? xform4(raw[t], sc, sh, relu) : raw[t];
+            if (a.x > best.x) { best.x = a.x; bx = t; }
+            if (a.y > best.y) { best.y = a.y; by = t; }
+            if (a.z > best.z) { best.z = a.z; bz = t; }
+            if (a.w > best.w) { best.w = a.w; bw = t; }
+        }
+        // ... then between the two w: scan position 2 (d, h) + w, so on equal maxima the odd w wins only with a strictly
+        // smaller (d, h) index
+        const int mine = bx | (by << 2) | (bz << 4) | (bw << 6);
+        const int theirs = __shfl_xor(mine, nq);
+        const float4 ob = make_float4(__shfl_xor(best.x, nq), __shfl_xor(best.y, nq), __shfl_xor(best.z, nq),
+                                      __shfl_xor(best.w, nq));
+        const int ox = theirs & 3, oy = (theirs >> 2) & 3, oz = (theirs >> 4) & 3, ow = (theirs >> 6) & 3;
+        const bool wx = upper ? (best.x > ob.x || (best.x == ob.x && bx < ox)) : !(ob.x > best.x || (ob.x == best.x && ox < bx));
+        const bool wy = upper ? (best.y > ob.y || (best.y == ob.y && by < oy)) : !(ob.y > best.y || (ob.y == best.y && oy < by));
+        const bool wz = upper ? (best.z > ob.z || (best.z == ob.z && bz < oz)) : !(ob.z > best.z || (ob.z == best.z && oz < bz));
+        const bool ww = upper ? (best.w > ob.w || (best.w == ob.w && bw < ow)) : !(ob.w > best.w || (ob.w == best.w && ow < bw));
+        if (!wx) bx = -1;
+        if (!wy) by = -1;
+        if (!wz) bz = -1;
+        if (!ww) bw = -1;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float4 o = r[t];
+            if (bx == t) o.x += go.x;
+            if (by == t) o.y += go.y;
+            if (bz == t) o.z += go.z;
+            if (bw == t) o.w += go.w;
+            o = rnd4<T>(o);                      // the reduction sees what the BatchNorm-backward apply pass will read back
+            st4<T>(gin + (vox + ((size_t)(t >> 1) * H + (t & 1)) * W) * gin_cs + qd * 4, o);
+            if constexpr (RED) {
+                const float4 y = raw[t];
+                gz[t].x = (fmaf(y.x, sc.x, sh.x) > 0.f) ? o.x : 0.f; gz[t].y = (fmaf(y.y, sc.y, sh.y) > 0.f) ? o.y : 0.f;
+                gz[t].z = (fmaf(y.z, sc.z, sh.z) > 0.f) ? o.z : 0.f; gz[t].w = (fmaf(y.w, sc.w, sh.w) > 0.f) ? o.w : 0.f;
+            }
+        }
+        if constexpr (RED) {
+            // the window's eight terms in scan order, (d, h) outer and w inner: the even-w lane takes the odd-w lane's
+            // four {masked gradient, raw value} and sums for the pair
+            float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a1;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                float4 y = raw[t];
+                float4 z = gz[t];
+                const float4 yo = make_float4(__shfl_xor(y.x, nq), __shfl_xor(y.y, nq), __shfl_xor(y.z, nq), __shfl_xor(y.w, nq));
+                const float4 zo = make_float4(__shfl_xor(z.x, nq), __shfl_xor(z.y, nq), __shfl_xor(z.z, nq), __shfl_xor(z.w, nq));
+#pragma unroll
+                for (int w = 0; w < 2; ++w) {
+                    float gz_;
+                    gz_ = z.x; a1.x += gz_; a2.x += gz_ * (y.x - mu.x) * is.x;
+                    gz_ = z.y; a1.y += gz_; a2.y += gz_ * (y.y - mu.y) * is.y;
+                    gz_ = z.z; a1.z += gz_; a2.z += gz_ * (y.z - mu.z) * is.z;
+                    gz_ = z.w; a1.w += gz_; a2.w += gz_ * (y.w - mu.w) * is.w;
+                    y = yo; z = zo;
+                }
+            }
+            if (!upper) {
+                float* r_ = &red[(((slot >> (g.lg_nq + 1)) << g.lg_nq) + qd) * 8];      // item = pooled voxel of the row * nq + quad
+                r_[0] = a1.x; r_[1] = a1.y; r_[2] = a1.z; r_[3] = a1.w; r_[4] = a2.x; r_[5] = a2.y; r_[6] = a2.z; r_[7] = a2.w;
+            }
+        }
+    }
+    if constexpr (RED) {
+        // thread t < cp sums channel t over the row's items in a fixed order
+        __syncthreads();
+        if (threadIdx.x < cp) {
+            const int c = threadIdx.x, q = c >> 2, j = c & 3;
+            float s1 = 0.f, s2 = 0.f;
+            for (int l = 0; l < EW_BLOCK / nq; ++l) {
+                s1 += red[(l * nq + q) * 8 + j];
+                s2 += red[(l * nq + q) * 8 + 4 + j];
+            }
+            st_row(tail.counter != nullptr, partials + (size_t)blockIdx.x * 2 * cp + c, s1);
+            st_row(tail.counter != nullptr, partials + (size_t)blockIdx.x * 2 * cp + cp + c, s2);
+        }
+        if (tail.counter) bn_bwd_tail(tail, partials, gridDim.x, cp, gridDim.x);
+    }
+}
+
 // ------------------------------------------------------------------ channel sums
 template <class T>
 __global__ void channel_sum_partial_kernel(const T* __restrict__ x, int cs, int cp, int64_t nvox,
@@ -608,14 +792,39 @@ int bn_relu_bwd_apply_impl(const T* y, int y_cs, T* ga, int g_cs, int cp, const 
     return CTU_OK;
 }
 
+// launch shape of the row kernels: rows.total = 0 where they do not apply (cp / 4 not a power of two <= 32, or more positions
+// than 32-bit indices hold) and the (pooled voxel, quad) kernels run instead.  nb: at most 8 resident blocks per CU (the
+// backward with reduction rows launches ctu_maxpool2_bwd_bn_num_blocks blocks instead, one per row).
+struct PoolPlan { PoolRows rows; int nb; };
+PoolPlan pool_plan(int N, int D, int H, int W, int cp) {
+    PoolPlan p = {};
+    const int nq = cp >> 2;
+    const int64_t total = (int64_t)N * (D / 2) * (H / 2) * W * nq;
+    if (nq > 32 || (nq & (nq - 1)) != 0 || total <= 0 || total >= ((int64_t)1 << 31)) return p;
+    while ((1 << p.rows.lg_nq) < nq) ++p.rows.lg_nq;
+    p.rows.total = (unsigned)total;
+    p.rows.rowlen = (unsigned)(W * nq);
+    p.rows.Do = D / 2;
+    p.rows.Ho = H / 2;
+    const int64_t nb = ceil_div64(total, EW_BLOCK);
+    p.nb = (int)(nb > 2048 ? 2048 : nb);
+    return p;
+}
+
 template <class T>
 int maxpool2_fwd_impl(const T* in, int in_cs, int cp, const float* in_scale, const float* in_shift, int in_relu, T* out,
                       int out_cs, int N, int D, int H, int W, void* stream) {
     CTU_REQUIRE(in && out, "maxpool2_fwd: null pointer");
     CTU_REQUIRE(cp % 8 == 0 && cp > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool2_fwd: D,H,W must be even");
-    const int64_t total = (int64_t)N * (D / 2) * (H / 2) * (W / 2) * (cp >> 2);
-    maxpool2_fwd_kernel<T><<<(unsigned)ceil_div64(total, EW_BLOCK), EW_BLOCK, 0, (hipStream_t)stream>>>(
-        in, in_cs, cp, in_scale, in_shift, in_relu, out, out_cs, N, D, H, W);
+    const PoolPlan pl = pool_plan(N, D, H, W, cp);
+    if (pl.rows.total) {
+        maxpool2_fwd_row_kernel<T><<<pl.nb, EW_BLOCK, 0, (hipStream_t)stream>>>(in, in_cs, in_scale, in_shift, in_relu, out, out_cs,
+                                                                                D, H, W, pl.rows);
+    } else {
+        const int64_t total = (int64_t)N * (D / 2) * (H / 2) * (W / 2) * (cp >> 2);
+        maxpool2_fwd_kernel<T><<<(unsigned)ceil_div64(total, EW_BLOCK), EW_BLOCK, 0, (hipStream_t)stream>>>(
+            in, in_cs, cp, in_scale, in_shift, in_relu, out, out_cs, N, D, H, W);
+    }
     CTU_CHECK_LAUNCH("maxpool2_fwd");
     return CTU_OK;
 }
@@ -625,10 +834,17 @@ int maxpool2_bwd_impl(const T* in, int in_cs, int cp, const float* in_scale, con
                       int gout_cs, T* gin, int gin_cs, int accumulate, int N, int D, int H, int W, void* stream) {
     CTU_REQUIRE(in && gout && gin, "maxpool2_bwd: null pointer");
     CTU_REQUIRE(cp % 8 == 0 && cp > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool2_bwd: D,H,W must be even");
-    const int64_t total = (int64_t)N * (D / 2) * (H / 2) * (W / 2) * (cp >> 2);
-    maxpool2_bwd_kernel<false, T><<<(unsigned)ceil_div64(total, EW_BLOCK), EW_BLOCK, 0, (hipStream_t)stream>>>(
-        in, in_cs, cp, in_scale, in_shift, in_relu, gout, gout_cs, gin, gin_cs, accumulate, N, D, H, W, nullptr, nullptr, nullptr,
-        bwd_tail_or_off(nullptr));
+    const PoolPlan pl = pool_plan(N, D, H, W, cp);
+    if (pl.rows.total) {
+        maxpool2_bwd_row_kernel<false, T><<<pl.nb, EW_BLOCK, 0, (hipStream_t)stream>>>(
+            in, in_cs, cp, in_scale, in_shift, in_relu, gout, gout_cs, gin, gin_cs, accumulate, D, H, W, pl.rows, nullptr, nullptr,
+            nullptr, bwd_tail_or_off(nullptr));
+    } else {
+        const int64_t total = (int64_t)N * (D / 2) * (H / 2) * (W / 2) * (cp >> 2);
+        maxpool2_bwd_kernel<false, T><<<(unsigned)ceil_div64(total, EW_BLOCK), EW_BLOCK, 0, (hipStream_t)stream>>>(
+            in, in_cs, cp, in_scale, in_shift, in_relu, gout, gout_cs, gin, gin_cs, accumulate, N, D, H, W, nullptr, nullptr, nullptr,
+            bwd_tail_or_off(nullptr));
+    }
     CTU_CHECK_LAUNCH("maxpool2_bwd");
     return CTU_OK;
 }
@@ -644,9 +860,15 @@ int maxpool2_bwd_bn_impl(const T* in, int in_cs, int cp, const float* in_scale, 
     CTU_REQUIRE(cp % 8 == 0 && cp > 0 && cp <= EW_BLOCK && EW_BLOCK % (cp >> 2) == 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0,
                 "maxpool2_bwd_bn: cp=%d must be a multiple of 8 whose quads divide the block; D,H,W even", cp);
     const int nb = ctu_maxpool2_bwd_bn_num_blocks(N, D, H, W, cp);
-    maxpool2_bwd_kernel<true, T><<<nb, EW_BLOCK, 0, (hipStream_t)stream>>>(
-        in, in_cs, cp, in_scale, in_shift, 1, gout, gout_cs, gin, gin_cs, accumulate, N, D, H, W, mean, invstd, partials,
-        bwd_tail_or_off(tail));
+    const PoolPlan pl = pool_plan(N, D, H, W, cp);
+    if (pl.rows.total)
+        maxpool2_bwd_row_kernel<true, T><<<nb, EW_BLOCK, 0, (hipStream_t)stream>>>(
+            in, in_cs, cp, in_scale, in_shift, 1, gout, gout_cs, gin, gin_cs, accumulate, D, H, W, pl.rows, mean, invstd, partials,
+            bwd_tail_or_off(tail));
+    else
+        maxpool2_bwd_kernel<true, T><<<nb, EW_BLOCK, 0, (hipStream_t)stream>>>(
+            in, in_cs, cp, in_scale, in_shift, 1, gout, gout_cs, gin, gin_cs, accumulate, N, D, H, W, mean, invstd, partials,
+            bwd_tail_or_off(tail));
     CTU_CHECK_LAUNCH("maxpool2_bwd_bn");
     return CTU_OK;
 }
