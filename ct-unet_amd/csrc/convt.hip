@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void convt2_kernel(CtP p, int tps) {
     const int64_t vme = v0 + wave * 16 + m;           // this lane's voxel (column of the MFMA tile)
     const size_t fme = vme < p.nvox ? fine_base(vme, p.D, p.H, p.W) : 0;
     // MODE 1 staging: this thread's gather items (voxel of item k = (tid + 256 k) / nq) and their fine-grid bases
-    constexpr int GMAX = 8;                           // 64 * nq / 256 <= 8 for rin_p <= 128
+    constexpr int GMAX = 8;                           // 64 * nq / 256 <= 8 for rin_p <= 128 (ct_channels_ok refuses more)
     size_t gbase[GMAX];
     if (MODE == 1) {
 #pragma unroll
@@ -356,30 +356,75 @@ __global__ __launch_bounds__(1024) void convt2_wgrad_reduce_kernel(const float* 
     if (part == 0 && okb) dbias[co] = red_total(red, e);
 }
 
-inline int ct_wgrad_gx(int ntiles, int pairs) {
-    int gx = 512 / pairs;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
-    return gx;
+// ------------------------------------------------------------------ launch plans (host only)
+// The plan of a forward / data-gradient launch: ctu_convt2_plan and launch_convt read this one function.
+// The kernel stages GMAX = 8 float4 items per thread, which covers 64 voxels x rin_p channels only up to rin_p = 128.
+inline bool ct_channels_ok(int rin_p, int nout_p) {
+    return rin_p > 0 && rin_p % 8 == 0 && rin_p <= 128 && nout_p > 0 && nout_p % 8 == 0 && nout_p <= 128;
+}
+
+struct CtPlan {
+    int ntt_total, ntt;      // 16-wide output tiles in the packed weights / per block
+    int gx, gy;              // blocks of 64 coarse voxels x groups of ntt tiles
+    int tps;                 // taps staged per barrier pair
+    size_t lds;              // dynamic LDS bytes
+    const char* name;
+};
+
+inline CtPlan ct_plan(int mode, int rin_p, int nout_p, int64_t nvox) {
+    static const char* const names[2][4] = {
+        {"convt2_kernel<1, 0>", "convt2_kernel<2, 0>", "convt2_kernel<4, 0>", "convt2_kernel<8, 0>"},
+        {"convt2_kernel<1, 1>", "convt2_kernel<2, 1>", "convt2_kernel<4, 1>", "convt2_kernel<8, 1>"}};
+    CtPlan r;
+    r.ntt_total = pick_ntt(nout_p);
+    r.gx = (int)ceil_div64(nvox, 64);
+    r.ntt = r.ntt_total;                                   // tiles per block: split across blockIdx.y until the grid fills the chip
+    while (r.ntt > 1 && (long)r.gx * (r.ntt_total / r.ntt) < 256) r.ntt >>= 1;
+    r.gy = r.ntt_total / r.ntt;
+    const size_t a_b = (size_t)64 * (rin_p + 4) * sizeof(float);
+    const size_t w_b = (size_t)(rin_p / 8) * r.ntt * 128 * sizeof(float);      // one tap's share of the packed weights
+    r.tps = 8;
+    while (r.tps > 1 && a_b + r.tps * w_b > 72 * 1024) r.tps >>= 1;
+    r.lds = a_b + r.tps * w_b;
+    r.name = names[mode ? 1 : 0][r.ntt == 1 ? 0 : (r.ntt == 2 ? 1 : (r.ntt == 4 ? 2 : 3))];
+    return r;
+}
+
+// The plan of a weight-gradient launch: ctu_convt2_wgrad_ws_floats, ctu_convt2_wgrad_plan and ctu_convt2_wgrad read it.
+struct CtWgPlan {
+    int mi, nj;              // 16-channel tiles per block (input side, output side)
+    int n_ci_t, n_co_t;      // channel groups: grid.y = n_ci_t * n_co_t
+    int ntiles, gx;          // 64-voxel tiles; a block walks tiles blockIdx.x, blockIdx.x + gx, ...
+    const char* name;
+};
+
+inline CtWgPlan ct_wgrad_plan(int64_t nvox, int cin_p, int cout_p) {
+    static const char* const names[2][2] = {{"convt2_wgrad_kernel<1, 1>", "convt2_wgrad_kernel<1, 2>"},
+                                            {"convt2_wgrad_kernel<2, 1>", "convt2_wgrad_kernel<2, 2>"}};
+    CtWgPlan r;
+    r.mi = cin_p > 16 ? 2 : 1;
+    r.nj = cout_p > 16 ? 2 : 1;
+    r.n_ci_t = ceil_div(cin_p, 16 * r.mi);
+    r.n_co_t = ceil_div(cout_p, 16 * r.nj);
+    r.ntiles = (int)ceil_div64(nvox, 64);
+    r.gx = 512 / (r.n_ci_t * r.n_co_t);
+    if (r.gx < 1) r.gx = 1;
+    if (r.gx > r.ntiles) r.gx = r.ntiles;
+    r.name = names[r.mi - 1][r.nj - 1];
+    return r;
 }
 
 template <int MODE>
 int launch_convt(const CtP& p, hipStream_t st, const char* name) {
-    const int ntt_total = pick_ntt(p.nout_p);
-    const unsigned grid = (unsigned)ceil_div64(p.nvox, 64);
-    int ntt = ntt_total;                                   // tiles per block: split across blockIdx.y until the grid fills the chip
-    while (ntt > 1 && (long)grid * (ntt_total / ntt) < 256) ntt >>= 1;
-    const size_t a_b = (size_t)64 * (p.rin_p + 4) * sizeof(float);
-    const size_t w_b = (size_t)(p.rin_p / 8) * ntt * 128 * sizeof(float);      // one tap's share of the packed weights
-    int tps = 8;                                                                // taps staged per barrier pair
-    while (tps > 1 && a_b + tps * w_b > 72 * 1024) tps >>= 1;
-    const size_t lds = a_b + tps * w_b;
+    CTU_REQUIRE(p.nvox < (1LL << 31), "%s: more than 2^31 coarse voxels", name);
+    const CtPlan r = ct_plan(MODE, p.rin_p, p.nout_p, p.nvox);
+    const size_t lds = r.lds;
+    const int tps = r.tps;
     CTU_REQUIRE(lds <= 160 * 1024, "%s: rin_p=%d nout_p=%d needs %zu B of LDS", name, p.rin_p, p.nout_p, lds);
     CTU_REQUIRE(p.out_cs % 4 == 0 && ((uintptr_t)p.out & 15) == 0, "%s: output must be 16-byte aligned", name);
-    CTU_REQUIRE(p.nvox < (1LL << 31), "%s: more than 2^31 coarse voxels", name);
     CtP q = p;
-    q.ntt_total = ntt_total;
-    const dim3 grid2(grid, ntt_total / ntt);
+    q.ntt_total = r.ntt_total;
+    const dim3 grid2(r.gx, r.gy);
 #define CT_LAUNCH(N_)                                                                                             \
     do {                                                                                                          \
         if (lds > 64 * 1024)                                                                                      \
@@ -387,7 +432,7 @@ int launch_convt(const CtP& p, hipStream_t st, const char* name) {
                                       (int)lds);                                                                  \
         convt2_kernel<N_, MODE><<<grid2, 256, lds, st>>>(q, tps);                                                 \
     } while (0)
-    switch (ntt) {
+    switch (r.ntt) {
         case 1: CT_LAUNCH(1); break;
         case 2: CT_LAUNCH(2); break;
         case 4: CT_LAUNCH(4); break;
@@ -422,8 +467,7 @@ extern "C" int ctu_convt2_fwd(const float* in, int in_cs, int rin_p, const float
                               int in_relu, const float* wp, const float* bias, int nbias, float* out, int out_cs,
                               int nout_p, int N, int D, int H, int W, void* stream) {
     CTU_REQUIRE(in && wp && out, "convt2_fwd: null pointer");
-    CTU_REQUIRE(rin_p > 0 && rin_p % 8 == 0 && nout_p > 0 && nout_p % 8 == 0 && nout_p <= 128,
-                "convt2_fwd: rin_p=%d nout_p=%d", rin_p, nout_p);
+    CTU_REQUIRE(ct_channels_ok(rin_p, nout_p), "convt2_fwd: rin_p=%d nout_p=%d (multiples of 8, at most 128)", rin_p, nout_p);
     CTU_REQUIRE(in_cs >= rin_p && in_cs % 4 == 0 && out_cs >= nout_p, "convt2_fwd: bad stride");
     CTU_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "convt2_fwd: scale/shift must come together");
     CtP p;
@@ -437,8 +481,7 @@ extern "C" int ctu_convt2_fwd(const float* in, int in_cs, int rin_p, const float
 extern "C" int ctu_convt2_bwd_data(const float* gout, int g_cs, int rout_p, const float* wp, float* gin, int gin_cs,
                                    int nin_p, int N, int D, int H, int W, void* stream) {
     CTU_REQUIRE(gout && wp && gin, "convt2_bwd_data: null pointer");
-    CTU_REQUIRE(rout_p > 0 && rout_p % 8 == 0 && nin_p > 0 && nin_p % 8 == 0 && nin_p <= 128,
-                "convt2_bwd_data: rout_p=%d nin_p=%d", rout_p, nin_p);
+    CTU_REQUIRE(ct_channels_ok(rout_p, nin_p), "convt2_bwd_data: rout_p=%d nin_p=%d (multiples of 8, at most 128)", rout_p, nin_p);
     CTU_REQUIRE(g_cs >= rout_p && g_cs % 4 == 0 && gin_cs >= nin_p, "convt2_bwd_data: bad stride");
     CtP p;
     p.in = gout; p.in_scale = nullptr; p.in_shift = nullptr; p.wp = wp; p.bias = nullptr; p.out = gin;
@@ -447,18 +490,9 @@ extern "C" int ctu_convt2_bwd_data(const float* gout, int g_cs, int rout_p, cons
     return launch_convt<1>(p, (hipStream_t)stream, "convt2_bwd_data");
 }
 
-static void ct_wgrad_geom(int64_t nvox, int cin_p, int cout_p, int* mi, int* nj, int* n_ci_t, int* n_co_t, int* gx) {
-    *mi = cin_p > 16 ? 2 : 1;
-    *nj = cout_p > 16 ? 2 : 1;
-    *n_ci_t = ceil_div(cin_p, 16 * *mi);
-    *n_co_t = ceil_div(cout_p, 16 * *nj);
-    *gx = ct_wgrad_gx((int)ceil_div64(nvox, 64), *n_ci_t * *n_co_t);
-}
-
 extern "C" size_t ctu_convt2_wgrad_ws_floats(int N, int D, int H, int W, int cin_p, int cout_p) {
-    int mi, nj, nci, nco, gx;
-    ct_wgrad_geom((int64_t)N * D * H * W, cin_p, cout_p, &mi, &nj, &nci, &nco, &gx);
-    return (size_t)nci * nco * gx * 8 * mi * nj * 256 + (size_t)nco * gx * 16 * nj;
+    const CtWgPlan r = ct_wgrad_plan((int64_t)N * D * H * W, cin_p, cout_p);
+    return (size_t)r.n_ci_t * r.n_co_t * r.gx * 8 * r.mi * r.nj * 256 + (size_t)r.n_co_t * r.gx * 16 * r.nj;
 }
 
 template <int MI, int NJ>
@@ -484,12 +518,35 @@ extern "C" int ctu_convt2_wgrad(const float* in, int in_cs, int cin_p, const flo
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.g = gout; p.ws = ws;
     p.in_cs = in_cs; p.cin_p = cin_p; p.in_relu = in_relu; p.g_cs = g_cs; p.cout_p = cout_p;
     p.N = N; p.D = D; p.H = H; p.W = W; p.nvox = (int64_t)N * D * H * W;
-    p.ntiles = (int)ceil_div64(p.nvox, 64);
     CTU_REQUIRE(p.nvox < (1LL << 31), "convt2_wgrad: more than 2^31 coarse voxels");
-    int mi, nj, n_co_t, gx;
-    ct_wgrad_geom(p.nvox, cin_p, cout_p, &mi, &nj, &p.n_ci_t, &n_co_t, &gx);
+    const CtWgPlan r = ct_wgrad_plan(p.nvox, cin_p, cout_p);
+    p.ntiles = r.ntiles; p.n_ci_t = r.n_ci_t;
+    const int mi = r.mi, nj = r.nj, n_co_t = r.n_co_t, gx = r.gx;
     if (mi == 1 && nj == 1) return launch_ct_wgrad<1, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
     if (mi == 1) return launch_ct_wgrad<1, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
     if (nj == 1) return launch_ct_wgrad<2, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
     return launch_ct_wgrad<2, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
+}
+
+// Host-only plan queries (no GPU): the instantiation a call of this geometry launches, or NULL where the call is refused.
+// plan[4] = grid.x, grid.y, taps staged per barrier pair, dynamic LDS bytes.  mode 0 forward, 1 data gradient
+// (rin_p = the reduction side: padded input channels resp. padded channels of the gradient).
+extern "C" const char* ctu_convt2_plan(int mode, int rin_p, int nout_p, int N, int D, int H, int W, int* plan) {
+    const int64_t nvox = (int64_t)N * D * H * W;
+    if ((mode != 0 && mode != 1) || !ct_channels_ok(rin_p, nout_p) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || nvox >= (1LL << 31))
+        return nullptr;
+    const CtPlan r = ct_plan(mode, rin_p, nout_p, nvox);
+    if (r.lds > 160 * 1024) return nullptr;
+    if (plan) { plan[0] = r.gx; plan[1] = r.gy; plan[2] = r.tps; plan[3] = (int)r.lds; }
+    return r.name;
+}
+
+// plan[3] = grid.x (slabs per channel group), grid.y (channel groups), 64-voxel tiles the grid.x blocks share
+extern "C" const char* ctu_convt2_wgrad_plan(int cin_p, int cout_p, int N, int D, int H, int W, int* plan) {
+    const int64_t nvox = (int64_t)N * D * H * W;
+    if (cin_p <= 0 || cin_p % 8 || cout_p <= 0 || cout_p % 8 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || nvox >= (1LL << 31))
+        return nullptr;
+    const CtWgPlan r = ct_wgrad_plan(nvox, cin_p, cout_p);
+    if (plan) { plan[0] = r.gx; plan[1] = r.n_ci_t * r.n_co_t; plan[2] = r.ntiles; }
+    return r.name;
 }

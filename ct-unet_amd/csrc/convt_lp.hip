@@ -434,13 +434,73 @@ __global__ __launch_bounds__(256) void lp_convt_wgrad_reduce_kernel(const float*
     if (ok && part == 0) dw[idx] = s;
 }
 
-void ctw_grid(int64_t nvox, int pairs, int* gx, int* cpb) {
+// ------------------------------------------------------------------ launch plans (host only)
+// The plan of a forward (mode 0) / data-gradient (mode 1) launch: ctu_lp_convt2_plan and the two launchers read this function.
+struct LpCtPlan {
+    bool wide;               // 64 voxels per wave (CTV = 4) only where that still fills the chip
+    int ksn;                 // forward: K-steps of 32 input channels held in registers
+    int gx, gy;              // blocks of 4 waves x output tiles (forward) / pairs of output tiles (data gradient)
+    const char* name;
+};
+
+inline LpCtPlan lp_ct_plan(int mode, int rin_p, int nout_p, int64_t nvox) {
+    static const char* const fwd_names[8][2] = {
+        {"lp_convt_fwd_kernel<T, 1, 1>", "lp_convt_fwd_kernel<T, 1, 4>"}, {"lp_convt_fwd_kernel<T, 2, 1>", "lp_convt_fwd_kernel<T, 2, 4>"},
+        {"lp_convt_fwd_kernel<T, 3, 1>", "lp_convt_fwd_kernel<T, 3, 4>"}, {"lp_convt_fwd_kernel<T, 4, 1>", "lp_convt_fwd_kernel<T, 4, 4>"},
+        {"lp_convt_fwd_kernel<T, 5, 1>", "lp_convt_fwd_kernel<T, 5, 4>"}, {"lp_convt_fwd_kernel<T, 6, 1>", "lp_convt_fwd_kernel<T, 6, 4>"},
+        {"lp_convt_fwd_kernel<T, 7, 1>", "lp_convt_fwd_kernel<T, 7, 4>"}, {"lp_convt_fwd_kernel<T, 8, 1>", "lp_convt_fwd_kernel<T, 8, 4>"}};
+    LpCtPlan r;
+    r.wide = nvox > 65536;
+    r.gx = (int)ceil_div64(nvox, r.wide ? 256 : 64);
+    const int n16 = (nout_p + 15) >> 4;
+    if (mode == 0) {
+        r.ksn = (rin_p + 31) >> 5;
+        if (r.ksn > 8) r.ksn = 8;
+        // deep levels: 64 blocks x 8 output tiles x 8 taps was one serial chain per wave -- one output tile per blockIdx.y there
+        r.gy = r.gx < 256 ? n16 : 1;
+        r.name = fwd_names[r.ksn - 1][r.wide ? 1 : 0];
+    } else {
+        r.ksn = 0;
+        const int passes = (n16 + 1) >> 1;                 // pairs of 16-wide output tiles
+        r.gy = (r.gx < 256 && passes > 1) ? passes : 1;
+        r.name = r.wide ? "lp_convt_bwd_data_kernel<T, 4>" : "lp_convt_bwd_data_kernel<T, 1>";
+    }
+    return r;
+}
+
+// The plan of a weight-gradient launch: ctu_lp_convt2_wgrad_ws_floats, ctu_lp_convt2_wgrad_plan and ctu_lp_convt2_wgrad read it.
+#ifndef LP_CTW_MT4
+#define LP_CTW_MT4 1
+#endif
+struct LpCtWgPlan {
+    int nci, nco, pairs;     // 16-channel tiles of the two sides
+    int mt, ntl;             // tiles per block (input side, output side)
+    int gx, gy, cpb;         // blocks along the 128-voxel chunks, tile groups, chunks per block
+    size_t lds;
+    const char* name;
+};
+
+inline LpCtWgPlan lp_ctw_plan(int64_t nvox, int cin_p, int cout_p) {
+    LpCtWgPlan r;
+    r.nci = (cin_p + 15) >> 4; r.nco = (cout_p + 15) >> 4; r.pairs = r.nci * r.nco;
     const int64_t nchunks = (nvox + 127) / 128;
-    int64_t g = 1024 / pairs;
+    int64_t g = 1024 / r.pairs;
     if (g < 16) g = 16;
     if (g > nchunks) g = nchunks;
-    *cpb = (int)((nchunks + g - 1) / g);
-    *gx = (int)((nchunks + *cpb - 1) / *cpb);
+    r.cpb = (int)((nchunks + g - 1) / g);
+    r.gx = (int)((nchunks + r.cpb - 1) / r.cpb);
+    // tile groups per block: 2 x 2 while the accumulators (8 taps x MT x NTL) and the gradient image fit;
+    // 4 x 1 groups where there are at least four input-channel tiles: the gradient (8x the input's bytes) is then read ONCE per
+    // output-channel tile instead of once per pair of input-channel tiles, and a block's LDS image is 48 KB instead of 74
+    const bool mt4 = LP_CTW_MT4 && r.nci >= 4;
+    r.mt = mt4 ? 4 : (r.nci >= 2 ? 2 : 1);
+    r.ntl = mt4 ? 1 : (r.nco >= 2 ? 2 : 1);
+    r.gy = ceil_div(r.nci, r.mt) * ceil_div(r.nco, r.ntl);
+    r.lds = 512 + 128 * (size_t)r.mt * 32 + 8 * 128 * (size_t)r.ntl * 32;
+    r.name = r.mt == 4 ? "lp_convt_wgrad_kernel<T, 4, 1>"
+           : r.mt == 2 ? (r.ntl == 2 ? "lp_convt_wgrad_kernel<T, 2, 2>" : "lp_convt_wgrad_kernel<T, 2, 1>")
+                       : (r.ntl == 2 ? "lp_convt_wgrad_kernel<T, 1, 2>" : "lp_convt_wgrad_kernel<T, 1, 1>");
+    return r;
 }
 
 }  // namespace
@@ -476,19 +536,17 @@ extern "C" int ctu_lp_convt2_fwd(int dtype, const void* in, int in_cs, int rin_p
     p.in = in; p.wp = wp; p.out = out; p.scale = in_scale; p.shift = in_shift; p.bias = bias;
     p.in_cs = in_cs; p.rin_p = rin_p; p.relu = in_relu; p.out_cs = out_cs; p.nout_p = nout_p; p.nbias = bias ? nbias : 0;
     p.N = N; p.D = D; p.H = H; p.W = W; p.nvox = (int64_t)N * D * H * W;
-    const int ksn = (rin_p + 31) >> 5;
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = p.nvox > 65536;                  // 64 voxels per wave only where that still fills the chip
-    const unsigned gx = (unsigned)ceil_div64(p.nvox, wide ? 256 : 64);
-    // deep levels: 64 blocks x 8 output tiles x 8 taps was one serial chain per wave -- one output tile per blockIdx.y there
-    const dim3 grid(gx, gx < 256 ? (unsigned)((nout_p + 15) >> 4) : 1u);
+    const LpCtPlan r = lp_ct_plan(0, rin_p, nout_p, p.nvox);
+    const bool wide = r.wide;
+    const dim3 grid(r.gx, r.gy);
 #define CTU_CT_FWD(K)                                                                   \
     case K:                                                                             \
         if (wide) lp_convt_fwd_kernel<T, K, 4><<<grid, 256, 0, st>>>(p);                \
         else lp_convt_fwd_kernel<T, K, 1><<<grid, 256, 0, st>>>(p);                     \
         break;
     CTU_DISPATCH_LP(dtype, {
-        switch (ksn) {
+        switch (r.ksn) {
             CTU_CT_FWD(1) CTU_CT_FWD(2) CTU_CT_FWD(3) CTU_CT_FWD(4) CTU_CT_FWD(5) CTU_CT_FWD(6) CTU_CT_FWD(7)
             default:
                 if (wide) lp_convt_fwd_kernel<T, 8, 4><<<grid, 256, 0, st>>>(p);
@@ -509,10 +567,9 @@ extern "C" int ctu_lp_convt2_bwd_data(int dtype, const void* gout, int g_cs, int
     LpCtP p{};
     p.in = gout; p.wp = wp; p.out = gin; p.in_cs = g_cs; p.rin_p = rout_p; p.out_cs = gin_cs; p.nout_p = nin_p;
     p.N = N; p.D = D; p.H = H; p.W = W; p.nvox = (int64_t)N * D * H * W;
-    const bool wide = p.nvox > 65536;
-    const unsigned gx = (unsigned)ceil_div64(p.nvox, wide ? 256 : 64);
-    const int passes = (((nin_p + 15) >> 4) + 1) >> 1;              // pairs of 16-wide output tiles
-    const dim3 grid(gx, (gx < 256 && passes > 1) ? passes : 1);
+    const LpCtPlan r = lp_ct_plan(1, rout_p, nin_p, p.nvox);
+    const bool wide = r.wide;
+    const dim3 grid(r.gx, r.gy);
     CTU_DISPATCH_LP(dtype, {
         if (wide) lp_convt_bwd_data_kernel<T, 4><<<grid, 256, 0, (hipStream_t)stream>>>(p);
         else lp_convt_bwd_data_kernel<T, 1><<<grid, 256, 0, (hipStream_t)stream>>>(p);
@@ -522,10 +579,8 @@ extern "C" int ctu_lp_convt2_bwd_data(int dtype, const void* gout, int g_cs, int
 }
 
 extern "C" size_t ctu_lp_convt2_wgrad_ws_floats(int N, int D, int H, int W, int cin_p, int cout_p) {
-    const int pairs = ((cin_p + 15) >> 4) * ((cout_p + 15) >> 4);
-    int gx, cpb;
-    ctw_grid((int64_t)N * D * H * W, pairs, &gx, &cpb);
-    return (size_t)gx * pairs * 2048;
+    const LpCtWgPlan r = lp_ctw_plan((int64_t)N * D * H * W, cin_p, cout_p);
+    return (size_t)r.gx * r.pairs * 2048;
 }
 
 extern "C" int ctu_lp_convt2_wgrad(int dtype, const void* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
@@ -541,20 +596,11 @@ extern "C" int ctu_lp_convt2_wgrad(int dtype, const void* in, int in_cs, int cin
     p.x = in; p.g = gout; p.scale = in_scale; p.shift = in_shift; p.ws = ws;
     p.x_cs = in_cs; p.cin_p = cin_p; p.relu = in_relu; p.g_cs = g_cs; p.cout_p = cout_p;
     p.N = N; p.D = D; p.H = H; p.W = W; p.nvox = (int64_t)N * D * H * W;
-    const int nci = (cin_p + 15) >> 4, nco = (cout_p + 15) >> 4, pairs = nci * nco;
-    int gx, cpb;
-    ctw_grid(p.nvox, pairs, &gx, &cpb);
+    const LpCtWgPlan r = lp_ctw_plan(p.nvox, cin_p, cout_p);
+    const int mt = r.mt, ntl = r.ntl, gx = r.gx, cpb = r.cpb;
     hipStream_t st = (hipStream_t)stream;
-    // tile groups per block: 2 x 2 while the accumulators (8 taps x MT x NTL) and the gradient image fit
-#ifndef LP_CTW_MT4
-#define LP_CTW_MT4 1
-#endif
-    // 4 x 1 groups where there are at least four input-channel tiles: the gradient (8x the input's bytes) is then read ONCE per
-    // output-channel tile instead of once per pair of input-channel tiles, and a block's LDS image is 48 KB instead of 74
-    const bool mt4 = LP_CTW_MT4 && nci >= 4;
-    const int mt = mt4 ? 4 : (nci >= 2 ? 2 : 1), ntl = mt4 ? 1 : (nco >= 2 ? 2 : 1);
-    const dim3 grid(gx, ceil_div(nci, mt) * ceil_div(nco, ntl));
-    const size_t lds = 512 + 128 * (size_t)mt * 32 + 8 * 128 * (size_t)ntl * 32;
+    const dim3 grid(r.gx, r.gy);
+    const size_t lds = r.lds;
     CTU_DISPATCH_LP(dtype, {
         if (mt == 2 && ntl == 2) {
             // the dynamic-LDS limit is raised only for launches that need more than the default 64 KB, and only to what they need
@@ -574,4 +620,26 @@ extern "C" int ctu_lp_convt2_wgrad(int dtype, const void* in, int in_cs, int cin
     lp_convt_wgrad_reduce_kernel<<<ceil_div(Ci * Co * 8, 16), 256, 0, st>>>(ws, dw, Ci, Co, imap, cout_p, gx);
     CTU_CHECK_LAUNCH("lp_convt2_wgrad reduce");
     return CTU_OK;
+}
+
+// Host-only plan queries (no GPU): the instantiation a call of this geometry launches (T = the 16-bit type), or NULL where
+// the call is refused.  mode 0 forward, 1 data gradient (rin_p = the reduction side).  plan[2] = grid.x, grid.y.
+extern "C" const char* ctu_lp_convt2_plan(int mode, int rin_p, int nout_p, int N, int D, int H, int W, int* plan) {
+    const int64_t nvox = (int64_t)N * D * H * W;
+    if ((mode != 0 && mode != 1) || rin_p <= 0 || rin_p % 8 || nout_p <= 0 || nout_p % 8 || (mode == 0 && rin_p > 256) ||
+        N <= 0 || D <= 0 || H <= 0 || W <= 0 || nvox >= (1LL << 31))
+        return nullptr;
+    const LpCtPlan r = lp_ct_plan(mode, rin_p, nout_p, nvox);
+    if (plan) { plan[0] = r.gx; plan[1] = r.gy; }
+    return r.name;
+}
+
+// plan[4] = grid.x (slabs per tile pair), grid.y (tile groups), 128-voxel chunks per block, dynamic LDS bytes
+extern "C" const char* ctu_lp_convt2_wgrad_plan(int cin_p, int cout_p, int N, int D, int H, int W, int* plan) {
+    const int64_t nvox = (int64_t)N * D * H * W;
+    if (cin_p <= 0 || cin_p % 8 || cout_p <= 0 || cout_p % 8 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || nvox >= (1LL << 31))
+        return nullptr;
+    const LpCtWgPlan r = lp_ctw_plan(nvox, cin_p, cout_p);
+    if (plan) { plan[0] = r.gx; plan[1] = r.gy; plan[2] = r.cpb; plan[3] = (int)r.lds; }
+    return r.name;
 }

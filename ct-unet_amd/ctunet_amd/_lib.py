@@ -86,6 +86,8 @@ SIGNATURES = {
     "ctu_convt2_bwd_data": (I, [P, I, I, P, P, I, I, I, I, I, I, P]),
     "ctu_convt2_wgrad_ws_floats": (Z, [I, I, I, I, I, I]),
     "ctu_convt2_wgrad": (I, [P, I, I, P, P, I, P, I, I, P, P, I, I, P, P, I, I, I, I, P]),
+    "ctu_convt2_plan": (C.c_char_p, [I, I, I, I, I, I, I, P]),
+    "ctu_convt2_wgrad_plan": (C.c_char_p, [I, I, I, I, I, I, P]),
     "ctu_head_fwd": (I, [P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, I, L, P]),
     "ctu_head_bwd_ws_floats": (Z, [I, L, I, I]),
     "ctu_head_bwd": (I, [P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P]),
@@ -167,6 +169,8 @@ SIGNATURES = {
     "ctu_lp_convt2_bwd_data": (I, [I, P, I, I, P, P, I, I, I, I, I, I, P]),
     "ctu_lp_convt2_wgrad_ws_floats": (Z, [I, I, I, I, I, I]),
     "ctu_lp_convt2_wgrad": (I, [I, P, I, I, P, P, I, P, I, I, P, I, I, P, P, I, I, I, I, P]),
+    "ctu_lp_convt2_plan": (C.c_char_p, [I, I, I, I, I, I, I, P]),
+    "ctu_lp_convt2_wgrad_plan": (C.c_char_p, [I, I, I, I, I, I, P]),
     "ctu_lp_ncdhw_to_ndhwc": (I, [I, P, P, I, I, I, I, I, I, I, P]),
     "ctu_lp_ndhwc_to_ncdhw": (I, [I, P, P, I, I, I, I, I, I, P]),
     "ctu_lp_bn_relu_bwd_reduce": (I, [I, P, I, P, I, I, P, P, P, P, L, P, P, P]),

@@ -287,6 +287,13 @@ int ctu_convt2_wgrad(const float* in, int in_cs, int cin_p, const float* in_scal
                      const float* in_shift, int in_relu, const float* gout, int g_cs,
                      int cout_p, float* dw, float* dbias, int Ci, int Co,
                      const int32_t* imap, float* ws, int N, int D, int H, int W, void* stream);
+/* Launch plans (host only, no GPU needed; the launchers read the same plan functions).  Each returns the kernel
+ * instantiation a call of this geometry launches, e.g. "convt2_kernel<4, 0>", or NULL for a geometry the call refuses,
+ * and fills plan[] when it is not NULL.  mode 0 forward, 1 data gradient (rin_p = the reduction side).
+ *  ctu_convt2_plan ......... plan[4] = grid.x, grid.y, taps staged per barrier pair, dynamic LDS bytes
+ *  ctu_convt2_wgrad_plan ... plan[3] = grid.x (slabs per channel group), grid.y, 64-voxel tiles the grid.x blocks share */
+const char* ctu_convt2_plan(int mode, int rin_p, int nout_p, int N, int D, int H, int W, int* plan);
+const char* ctu_convt2_wgrad_plan(int cin_p, int cout_p, int N, int D, int H, int W, int* plan);
 
 /* ------------------------------------------------------------------- head ---- */
 /* last_conv 1x1x1 + bias, optional softmax(dim=1), optional sigmoid, optional SP
@@ -646,6 +653,11 @@ size_t ctu_lp_convt2_wgrad_ws_floats(int N, int D, int H, int W, int cin_p, int 
 int ctu_lp_convt2_wgrad(int dtype, const void* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                         int in_relu, const void* gout, int g_cs, int cout_p, float* dw, int Ci, int Co,
                         const int32_t* imap, float* ws, int N, int D, int H, int W, void* stream);
+/* Launch plans of the three (host only, as ctu_convt2_plan; T in the name stands for the 16-bit type).
+ *  ctu_lp_convt2_plan ......... plan[2] = grid.x, grid.y
+ *  ctu_lp_convt2_wgrad_plan ... plan[4] = grid.x (slabs per tile pair), grid.y, 128-voxel chunks per block, dynamic LDS bytes */
+const char* ctu_lp_convt2_plan(int mode, int rin_p, int nout_p, int N, int D, int H, int W, int* plan);
+const char* ctu_lp_convt2_wgrad_plan(int cin_p, int cout_p, int N, int D, int H, int W, int* plan);
 /* HBM-bound glue: same kernels as the fp32 entry points, instantiated for 16-bit storage */
 /* 16-bit fused decoder up-convolution (upconv_lp.hip; ConvTranspose3d(C,C,2,2) -> Conv3d(C,Co<=8,3,p=1), models.py:37-38) on
  * v_mfma_f32_16x16x32_{bf16,f16}: the twins of ctu_upconv_fused_fwd / _wgrad / _project / _bwd_data for 16-bit tensors.
