@@ -657,9 +657,22 @@ __global__ void adam_step_inc_kernel(float* step, const float* __restrict__ skip
     step[0] += 1.f;
 }
 
-__global__ void adam_amsgrad_kernel(AdamTable tb, const float* __restrict__ step, float lr, float beta1, float beta2,
-                                    float omb1, float omb2, float eps, float wd, int decoupled, const float* __restrict__ skip) {
+// One body of arithmetic for both entry points.  DEV: the learning rate is a double in device memory, rounded to float
+// here exactly where the host call rounds its argument, and the gradient is multiplied by an optional device coefficient
+// (gradient clipping) before weight decay, as clip_grad_norm_ scales p.grad before the optimizer reads it.
+template <bool DEV>
+__device__ __forceinline__ void adam_amsgrad_body(const AdamTable& tb, const float* __restrict__ step, float lr, float beta1,
+                                                  float beta2, float omb1, float omb2, float eps, float wd, int decoupled,
+                                                  const float* __restrict__ skip, const double* __restrict__ dlr,
+                                                  const float* __restrict__ gcoef) {
     if (skip && skip[0] != 0.f) return;
+    float coef = 1.f;
+    bool clip = false;
+    if (DEV) {
+        lr = (float)dlr[0];
+        clip = gcoef != nullptr;
+        if (clip) coef = gcoef[0];
+    }
     const int t = blockIdx.y;
     const int64_t n = tb.n[t];
     float* __restrict__ p = tb.p[t];
@@ -674,6 +687,10 @@ __global__ void adam_amsgrad_kernel(AdamTable tb, const float* __restrict__ step
     const float step_size = lr / bc1;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float gr = g[i];
+        if (DEV && clip) {
+            gr *= coef;
+            asm volatile("" : "+v"(gr));            // the product is rounded on its own: never contracted into the FMAs below
+        }
         float pv = p[i];
         if (wd != 0.f) {
             if (decoupled) pv *= 1.f - lr * wd;     // AdamW
@@ -687,6 +704,107 @@ __global__ void adam_amsgrad_kernel(AdamTable tb, const float* __restrict__ step
         const float denom = sqrtf(vmx) / bc2_sqrt + eps;
         p[i] = pv - step_size * (mi / denom);
     }
+}
+
+__global__ void adam_amsgrad_kernel(AdamTable tb, const float* __restrict__ step, float lr, float beta1, float beta2,
+                                    float omb1, float omb2, float eps, float wd, int decoupled, const float* __restrict__ skip) {
+    adam_amsgrad_body<false>(tb, step, lr, beta1, beta2, omb1, omb2, eps, wd, decoupled, skip, nullptr, nullptr);
+}
+
+__global__ void adam_amsgrad_dev_kernel(AdamTable tb, const float* __restrict__ step, const double* __restrict__ dlr,
+                                        float beta1, float beta2, float omb1, float omb2, float eps, float wd, int decoupled,
+                                        const float* __restrict__ skip, const float* __restrict__ gcoef) {
+    adam_amsgrad_body<true>(tb, step, 0.f, beta1, beta2, omb1, omb2, eps, wd, decoupled, skip, dlr, gcoef);
+}
+
+// ------------------------------------------------------------------ global gradient norm and clip coefficient
+// torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite=False) over a pointer table, in two launches and in a
+// fixed order: per-thread double sums of g*g, a fixed-order tree per block, one float partial per block (stage one);
+// one block sums the partials in double and writes the norm and the coefficient (stage two).
+struct NormTable {
+    const float* g[ADAM_MAXT];
+    int64_t n[ADAM_MAXT];
+};
+constexpr int NORM_MAX_GX = 64;
+static inline int grad_norm_gx(int64_t mx) {
+    int64_t gx = ceil_div64(mx, (int64_t)EW_BLOCK * 16);             // four 16-byte loads per thread and trip
+    return gx > NORM_MAX_GX ? NORM_MAX_GX : (gx < 1 ? 1 : (int)gx);
+}
+
+__device__ __forceinline__ double block_sum_fixed(double s, double* r) {
+    r[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = EW_BLOCK / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
+        __syncthreads();
+    }
+    return r[0];
+}
+
+__global__ void grad_sqsum_kernel(NormTable tb, float* __restrict__ partials) {
+    __shared__ double r[EW_BLOCK];
+    const int t = blockIdx.y;
+    const float* __restrict__ g = tb.g[t];
+    const int64_t n = tb.n[t];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    double s = 0.0;
+    // 16-byte loads when the base allows it (a view at an odd offset of its storage is only 4-byte aligned), scalar tail
+    const int64_t n4 = ((reinterpret_cast<uintptr_t>(g) & 15) == 0) ? (n >> 2) : 0;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    for (int64_t i = tid; i < n4; i += nthr) {
+        const float4 q = g4[i];
+        s += (double)q.x * (double)q.x; s += (double)q.y * (double)q.y;
+        s += (double)q.z * (double)q.z; s += (double)q.w * (double)q.w;
+    }
+    for (int64_t i = (n4 << 2) + tid; i < n; i += nthr) s += (double)g[i] * (double)g[i];
+    const double tot = block_sum_fixed(s, r);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (float)tot;
+}
+
+__global__ void grad_clip_coef_kernel(const float* __restrict__ partials, int nb, float max_norm, float* __restrict__ norm_out,
+                                      float* __restrict__ coef_out) {
+    __shared__ double r[EW_BLOCK];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) s += (double)partials[b];
+    const double tot = block_sum_fixed(s, r);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(tot);
+        const float c = max_norm / (norm + 1e-6f);
+        norm_out[0] = norm;
+        coef_out[0] = c > 1.f ? 1.f : c;            // torch.clamp(max=1): a NaN norm stays a NaN coefficient
+    }
+}
+
+// ------------------------------------------------------------------ ReduceLROnPlateau on the device
+// torch.optim.lr_scheduler.ReduceLROnPlateau.step(float(metric)) for one parameter group on one thread, in double, with
+// torch's own expressions (_is_better, _reduce_lr), so the learning rate follows torch's to the last bit.
+// state[0] = best; counters = {num_bad_epochs, cooldown_counter, last_epoch, number of reductions}.
+__global__ void plateau_update_kernel(const float* __restrict__ metric, double* lr, double* state, int32_t* counters,
+                                      int mode_max, int threshold_rel, double factor, int patience, double threshold,
+                                      int cooldown, double min_lr, double eps) {
+#pragma clang fp contract(off)
+    const double cur = (double)metric[0];
+    const double best = state[0];
+    int bad = counters[0], cool = counters[1];
+    counters[2] += 1;
+    bool better;
+    if (!mode_max && threshold_rel) better = cur < best * (1.0 - threshold);
+    else if (!mode_max) better = cur < best - threshold;
+    else if (threshold_rel) better = cur > best * (threshold + 1.0);
+    else better = cur > best + threshold;              // (a NaN metric compares false: never better)
+    if (better) { state[0] = cur; bad = 0; }
+    else bad += 1;
+    if (cool > 0) { cool -= 1; bad = 0; }               // bad epochs do not count during cooldown
+    if (bad > patience) {
+        const double old_lr = lr[0];
+        const double scaled = old_lr * factor;
+        const double new_lr = scaled > min_lr ? scaled : min_lr;          // Python's max(scaled, min_lr)
+        if (old_lr - new_lr > eps) { lr[0] = new_lr; counters[3] += 1; }
+        cool = cooldown;
+        bad = 0;
+    }
+    counters[0] = bad;
+    counters[1] = cool;
 }
 
 struct ScaleTable {
@@ -1083,6 +1201,88 @@ extern "C" int ctu_adam_amsgrad(void* const* ptrs, const int64_t* sizes, int n, 
                                                               (float)weight_decay, decoupled, skip_flag);
         CTU_CHECK_LAUNCH("adam_amsgrad");
     }
+    return CTU_OK;
+}
+
+extern "C" int ctu_adam_amsgrad_dev(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr, double beta1,
+                                    double beta2, double eps, double weight_decay, int decoupled, const float* grad_coef,
+                                    const float* skip_flag, void* stream) {
+    CTU_REQUIRE(ptrs && sizes && n > 0 && step && lr, "adam_amsgrad_dev: bad argument");
+    for (int t = 0; t < n; ++t) {
+        void* const* q = ptrs + (size_t)t * 5;
+        CTU_REQUIRE(q[0] && q[1] && q[2] && q[3] && q[4] && sizes[t] >= 0, "adam_amsgrad_dev: null tensor pointer at %d", t);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    adam_step_inc_kernel<<<1, 1, 0, st>>>(step, skip_flag);
+    CTU_CHECK_LAUNCH("adam_step_inc");
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
+        const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
+        AdamTable tb;
+        int64_t mx = 1;
+        for (int t = 0; t < nt; ++t) {
+            void* const* q = ptrs + (size_t)(t0 + t) * 5;
+            tb.p[t] = (float*)q[0]; tb.g[t] = (const float*)q[1]; tb.m[t] = (float*)q[2]; tb.v[t] = (float*)q[3];
+            tb.vm[t] = (float*)q[4]; tb.n[t] = sizes[t0 + t];
+            if (tb.n[t] > mx) mx = tb.n[t];
+        }
+        int gx = (int)ceil_div64(mx, EW_BLOCK * 4);
+        if (gx > 128) gx = 128;
+        if (gx < 1) gx = 1;
+        adam_amsgrad_dev_kernel<<<dim3(gx, nt), EW_BLOCK, 0, st>>>(tb, step, lr, (float)beta1, (float)beta2,
+                                                                  (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
+                                                                  (float)weight_decay, decoupled, skip_flag, grad_coef);
+        CTU_CHECK_LAUNCH("adam_amsgrad_dev");
+    }
+    return CTU_OK;
+}
+
+extern "C" int ctu_grad_norm_num_blocks(const int64_t* sizes, int n) {
+    if (!sizes || n <= 0 || n > (1 << 20)) return 0;           // (64 blocks per tensor at most: the count fits an int)
+    int nb = 0;
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
+        const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
+        int64_t mx = 1;
+        for (int t = 0; t < nt; ++t) if (sizes[t0 + t] > mx) mx = sizes[t0 + t];
+        nb += grad_norm_gx(mx) * nt;
+    }
+    return nb;
+}
+
+extern "C" int ctu_grad_clip_coef(void* const* gptrs, const int64_t* sizes, int n, float max_norm, float* partials_ws,
+                                  float* norm_out, float* coef_out, void* stream) {
+    CTU_REQUIRE(gptrs && sizes && n > 0 && n <= (1 << 20) && partials_ws && norm_out && coef_out, "grad_clip_coef: bad argument");
+    for (int t = 0; t < n; ++t)
+        CTU_REQUIRE(gptrs[t] && sizes[t] >= 0 && ((uintptr_t)gptrs[t] & 3) == 0, "grad_clip_coef: bad tensor at %d", t);
+    hipStream_t st = (hipStream_t)stream;
+    int64_t nb = 0;
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
+        const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
+        NormTable tb;
+        int64_t mx = 1;
+        for (int t = 0; t < nt; ++t) {
+            tb.g[t] = (const float*)gptrs[t0 + t];
+            tb.n[t] = sizes[t0 + t];
+            if (tb.n[t] > mx) mx = tb.n[t];
+        }
+        const int gx = grad_norm_gx(mx);
+        grad_sqsum_kernel<<<dim3(gx, nt), EW_BLOCK, 0, st>>>(tb, partials_ws + nb);
+        CTU_CHECK_LAUNCH("grad_sqsum");
+        nb += (int64_t)gx * nt;
+    }
+    grad_clip_coef_kernel<<<1, EW_BLOCK, 0, st>>>(partials_ws, (int)nb, max_norm, norm_out, coef_out);
+    CTU_CHECK_LAUNCH("grad_clip_coef");
+    return CTU_OK;
+}
+
+extern "C" int ctu_plateau_update(const float* metric, double* lr, double* state, int32_t* counters, int mode_max,
+                                  int threshold_rel, double factor, int patience, double threshold, int cooldown, double min_lr,
+                                  double eps, void* stream) {
+    CTU_REQUIRE(metric && lr && state && counters, "plateau_update: null pointer");
+    CTU_REQUIRE(factor < 1.0 && patience >= 0 && cooldown >= 0, "plateau_update: factor=%g patience=%d cooldown=%d", factor,
+                patience, cooldown);
+    plateau_update_kernel<<<1, 1, 0, (hipStream_t)stream>>>(metric, lr, state, counters, mode_max, threshold_rel, factor,
+                                                           patience, threshold, cooldown, min_lr, eps);
+    CTU_CHECK_LAUNCH("plateau_update");
     return CTU_OK;
 }
 

@@ -194,6 +194,10 @@ SIGNATURES = {
     "ctu_channel_sum_num_blocks": (I, [L]),
     "ctu_channel_sum": (I, [P, I, I, L, P, P, I, P]),
     "ctu_adam_amsgrad": (I, [P, P, I, P, D, D, D, D, D, I, P, P]),
+    "ctu_adam_amsgrad_dev": (I, [P, P, I, P, P, D, D, D, D, I, P, P, P]),
+    "ctu_grad_norm_num_blocks": (I, [P, I]),
+    "ctu_grad_clip_coef": (I, [P, P, I, F, P, P, P, P]),
+    "ctu_plateau_update": (I, [P, P, P, P, I, I, D, I, D, I, D, D, P]),
 }
 
 _lib = None

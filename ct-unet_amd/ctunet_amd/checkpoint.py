@@ -29,3 +29,22 @@ def load_state(model: torch.nn.Module, source, strict: bool = True) -> torch.nn.
 def save_state(model: torch.nn.Module, path: str) -> None:
     """Same format as the reference: a bare state_dict the reference's ``load_model`` can read."""
     torch.save(OrderedDict((k, v.detach().cpu()) for k, v in model.state_dict().items()), path)
+
+
+def save_train_state(optimizer: torch.optim.Optimizer, path: str, scheduler=None) -> None:
+    """Optimizer and (optionally) scheduler state beside the model file: ``{"optimizer": ..., "scheduler": ...}``.  With
+    ``optim.Adam(device_lr=True)`` the param groups carry the device learning rate (``lr_t``) and step counter; a
+    ``lr_scheduler.ReduceLROnPlateau`` saves torch's keys (one sync each)."""
+    torch.save({"optimizer": optimizer.state_dict(), "scheduler": None if scheduler is None else scheduler.state_dict()}, path)
+
+
+def load_train_state(optimizer: torch.optim.Optimizer, source, scheduler=None) -> None:
+    """source: what ``save_train_state`` wrote (a path or the mapping).  Tensors arrive on the host; the optimizer moves them
+    to its parameters' GPU at its next step."""
+    if isinstance(source, (str, bytes)):
+        source = torch.load(source, map_location="cpu", weights_only=True)
+    optimizer.load_state_dict(source["optimizer"])
+    if scheduler is not None:
+        if source.get("scheduler") is None:
+            raise RuntimeError("ctunet_amd.checkpoint: the file holds no scheduler state")
+        scheduler.load_state_dict(source["scheduler"])

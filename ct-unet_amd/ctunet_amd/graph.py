@@ -13,6 +13,11 @@ segment k ends by flattening bucket k into a static buffer; its all-reduce (RCCL
 launched on a side stream behind an event and runs UNDER segment k+1; the last segment is the fused optimizer step,
 which waits for every bucket.  Only the last, smallest bucket's collective is exposed.  Without it the same step body
 is one graph: the chain without bucket boundaries.
+
+Train controls: with an ``optim.Adam(device_lr=True)`` every call uploads a changed ``group["lr"]`` before the
+replay, so host schedulers and manual edits take effect; ``scheduler=`` (``lr_scheduler.ReduceLROnPlateau``) is stepped
+with the total loss INSIDE the captured step, right behind the optimizer: the reference's per-batch
+``scheduler.step(pt_loss)`` without its host sync.
 """
 from __future__ import annotations
 
@@ -73,8 +78,14 @@ class GraphedTrainStep:
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, example_input: torch.Tensor,
                  example_targets: Sequence[torch.Tensor], ce_lambda: float, dice_lambda: float,
                  input_requires_grad: bool = True, warmup: int = 3, distributed: bool = False, process_group=None,
-                 bucket_bytes: Optional[int] = None):
+                 bucket_bytes: Optional[int] = None, scheduler=None):
         self.model, self.opt = model, optimizer
+        self.scheduler = scheduler
+        if scheduler is not None and getattr(scheduler, "optimizer", optimizer) is not optimizer:
+            raise ValueError("GraphedTrainStep: the scheduler belongs to another optimizer")
+        # distributed + scheduler: the ranks' mean total loss, so that every rank takes the same decision (one float)
+        self._metric = torch.zeros(1, dtype=torch.float32, device=example_input.device) \
+            if scheduler is not None and distributed else None
         self.ce, self.dice = float(ce_lambda), float(dice_lambda)
         if not self.ce and not self.dice:
             raise ValueError("GraphedTrainStep: ce_lambda and dice_lambda are both 0: there is no loss to train on")
@@ -149,10 +160,16 @@ class GraphedTrainStep:
                 heads.append((terms[0], terms[1]))
             keys, tl = select_terms(heads, self.ce != 0, self.dice != 0)
             values = torch.stack(tl + [_total(tl)])
+            if self._metric is not None:
+                self._metric.copy_(values[-1:])            # (before backward: in the first segment of the chain)
+                if not torch.cuda.is_current_stream_capturing():
+                    self._allreduce_now(-1, self._metric)  # warm-up; replays launch it from __call__, never captured
             grads, _ = eng.backward(P, ctx, gouts[0], gouts[1] if two else None, self.x_req, sync)
             for name, p in model.named_parameters():
                 p.grad = grads.get(name) if p.requires_grad else None
             self.opt.step()
+            if self.scheduler is not None:
+                self.scheduler.step(values[-1] if self._metric is None else self._metric)
             for p in self._params:
                 p.grad = None
         self.keys = keys + ["epoch_loss"]
@@ -199,6 +216,8 @@ class GraphedTrainStep:
         if targets is not None:
             for dst, src in zip(self.targets, targets):
                 dst.copy_(src)
+        if hasattr(self.opt, "sync_lr"):
+            self.opt.sync_lr()                     # a host-side edit of group["lr"] reaches the replay (device_lr=True only)
         if not self.distributed:
             self.graph.replay()
         else:
@@ -207,6 +226,8 @@ class GraphedTrainStep:
                 self.segments[k].replay()
                 if not self.skip_comm:
                     self._launch_allreduce(flat)           # runs under segment k + 1
+                    if k == 0 and self._metric is not None:
+                        self._launch_allreduce(self._metric)        # 4 bytes, under the rest of backward
             cur.wait_stream(self.comm_stream)
             self.segments[-1].replay()                    # the fused optimizer step, reading the averaged buckets
         # the replayed optimizer kernel wrote the parameters through raw pointers: bump their version counters, so that

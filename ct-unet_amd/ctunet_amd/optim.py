@@ -10,6 +10,12 @@ Deviation from torch: ONE step counter per parameter group (``group["step_t"]``,
 refers to), where torch keeps one per tensor -- a parameter that receives its first gradient later than the others
 of its group therefore shares their bias correction (no shipped model has such a parameter: the dead centre block
 never gets a gradient at all).
+
+Opt-in train controls that stay on the device, so a replayed graph follows them:
+``device_lr=True`` keeps each group's learning rate in a float64[1] device tensor (``group["lr_t"]``) that the kernel
+reads; ``group["lr"]`` stays the Python float every torch scheduler edits, and ``sync_lr()`` uploads it when it changed.
+``max_grad_norm=x`` clips the global gradient norm as ``clip_grad_norm_(model.parameters(), x)`` does: two launches
+form the norm and the coefficient, the Adam launch multiplies each gradient by it.
 """
 from __future__ import annotations
 
@@ -23,11 +29,13 @@ from . import _lib
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=True,
-                 decoupled_weight_decay=False):
+                 decoupled_weight_decay=False, device_lr=False, max_grad_norm=None):
         if not amsgrad:
             raise NotImplementedError("ctunet_amd.optim.Adam implements the amsgrad variant the reference uses")
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameter")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"ctunet_amd.optim.Adam: max_grad_norm must be positive, got {max_grad_norm}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=True,
                                       decoupled_weight_decay=decoupled_weight_decay))
         # fp16 training: a float32[1] device flag (model.overflow_flag()) that the backward sets when a loss-scaled gradient
@@ -35,6 +43,12 @@ class Adam(torch.optim.Optimizer):
         # HIP graph.  None: every step is applied.
         self.skip_flag = None
         self._guarded = None
+        # the learning rate as a device operand (ctu_adam_amsgrad_dev); clipping needs that entry point too
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.device_lr = bool(device_lr) or self.max_grad_norm is not None
+        self.last_grad_norm = None             # float32[1] device tensor: the global gradient norm of the last step (clipping)
+        self._clip_coef = None
+        self._clip_ws = None
 
     def guard(self, model) -> "Adam":
         """Skip every step whose float16 backward overflowed (``model.overflow_flag()``); no-op for fp32 / bf16 models.
@@ -50,6 +64,71 @@ class Adam(torch.optim.Optimizer):
         """The dynamic loss scaler of the guarded model (None: static scaling or none)."""
         return None if self._guarded is None else self._guarded.loss_scaler
 
+    # ------------------------------------------------------------------ the learning rate on the device
+    @staticmethod
+    def _group_device(group):
+        for p in group["params"]:
+            return p.device
+        return None
+
+    def sync_lr(self) -> None:
+        """Uploads every ``group["lr"]`` that differs from what its device tensor was last given (one ``fill_``, no host
+        sync); creates the tensor on first use and moves it behind ``load_state_dict(map_location="cpu")``.  Nothing to do
+        during a capture, where both agree."""
+        if not self.device_lr:
+            return
+        for group in self.param_groups:
+            lr, dev = float(group["lr"]), self._group_device(group)
+            if dev is None or dev.type != "cuda":
+                continue
+            lr_t = group.get("lr_t")
+            if lr_t is not None and lr_t.device == dev and group.get("lr_shadow") == lr:
+                continue
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd.optim.Adam: the device learning rate must be in place before a graph capture "
+                                   "(run one eager step or call sync_lr() first, and edit group['lr'] between replays only)")
+            if lr_t is None:
+                group["lr_t"] = torch.full((1,), lr, dtype=torch.float64, device=dev)
+            elif lr_t.device != dev:
+                group["lr_t"] = lr_t.to(dev)               # a checkpoint's value, kept: it may be ahead of group["lr"]
+                if group.get("lr_shadow") != lr:
+                    group["lr_t"].fill_(lr)
+            else:
+                lr_t.fill_(lr)
+            group["lr_shadow"] = lr
+
+    def get_lr(self) -> List[float]:
+        """The learning rates the kernels read (one sync); refreshes ``group["lr"]`` with them, which matters after a
+        device-side scheduler reduced them."""
+        if not self.device_lr:
+            return [float(g["lr"]) for g in self.param_groups]
+        self.sync_lr()
+        have = [g for g in self.param_groups if "lr_t" in g]
+        vals = torch.cat([g["lr_t"] for g in have]).tolist() if have else []
+        for g, v in zip(have, vals):
+            g["lr"] = g["lr_shadow"] = v
+        return [float(g["lr"]) for g in self.param_groups]
+
+    def _clip(self, lib, grads: List[torch.Tensor]):
+        """Global norm of ``grads`` and its clip coefficient (``ctu_grad_clip_coef``); returns the coefficient tensor."""
+        n = len(grads)
+        sa = (C.c_int64 * n)(*[g.numel() for g in grads])
+        need = int(lib.ctu_grad_norm_num_blocks(sa, n))
+        dev = grads[0].device
+        if self._clip_ws is None or self._clip_ws.numel() < need or self._clip_ws.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd.optim.Adam: the clipping workspace is allocated by the first eager step; run "
+                                   "one before capturing a graph (GraphedTrainStep's warm-up does)")
+            self._clip_ws = torch.empty(need, dtype=torch.float32, device=dev)
+            if self.last_grad_norm is None or self.last_grad_norm.device != dev:
+                self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+                self._clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
+        ga = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
+        _lib.check(lib.ctu_grad_clip_coef(ga, sa, n, self.max_grad_norm, self._clip_ws.data_ptr(),
+                                          self.last_grad_norm.data_ptr(), self._clip_coef.data_ptr(),
+                                          torch.cuda.current_stream().cuda_stream), "grad_clip_coef")
+        return self._clip_coef
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -60,10 +139,21 @@ class Adam(torch.optim.Optimizer):
         scaler = self.guarded_scaler()
         skip = scaler.found_inf if scaler is not None else self.skip_flag
         stepped = False
+        if self.device_lr and not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()
+        work = []
         for group in self.param_groups:
             live: List[torch.Tensor] = [p for p in group["params"] if p.grad is not None]
             if not live:
                 continue
+            for p in live:
+                if not p.is_cuda or p.dtype != torch.float32:
+                    raise RuntimeError("ctunet_amd.optim.Adam: parameters must be float32 on the GPU (no CPU fallback)")
+            work.append((group, live, [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in live]))
+        coef = None
+        if self.max_grad_norm is not None and work:
+            coef = self._clip(lib, [g for _, _, grads in work for g in grads])      # ONE norm over all groups
+        for group, live, grads in work:
             if "step_t" not in group:
                 group["step_t"] = torch.zeros(1, dtype=torch.float32, device=live[0].device)
             elif group["step_t"].device != live[0].device:
@@ -71,16 +161,13 @@ class Adam(torch.optim.Optimizer):
                 # where the checkpoint had them (map_location="cpu"): the kernel must never see a host pointer
                 group["step_t"] = group["step_t"].to(live[0].device)
             ptrs, sizes = [], []
-            for p in live:
-                if not p.is_cuda or p.dtype != torch.float32:
-                    raise RuntimeError("ctunet_amd.optim.Adam: parameters must be float32 on the GPU (no CPU fallback)")
+            for p, g in zip(live, grads):
                 st = self.state[p]
                 if not st:
                     st["step"] = group["step_t"]                    # shared device counter (torch keeps one per tensor)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 ptrs += [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                          st["max_exp_avg_sq"].data_ptr()]
                 sizes.append(p.numel())
@@ -88,11 +175,21 @@ class Adam(torch.optim.Optimizer):
             pa = (C.c_void_p * (5 * n))(*ptrs)
             sa = (C.c_int64 * n)(*sizes)
             b1, b2 = group["betas"]
-            _lib.check(lib.ctu_adam_amsgrad(pa, sa, n, group["step_t"].data_ptr(), float(group["lr"]), float(b1),
-                                            float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                            int(bool(group["decoupled_weight_decay"])),
-                                            None if skip is None else skip.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), "adam_amsgrad")
+            stream = torch.cuda.current_stream().cuda_stream
+            if not self.device_lr:
+                _lib.check(lib.ctu_adam_amsgrad(pa, sa, n, group["step_t"].data_ptr(), float(group["lr"]), float(b1),
+                                                float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                                int(bool(group["decoupled_weight_decay"])),
+                                                None if skip is None else skip.data_ptr(), stream), "adam_amsgrad")
+            else:
+                if "lr_t" not in group or group["lr_t"].device != live[0].device:
+                    raise RuntimeError("ctunet_amd.optim.Adam: the device learning rate must be in place before a graph "
+                                       "capture (run one eager step or call sync_lr() first)")
+                _lib.check(lib.ctu_adam_amsgrad_dev(pa, sa, n, group["step_t"].data_ptr(), group["lr_t"].data_ptr(),
+                                                    float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                                    int(bool(group["decoupled_weight_decay"])),
+                                                    None if coef is None else coef.data_ptr(),
+                                                    None if skip is None else skip.data_ptr(), stream), "adam_amsgrad_dev")
             # the kernel wrote the parameters through raw pointers: tell autograd / every (version-keyed) cache of
             # derived data -- the engine's MFMA-ordered weight copies -- that they changed
             torch.autograd.graph.increment_version(live)
@@ -103,5 +200,7 @@ class Adam(torch.optim.Optimizer):
 
 
 class AdamW(Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=True):
-        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, decoupled_weight_decay=True)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=True, device_lr=False,
+                 max_grad_norm=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, decoupled_weight_decay=True, device_lr=device_lr,
+                         max_grad_norm=max_grad_norm)

@@ -15,6 +15,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ProblemHandler as _handlers
+from . import lr_scheduler as _lr_scheduler
 from . import models as _models
 from . import optim as _optim
 
@@ -55,10 +56,17 @@ class StepRunner:
         p, net = self.params, self.models["main"]
         name = p.get("optimizer", "adam")
         lr, wd = p["learning_rate"], p.get("weight_decay", 0.0) or 0.0
+        # device_lr (opt-in ini key): learning rate, plateau schedule and max_grad_norm clipping stay on the device -- no
+        # per-batch float(loss) for the scheduler
+        dev_lr = bool(p.get("device_lr", False))
+        ctl = dict(device_lr=True, max_grad_norm=p.get("max_grad_norm")) if dev_lr else {}
+        if dev_lr and not (name in ("adam", "adamw") or getattr(name, "device_lr", False)):
+            raise ValueError(f"ctunet_amd: device_lr needs the fused optimizer ('adam' or 'adamw'), not '{name}': "
+                             "torch.optim optimizers take their learning rate from the host")
         if name == "adam":                      # fused multi-tensor kernels (same update rule as optim.Adam(amsgrad=True))
-            p["optimizer"] = _optim.Adam(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True)
+            p["optimizer"] = _optim.Adam(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True, **ctl)
         elif name == "adamw":
-            p["optimizer"] = _optim.AdamW(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True)
+            p["optimizer"] = _optim.AdamW(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True, **ctl)
         elif name == "rmsprop":
             p["optimizer"] = torch.optim.RMSprop(net.parameters(), lr=lr, weight_decay=wd, momentum=p.get("momentum", 0) or 0)
         elif name == "sgd":
@@ -68,7 +76,7 @@ class StepRunner:
         if hasattr(p["optimizer"], "guard"):
             p["optimizer"].guard(net)          # float16 activations: steps whose backward overflowed are skipped
         if "scheduler" in p:      # built whenever the key exists, whatever its value (Model.py:544-546)
-            p["scheduler"] = torch.optim.lr_scheduler.ReduceLROnPlateau(p["optimizer"])
+            p["scheduler"] = (_lr_scheduler if dev_lr else torch.optim.lr_scheduler).ReduceLROnPlateau(p["optimizer"])
 
     def forward_pass(self, phase: str, data_loader) -> None:
         """One pass over ``data_loader``: 'train' updates the parameters, 'validation'/'val' only evaluates the
@@ -97,7 +105,9 @@ class StepRunner:
                     else:
                         opt.step()
                     if self.params.get("scheduler") is not None:
-                        self.params["scheduler"].step(self.pt_loss)
+                        sched = self.params["scheduler"]
+                        sched.step(self.pt_loss.detach() if isinstance(sched, _lr_scheduler.ReduceLROnPlateau)
+                                   else self.pt_loss)
                     for param in net.parameters():
                         param.grad = None
 

@@ -783,6 +783,35 @@ int ctu_adam_amsgrad(void* const* ptrs, const int64_t* sizes, int n, float* step
                      double lr, double beta1, double beta2, double eps, double weight_decay,
                      int decoupled, const float* skip_flag, void* stream);
 
+/* --------------------------------------------------------------- train controls kept on the device ---- */
+/* Learning rate, gradient clipping and the plateau schedule as DEVICE operands, so a captured graph replays the values
+ * current at replay time.  No allocation, no host sync, no float atomics; results are reproducible call to call.
+ *   ctu_adam_amsgrad_dev ..... ctu_adam_amsgrad with lr = (float)lr[0] read on the device (lr: DEVICE double[1], rounded
+ *                              where the host call rounds its argument).  grad_coef: NULL or a DEVICE float[1]; every
+ *                              gradient value is multiplied by it (one IEEE multiply) before weight decay, what
+ *                              clip_grad_norm_ does to p.grad.  With grad_coef NULL or *grad_coef == 1 the result is
+ *                              bit-equal to ctu_adam_amsgrad at the same learning rate.
+ *   ctu_grad_norm_num_blocks . number of floats ctu_grad_clip_coef needs in partials_ws for these sizes (0: bad argument)
+ *   ctu_grad_clip_coef ....... global 2-norm of n gradient tensors (gptrs: HOST array of n DEVICE float pointers, 4-byte
+ *                              aligned; sizes: HOST int64[n]) and torch's clip coefficient:
+ *                              norm_out[0] = (float)sqrt(sum g*g), summed in double in a fixed order;
+ *                              coef_out[0] = min(1, max_norm / (norm + 1e-6f)) in float32, NaN if the norm is NaN and 0 if
+ *                              it is inf (clip_grad_norm_ with error_if_nonfinite=False).
+ *   ctu_plateau_update ....... torch.optim.lr_scheduler.ReduceLROnPlateau.step((double)metric[0]) for one parameter group
+ *                              on one thread, in double.  lr: DEVICE double[1]; state: DEVICE double[1] = best (the host
+ *                              seeds +inf for min mode, -inf for max mode); counters: DEVICE int32[4] = {num_bad_epochs,
+ *                              cooldown_counter, last_epoch, reductions applied}.  mode_max / threshold_rel select the
+ *                              four is-better forms; the reduced rate max(lr * factor, min_lr) is applied only if
+ *                              lr - new > eps. */
+int ctu_adam_amsgrad_dev(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr, double beta1,
+                         double beta2, double eps, double weight_decay, int decoupled, const float* grad_coef,
+                         const float* skip_flag, void* stream);
+int ctu_grad_norm_num_blocks(const int64_t* sizes, int n);
+int ctu_grad_clip_coef(void* const* gptrs, const int64_t* sizes, int n, float max_norm, float* partials_ws, float* norm_out,
+                       float* coef_out, void* stream);
+int ctu_plateau_update(const float* metric, double* lr, double* state, int32_t* counters, int mode_max, int threshold_rel,
+                       double factor, int patience, double threshold, int cooldown, double min_lr, double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
