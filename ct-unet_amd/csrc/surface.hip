@@ -19,17 +19,18 @@
 // Replaces: nothing in the reference (its only distance metric is utilities.hausdorff, ctunet/utilities.py:62-70, kept
 //           as ctu_hausdorff); evaluation users would call monai / scipy on the CPU.
 #include "common.h"
+#include "edt_line.h"
 
 namespace {
+
+using namespace ctu_edt;             // INF_I, LINE_LDS, DistT, is_inf, dist_inf, line_lanes, edt_line
 
 constexpr int EB = 256;                 // edge_x block: 4 waves, one row per wave
 constexpr int RT = 256;                 // reduce / histogram block
 constexpr int RB_MAX = 256;             // reduce blocks per directed plane
 constexpr int MAXG = 64;                // pairs per group (kernel-argument spacing table)
 constexpr int MAXC = 16;
-constexpr int INF_I = 0x3fffffff;       // "no edge on this line" in the int32 maps (3 * 1023^2 << INF_I)
 constexpr int NONE_POS = 1 << 20;
-constexpr int LINE_LDS = 64 * 1024;     // LDS budget of one line-pass block
 
 struct Side {
     const void* p;
@@ -106,16 +107,6 @@ __device__ __forceinline__ uint32_t row_bits(const Side& s, int64_t off, int nv,
     }
     return bits;
 }
-
-template <bool FLT> struct DistT;
-template <> struct DistT<false> { typedef int T; typedef long long A; };
-template <> struct DistT<true> { typedef float T; typedef float A; };
-
-__device__ __forceinline__ bool is_inf(int v) { return v == INF_I; }
-__device__ __forceinline__ bool is_inf(float v) { return v == __builtin_inff(); }
-template <bool FLT> __device__ __forceinline__ typename DistT<FLT>::T dist_inf();
-template <> __device__ __forceinline__ int dist_inf<false>() { return INF_I; }
-template <> __device__ __forceinline__ float dist_inf<true>() { return __builtin_inff(); }
 
 // ------------------------------------------------------------------------------------------------ 1. edges + x pass
 template <bool FLT>
@@ -227,13 +218,11 @@ __global__ void __launch_bounds__(EB) surf_edge_x_kernel(GroupArgs g, int64_t Vp
 // ------------------------------------------------------------------------------------------------ 2. y / z passes
 // One lane per line of length L (element stride lstride), lanes at consecutive x; blockIdx.x = o * nbx + x block, the
 // line of lane x starts at o * ostride + x.  f(q) = min_k src(k) + s2 (q - k)^2 over the finite src(k), in place.
-// Stack of the lower envelope: positions (uint16) and values in LDS, [entry][lane].  The intersection of parabolas a < b
-// lies at num / den with num = (f_b - f_a) + s2 (b - a)(b + a), den = 2 (b - a) > 0 (s2 cancels from the comparison).
+// Stack of the lower envelope: positions (uint16) and values in LDS, [entry][lane] (the routine: edt_line.h).
 template <bool FLT>
 __global__ void surf_line_kernel(GroupArgs g, int64_t Vp, void* __restrict__ dist, int L, int64_t lstride,
                                  int64_t ostride, int nbx, int axis) {
     typedef typename DistT<FLT>::T T;
-    typedef typename DistT<FLT>::A A;
     extern __shared__ uint8_t smem[];
     const int NL = blockDim.x, lane = threadIdx.x;
     T* Fs = reinterpret_cast<T*>(smem);
@@ -246,61 +235,7 @@ __global__ void surf_line_kernel(GroupArgs g, int64_t Vp, void* __restrict__ dis
     const T s2 = FLT ? (T)(sp * sp) : (T)1;
     T* d = (T*)dist + (int64_t)plane * Vp + (int64_t)o * ostride + x;
 
-    int n = 0, vtop = 0;
-    T ftop = 0;
-    A zn = 0, zd = 1;                      // intersection of the two top entries (valid when n >= 2)
-    for (int q0 = 0; q0 < L; q0 += 8) {
-        T buf[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) buf[u] = (q0 + u < L) ? d[(int64_t)(q0 + u) * lstride] : dist_inf<FLT>();
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int q = q0 + u;
-            const T fq = buf[u];
-            if (q >= L || is_inf(fq)) continue;
-            A num = 0, den = 1;
-            while (n > 0) {
-                num = (A)(fq - ftop) + (A)s2 * (A)((q - vtop) * (q + vtop));
-                den = (A)(2 * (q - vtop));
-                if (n >= 2 && num * zd <= zn * den) {
-                    --n;
-                    vtop = Vs[(n - 1) * NL + lane];
-                    ftop = Fs[(n - 1) * NL + lane];
-                    if (n >= 2) {
-                        const int va = Vs[(n - 2) * NL + lane];
-                        const T fa = Fs[(n - 2) * NL + lane];
-                        zn = (A)(ftop - fa) + (A)s2 * (A)((vtop - va) * (vtop + va));
-                        zd = (A)(2 * (vtop - va));
-                    }
-                } else {
-                    break;
-                }
-            }
-            if (n > 0) { zn = num; zd = den; }
-            Fs[n * NL + lane] = fq;
-            Vs[n * NL + lane] = (uint16_t)q;
-            ++n;
-            vtop = q;
-            ftop = fq;
-        }
-    }
-    if (n == 0) {
-        for (int q = 0; q < L; ++q) d[(int64_t)q * lstride] = dist_inf<FLT>();
-        return;
-    }
-    int j = 0, vj = Vs[lane], vn = 0;
-    T fj = Fs[lane], fn = 0;
-    if (n > 1) { vn = Vs[NL + lane]; fn = Fs[NL + lane]; }
-    for (int q = 0; q < L; ++q) {
-        T ej = fj + s2 * (T)((q - vj) * (q - vj));
-        while (j + 1 < n) {
-            const T en = fn + s2 * (T)((q - vn) * (q - vn));
-            if (en > ej) break;
-            ++j; vj = vn; fj = fn; ej = en;
-            if (j + 1 < n) { vn = Vs[(j + 1) * NL + lane]; fn = Fs[(j + 1) * NL + lane]; }
-        }
-        d[(int64_t)q * lstride] = ej;
-    }
+    edt_line<FLT, false>(d, L, lstride, s2, Fs, Vs, NL, lane, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ 3. reduction
@@ -510,12 +445,6 @@ Layout layout(int N, int Cs, int D, int H, int W) {
     l.slab = off;   off = align256(off + (size_t)pairs * 2 * l.RB * sizeof(SlabEntry));
     l.total = off;
     return l;
-}
-
-int line_lanes(int L) {
-    int nl = 64;
-    while (nl > 8 && (size_t)6 * L * nl > (size_t)LINE_LDS) nl >>= 1;
-    return nl;
 }
 
 template <bool FLT>

@@ -127,6 +127,8 @@ SIGNATURES = {
     "ctu_binary_morphology": (I, [P, I, I, I, I, I, I, C.c_uint32, I, I, I, L, P, P, P]),
     "ctu_fill_holes": (I, [P, I, I, I, I, I, I, I, L, P, P, P]),
     "ctu_implant_mask": (I, [P, I, P, I, I, I, I, I, C.c_uint32, I, I, I, I, P, P, P]),
+    "ctu_distance_ws_bytes": (Z, [I, I, I, I, I, I]),
+    "ctu_distance_transform": (I, [P, I, I, I, I, I, I, L, I, I, P, I, P, P, F, P, P]),
     "ctu_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),

@@ -44,6 +44,32 @@ Binary morphology (``binary_erosion`` / ``binary_dilation`` / ``binary_opening``
   ``binary_opening(m, structure, opening_iterations)``; ``fill_holes``: ``binary_fill_holes(., 1)``;
   ``keep_largest_connected_component(., connectivity=connectivity, num_components=num_components)``; a uint8 0 / 1 mask.
 
+Distance transform and ball morphology (``distance_transform_edt`` / ``signed_distance`` / ``ball_erosion`` /
+``ball_dilation`` / ``ball_opening`` / ``ball_closing``; ``ctu_distance_transform`` of ``csrc/distance.hip``) follow
+``scipy.ndimage.distance_transform_edt``:
+
+- **Foreground** as above (nonzero, or ``== label``).  The **sites** are the background voxels; every voxel gets the
+  Euclidean distance ``sqrt(sum_i ((v_i - p_i) s_i)^2)`` to its nearest site ``p``, a site gets 0; ``s`` is ``sampling``
+  (z, y, x), a scalar, a triple or one triple per item, ``None`` = 1.
+- **Exactness**: with unit sampling (``None`` or all 1) the squared distances are int32 and exact, and the distance is the
+  correctly rounded float32 square root; otherwise squared distances are float32 sums of ``(k_i s_i)^2``.
+  ``squared=True`` returns the squared map: int32 at unit sampling, float32 otherwise.
+- **Indices**: ``return_indices=True`` gives int32 ``[3,D,H,W]`` / ``[N,3,D,H,W]``, the (z, y, x) of *a* nearest site;
+  between equidistant sites the choice is fixed (two calls agree) but need not be scipy's.
+- **Empty site set**: an item without background gives ``+inf`` (``INT32_MAX`` for the int32 squared map) everywhere and
+  indices -1.  scipy's result is undefined there; this is a documented divergence.
+- **Signed distance**: ``edt(sites = foreground) - edt(sites = background)``: positive outside the object, negative
+  inside, never 0; ``-inf`` / ``+inf`` everywhere for an all-foreground / all-background item.
+- **Ball**: with ``B = {o : ||o * s|| <= radius}`` (``radius`` in the units of ``sampling``), dilation is
+  ``{v : d(v, foreground) <= radius}`` and erosion ``{v : d(v, background or outside the volume) > radius}``: scipy's
+  ``binary_dilation`` / ``binary_erosion`` with the structure ``B`` and ``border_value=0``, at the cost of one transform
+  whatever the radius.  Opening is erosion then dilation, closing dilation then erosion (which erodes at the border, as
+  scipy's does).  The comparison is made on squared distances (``d2 <= float32(radius^2)``): a radius within float32
+  rounding (about 1e-6 relative) of an offset's length may fall on either side.
+- **Limits**: every side at most 1024 (the line passes keep 6 bytes per line element in LDS; 1365 elements is their hard
+  limit), fewer than 2^31 voxels per item, N <= 65535.  Anything larger raises.
+- ``extract_implant(..., opening_radius=r, sampling=s)`` replaces the iterated opening with ``ball_opening(m, r, s)``.
+
 Each item of a batch is processed on its own.  The morphology calls use no atomics and no host synchronisation, so a
 call can be captured into a graph.  The output and the workspace are ``torch.empty`` tensors, which a capture draws from
 the graph's private pool.  Under capture give ``structure`` as an int or a host array: a structure tensor on the device
@@ -51,7 +77,8 @@ is copied to the host to form its 27-bit code, which synchronises and is refused
 """
 from __future__ import annotations
 
-from numbers import Integral
+import math
+from numbers import Integral, Real
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -312,9 +339,11 @@ def binary_fill_holes(mask: torch.Tensor, connectivity: int = 1, label: Optional
 
 
 def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, opening_iterations: int = 1, structure=1,
-                    connectivity: int = 3, num_components: int = 1, fill_holes: bool = False) -> torch.Tensor:
+                    connectivity: int = 3, num_components: int = 1, fill_holes: bool = False, *,
+                    opening_radius: Optional[float] = None, sampling=None) -> torch.Tensor:
     """The implant of a (full skull, defective skull) prediction pair: ``full AND NOT defective``, opened, optionally
-    hole-filled, reduced to its ``num_components`` largest components (module docstring); a uint8 0 / 1 mask."""
+    hole-filled, reduced to its ``num_components`` largest components (module docstring); a uint8 0 / 1 mask.  With
+    ``opening_radius`` (in the units of ``sampling``) the opening is ``ball_opening`` instead of the iterated one."""
     n, shape = _volume(full_skull, "full_skull", _MASK_DTYPES)
     n2, shape2 = _volume(defective_skull, "defective_skull", _MASK_DTYPES)
     if tuple(full_skull.shape) != tuple(defective_skull.shape):
@@ -328,10 +357,26 @@ def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, ope
         raise ValueError(f"postprocess: num_components must lie in 1..{MAX_COMPONENTS}, got {num_components!r}")
     if not isinstance(fill_holes, (bool, Integral)):
         raise ValueError(f"postprocess: fill_holes must be a bool, got {fill_holes!r}")
+    if opening_radius is None and sampling is not None:
+        raise ValueError("postprocess: sampling is the unit of opening_radius; give both or neither")
+    if opening_radius is not None:
+        if it != 1:
+            raise ValueError(f"postprocess: give opening_radius or opening_iterations, not both (got "
+                             f"opening_iterations={opening_iterations!r}, opening_radius={opening_radius!r})")
+        _distance_sides(shape)
+        r2 = _radius2(opening_radius, "opening_radius")
+        spacing = _sampling(sampling, n)
     _check_device(full_skull)
     _check_device(defective_skull)
     if full_skull.device != defective_skull.device:
         raise ValueError("postprocess: full_skull and defective_skull must live on the same GPU")
+    if opening_radius is not None:
+        m = ((full_skull != 0) & (defective_skull == 0)).view(torch.uint8)
+        m = _ball(m, _ERODE, r2, spacing)
+        m = _ball(m, _DILATE, r2, spacing)
+        if fill_holes:
+            m = binary_fill_holes(m, 1)
+        return keep_largest_connected_component(m, connectivity=conn, num_components=int(num_components))
     lib = _lib.load()
     a, da = _as_bytes(full_skull)
     b, db = _as_bytes(defective_skull)
@@ -349,3 +394,147 @@ def morphology_workspace_bytes(n: int, shape, iterations: int = 1) -> int:
     bit images, whatever ``iterations`` is (``ctu_morphology_ws_bytes`` also sizes fill-holes and implant calls)."""
     _iterations(iterations)
     return int(_lib.load().ctu_morphology_ws_bytes(n, *shape, _WS_MORPH))
+
+
+# ------------------------------------------------------------------------------------------------ distance transform
+MAX_DISTANCE_SIDE = 1024
+_DIST_EDT, _DIST_SQUARED, _DIST_SIGNED, _DIST_BALL = 0, 1, 2, 3
+
+
+def _distance_sides(shape) -> None:
+    if any(s > MAX_DISTANCE_SIDE for s in shape):
+        raise ValueError(f"postprocess: the distance transform takes sides up to {MAX_DISTANCE_SIDE}, got {tuple(shape)}")
+
+
+def _sampling(sampling, n: int):
+    """None for unit sampling (the exact int32 path), else N (z, y, x) triples."""
+    from .metrics import parse_spacing
+    import ctypes
+    try:
+        sp = parse_spacing(sampling, n)
+    except ValueError as e:
+        raise ValueError(str(e).replace("metrics: spacing", "postprocess: sampling")) from e
+    if sp is None or all(ctypes.c_float(v).value == 1.0 for t in sp for v in t):
+        return None
+    return sp
+
+
+def _radius2(radius, what: str = "radius") -> float:
+    if isinstance(radius, bool) or not isinstance(radius, Real):
+        raise ValueError(f"postprocess: {what} must be a real number, got {radius!r}")
+    r = float(radius)
+    if not (math.isfinite(r) and r > 0.0 and r * r < 3.0e38):
+        raise ValueError(f"postprocess: {what} must be positive and finite, got {radius!r}")
+    return r * r
+
+
+def _flag(v, what: str) -> bool:
+    if not isinstance(v, (bool, Integral)):
+        raise ValueError(f"postprocess: {what} must be a bool, got {v!r}")
+    return bool(v)
+
+
+def _distance(mask, n, shape, kind: int, spacing, has_label: int, lab: int, invert: int, border: int, want_indices: bool,
+              r2: float = -1.0):
+    import ctypes
+    lib = _lib.load()
+    src, dt = _as_bytes(mask)
+    dev = mask.device
+    unit = spacing is None
+    if kind == _DIST_BALL:
+        out = torch.empty(mask.shape, dtype=torch.uint8, device=dev)
+    else:
+        out = torch.empty(mask.shape, dtype=torch.int32 if (kind == _DIST_SQUARED and unit) else torch.float32, device=dev)
+    idx = None
+    if want_indices:
+        idx = torch.empty(tuple(mask.shape[:-3]) + (3,) + tuple(shape), dtype=torch.int32, device=dev)
+    sp = None
+    if not unit:
+        flat = [v for t in spacing for v in t]
+        sp = (ctypes.c_float * len(flat))(*flat)
+    ws = torch.empty(lib.ctu_distance_ws_bytes(n, *shape, kind, int(want_indices)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_distance_transform(src.data_ptr(), dt, n, *shape, has_label, lab, invert, border, sp, kind,
+                                              out.data_ptr(), idx.data_ptr() if want_indices else None, r2, ws.data_ptr(),
+                                              stream), "distance_transform")
+    return out, idx
+
+
+def distance_transform_edt(mask: torch.Tensor, sampling=None, return_distances: bool = True, return_indices: bool = False,
+                           label: Optional[int] = None, squared: bool = False):
+    """``scipy.ndimage.distance_transform_edt`` of a bool / uint8 / int64 mask [D,H,W] or [N,D,H,W]: the distance of every
+    voxel to the nearest background voxel (module docstring).  Returns the float32 distances (``squared=True``: the squared
+    distances, int32 at unit sampling), the int32 indices, or the tuple of both, as scipy does."""
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    _distance_sides(shape)
+    sp = _sampling(sampling, n)
+    has_label, lab = _label_arg(label)
+    want_d, want_i, sq = _flag(return_distances, "return_distances"), _flag(return_indices, "return_indices"), \
+        _flag(squared, "squared")
+    if not (want_d or want_i):
+        raise ValueError("postprocess: at least one of return_distances and return_indices must be true")
+    _check_device(mask)
+    out, idx = _distance(mask, n, shape, _DIST_SQUARED if sq else _DIST_EDT, sp, has_label, lab, 0, 0, want_i)
+    if want_d and want_i:
+        return out, idx
+    return out if want_d else idx
+
+
+def signed_distance(mask: torch.Tensor, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """float32 signed distance of a bool / uint8 / int64 mask [D,H,W] or [N,D,H,W]: the distance to the object outside it,
+    minus the distance to the background inside it (module docstring)."""
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    _distance_sides(shape)
+    sp = _sampling(sampling, n)
+    has_label, lab = _label_arg(label)
+    _check_device(mask)
+    return _distance(mask, n, shape, _DIST_SIGNED, sp, has_label, lab, 0, 0, False)[0]
+
+
+def _ball(mask: torch.Tensor, mode: int, r2: float, spacing, has_label: int = 0, lab: int = 0) -> torch.Tensor:
+    """One ball erosion / dilation of a validated device mask; uint8 0 / 1."""
+    n = 1 if mask.dim() == 3 else mask.shape[0]
+    erode = mode == _ERODE
+    return _distance(mask, n, tuple(mask.shape[-3:]), _DIST_BALL, spacing, has_label, lab, 0 if erode else 1,
+                     1 if erode else 0, False, r2)[0]
+
+
+def _ball_op(mask, modes, radius, sampling, label) -> torch.Tensor:
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    _distance_sides(shape)
+    r2 = _radius2(radius)
+    sp = _sampling(sampling, n)
+    has_label, lab = _label_arg(label)
+    _check_device(mask)
+    out = _ball(mask, modes[0], r2, sp, has_label, lab)
+    for mode in modes[1:]:
+        out = _ball(out, mode, r2, sp)
+    return _finish(out, mask)
+
+
+def ball_erosion(mask: torch.Tensor, radius: float, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """Erosion by the ball of ``radius`` (units of ``sampling``): the voxels farther than ``radius`` from every background
+    voxel and from the outside of the volume; ``scipy.ndimage.binary_erosion`` with the ball structure, border value 0."""
+    return _ball_op(mask, (_ERODE,), radius, sampling, label)
+
+
+def ball_dilation(mask: torch.Tensor, radius: float, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """Dilation by the ball of ``radius``: the voxels within ``radius`` of a foreground voxel."""
+    return _ball_op(mask, (_DILATE,), radius, sampling, label)
+
+
+def ball_opening(mask: torch.Tensor, radius: float, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """Ball erosion, then ball dilation."""
+    return _ball_op(mask, (_ERODE, _DILATE), radius, sampling, label)
+
+
+def ball_closing(mask: torch.Tensor, radius: float, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """Ball dilation, then ball erosion (border value 0: closing erodes at the volume border, as scipy's does)."""
+    return _ball_op(mask, (_DILATE, _ERODE), radius, sampling, label)
+
+
+def distance_workspace_bytes(n: int, shape, return_indices: bool = False) -> int:
+    """Device workspace (bytes) of one ``distance_transform_edt`` call on n items of a (D, H, W) volume: the maps are
+    computed inside the result, so only the indices need room (three int16 planes, 6 bytes per voxel)."""
+    return int(_lib.load().ctu_distance_ws_bytes(n, *shape, _DIST_EDT, int(bool(return_indices))))

@@ -25,6 +25,8 @@
  *    partials; ctu_bn_finalize turns those into per-channel scale/shift; every consumer
  *    applies  a = relu(raw*scale + shift)  while loading (`in_scale`,`in_shift`,
  *    `in_relu`; NULL scale = identity).  Raw tensors are what backward re-reads.
+ *  - Post-processing (ctu_*_components, ctu_binary_morphology, ctu_distance_transform: exact Euclidean distance, signed
+ *    distance and ball morphology in physical units) works on contiguous label maps [N,D,H,W], each item on its own.
  */
 #ifndef CTUNET_HIP_H
 #define CTUNET_HIP_H
@@ -498,6 +500,33 @@ int ctu_fill_holes(const void* in, int dtype, int N, int D, int H, int W, int co
 int ctu_implant_mask(const void* full, int full_dtype, const void* defective, int defective_dtype, int N, int D, int H,
                      int W, uint32_t structure, int opening_iterations, int fill_holes, int connectivity,
                      int num_components, uint8_t* out, void* ws, void* stream);
+
+/* Exact Euclidean distance transform of masks, signed distance and the ball threshold behind ball erosion / dilation (no
+ * reference counterpart: the reference erodes / dilates with SimpleITK balls on the host, ctunet/pytorch/transforms.py:97-127;
+ * pinned here on scipy.ndimage.distance_transform_edt, definitions in ctunet_amd/postprocess.py).  in: DEVICE [N,D,H,W] of
+ * dtype CTU_U8 or CTU_I64; a voxel is foreground if it is nonzero or, with has_label != 0, equal to label.  The SITES are the
+ * background voxels (invert != 0: the foreground voxels) and, with border_background != 0, every voxel outside the volume;
+ * each voxel gets the distance to its nearest site, a site 0.  spacing: HOST float [N][3] = (z, y, x) per item, NULL or all
+ * 1 = unit: int32 squared distances, exact; otherwise fp32 sum (k_i s_i)^2.  An item without a site gets +inf / INT32_MAX
+ * and indices -1 (scipy leaves that case undefined).  out, one buffer of [N,D,H,W] by out_kind:
+ *   CTU_DIST_EDT:     float32 distance = sqrt of the squared distance;
+ *   CTU_DIST_SQUARED: the squared distance, int32 at unit spacing, float32 otherwise;
+ *   CTU_DIST_SIGNED:  float32 edt(sites = foreground) - edt(sites = background): > 0 outside, < 0 inside (invert ignored);
+ *   CTU_DIST_BALL:    uint8 0 / 1: invert != 0: d2 <= ball_r2 (dilation by the ball), else d2 > ball_r2 (erosion; pass
+ *                     border_background = 1 for a border value of 0).
+ * indices (NULL: none; CTU_DIST_EDT / CTU_DIST_SQUARED without the virtual border only): DEVICE int32 [N][3][D,H,W], the
+ * (z, y, x) of a nearest site of every voxel.  ws: ctu_distance_ws_bytes() bytes, 0 for an invalid shape or kind: 4 bytes
+ * per voxel for CTU_DIST_SIGNED / CTU_DIST_BALL (the other kinds work inside out), plus 6 per voxel with indices.
+ * Limits: every side <= 1024 (a line pass stacks 6 bytes per line element in LDS), D*H*W < 2^31, N <= 65535; anything
+ * beyond is refused, never truncated.  Deterministic, no atomics, no host sync, capture-safe. */
+#define CTU_DIST_EDT 0
+#define CTU_DIST_SQUARED 1
+#define CTU_DIST_SIGNED 2
+#define CTU_DIST_BALL 3
+size_t ctu_distance_ws_bytes(int N, int D, int H, int W, int out_kind, int want_indices);
+int ctu_distance_transform(const void* in, int dtype, int N, int D, int H, int W, int has_label, int64_t label, int invert,
+                           int border_background, const float* spacing, int out_kind, void* out, int32_t* indices,
+                           float ball_r2, void* ws, void* stream);
 
 /* Resampling of volumes between voxel grids (no reference counterpart: the reference resizes on the host in its datasets,
  * ctunet/pytorch/datasets.py:89-112; rule and tables pinned in ctunet_amd/resample.py).  in: DEVICE [N,D,H,W], out: DEVICE
