@@ -28,6 +28,7 @@
 //
 // Replaces: nothing in the reference; users would copy the label map to the host for scipy.ndimage.label.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -353,26 +354,7 @@ __global__ void __launch_bounds__(TB) cc_flatten_kernel(CcArgs a, int* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ 4. number
-__device__ __forceinline__ int block_exclusive_scan(int x, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int s = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(s, o);
-        if (lane >= o) s += y;
-    }
-    if (lane == 63) lds[wid] = s;
-    __syncthreads();
-    int wo = 0;
-    total = 0;
-    for (int i = 0; i < nw; ++i) {
-        if (i < wid) wo += lds[i];
-        total += lds[i];
-    }
-    __syncthreads();
-    return wo + s - x;
-}
-
+// block_exclusive_scan: scan.h
 // 16 C-order voxels of chunk blockIdx.x: root flags
 __device__ __forceinline__ uint32_t root_flags(const int* P, int64_t V, int64_t v0) {
     uint32_t f = 0;

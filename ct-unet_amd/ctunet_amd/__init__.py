@@ -6,6 +6,7 @@ for the hot path only.  Importing it does not need a GPU; running a model does.
 """
 from . import _lib  # noqa: F401
 from . import lr_scheduler  # noqa: F401
+from . import mesh  # noqa: F401
 from . import metrics  # noqa: F401
 from . import optim  # noqa: F401
 from . import postprocess  # noqa: F401
@@ -20,4 +21,4 @@ from .transforms import FlapRecTransform, SaltAndPepper, SkullRandomHole, flap_r
 __all__ = ["UNet", "UNet4b2i3o", "UNet5b2i3o", "UNet4b1i3o", "UNetSP", "UNetSPSmall", "UNetDO", "recAE_v2_fixed",
            "UNet4_2IC", "DynamicLossScale", "predict_volume", "Prediction",
            "SkullRandomHole", "SaltAndPepper", "FlapRecTransform", "flap_rec_transform", "FlapRecWShapePrior2OTrainDataset",
-           "FlapRec2OTrainDataset", "metrics", "postprocess", "resample", "lr_scheduler", "optim"]
+           "FlapRec2OTrainDataset", "metrics", "postprocess", "resample", "mesh", "lr_scheduler", "optim"]

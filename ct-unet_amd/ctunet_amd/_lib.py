@@ -130,6 +130,10 @@ SIGNATURES = {
     "ctu_distance_ws_bytes": (Z, [I, I, I, I, I, I]),
     "ctu_distance_transform": (I, [P, I, I, I, I, I, I, L, I, I, P, I, P, P, F, P, P]),
     "ctu_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P]),
+    "ctu_mesh_ws_bytes": (Z, [I, I, I]),
+    "ctu_mesh_count": (I, [P, I, I, I, I, I, L, F, P, P]),
+    "ctu_mesh_emit": (I, [P, I, I, I, I, F, F, P, P, L, L, P, P, P, P]),
+    "ctu_mesh_measure": (I, [P, L, P, L, P, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

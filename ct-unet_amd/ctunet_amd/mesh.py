@@ -1,0 +1,271 @@
+"""Surface meshes of label volumes and scalar fields on the GPU, and their export as binary STL: the last step of the
+segmentation-to-implant pipeline (``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of ``csrc/mesh.hip``); no
+CPU fallback.
+
+    m = mesh.extract_surface(implant, spacing=(0.8, 0.45, 0.45))      # Mesh: vertices [V,3] (z, y, x) in mm, faces [F,3]
+    area, volume = mesh.measure(m).tolist()
+    mesh.write_stl("implant.stl", m)
+
+``volume`` is one ``[D,H,W]`` tensor.  Meshes are ragged (V and F depend on the data), so a batch is a Python loop over its
+items.  bool, uint8 and int64 volumes are masks or label maps: inside = ``v != 0``, or ``v == label`` with ``label=``;
+float32 volumes are scalar fields (probabilities, or ``-signed_distance``): inside = ``v > level``.
+
+The pinned rule (``tests/mesh_ref.py`` restates it in numpy): **marching tetrahedra on the Kuhn split, welded and closed**.
+
+- **Padded grid.**  The grid is padded by one virtual layer of *outside* points on every face; padded point ``p`` is voxel
+  ``p - 1``.  The cells are the (D+1)(H+1)(W+1) cubes of the padded grid, so the mesh is closed at the volume border too.
+  A mask reads as 1 / 0 against level 0.5.  Virtual points hold ``fill_value``: 0 for masks, ``level - 1`` by default for
+  float32, never above ``level``.
+- **Tetrahedra.**  Every cell splits into the six tetrahedra around its diagonal (0,0,0)-(1,1,1): the paths ``c0`` = corner
+  0, ``c1 = c0 + e_a``, ``c2 = c1 + e_b``, ``c3 = c2 + e_c`` for the permutations (a, b, c) of the axes (z, y, x) = (0, 1, 2)
+  in lexicographic order.  The split is translation invariant, so neighbouring cells agree on every shared face.
+- **Vertices** lie on the lattice edges whose ends differ in insideness.  An edge belongs to the cell at its lower end; a
+  cell owns seven edges, in this order of (dz, dy, dx): (0,0,1), (0,1,0), (1,0,0), (0,1,1), (1,0,1), (1,1,0), (1,1,1).
+  Vertex order: cells in C order of the padded grid, then owned crossing edges in that order.  With ``v0`` the value at
+  the owner's corner 0 and ``v1`` at the far end, ``t = (level - v0) / (v1 - v0)`` in float32 (exactly 0.5 for masks), and the
+  coordinate on axis i is ``origin_i + (float32(p_i - 1) + t * d_i) * spacing_i``, every float32 operation rounded on its own.
+- **Faces.**  Order: cells in C order, then tetrahedra in order, then: with one or three corners inside, ``i`` the lone corner
+  and ``o0 < o1 < o2`` the others in path order, one triangle (i-o0, i-o1, i-o2); with two inside, ``i0 < i1`` inside and
+  ``o0 < o1`` outside, the quad a = i0-o0, b = i0-o1, c = i1-o1, d = i1-o0 as the triangles (a, b, c) and (a, c, d).  The
+  first index of a triangle stays; the other two are swapped where needed so that the right-hand normal, computed in
+  (x, y, z) (the vertex columns reversed), points from inside to outside.  On the device that winding is a table by
+  (permutation, case), derived at compile time from the tetrahedron's geometry.
+- **Degenerate values.**  A sample equal to ``level`` is outside.  Vertices may then coincide at a lattice point and give faces
+  without area; the mesh stays combinatorially a closed 2-manifold.  Nothing is snapped or removed: the result is a function
+  of the rule alone.  The field must be finite (a NaN sample is outside and makes the vertices on its edges NaN).
+
+Every input gives a closed, consistently oriented 2-manifold, without ambiguous cases.  A known property of the Kuhn split:
+two voxels that touch only across the (0,0,0)-(1,1,1) body diagonal are joined, across the other three body diagonals they
+are not.
+
+One host synchronisation per call is inherent, because the output size depends on the data: the count pass runs, the host
+reads (V, F), allocates ``vertices`` and ``faces``, and the emit pass runs.  There is no other synchronisation and no atomic
+operation: every output position comes from a fixed-order scan, so two calls are bit-equal (``measure`` too: block sums,
+then one fixed-order sum).  A call cannot be captured into a graph.
+
+Limits: every side <= 1024, (D+1)(H+1)(W+1) < 2^31, V and F < 2^31; anything beyond raises, nothing is truncated.
+Out of scope: smoothing, decimation, formats other than binary STL, marching cubes.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from numbers import Integral, Real
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .metrics import parse_spacing
+
+MAX_SIDE = 1024
+SCAN_BLOCK = 1024          # CTU_MESH_SCAN_BLOCK: more cell rows, (D+1)(H+1), than this take the scan's second level
+_MEASURE_WS = 16384        # CTU_MESH_MEASURE_WS
+_MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
+_DTYPES = _MASK_DTYPES + (torch.float32,)
+CTU_F32, CTU_U8, CTU_I64 = 0, 3, 4
+
+
+class Mesh(NamedTuple):
+    """``vertices`` float32 [V,3] in (z, y, x) physical units, ``faces`` int32 [F,3]; both on the volume's device."""
+    vertices: torch.Tensor
+    faces: torch.Tensor
+
+
+def _shape(shape) -> tuple:
+    try:
+        vals = tuple(shape)
+    except TypeError:
+        raise ValueError(f"mesh: the shape must be a (D, H, W) triple, got {shape!r}") from None
+    if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Integral) for s in vals):
+        raise ValueError(f"mesh: the shape must be a (D, H, W) triple of integers, got {shape!r}")
+    if any(s < 1 or s > MAX_SIDE for s in vals):
+        raise ValueError(f"mesh: every side must lie in 1..{MAX_SIDE}, got {vals}")
+    if (vals[0] + 1) * (vals[1] + 1) * (vals[2] + 1) >= 1 << 31:
+        raise ValueError(f"mesh: (D+1)(H+1)(W+1) must stay below 2^31, got {vals}")
+    return tuple(int(s) for s in vals)
+
+
+def _spacing(spacing):
+    try:
+        sp = parse_spacing(spacing, 1)
+    except ValueError as e:
+        raise ValueError(str(e).replace("metrics: spacing", "mesh: spacing")) from e
+    if sp is not None and len(sp) == 1 and isinstance(spacing, (list, tuple)) and len(spacing) == 1:
+        raise ValueError(f"mesh: spacing must be a number or a (z, y, x) triple, got {spacing!r}")
+    if sp is not None and any(not math.isfinite(v) or ctypes.c_float(v).value <= 0.0
+                              or not math.isfinite(ctypes.c_float(v).value) for v in sp[0]):
+        raise ValueError(f"mesh: spacing must be positive and finite in float32, got {spacing!r}")
+    return None if sp is None else sp[0]
+
+
+def _origin(origin):
+    if origin is None:
+        return None
+    if isinstance(origin, torch.Tensor):
+        origin = origin.tolist()
+    if isinstance(origin, Real) and not isinstance(origin, bool):
+        vals = [origin] * 3
+    else:
+        try:
+            vals = list(origin)
+        except TypeError:
+            raise ValueError(f"mesh: origin must be a number or a (z, y, x) triple, got {origin!r}") from None
+    if len(vals) != 3 or any(isinstance(v, bool) or not isinstance(v, Real) for v in vals):
+        raise ValueError(f"mesh: origin must be a number or a (z, y, x) triple, got {origin!r}")
+    if any(not math.isfinite(ctypes.c_float(float(v)).value) for v in vals):
+        raise ValueError(f"mesh: origin must be finite in float32, got {origin!r}")
+    return [float(v) for v in vals]
+
+
+def _number(v, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(ctypes.c_float(float(v)).value):
+        raise ValueError(f"mesh: {what} must be a finite real number, got {v!r}")
+    return ctypes.c_float(float(v)).value
+
+
+def _check_mesh(m, who: str):
+    if not (isinstance(m, tuple) and len(m) == 2 and all(isinstance(t, torch.Tensor) for t in m)):
+        raise ValueError(f"mesh: {who} takes a Mesh (vertices, faces), got {type(m).__name__}")
+    v, f = m
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"mesh: vertices must be float32 [V,3], got {v.dtype} {tuple(v.shape)}")
+    if f.dtype != torch.int32 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"mesh: faces must be int32 [F,3], got {f.dtype} {tuple(f.shape)}")
+    if v.device != f.device:
+        raise ValueError("mesh: vertices and faces must live on the same device")
+    if f.shape[0] and not v.shape[0]:
+        raise ValueError("mesh: faces without vertices")
+    return v, f
+
+
+def workspace_bytes(shape) -> int:
+    """Device workspace (bytes) of one ``extract_surface`` call on a (D, H, W) volume: 5 bytes per cell of the padded grid
+    (rows of W+1 cells rounded up to 16), 12 per cell row and 256; the only allocation besides the mesh itself."""
+    return int(_lib.load().ctu_mesh_ws_bytes(*_shape(shape)))
+
+
+def extract_surface(volume: torch.Tensor, level: float = 0.5, spacing=None, origin=None, label: Optional[int] = None,
+                    fill_value: Optional[float] = None) -> Mesh:
+    """The closed triangle mesh of one ``[D,H,W]`` volume by the module docstring's rule.
+
+    bool / uint8 / int64: the surface of ``volume != 0`` (``volume == label`` with ``label=``); ``level`` stays 0.5 and
+    ``fill_value`` 0.  float32: the level set ``volume > level``, the virtual layer at ``fill_value`` (default ``level - 1``,
+    at most ``level``).  ``spacing`` and ``origin`` are a number or a (z, y, x) triple (default 1 and 0).  A batch is a Python
+    loop: meshes are ragged.  The call synchronises with the host once, to read (V, F) between its count and emit passes; a
+    non-contiguous view is copied first.  Returns ``Mesh(vertices float32 [V,3] (z, y, x), faces int32 [F,3])`` on the
+    volume's device; an empty surface gives V = F = 0."""
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
+        raise ValueError("mesh: volume must be one [D,H,W] tensor (loop over a batch: meshes are ragged)")
+    if volume.dtype not in _DTYPES:
+        raise ValueError(f"mesh: volume must be one of {', '.join(str(d) for d in _DTYPES)}, got {volume.dtype}")
+    shape = _shape(tuple(volume.shape))
+    field = volume.dtype == torch.float32
+    lev = _number(level, "level")
+    sp, org = _spacing(spacing), _origin(origin)
+    if field:
+        if label is not None:
+            raise ValueError("mesh: label belongs to bool / uint8 / int64 volumes; a float32 field is cut at level")
+        fill = ctypes.c_float(lev - 1.0).value if fill_value is None else _number(fill_value, "fill_value")
+        if fill > lev:
+            raise ValueError(f"mesh: fill_value must not exceed level ({lev}), got {fill_value!r}")
+        has_label, lab = 0, 0
+    else:
+        if lev != 0.5:
+            raise ValueError(f"mesh: a mask is cut at level 0.5 (inside = 1, outside = 0), got level={level!r}")
+        if fill_value is not None and _number(fill_value, "fill_value") != 0.0:
+            raise ValueError(f"mesh: the virtual layer of a mask is 0, got fill_value={fill_value!r}")
+        fill = 0.0
+        if label is None:
+            has_label, lab = 0, 0
+        elif isinstance(label, bool) or not isinstance(label, Integral) or not -(1 << 63) <= label < (1 << 63):
+            raise ValueError(f"mesh: label must be an integer of the map's range, got {label!r}")
+        else:
+            has_label, lab = 1, int(label)
+    if not volume.is_cuda:
+        raise ValueError("mesh: volume must live on the GPU; this path has no CPU fallback")
+    lib = _lib.load()
+    src = volume.contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    dt = CTU_F32 if field else (CTU_I64 if src.dtype == torch.int64 else CTU_U8)
+    dev = volume.device
+    c_sp = None if sp is None else (ctypes.c_float * 3)(*sp)
+    c_org = None if org is None else (ctypes.c_float * 3)(*org)
+    ws = torch.empty(lib.ctu_mesh_ws_bytes(*shape), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_count(src.data_ptr(), dt, *shape, has_label, lab, lev, ws.data_ptr(), stream), "mesh_count")
+        nv, nf = ws[:16].view(torch.int64).tolist()                     # the call's one host synchronisation
+        if nv >= 1 << 31 or nf >= 1 << 31:
+            raise ValueError(f"mesh: the surface has {nv} vertices and {nf} faces; both must stay below 2^31")
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        _lib.check(lib.ctu_mesh_emit(src.data_ptr(), dt, *shape, lev, fill, c_sp, c_org, nv, nf,
+                                     vertices.data_ptr() if nv else None, faces.data_ptr() if nf else None, ws.data_ptr(),
+                                     stream), "mesh_emit")
+    return Mesh(vertices, faces)
+
+
+def _measure(m, want_normals: bool, who: str):
+    v, f = _check_mesh(m, who)
+    if not v.is_cuda:
+        raise ValueError(f"mesh: {who} takes a mesh on the GPU; this path has no CPU fallback")
+    lib = _lib.load()
+    v, f = v.contiguous(), f.contiguous()
+    out = torch.empty(2, dtype=torch.float64, device=v.device)
+    normals = torch.empty((f.shape[0], 3), dtype=torch.float32, device=v.device) if want_normals else None
+    ws = torch.empty(_MEASURE_WS, dtype=torch.uint8, device=v.device)
+    with torch.cuda.device(v.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_measure(v.data_ptr() if v.shape[0] else None, v.shape[0],
+                                        f.data_ptr() if f.shape[0] else None, f.shape[0], out.data_ptr(),
+                                        normals.data_ptr() if want_normals and f.shape[0] else None, ws.data_ptr(), stream),
+                   "mesh_measure")
+    return out, normals
+
+
+def measure(m: Mesh) -> torch.Tensor:
+    """float64 device tensor [2] = (surface area, enclosed volume) in the units of the vertices: per-face area and signed
+    volume term ``p0 . (p1 x p2) / 6`` in float64 from the float32 vertices, summed in a fixed order (two calls are
+    bit-equal).  The volume is positive for the outward winding ``extract_surface`` gives.  No host synchronisation."""
+    return _measure(m, False, "measure")[0]
+
+
+def face_normals(m: Mesh) -> torch.Tensor:
+    """float32 [F,3] unit normals in (z, y, x), right-handed in (x, y, z): outward for ``extract_surface``'s winding; the zero
+    vector for a face without area."""
+    return _measure(m, True, "face_normals")[1]
+
+
+def stl_bytes(vertices, faces, header: bytes = b"") -> bytes:
+    """The binary STL of host arrays ``vertices [V,3]`` (z, y, x) and ``faces [F,3]``: the 80-byte header, the uint32 count and
+    50 bytes per triangle: normal and three corners as little-endian float32 in (x, y, z), then a zero uint16.  The winding
+    is kept, so the stored right-hand normal points outward."""
+    if not isinstance(header, (bytes, bytearray)) or len(header) > 80:
+        raise ValueError(f"mesh: an STL header is at most 80 bytes, got {header!r}")
+    if bytes(header[:5]).lower() == b"solid":
+        raise ValueError("mesh: a binary STL header must not begin with 'solid' (readers take it for the ASCII form)")
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32)[:, ::-1])
+    f = np.asarray(faces, dtype=np.int64)
+    if len(f) >= 1 << 32:
+        raise ValueError("mesh: binary STL counts its triangles in a uint32")
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("mesh: a face refers to a vertex that does not exist")
+    rec = np.zeros(len(f), dtype=np.dtype([("n", "<f4", 3), ("p", "<f4", (3, 3)), ("a", "<u2")]))
+    p = v[f] if len(f) else np.zeros((0, 3, 3), dtype=np.float32)
+    n = np.cross(p[:, 1].astype(np.float64) - p[:, 0], p[:, 2].astype(np.float64) - p[:, 0])
+    length = np.sqrt((n * n).sum(axis=1, keepdims=True))
+    rec["n"] = np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+    rec["p"] = p
+    return bytes(header).ljust(80, b"\0") + np.uint32(len(f)).astype("<u4").tobytes() + rec.tobytes()
+
+
+def write_stl(path, m: Mesh, header: bytes = b"") -> None:
+    """Write the mesh as binary STL (``stl_bytes``); the mesh may live on the GPU or on the host (it is copied to the host
+    either way: this is file output)."""
+    v, f = _check_mesh(m, "write_stl")
+    data = stl_bytes(v.detach().cpu().numpy(), f.detach().cpu().numpy(), header)
+    with open(path, "wb") as fh:
+        fh.write(data)

@@ -552,6 +552,35 @@ int ctu_distance_transform(const void* in, int dtype, int N, int D, int H, int W
 int ctu_resample(const void* in, int dtype, int mode, int num_classes, int64_t N, int D, int H, int W, int d, int h, int w,
                  const int32_t* i0, const float* wt, const int32_t* near, void* out, void* stream);
 
+/* Surface meshes of label volumes and scalar fields (no reference counterpart: the reference writes NIfTI volumes only;
+ * rule pinned in ctunet_amd/mesh.py): marching tetrahedra on the Kuhn split of the cells of the grid padded by one layer of
+ * outside points, welded (shared vertex indices) and closed.  volume: DEVICE contiguous [D,H,W] of dtype CTU_U8 or CTU_I64
+ * (inside = nonzero or, with has_label != 0, equal to label; the corner values are 1 / 0 against level 0.5, fill 0) or
+ * CTU_F32 (inside = value > level; the virtual layer holds fill_value <= level).
+ *   count:   classifies the (D+1)(H+1)(W+1) cells, numbers vertices and faces (cells in C order, then owned edges / then
+ *            tetrahedra) with a fixed-order scan and leaves the int64 totals (V, F) in the first 16 bytes of ws, which the
+ *            caller reads after synchronising the stream: the one host synchronisation of an extraction.
+ *   emit:    with the ws that count filled and the same volume: vertices DEVICE float32 [V][3] = (z, y, x) =
+ *            origin + (index + t * d) * spacing (HOST float [3] each, NULL = 0 / 1; each operation rounded on its own),
+ *            faces DEVICE int32 [F][3], the right-hand normal in (x, y, z) pointing from inside to outside.  V and F are the
+ *            totals count left; V or F >= 2^31 is refused, never truncated.
+ *   measure: out DEVICE double [2] = (area, enclosed volume = sum p0 . (p1 x p2) / 6 in (x, y, z)), float64 arithmetic on the
+ *            float32 vertices, summed in a fixed order; normals (NULL: none) DEVICE float32 [F][3] unit normals in (z, y, x),
+ *            0 for a face without area.  ws: CTU_MESH_MEASURE_WS bytes.
+ * ws of count / emit: ctu_mesh_ws_bytes() bytes, 0 for an invalid shape: 5 bytes per cell of the row-padded cell grid (rows
+ * of W+1 cells rounded up to 16) + 12 per cell row + 256; 16-byte aligned.  Cell rows are the blocks of the scan:
+ * CTU_MESH_SCAN_BLOCK threads scan them, several rows per thread beyond that many rows.
+ * Limits: every side <= 1024, (D+1)(H+1)(W+1) < 2^31.  No atomics; two calls are bitwise equal. */
+#define CTU_MESH_SCAN_BLOCK 1024
+#define CTU_MESH_MEASURE_WS 16384
+size_t ctu_mesh_ws_bytes(int D, int H, int W);
+int ctu_mesh_count(const void* volume, int dtype, int D, int H, int W, int has_label, int64_t label, float level, void* ws,
+                   void* stream);
+int ctu_mesh_emit(const void* volume, int dtype, int D, int H, int W, float level, float fill_value, const float* spacing,
+                  const float* origin, int64_t V, int64_t F, float* vertices, int32_t* faces, void* ws, void* stream);
+int ctu_mesh_measure(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double* out, float* normals, void* ws,
+                     void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
