@@ -134,6 +134,11 @@ SIGNATURES = {
     "ctu_mesh_count": (I, [P, I, I, I, I, I, L, F, P, P]),
     "ctu_mesh_emit": (I, [P, I, I, I, I, F, F, P, P, L, L, P, P, P, P]),
     "ctu_mesh_measure": (I, [P, L, P, L, P, P, P, P]),
+    "ctu_mesh_adjacency_ws_bytes": (Z, [L, L]),
+    "ctu_mesh_adjacency_build": (I, [P, L, L, P, P, P]),
+    "ctu_mesh_adjacency_emit": (I, [L, L, L, P, P, P, P]),
+    "ctu_mesh_smooth_ws_bytes": (Z, [L]),
+    "ctu_mesh_smooth": (I, [P, L, P, P, L, P, I, F, I, F, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

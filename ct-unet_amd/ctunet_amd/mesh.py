@@ -1,8 +1,9 @@
-"""Surface meshes of label volumes and scalar fields on the GPU, and their export as binary STL: the last step of the
-segmentation-to-implant pipeline (``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of ``csrc/mesh.hip``); no
-CPU fallback.
+"""Surface meshes of label volumes and scalar fields on the GPU, their smoothing, and their export as binary STL: the last
+step of the segmentation-to-implant pipeline (``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of
+``csrc/mesh.hip``, ``ctu_mesh_adjacency_*`` / ``ctu_mesh_smooth`` of ``csrc/mesh_smooth.hip``); no CPU fallback.
 
     m = mesh.extract_surface(implant, spacing=(0.8, 0.45, 0.45))      # Mesh: vertices [V,3] (z, y, x) in mm, faces [F,3]
+    m = mesh.smooth(m)                                                # Taubin: the staircase goes, the volume stays
     area, volume = mesh.measure(m).tolist()
     mesh.write_stl("implant.stl", m)
 
@@ -44,7 +45,35 @@ operation: every output position comes from a fixed-order scan, so two calls are
 then one fixed-order sum).  A call cannot be captured into a graph.
 
 Limits: every side <= 1024, (D+1)(H+1)(W+1) < 2^31, V and F < 2^31; anything beyond raises, nothing is truncated.
-Out of scope: smoothing, decimation, formats other than binary STL, marching cubes.
+
+**Smoothing** (``adjacency`` / ``smooth``; ``tests/mesh_smooth_ref.py`` restates the rule in numpy).  The surface of a mask is
+a staircase: every vertex sits at the midpoint of a lattice edge.  ``smooth`` moves the vertices and keeps the faces.
+
+- **Neighbours.**  ``N(i)`` is the set of distinct vertices ``j != i`` that occur in a face together with ``i``, in ascending
+  ``j``.  Both directions of every face edge count (an open or inconsistently wound mesh gets a symmetric table), duplicate
+  faces add nothing, a face with a repeated index such as ``[1, 1, 2]`` contributes only its distinct pairs, and a vertex in
+  no face has ``N(i)`` empty.  ``Adjacency(offsets int32 [V+1], neighbours int32 [E])`` holds the sets in vertex order:
+  ``offsets[i+1] - offsets[i] = |N(i)|``.  For the closed oriented meshes ``extract_surface`` gives, ``E = 3F``; nothing relies
+  on it.
+- **One step with factor s** (float32, every operation rounded on its own, Jacobi: all reads come from the previous
+  positions).  For a vertex with neighbours ``n_1 < n_2 < ...`` and ``fixed[i]`` false, per coordinate:
+  ``acc = v[n_1]; acc = acc + v[n_2]; ...`` in ascending order, ``mean = acc / float32(|N(i)|)`` (a true division),
+  ``v'_i = v_i + s * (mean - v_i)``.  A vertex without neighbours or with ``fixed[i]`` true keeps its bits; a fixed vertex
+  still enters its neighbours' sums.
+- **Iterations.**  One iteration is a step with ``lamb`` followed by a step with ``mu`` (Taubin's lambda|mu smoothing, which
+  keeps the enclosed volume where plain Laplacian smoothing shrinks it); ``mu=None`` is Laplacian smoothing, one ``lamb`` step
+  per iteration; ``iterations=0`` returns a bit-equal copy.  ``0 < lamb <= 1``; ``mu`` is finite with ``mu < -lamb`` (Taubin's
+  ``0 < lambda < -mu``: the pass-band frequency ``1/lambda + 1/mu`` is positive); both are rounded to float32 once.
+- **Bad indices.**  The build skips every face with an index outside ``[0, V)`` and counts it; ``adjacency`` then raises.  The
+  smoothing kernel compares every offset against ``E`` and every neighbour against ``V`` before use, so a hand-made or
+  corrupted ``Adjacency`` gives wrong positions, never an out-of-range read.
+- **Synchronisation.**  ``adjacency`` synchronises with the host once, to read ``E`` (and the bad-face count) and size
+  ``neighbours``; ``smooth(m)`` calls it; ``smooth(m, adjacency=a)`` neither synchronises nor builds.  The build uses integer
+  atomics only where the final value does not depend on arrival order (counts, fill cursors) and sorts every neighbour
+  list afterwards, so the table does not depend on the order of the faces and two calls are bit-equal.
+
+Limits of smoothing: V < 2^31 and 6F < 2^31 (E and every offset fit an int32); anything beyond raises.
+Out of scope: decimation, formats other than binary STL, marching cubes.
 """
 from __future__ import annotations
 
@@ -62,6 +91,8 @@ from .metrics import parse_spacing
 MAX_SIDE = 1024
 SCAN_BLOCK = 1024          # CTU_MESH_SCAN_BLOCK: more cell rows, (D+1)(H+1), than this take the scan's second level
 _MEASURE_WS = 16384        # CTU_MESH_MEASURE_WS
+ADJ_SCAN_CHUNK = 4096      # CTU_MESH_ADJ_SCAN_CHUNK: more vertices than this take the adjacency scan's second level
+MAX_ITERATIONS = 10000     # CTU_MESH_SMOOTH_MAX_ITERATIONS
 _MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
 _DTYPES = _MASK_DTYPES + (torch.float32,)
 CTU_F32, CTU_U8, CTU_I64 = 0, 3, 4
@@ -71,6 +102,13 @@ class Mesh(NamedTuple):
     """``vertices`` float32 [V,3] in (z, y, x) physical units, ``faces`` int32 [F,3]; both on the volume's device."""
     vertices: torch.Tensor
     faces: torch.Tensor
+
+
+class Adjacency(NamedTuple):
+    """The vertex -> neighbours table (CSR) of a mesh: ``offsets`` int32 [V+1], ``neighbours`` int32 [E], both on the mesh's
+    device; the neighbours of vertex i are ``neighbours[offsets[i]:offsets[i+1]]``, ascending."""
+    offsets: torch.Tensor
+    neighbours: torch.Tensor
 
 
 def _shape(shape) -> tuple:
@@ -237,6 +275,117 @@ def face_normals(m: Mesh) -> torch.Tensor:
     """float32 [F,3] unit normals in (z, y, x), right-handed in (x, y, z): outward for ``extract_surface``'s winding; the zero
     vector for a face without area."""
     return _measure(m, True, "face_normals")[1]
+
+
+def _check_sizes(v, f, who: str):
+    V, F = v.shape[0], f.shape[0]
+    if V >= 1 << 31 or 6 * F >= 1 << 31:
+        raise ValueError(f"mesh: {who} takes V < 2^31 vertices and 6F < 2^31, got V = {V}, F = {F}")
+    return V, F
+
+
+def adjacency(m: Mesh) -> Adjacency:
+    """The vertex -> neighbours table of a mesh on the GPU, by the module docstring's rule.  The call synchronises with the
+    host once, to read E between its build and emit passes; a face index outside ``[0, V)`` raises (such faces are skipped
+    on the device, never read through).  An empty mesh gives all-zero offsets and E = 0 without any launch."""
+    v, f = _check_mesh(m, "adjacency")
+    V, F = _check_sizes(v, f, "adjacency")
+    if not v.is_cuda:
+        raise ValueError("mesh: adjacency takes a mesh on the GPU; this path has no CPU fallback")
+    return _build_adjacency(f, V, F)
+
+
+def _build_adjacency(f: torch.Tensor, V: int, F: int) -> Adjacency:
+    dev = f.device
+    if V == 0 or F == 0:
+        return Adjacency(torch.zeros(V + 1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+    lib = _lib.load()
+    f = f.contiguous()
+    ws = torch.empty(lib.ctu_mesh_adjacency_ws_bytes(V, F), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_adjacency_build(f.data_ptr(), V, F, offsets.data_ptr(), ws.data_ptr(), stream), "mesh_adjacency_build")
+        ne, bad = ws[:16].view(torch.int64).tolist()                    # the call's one host synchronisation
+        if bad:
+            raise ValueError(f"mesh: a face refers to a vertex that does not exist ({bad} of {F} faces hold an index outside [0, {V}))")
+        neighbours = torch.empty(ne, dtype=torch.int32, device=dev)
+        _lib.check(lib.ctu_mesh_adjacency_emit(V, F, ne, offsets.data_ptr(), neighbours.data_ptr() if ne else None, ws.data_ptr(),
+                                               stream), "mesh_adjacency_emit")
+    return Adjacency(offsets, neighbours)
+
+
+def smooth_workspace_bytes(V: int, F: int) -> int:
+    """The most device memory (bytes) one ``smooth`` call on a contiguous mesh of V vertices and F faces allocates besides its
+    result: the two staged position buffers (16 bytes per vertex each), which is all a call with ``adjacency=`` allocates,
+    and the adjacency it builds otherwise: the build's workspace (``ctu_mesh_adjacency_ws_bytes``), ``offsets`` and at most
+    6F ``neighbours``."""
+    if any(isinstance(n, bool) or not isinstance(n, Integral) for n in (V, F)) or V < 0 or F < 0 or V >= 1 << 31 or 6 * F >= 1 << 31:
+        raise ValueError(f"mesh: smooth_workspace_bytes takes 0 <= V < 2^31 and 0 <= 6F < 2^31, got {V!r}, {F!r}")
+    lib = _lib.load()
+    return int(lib.ctu_mesh_smooth_ws_bytes(V)) + int(lib.ctu_mesh_adjacency_ws_bytes(V, F)) + 4 * (int(V) + 1) + 24 * int(F)
+
+
+def _factor(x, what: str) -> float:
+    if isinstance(x, bool) or not isinstance(x, Real) or not math.isfinite(float(x)):
+        raise ValueError(f"mesh: {what} must be a finite real number, got {x!r}")
+    return ctypes.c_float(float(x)).value
+
+
+def smooth(m: Mesh, iterations: int = 10, lamb: float = 0.5, mu: Optional[float] = -0.53, fixed: Optional[torch.Tensor] = None,
+           adjacency: Optional[Adjacency] = None) -> Mesh:
+    """``Mesh(new vertices, m.faces)`` after ``iterations`` of Taubin smoothing (``mu=None``: Laplacian) by the module
+    docstring's rule; ``m.vertices`` is left untouched and ``faces`` is the same tensor.  ``fixed``: a bool / uint8 ``[V]``
+    tensor on the mesh's device, true where a vertex must keep its position.  ``adjacency``: the table of ``adjacency(m)`` to
+    reuse; with it the call neither synchronises nor allocates anything besides the result and
+    ``ctu_mesh_smooth_ws_bytes(V)``; without it the table is built first (one synchronisation)."""
+    v, f = _check_mesh(m, "smooth")
+    V, F = _check_sizes(v, f, "smooth")
+    if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= MAX_ITERATIONS:
+        raise ValueError(f"mesh: iterations must be an integer in 0..{MAX_ITERATIONS}, got {iterations!r}")
+    lam = _factor(lamb, "lamb")
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f"mesh: lamb must lie in (0, 1], got {lamb!r}")
+    mu32 = None if mu is None else _factor(mu, "mu")
+    if mu32 is not None and not (math.isfinite(mu32) and mu32 < -lam):
+        raise ValueError(f"mesh: mu must be None or finite with mu < -lamb (Taubin's 0 < lambda < -mu), got mu={mu!r}, lamb={lamb!r}")
+    if fixed is not None:
+        if not isinstance(fixed, torch.Tensor) or fixed.dtype not in (torch.bool, torch.uint8) or tuple(fixed.shape) != (V,):
+            raise ValueError(f"mesh: fixed must be a bool or uint8 [V] tensor with V = {V}, got "
+                             f"{getattr(fixed, 'dtype', type(fixed).__name__)} {tuple(getattr(fixed, 'shape', ()))}")
+        if fixed.device != v.device:
+            raise ValueError("mesh: fixed must live on the mesh's device")
+    if adjacency is not None:
+        if not (isinstance(adjacency, tuple) and len(adjacency) == 2 and all(isinstance(t, torch.Tensor) for t in adjacency)):
+            raise ValueError(f"mesh: adjacency must be an Adjacency (offsets, neighbours), got {type(adjacency).__name__}")
+        off, nb = adjacency
+        if off.dtype != torch.int32 or nb.dtype != torch.int32 or off.dim() != 1 or nb.dim() != 1:
+            raise ValueError(f"mesh: offsets and neighbours must be int32 vectors, got {off.dtype} {tuple(off.shape)} and "
+                             f"{nb.dtype} {tuple(nb.shape)}")
+        if off.shape[0] != V + 1:
+            raise ValueError(f"mesh: offsets must have V + 1 = {V + 1} entries, got {off.shape[0]}")
+        if nb.shape[0] >= 1 << 31:
+            raise ValueError(f"mesh: neighbours must have fewer than 2^31 entries, got {nb.shape[0]}")
+        if off.device != v.device or nb.device != v.device:
+            raise ValueError("mesh: the adjacency must live on the mesh's device")
+    if not v.is_cuda:
+        raise ValueError("mesh: smooth takes a mesh on the GPU; this path has no CPU fallback")
+    off, nb = adjacency if adjacency is not None else _build_adjacency(f, V, F)
+    lib = _lib.load()
+    src, off, nb = v.contiguous(), off.contiguous(), nb.contiguous()
+    fx = None
+    if fixed is not None:
+        fx = fixed.contiguous()
+        fx = fx.view(torch.uint8) if fx.dtype == torch.bool else fx
+    out = torch.empty((V, 3), dtype=torch.float32, device=v.device)
+    ws = torch.empty(lib.ctu_mesh_smooth_ws_bytes(V), dtype=torch.uint8, device=v.device)
+    with torch.cuda.device(v.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_smooth(src.data_ptr() if V else None, V, off.data_ptr(), nb.data_ptr() if nb.shape[0] else None,
+                                       nb.shape[0], fx.data_ptr() if fx is not None and V else None, int(iterations), lam,
+                                       int(mu32 is not None), 0.0 if mu32 is None else mu32, out.data_ptr() if V else None,
+                                       ws.data_ptr(), stream), "mesh_smooth")
+    return Mesh(out, f)
 
 
 def stl_bytes(vertices, faces, header: bytes = b"") -> bytes:

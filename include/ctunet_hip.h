@@ -581,6 +581,37 @@ int ctu_mesh_emit(const void* volume, int dtype, int D, int H, int W, float leve
 int ctu_mesh_measure(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double* out, float* normals, void* ws,
                      void* stream);
 
+/* Vertex adjacency (CSR) and Taubin / Laplacian smoothing of surface meshes (no reference counterpart; rule pinned in
+ * ctunet_amd/mesh.py).  faces: DEVICE int32 [F][3]; N(i) = the distinct vertices j != i that share a face with i, ascending;
+ * offsets int32 [V+1], neighbours int32 [E] hold the sets in vertex order.
+ *   build: counts, scans, fills, sorts and de-duplicates into ws, writes offsets [V+1] and, at the head of ws, two int64:
+ *          (E, the number of faces with an index outside [0, V)).  Such faces are skipped, never read through.  The caller
+ *          reads the head (one synchronisation), refuses the mesh if the second word is non-zero, allocates neighbours [E]
+ *          and calls emit with the same ws.
+ *   emit:  neighbours [E] from ws; every write is bounded by E.
+ *   V = 0 or F = 0 (E = 0 for emit): nothing is launched or written; the table is empty (offsets all zero, E = 0).
+ *   ws: ctu_mesh_adjacency_ws_bytes(V, F) bytes, 0 outside the limits: 256 + 8 V + 24 F + 8 per scan chunk, each array
+ *       rounded up to 256; 16-byte aligned.  CTU_MESH_ADJ_SCAN_CHUNK vertices are one block of the scan; beyond that the
+ *       chunk sums are scanned by one block.
+ *   smooth: `iterations` times a step with factor lambda and, with has_mu != 0, a step with factor mu (Taubin); per step and
+ *          vertex with neighbours and fixed[i] == 0 (fixed NULL: none): v' = v + s * (sum of N(i) in order / |N(i)| - v) in
+ *          float32, every operation rounded on its own, all reads from the previous positions.  vertices, out: DEVICE float32
+ *          [V][3], distinct; fixed: DEVICE uint8 [V].  Offsets are bounded against E and neighbours against V before use.
+ *          0 < lambda <= 1; mu finite and < -lambda; iterations in 0..CTU_MESH_SMOOTH_MAX_ITERATIONS (0: a copy).
+ *          ws: ctu_mesh_smooth_ws_bytes(V) = two staged copies of 16 bytes per vertex; 16-byte aligned.
+ * Limits: V < 2^31 and 6 F < 2^31 (so E and every offset fit an int32).  Integer atomics only where the final value does
+ * not depend on arrival order; two calls are bitwise equal. */
+#define CTU_MESH_ADJ_SCAN_CHUNK 4096
+#define CTU_MESH_SMOOTH_MAX_ITERATIONS 10000
+size_t ctu_mesh_adjacency_ws_bytes(int64_t V, int64_t F);
+int ctu_mesh_adjacency_build(const int32_t* faces, int64_t V, int64_t F, int32_t* offsets, void* ws, void* stream);
+int ctu_mesh_adjacency_emit(int64_t V, int64_t F, int64_t E, const int32_t* offsets, int32_t* neighbours, void* ws,
+                            void* stream);
+size_t ctu_mesh_smooth_ws_bytes(int64_t V);
+int ctu_mesh_smooth(const float* vertices, int64_t V, const int32_t* offsets, const int32_t* neighbours, int64_t E,
+                    const uint8_t* fixed, int iterations, float lambda, int has_mu, float mu, float* out, void* ws,
+                    void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
