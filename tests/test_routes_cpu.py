@@ -9,7 +9,13 @@ Families with a name query (ctu_conv3d_*_kernel_name, ctu_lp_conv3d_*_kernel_nam
 up-convolutions and the first-layer kernels have none: `route()` restates their selection rules below, and
 `test_restated_grids_match_the_library` holds the restatement to the library's *_num_blocks queries at every swept shape.
 Where no query gives a grid, a block count cap mirrors the line of C++ that bounds it; boxes > cap then guarantees at least
-two boxes for a block."""
+two boxes for a block.
+
+The first encoder convolution is swept at both precisions.  Its 16-bit routes are the T = bf16 / half instantiations of the
+three first-layer kernels (one name `<CIN, T>` for both types), the matrix-pipe data gradient `lp_conv_fwd_pair_kernel<OUT32>`
+of volumes at least 32 wide and, for large volumes, the matrix-pipe weight gradient `lp_wgrad8_kernel<first>`; a GPU case
+forces the last one with the op spelling `first_wgrad_mfma` (it sets ops.FIRST_WGRAD_MFMA_MIN_VOX to 0).  First layers the
+first-layer kernels do not take (k = 5, W < 16) are swept as ordinary convolutions on 8 padded input channels."""
 from collections import namedtuple
 
 Case = namedtuple("Case", "route op dtype N Ci Co D H W k xf cs c0")
@@ -177,17 +183,29 @@ def route(c):
                        max(1, WG_BLOCKS // (8 * cdiv(cip, 16) * cdiv(cop, 16))), lz)
     if op.startswith("first_"):      # C_in <= 2 first layer, 8 padded outputs, 4 x 4 x 32 boxes
         part = op[len("first_"):].replace("_bn", "")
+        forced = part == "wgrad_mfma"                      # a GPU case that sets ops.FIRST_WGRAD_MFMA_MIN_VOX to 0
+        part = part.replace("_mfma", "")
+        if lp and part == "dgrad" and L.ctu_lp_conv3d_first_bwd_data_pair_supported(c.Ci, W):
+            # ops.conv_first_bwd_data: the 8 -> 8 pair-layout kernel with the float32-plane epilogue
+            return _capped("lp_conv_fwd_pair_kernel<OUT32>", N, D, H, W, (4, 8, 32), LP_PAIR_CAP)
+        if lp and part == "wgrad":
+            # ops.conv_first_wgrad: large volumes take a 16-bit copy of the input + the 8 -> 8 matrix-pipe weight gradient
+            from ctunet_amd import ops as O
+            if (forced or N * D * H * W >= O.FIRST_WGRAD_MFMA_MIN_VOX) \
+                    and L.ctu_lp_conv3d_wgrad_kernel_name(D, H, W, 3, 8, 8) == b"lp_wgrad8_kernel":
+                return _capped("lp_wgrad8_kernel<first>", N, D, H, W, (4, 8, 32), LP_WG8_CAP)
         box = (4, 4, 32)
         n = _boxes(N, D, H, W, box)
         gx, tpb = persist_grid(n, 256 * FIRST_PER_CU[part])
         kern = {"fwd": "first_fwd_kernel", "dgrad": "first_bwd_data_kernel", "wgrad": "first_wgrad_kernel"}[part]
-        return Route(f"{kern}<{c.Ci}>{lz}", True, box, n, tpb)
+        return Route(f"{kern}<{c.Ci}, T>" if lp else f"{kern}<{c.Ci}>{lz}", True, box, n, tpb)
     raise ValueError(f"unknown op {op}")
 
 
 def family(c):
-    """Forward and data gradient of a conv share the forward kernels; every other op is a family of its own."""
-    op = "fwd" if c.op == "dgrad" else c.op.replace("_bn", "")
+    """Forward and data gradient of a conv share the forward kernels; every other op is a family of its own (the forced
+    matrix-pipe spelling of the first layer's weight gradient belongs to that weight gradient's family)."""
+    op = "fwd" if c.op == "dgrad" else c.op.replace("_bn", "").replace("_mfma", "")
     return ("fp32" if c.dtype == "fp32" else "lp") + ":" + op
 
 
@@ -239,12 +257,12 @@ def sweep_cases():
                             continue
                         cases += [Case("", o, dt, n, ci, co, dd, hh, ww, 3, True, 0, 0) for o in ops]
                         continue
-                    if ci <= 2 and dt == "fp32" and _lib().ctu_conv3d_first_supported(k, ci, pad8(co), ww):
-                        ops = ("first_fwd", "first_dgrad", "first_wgrad", "first_wgrad_bn")
+                    if ci <= 2 and _lib().ctu_conv3d_first_supported(k, ci, pad8(co), ww):
+                        # (ops.conv_first_wgrad_bn is fp32 only: the 16-bit first layer has no lazy weight gradient)
+                        ops = ("first_fwd", "first_dgrad", "first_wgrad") + (("first_wgrad_bn",) if dt == "fp32" else ())
                         cases += [Case("", o, dt, n, ci, co, dd, hh, ww, k, False, 0, 0) for o in ops]
                         continue
-                    if ci <= 2:
-                        continue       # 16-bit first layers and narrow fallbacks: out of this manifest
+                    # (a first layer with k = 5 or W < 16 falls through: the generic kernels on 8 padded input channels)
                     ops = ["fwd", "dgrad", "wgrad"]
                     cip, cop = pad8(ci), pad8(co)
                     if dt == "fp32" and _lib().ctu_conv3d_wgrad_bn_supported(n, dd, hh, ww, k, cip, cop):
@@ -296,9 +314,15 @@ def test_restated_grids_match_the_library():
         elif c.op == "up_fwd":
             r = route(c)
             assert persist_grid(r.boxes, UL_CAP)[0] == L.ctu_lp_upconv_fused_num_blocks(N, D, H, W), c
-        elif c.op == "first_fwd":
+        elif c.op == "first_fwd":                                # fp32 and 16-bit: one template, one grid
             r = route(c)
+            assert r.name.startswith("first_fwd_kernel<") and r.name.endswith(", T>") == (c.dtype != "fp32"), c
             assert persist_grid(r.boxes, 256 * FIRST_PER_CU["fwd"])[0] == L.ctu_conv3d_first_num_blocks(N, D, H, W), c
+        elif c.op == "first_dgrad" and c.dtype != "fp32":
+            r = route(c)
+            if r.name != "lp_conv_fwd_pair_kernel<OUT32>":
+                continue
+            assert persist_grid(r.boxes, LP_PAIR_CAP)[0] == L.ctu_lp_conv3d_num_blocks(N, D, H, W, 3, 8, 8, 1), c
         elif c.op in ("fwd", "dgrad") and c.dtype != "fp32":
             r = route(c)
             if r.name.startswith("lp_conv_fwd_p1_kernel"):     # the restated lp_box gives the library's grid

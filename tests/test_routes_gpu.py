@@ -13,6 +13,9 @@ Gates (the per-op suites' gates, references in fp64):
   16-bit fused up-convolution ............ 6 ulps (the composite weights are rounded once more: test_lowp_gpu.py)
   weight gradients ....................... 1e-4 of max |ref| (fused up-convolution: 2e-4 fp32, 2e-3 16-bit, as per-op suites)
   raw-output gradients of the lazy path .. 2e-4 (fp32), 2 ulps (16-bit)
+  first layer ............................ 1e-5 of max |ref| for fp32 outputs and every float32 data gradient (the 16-bit
+                                           routes accumulate exact products in float32, like the fp32 kernel); 16-bit stored
+                                           outputs one ulp and bit-equal to the rounded fp32 kernel's
 A failure names the worst voxel, its box and the block that ran the box."""
 import zlib
 
@@ -106,6 +109,18 @@ CASES = [
     Case("first_wgrad_kernel<2>", "first_wgrad", "fp32", 1, 2, 8, 104, 104, 36, 3, False, 0, 0),
     Case("first_wgrad_kernel<1>+LZ", "first_wgrad_bn", "fp32", 1, 1, 7, 104, 104, 36, 3, False, 16, 8),
     Case("first_wgrad_kernel<2>+LZ", "first_wgrad_bn", "fp32", 2, 2, 8, 96, 112, 36, 3, False, 8, 0),
+    # ---- 16-bit first layer: the T = bf16 / half instantiations, the matrix-pipe data gradient with float32 planes (>= 32
+    # wide) and the matrix-pipe weight gradient of large volumes (forced: first_wgrad_mfma).  Each volume is the smallest that
+    # gives every block two boxes; outputs and gradients are a slice at offset 8 of a 16-channel sentinel-filled buffer.
+    Case("first_fwd_kernel<1, T>", "first_fwd", "bf16", 1, 1, 7, 50, 62, 132, 3, False, 16, 8),
+    Case("first_fwd_kernel<2, T>", "first_fwd", "fp16", 2, 2, 8, 44, 64, 68, 3, False, 16, 8),
+    Case("lp_conv_fwd_pair_kernel<OUT32>", "first_dgrad", "fp16", 1, 1, 7, 110, 108, 36, 3, False, 16, 8),
+    Case("lp_conv_fwd_pair_kernel<OUT32>", "first_dgrad", "bf16", 2, 2, 4, 54, 108, 36, 3, False, 16, 8),
+    Case("first_bwd_data_kernel<2, T>", "first_dgrad", "fp16", 1, 2, 7, 100, 124, 24, 3, False, 16, 8),     # 16 <= W < 32
+    Case("first_wgrad_kernel<1, T>", "first_wgrad", "bf16", 1, 1, 7, 104, 104, 36, 3, False, 16, 8),
+    Case("first_wgrad_kernel<2, T>", "first_wgrad", "fp16", 2, 2, 8, 50, 106, 36, 3, False, 16, 8),
+    Case("lp_wgrad8_kernel<first>", "first_wgrad_mfma", "bf16", 1, 2, 7, 40, 104, 128, 3, False, 16, 8),
+    Case("lp_wgrad8_kernel<first>", "first_wgrad_mfma", "fp16", 2, 1, 4, 20, 104, 128, 3, False, 16, 8),
 ]
 
 
@@ -400,40 +415,87 @@ def test_fused_upconv(c):
 
 
 # ------------------------------------------------------------------ first layer (C_in <= 2, NCDHW input, 8 padded outputs)
+def first_buffer(c, dt, n, d, h, w):
+    """The 8-channel output slice of a first-layer case in a sentinel-filled buffer (default: offset 8 of 16 channels)."""
+    cs, c0 = (c.cs, c.c0) if c.cs else (16, 8)
+    return _ops().CL(torch.full((n, d, h, w, cs), SENT, dtype=DT[dt], device="cuda"), c0, 8)
+
+
+def first_grad(c, ga, dt):
+    """The gradient of a first-layer case as a channels-last slice (c.cs = 0: a plain 8-channel tensor)."""
+    return to_cl(ga, 8, dt, c.cs or None, c.c0, SENT)
+
+
+def check_first_fwd(c, out, stats, ref, co, tol_rel):
+    """Output, neighbouring and padded channels and the BatchNorm partial rows of a first-layer forward.  16-bit: the sums are
+    taken over the ROUNDED stored outputs."""
+    got = from_cl(out, co)
+    check(c, got, ref, tol_rel)
+    check_sentinel_and_padding(c, out, co)
+    assert torch.all(out.buf[..., out.c0 + 8:].float() == SENT), f"{_id(c)}: the channels behind the slice were written"
+    s = stats.sum(0).cpu().double()
+    assert not torch.isnan(s).any(), f"{_id(c)}: a stats row was not written"
+    base = ref if c.dtype == "fp32" else got.double()
+    s1, s2 = base.sum((0, 2, 3, 4)), (base * base).sum((0, 2, 3, 4))
+    assert torch.allclose(s[0, :co], s1, rtol=1e-4, atol=1e-3 * s2.max().sqrt().item()), f"{_id(c)}: channel sums"
+    assert torch.allclose(s[1, :co], s2, rtol=1e-4), f"{_id(c)}: channel sums of squares"
+    assert co == 8 or float(s[:, co:].abs().max()) == 0.0, f"{_id(c)}: statistics of the padded channels"
+    return got
+
+
 @pytest.mark.parametrize("c", [pytest.param(c, id=_id(c)) for c in CASES if c.op.startswith("first_")])
-def test_first_layer(c):
+def test_first_layer(c, monkeypatch):
     ops = _ops()
-    n, ci, co, d, h, w = c.N, c.Ci, c.Co, c.D, c.H, c.W
+    dt, n, ci, co, d, h, w = c.dtype, c.N, c.Ci, c.Co, c.D, c.H, c.W
+    lp = dt != "fp32"
     assert ops.conv_first_supported(3, ci, 8, w)
     g = gen(c)
-    x = torch.randn(n, ci, d, h, w, generator=g)
+    x = torch.randn(n, ci, d, h, w, generator=g)                 # float32, never rounded: the kernels read it as it is
     wt = torch.randn(co, ci, 3, 3, 3, generator=g) * 0.3
     if c.op == "first_fwd":
-        out = out_buffer(n, d, h, w, 8, "fp32", c)
         nb = ops.conv_first_num_blocks((n, d, h, w))
-        stats = torch.full((nb, 2, 8), float("nan"), device="cuda")
-        ops.conv_first_fwd(x.cuda(), wt.cuda(), None, out, stats)
-        torch.cuda.synchronize()
+
+        def run(dtype):
+            out = first_buffer(c, dtype, n, d, h, w)
+            stats = torch.full((nb, 2, 8), float("nan"), device="cuda")          # every row must be written
+            ops.conv_first_fwd(x.cuda(), wt.cuda(), None, out, stats)
+            torch.cuda.synchronize()
+            return out, stats
+        out, stats = run(dt)
         ref = F.conv3d(x.double(), wt.double(), None, 1, 1)
-        check(c, from_cl(out, co), ref, 1e-5)
-        check_sentinel_and_padding(c, out, co)
-        s = stats.sum(0).cpu().double()
-        assert not torch.isnan(s).any(), f"{_id(c)}: a stats row was not written"
-        s1, s2 = ref.sum((0, 2, 3, 4)), (ref * ref).sum((0, 2, 3, 4))
-        assert torch.allclose(s[0, :co], s1, rtol=1e-4, atol=1e-3 * s2.max().sqrt().item()), f"{_id(c)}: channel sums"
-        assert torch.allclose(s[1, :co], s2, rtol=1e-4), f"{_id(c)}: channel sums of squares"
+        got = check_first_fwd(c, out, stats, ref, co, ULP[dt] if lp else 1e-5)
+        if lp:      # the same template does the same float32 arithmetic: the stored output is the fp32 kernel's, rounded
+            o32 = from_cl(run("fp32")[0], co)
+            assert torch.equal(got, rnd(o32, dt)), where(c, got, rnd(o32, dt))
         return
-    ga = torch.randn(n, co, d, h, w, generator=gen(c, 3))
+    ga = rnd(torch.randn(n, co, d, h, w, generator=gen(c, 3)), dt)
     if c.op == "first_dgrad":
-        dx = ops.conv_first_bwd_data(to_cl(ga, 8, "fp32"), wt.cuda(), ci)
+        dx = ops.conv_first_bwd_data(first_grad(c, ga, dt), wt.cuda(), ci)
         torch.cuda.synchronize()
-        check(c, dx.cpu(), torch.nn.grad.conv3d_input(x.shape, wt.double(), ga.double(), 1, 1), 1e-5)
+        assert dx.shape == x.shape and dx.dtype == torch.float32
+        # the matrix-pipe route holds the weights as 16-bit fragments; the direct kernels read them as float32
+        pair = c.route.startswith("lp_conv_fwd_pair_kernel")
+        ref = torch.nn.grad.conv3d_input(x.shape, (rnd(wt, dt) if pair else wt).double(), ga.double(), 1, 1)
+        check(c, dx.cpu(), ref, 1e-5)
+        if lp and not pair:                                      # the fp32 instantiation on the same (rounded) gradient
+            dx32 = ops.conv_first_bwd_data(first_grad(c, ga, "fp32"), wt.cuda(), ci)
+            torch.cuda.synchronize()
+            assert torch.equal(dx.cpu(), dx32.cpu()), where(c, dx.cpu(), dx32.cpu())
         return
     ws = torch.empty(ops.conv_first_wgrad_ws((n, d, h, w), ci), device="cuda")
-    if c.op == "first_wgrad":
-        dw = ops.conv_first_wgrad(x.cuda(), to_cl(ga, 8, "fp32"), co, ws)
+    if c.op in ("first_wgrad", "first_wgrad_mfma"):
+        xr = x
+        if c.op == "first_wgrad_mfma":                           # the input enters the matrix pipe rounded to the storage type
+            from ctunet_amd import _lib
+            assert lp and _lib.load().ctu_lp_conv3d_wgrad_kernel_name(d, h, w, 3, 8, 8) == b"lp_wgrad8_kernel"
+            monkeypatch.setattr(ops, "FIRST_WGRAD_MFMA_MIN_VOX", 0)
+            xr = rnd(x, dt)
+        elif lp:                                                 # below the threshold: the direct kernel
+            assert n * d * h * w < ops.FIRST_WGRAD_MFMA_MIN_VOX
+        dw = ops.conv_first_wgrad(x.cuda(), first_grad(c, ga, dt), co, ws)
         torch.cuda.synchronize()
-        check_w(c, "dW", dw, torch.nn.grad.conv3d_weight(x.double(), wt.shape, ga.double(), 1, 1), 1e-4)
+        assert dw.shape == wt.shape
+        check_w(c, "dW", dw, torch.nn.grad.conv3d_weight(xr.double(), wt.shape, ga.double(), 1, 1), 1e-4)
         return
     y = torch.randn(n, co, d, h, w, generator=gen(c, 5)) * 0.9 - 0.1
     gamma, beta, vec = bn_setup(c, y, co, 8)
@@ -451,3 +513,38 @@ def test_first_layer(c):
         other[c.c0:c.c0 + 8] = False
         assert torch.all(gy.buf[..., other.cuda()] == SENT), f"{_id(c)}: channels outside the slice were written"
     check_w(c, "dW", dw, torch.nn.grad.conv3d_weight(x.double(), wt.shape, gy64, 1, 1), 1e-4)
+
+
+# ------------------------------------------------------------------ first layer: arguments the shipped classes do not use
+def test_first_layer_pair_data_gradient_with_three_input_channels():
+    """ctu_lp_conv3d_first_bwd_data_pair accepts C_in <= 4: with C_in = 3 and N = 2 every float32 plane of [2, 3, D, H, W]
+    is written at its own (n * C_in + c) index.  Reference and gate as for the pair route of test_first_layer."""
+    ops = _ops()
+    c = Case("lp_conv_fwd_pair_kernel<OUT32>", "first_dgrad", "bf16", 2, 3, 7, 6, 12, 40, 3, False, 16, 8)
+    g = gen(c)
+    wt = torch.randn(c.Co, c.Ci, 3, 3, 3, generator=g) * 0.3
+    ga = rnd(torch.randn(c.N, c.Co, c.D, c.H, c.W, generator=g), c.dtype)
+    dx = ops.conv_first_bwd_data(first_grad(c, ga, c.dtype), wt.cuda(), c.Ci)
+    torch.cuda.synchronize()
+    shape = (c.N, c.Ci, c.D, c.H, c.W)
+    assert tuple(dx.shape) == shape and dx.dtype == torch.float32
+    check(c, dx.cpu(), torch.nn.grad.conv3d_input(shape, rnd(wt, c.dtype).double(), ga.double(), 1, 1), 1e-5)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_first_layer_forward_with_a_bias(dt):
+    """The bias / nbias arguments of the first-layer forward, with C_out = 4: a whole quad of the 8 outputs is padding and
+    stays exactly zero, in the output and in the statistics, bias or not."""
+    ops = _ops()
+    c = Case("first_fwd_kernel", "first_fwd", dt, 1, 2, 4, 6, 10, 40, 3, False, 16, 8)
+    n, ci, co, d, h, w = c.N, c.Ci, c.Co, c.D, c.H, c.W
+    g = gen(c)
+    x = torch.randn(n, ci, d, h, w, generator=g)
+    wt = torch.randn(co, ci, 3, 3, 3, generator=g) * 0.3
+    bias = torch.randn(co, generator=g)
+    out = first_buffer(c, dt, n, d, h, w)
+    stats = torch.full((ops.conv_first_num_blocks((n, d, h, w)), 2, 8), float("nan"), device="cuda")
+    ops.conv_first_fwd(x.cuda(), wt.cuda(), bias.cuda(), out, stats)
+    torch.cuda.synchronize()
+    ref = F.conv3d(x.double(), wt.double(), bias.double(), 1, 1)
+    check_first_fwd(c, out, stats, ref, co, 1e-5 if dt == "fp32" else ULP[dt])
