@@ -198,6 +198,15 @@ class UNetEngine:
                 self._pack_cache[key] = (ver, ent[1], ent[2])
         ops.pack_batch(jobs, self.dtype)
 
+    def invalidate_packs(self) -> None:
+        """Forget which weights every packed copy was made from: the next forward re-packs all of them, into the same
+        buffers (a captured graph keeps reading the pointers it recorded).  For writes the version key cannot see --
+        ``p.data.mul_()``, ``p.data.copy_()`` leave ``p._version`` and ``p.data_ptr()`` as they were."""
+        for key, ent in self._pack_cache.items():
+            self._pack_cache[key] = (None,) + tuple(ent[1:])
+        for prefix, hit in self._up_cache.items():
+            self._up_cache[prefix] = (None,) + tuple(hit[1:])
+
     # ------------------------------------------------------------------ forward pieces
     def _fwd_tail(self, P, bn: str, c: int, nvox: int, n_upd: int, vec4: torch.Tensor, device):
         counter = self._counter(bn, "fwd", device)
@@ -705,6 +714,7 @@ class _UNetFn(torch.autograd.Function):
         fctx.engine, fctx.module, fctx.names, fctx.ctx = engine, module, names, ctx
         fctx.two = out1 is not None
         fctx.x_req = x_req
+        fctx.versions = _versions(P, names)
         if out1 is None:
             return out0
         return out0, out1
@@ -721,6 +731,12 @@ class _UNetFn(torch.autograd.Function):
         if fctx.two and g1 is None:
             g1 = torch.zeros_like(g0)
         P = _tensor_dict(fctx.module)
+        # backward packs its data-gradient weights from the module's CURRENT parameters: like torch's saved-tensor check,
+        # refuse a parameter written (or re-seated) since the forward instead of differentiating through other weights
+        for nm, then, now in zip(fctx.names, fctx.versions, _versions(P, fctx.names)):
+            if then != now:
+                raise RuntimeError(f"ctunet_amd: parameter {nm} needed for gradient computation has been modified since the "
+                                   f"forward pass (version {then[0]} then, {now[0]} now): run backward before changing weights")
         from .parallel import make_sync
         with torch.no_grad():
             grads, dx = fctx.engine.backward(P, ctx, g0, g1, fctx.x_req, make_sync(fctx.module))
@@ -734,6 +750,10 @@ def _out_shape(ctx, fctx, idx):
     n, d, h, w = ctx["dims"]
     c = 2 if fctx.two else fctx.engine.plan.out_ch
     return (n, c, d, h, w)
+
+
+def _versions(P: Dict[str, torch.Tensor], names) -> Tuple[Tuple[int, int], ...]:
+    return tuple((P[nm]._version, P[nm].data_ptr()) for nm in names)
 
 
 def _tensor_dict(module) -> Dict[str, torch.Tensor]:

@@ -126,6 +126,26 @@ class _HipNet(nn.Module):
         eng.scaler = self.loss_scaler         # (the model owns the dynamic state: an engine rebuild keeps it)
         return eng
 
+    def __getstate__(self):
+        """``copy.deepcopy`` and pickling (``torch.save(model)``) leave the engine behind: it holds only device buffers
+        derived from the parameters (packed weight copies keyed by the ORIGINAL's tensors), and the copy builds its own at
+        its first forward.  Precision, static loss scale and the dynamic loss-scaler state go along."""
+        state = self.__dict__.copy()
+        state.pop("_eng", None)
+        return state
+
+    def invalidate_packed_weights(self):
+        """Call after writing parameters through ``.data`` in place (``p.data.mul_()``, ``p.data.copy_()`` -- the usual EMA
+        swap) or stepping a ``torch.optim`` optimizer built with ``fused=True``: such writes leave ``p._version`` and the
+        address unchanged, which is all the packed-weight caches look at, so the next forward would run on the old
+        MFMA-ordered copies.  Every other way of changing weights (``no_grad`` in-place ops, the other optimizers,
+        ``load_state_dict``, ``torch.nn.init``, re-seating ``p.data``) is noticed without it.  The next forward re-packs
+        everything into the same buffers.  Returns self."""
+        eng = self.__dict__.get("_eng")
+        if eng is not None:
+            eng.invalidate_packs()
+        return self
+
     def set_precision(self, dtype=torch.float32, loss_scale=None):
         """Storage type of the activations between the kernels: ``torch.float32`` (default: the reference's arithmetic,
         1e-4 parity), ``torch.bfloat16`` or ``torch.float16`` (BASELINE configs 4 / 5: 16-bit tensors in HBM,
