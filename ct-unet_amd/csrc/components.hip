@@ -29,6 +29,7 @@
 // Replaces: nothing in the reference; users would copy the label map to the host for scipy.ndimage.label.
 #include "common.h"
 #include "scan.h"
+#include "voxel_rows.h"
 
 namespace {
 
@@ -53,7 +54,7 @@ struct CcArgs {
     long long al[MAXAL];
 };
 
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
+using ctu_vox::i64x2;
 
 __device__ __forceinline__ long long fg_code(long long v, const CcArgs& a) {
     if (v == 0) return 0;
@@ -634,8 +635,9 @@ __global__ void __launch_bounds__(FB) fh_complement_kernel(const T* __restrict__
     long long c[16];
     load8(src, nv < VPT ? nv : VPT, c);
     load8(src + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
+    const ctu_vox::Foreground fg{has_label, label};
 #pragma unroll
-    for (int u = 0; u < 16; ++u) c[u] = (has_label ? c[u] == label : c[u] != 0) ? 0 : 1;
+    for (int u = 0; u < 16; ++u) c[u] = fg(c[u]) ? 0 : 1;
     store8(dst, nv < VPT ? nv : VPT, c);
     store8(dst + VPT, nv > VPT ? nv - VPT : 0, c + VPT);
 }

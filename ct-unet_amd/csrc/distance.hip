@@ -3,10 +3,10 @@
 // scipy.ndimage.distance_transform_edt).
 //
 // The sites are the background voxels (invert: the foreground voxels); every voxel gets the distance to its nearest site.
-//   1. x pass:  one wave per image row reads the map (16 x-consecutive voxels per lane, 16-byte loads where aligned), tests
-//               the foreground there (nonzero or == label), and writes the 1-D squared distance to the nearest site of the
-//               row from per-lane 16-bit masks and two wave scans; with indices, the nearest site's x as int16.  The signed
-//               map needs both transforms: the x pass writes both planes from the one membership mask it has read.
+//   1. x pass:  one wave per image row reads the foreground (nonzero or == label) of the map as one 16-bit mask per lane
+//               (mask16 of voxel_rows.h) and writes the 1-D squared distance to the nearest site of the row (row_nearest of
+//               edt_line.h); with indices, the nearest site's x as int16.  The signed map needs both transforms: the x pass
+//               writes both planes from the one membership mask it has read.
 //   2. y, z:    one lane per line, lanes at consecutive x (coalesced), the lower envelope of edt_line.h with its stack in
 //               LDS, in place; with indices, the chosen y / z as int16.
 //   3. finish:  the virtual border, sqrt, sign, threshold and the index gather iz = zsel[v], iy = ysel[iz, y, x],
@@ -29,13 +29,12 @@
 namespace {
 
 using namespace ctu_edt;
+using namespace ctu_vox;
 
 constexpr int XB = 256;                 // x pass block: 4 waves, one row per wave
 constexpr int FB = 256;                 // finish block
 constexpr int MAXG = 64;                // items per launch with a spacing table in the kernel arguments
 constexpr int MAXU = 32768;             // items per launch at unit spacing (grid.y)
-constexpr int MAX_SIDE = 1024;
-constexpr int NONE_POS = 1 << 20;
 constexpr int KIND_DIST = CTU_DIST_EDT, KIND_SQ = CTU_DIST_SQUARED, KIND_SIGNED = CTU_DIST_SIGNED, KIND_BALL = CTU_DIST_BALL;
 
 struct DArgs {
@@ -49,39 +48,6 @@ struct DArgs {
     float r2;
     float sp[MAXG][3];                  // (z, y, x) spacing of each item of the launch (read at non-unit spacing only)
 };
-
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool is_fg(long long v, int has_label, long long label) { return has_label ? v == label : v != 0; }
-
-// bit u: voxel p[u] is foreground (u < nv <= 16; the rest 0)
-__device__ __forceinline__ uint32_t fg_bits16(const uint8_t* p, int nv, int has_label, long long label) {
-    uint32_t b = 0;
-    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) b |= (uint32_t)is_fg((w[j] >> (8 * u)) & 0xff, has_label, label) << (4 * j + u);
-    } else {
-        for (int u = 0; u < nv; ++u) b |= (uint32_t)is_fg(p[u], has_label, label) << u;
-    }
-    return b;
-}
-__device__ __forceinline__ uint32_t fg_bits16(const long long* p, int nv, int has_label, long long label) {
-    uint32_t b = 0;
-    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const i64x2 q = reinterpret_cast<const i64x2*>(p)[j];
-            b |= (uint32_t)is_fg(q.x, has_label, label) << (2 * j) | (uint32_t)is_fg(q.y, has_label, label) << (2 * j + 1);
-        }
-    } else {
-        for (int u = 0; u < nv; ++u) b |= (uint32_t)is_fg(p[u], has_label, label) << u;
-    }
-    return b;
-}
 
 // ------------------------------------------------------------------------------------------------ 1. x pass
 template <bool FLT, bool TRACK>
@@ -101,73 +67,22 @@ __global__ void __launch_bounds__(XB) dist_x_kernel(DArgs a, void* __restrict__ 
     const int nrows = D * H;
     const int nwaves = gridDim.x * (XB / 64);
     const int nsides = a.both ? 2 : 1;
+    const Foreground fg{a.has_label, a.label};
     for (int r = blockIdx.x * (XB / 64) + (threadIdx.x >> 6); r < nrows; r += nwaves) {    // wave-uniform
         const int64_t vrow = item + (int64_t)r * W + x0;
         uint32_t m = 0;
         if (nv) {
-            m = a.dtype == CTU_U8 ? fg_bits16((const uint8_t*)a.in + vrow, nv, a.has_label, a.label)
-                                  : fg_bits16((const long long*)a.in + vrow, nv, a.has_label, a.label);
+            m = a.dtype == CTU_U8 ? mask16((const uint8_t*)a.in + vrow, nv, fg) : mask16((const long long*)a.in + vrow, nv, fg);
         }
         for (int s = 0; s < nsides; ++s) {
             const int inv = a.both ? s : a.invert;
             const uint32_t es = inv ? m : (~m & valid);            // the sites of this lane's voxels
-            // nearest site at or left of each voxel: exclusive prefix max over lanes of the lane's last site
-            int last = es ? x0 + 31 - __clz(es) : -1;
-            int first = es ? x0 + __ffs(es) - 1 : NONE_POS;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int tl = __shfl_up(last, o), tf = __shfl_down(first, o);
-                if (lane >= o) last = max(last, tl);
-                if (lane + o < 64) first = min(first, tf);
-            }
-            int prev_last = __shfl_up(last, 1), next_first = __shfl_down(first, 1);
-            if (lane == 0) prev_last = -1;
-            if (lane == 63) next_first = NONE_POS;
+            T val[16];
+            int16_t pos[16];
+            row_nearest<FLT, TRACK>(es, x0, lane, sx2, val, pos);
             if (nv) {
-                T val[16];
-                int16_t pos[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    const int x = x0 + u;
-                    const uint32_t le = es & ((2u << u) - 1u), re = es >> u;
-                    const int lp = le ? x0 + 31 - __clz(le) : prev_last;
-                    const int rp = re ? x + __ffs(re) - 1 : next_first;
-                    int dmin = NONE_POS, at = -1;
-                    if (lp >= 0) { dmin = x - lp; at = lp; }
-                    if (rp < NONE_POS && rp - x < dmin) { dmin = rp - x; at = rp; }
-                    if (dmin == NONE_POS) val[u] = dist_inf<FLT>();
-                    else if (FLT) val[u] = (T)(sx2 * (float)(dmin * dmin));
-                    else val[u] = (T)(dmin * dmin);
-                    pos[u] = (int16_t)at;
-                }
-                T* dp = (T*)(s ? p1 : p0) + vrow;
-                if (nv == 16 && ((uintptr_t)dp & 15) == 0) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        uint4 w;
-                        w.x = __builtin_bit_cast(uint32_t, val[4 * j]); w.y = __builtin_bit_cast(uint32_t, val[4 * j + 1]);
-                        w.z = __builtin_bit_cast(uint32_t, val[4 * j + 2]); w.w = __builtin_bit_cast(uint32_t, val[4 * j + 3]);
-                        reinterpret_cast<uint4*>(dp)[j] = w;
-                    }
-                } else {
-                    for (int u = 0; u < nv; ++u) dp[u] = val[u];
-                }
-                if (TRACK) {
-                    int16_t* sp = xsel + vrow;
-                    if (nv == 16 && ((uintptr_t)sp & 15) == 0) {
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            uint4 w;
-                            w.x = (uint16_t)pos[8 * j] | (uint32_t)(uint16_t)pos[8 * j + 1] << 16;
-                            w.y = (uint16_t)pos[8 * j + 2] | (uint32_t)(uint16_t)pos[8 * j + 3] << 16;
-                            w.z = (uint16_t)pos[8 * j + 4] | (uint32_t)(uint16_t)pos[8 * j + 5] << 16;
-                            w.w = (uint16_t)pos[8 * j + 6] | (uint32_t)(uint16_t)pos[8 * j + 7] << 16;
-                            reinterpret_cast<uint4*>(sp)[j] = w;
-                        }
-                    } else {
-                        for (int u = 0; u < nv; ++u) sp[u] = pos[u];
-                    }
-                }
+                store16((T*)(s ? p1 : p0) + vrow, nv, val);
+                if (TRACK) store16(xsel + vrow, nv, pos);
             }
         }
     }
@@ -224,30 +139,20 @@ __global__ void __launch_bounds__(FB) dist_finish_kernel(DArgs a, const uint32_t
     const int nv = (int)min((int64_t)VPT, V - v0);
     const int64_t base = (int64_t)n * V + v0;
     uint32_t k0[VPT], k1[VPT];
-    const uint32_t* s0 = src0 + base;
-    if (nv == VPT && ((uintptr_t)s0 & 15) == 0) {
-#pragma unroll
-        for (int j = 0; j < VPT / 4; ++j) {
-            const uint4 w = reinterpret_cast<const uint4*>(s0)[j];
-            k0[4 * j] = w.x; k0[4 * j + 1] = w.y; k0[4 * j + 2] = w.z; k0[4 * j + 3] = w.w;
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < VPT; ++u) k0[u] = u < nv ? s0[u] : 0u;
-    }
-    if (KIND == KIND_SIGNED) {
-        const uint32_t* s1 = src1 + base;
-        if (nv == VPT && ((uintptr_t)s1 & 15) == 0) {
+    auto load = [&](const uint32_t* sp, uint32_t* k) {
+        if (nv == VPT && ((uintptr_t)sp & 15) == 0) {
 #pragma unroll
             for (int j = 0; j < VPT / 4; ++j) {
-                const uint4 w = reinterpret_cast<const uint4*>(s1)[j];
-                k1[4 * j] = w.x; k1[4 * j + 1] = w.y; k1[4 * j + 2] = w.z; k1[4 * j + 3] = w.w;
+                const uint4 w = reinterpret_cast<const uint4*>(sp)[j];
+                k[4 * j] = w.x; k[4 * j + 1] = w.y; k[4 * j + 2] = w.z; k[4 * j + 3] = w.w;
             }
         } else {
 #pragma unroll
-            for (int u = 0; u < VPT; ++u) k1[u] = u < nv ? s1[u] : 0u;
+            for (int u = 0; u < VPT; ++u) k[u] = u < nv ? sp[u] : 0u;
         }
-    }
+    };
+    load(src0 + base, k0);
+    if (KIND == KIND_SIGNED) load(src1 + base, k1);
     // coordinates of the first voxel; the others follow by carrying
     int x = (int)(v0 % W);
     const int64_t row = v0 / W;
@@ -293,17 +198,7 @@ __global__ void __launch_bounds__(FB) dist_finish_kernel(DArgs a, const uint32_t
         if (++x == W) { x = 0; if (++y == H) { y = 0; ++z; } }
     }
     if (KIND == KIND_BALL) {
-        uint8_t* op = (uint8_t*)out + base;
-        if (nv == VPT && ((uintptr_t)op & 15) == 0) {
-            uint4 o;                                              // 4 bits -> 4 bytes of 0 / 1 (morphology.hip's unpack)
-            o.x = ((ballbits & 0xf) * 0x00204081u) & 0x01010101u;
-            o.y = (((ballbits >> 4) & 0xf) * 0x00204081u) & 0x01010101u;
-            o.z = (((ballbits >> 8) & 0xf) * 0x00204081u) & 0x01010101u;
-            o.w = (((ballbits >> 12) & 0xf) * 0x00204081u) & 0x01010101u;
-            *reinterpret_cast<uint4*>(op) = o;
-        } else {
-            for (int u = 0; u < nv; ++u) op[u] = (ballbits >> u) & 1;
-        }
+        store_mask16((uint8_t*)out + base, nv, ballbits);
     } else {
         uint32_t* op = (uint32_t*)out + base;
         if (nv == VPT && ((uintptr_t)op & 15) == 0) {
@@ -351,9 +246,7 @@ Layout layout(int N, int D, int H, int W, int kind, int want_indices) {
     return l;
 }
 
-bool shape_ok(int N, int D, int H, int W) {
-    return geometry_ok(N, D, H, W) && D <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE;
-}
+bool shape_ok(int N, int D, int H, int W) { return geometry_ok(N, D, H, W) && sides_ok(D, H, W); }
 
 template <bool FLT, int KIND>
 int launch_finish(const DArgs& a, int np, const uint32_t* s0, const uint32_t* s1, void* out, const int16_t* xs,
@@ -415,7 +308,7 @@ extern "C" int ctu_distance_transform(const void* in, int dtype, int N, int D, i
     CTU_REQUIRE(dtype == CTU_U8 || dtype == CTU_I64, "distance_transform: unsupported dtype %d (uint8 or int64)", dtype);
     CTU_REQUIRE(geometry_ok(N, D, H, W), "distance_transform: bad shape N=%d D=%d H=%d W=%d (every side >= 1, D*H*W < 2^31)",
                 N, D, H, W);
-    CTU_REQUIRE(D <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE, "distance_transform: volume side above %d (shape %d %d %d)",
+    CTU_REQUIRE(sides_ok(D, H, W), "distance_transform: volume side above %d (shape %d %d %d)",
                 MAX_SIDE, D, H, W);
     CTU_REQUIRE(out_kind >= KIND_DIST && out_kind <= KIND_BALL, "distance_transform: unknown out_kind %d", out_kind);
     CTU_REQUIRE(!indices || ((out_kind == KIND_DIST || out_kind == KIND_SQ) && !border_background),

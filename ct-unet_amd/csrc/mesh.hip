@@ -4,10 +4,10 @@
 // A CELL ROW is the W+1 cells of one (cz, cy) of the padded grid; rows in C order are the blocks of the numbering, so
 // "cells in C order" is "rows in order, then x".  The workspace keeps the rows at a stride of WCP = W+1 rounded up to 16
 // cells (the pad cells hold code 0), so every lane's 16 cells are 16-byte aligned in every per-cell array.
-//   1. count   one wave per cell row, a lane owns 16 cells along x per step: it loads the 16 voxels of each of the row's four
-//              voxel rows (one 16-byte load per 16 / sizeof(T) voxels when the rows are aligned, voxel by voxel with
-//              bounds otherwise), turns them into 16 inside bits per voxel row, gets the 17th (the voxel left of its first)
-//              from the lane below, and forms each cell's 8-bit inside code (bit dz*4 + dy*2 + dx).  Per cell it writes the
+//   1. count   one wave per cell row, a lane owns 16 cells along x per step: it reads the 16 voxels of each of the row's four
+//              voxel rows as 16 inside bits per voxel row (mask16 of voxel_rows.h: 16-byte loads where the 16 voxels are
+//              aligned, voxel by voxel otherwise), gets the 17th (the voxel left of its first) from the lane below, and
+//              forms each cell's 8-bit inside code (bit dz*4 + dy*2 + dx).  Per cell it writes the
 //              code (1 byte; the 7-bit crossing mask of the owned edges is a function of it, edge_mask()) and the packed
 //              exclusive prefix of (vertices, triangles) within the row (uint32: low 16 / high 16 bits; a row has at most
 //              7 * 1025 vertices and 12 * 1025 triangles), from a wave scan of the lanes' sums.  Per row: the packed total.
@@ -25,10 +25,13 @@
 // No reference counterpart: the reference writes NIfTI volumes only.
 #include "common.h"
 #include "scan.h"
+#include "voxel_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using ctu_vox::MAX_SIDE;
 
 constexpr int CB = 256;                         // count block: CB / 64 cell rows
 constexpr int VPT = 16;                         // cells of a lane per step (and of a thread of the emit kernels)
@@ -36,7 +39,6 @@ constexpr int SB = CTU_MESH_SCAN_BLOCK;         // scan block
 constexpr int EB = 256;                         // emit block
 constexpr int MB = 256;                         // measure block
 constexpr int MAX_MB = CTU_MESH_MEASURE_WS / 16;  // measure blocks: two doubles each
-constexpr int MAX_SIDE = 1024;
 
 // owned edge slot k -> the cell corner (dz*4 + dy*2 + dx) at its far end, and back
 constexpr int SLOT_CORNER[7] = {1, 2, 4, 3, 5, 6, 7};
@@ -160,36 +162,11 @@ Layout layout(int D, int H, int W) {
 }
 
 bool shape_ok(int D, int H, int W) {
-    return D > 0 && H > 0 && W > 0 && D <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE &&
-           (int64_t)(D + 1) * (H + 1) * (W + 1) < ((int64_t)1 << 31);
-}
-
-template <class T> __device__ __forceinline__ bool inside_of(T v, const MeshArgs& a) {
-    return a.has_label ? (long long)v == a.label : v != 0;
-}
-template <> __device__ __forceinline__ bool inside_of<float>(float v, const MeshArgs& a) { return v > a.level; }
-
-// inside bits of voxels x0 .. x0+15 of one voxel row (bit i for x0 + i; 0 outside the row)
-template <class T, bool ALIGNED>
-__device__ __forceinline__ uint32_t row_bits(const T* __restrict__ row, int x0, const MeshArgs& a) {
-    constexpr int PER = 16 / (int)sizeof(T);    // voxels of one 16-byte load
-    uint32_t b = 0;
-    if (ALIGNED && x0 + VPT <= a.W) {
-#pragma unroll
-        for (int q = 0; q < VPT / PER; ++q) {
-            struct alignas(16) Pack { T v[PER]; };
-            const Pack pk = *reinterpret_cast<const Pack*>(row + x0 + q * PER);
-#pragma unroll
-            for (int u = 0; u < PER; ++u) b |= (uint32_t)inside_of<T>(pk.v[u], a) << (q * PER + u);
-        }
-    } else {
-        for (int i = 0; i < VPT && x0 + i < a.W; ++i) b |= (uint32_t)inside_of<T>(row[x0 + i], a) << i;
-    }
-    return b;
+    return ctu_vox::sides_ok(D, H, W) && (int64_t)(D + 1) * (H + 1) * (W + 1) < ((int64_t)1 << 31);
 }
 
 // ------------------------------------------------------------------------------------------------ 1. count
-template <class T, bool ALIGNED>
+template <class T>
 __global__ void __launch_bounds__(CB) mesh_count_kernel(MeshArgs a, const T* __restrict__ vol) {
     __shared__ uint8_t ntri[256];
     ntri[threadIdx.x] = TAB.ntri[threadIdx.x];
@@ -205,6 +182,7 @@ __global__ void __launch_bounds__(CB) mesh_count_kernel(MeshArgs a, const T* __r
         const int z = cz - 1 + (r >> 1), y = cy - 1 + (r & 1);
         vrow[r] = (z >= 0 && z < a.D && y >= 0 && y < a.H) ? vol + ((int64_t)z * a.H + y) * a.W : nullptr;
     }
+    const ctu_vox::Inside inside{{a.has_label, a.label}, a.level};
     uint32_t carry[4] = {0, 0, 0, 0};                              // bit of the voxel left of lane 0's first
     uint32_t run = 0;                                              // packed (vertices, triangles) of the cells so far
     uint8_t* crow = a.code + (int64_t)row * a.Wcp;
@@ -214,7 +192,8 @@ __global__ void __launch_bounds__(CB) mesh_count_kernel(MeshArgs a, const T* __r
         uint32_t ext[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint32_t b = (vrow[r] && x0 < a.W) ? row_bits<T, ALIGNED>(vrow[r], x0, a) : 0u;
+            // inside bits of voxels x0 .. x0+15 of the voxel row (bit i for x0 + i; 0 outside the row)
+            const uint32_t b = (vrow[r] && x0 < a.W) ? ctu_vox::mask16(vrow[r] + x0, min(a.W - x0, VPT), inside) : 0u;
             const uint32_t below = __shfl_up(b >> (VPT - 1), 1);
             ext[r] = b << 1 | (lane ? below : carry[r]);
             carry[r] = __shfl(b >> (VPT - 1), 63);
@@ -464,10 +443,7 @@ MeshArgs make_args(int D, int H, int W, void* ws) {
 template <class T>
 int launch_count(const MeshArgs& a, const void* vol, hipStream_t st) {
     const int grid = ceil_div(a.nrows, CB / 64);
-    if ((uintptr_t)vol % 16 == 0 && ((size_t)a.W * sizeof(T)) % 16 == 0)
-        mesh_count_kernel<T, true><<<grid, CB, 0, st>>>(a, (const T*)vol);
-    else
-        mesh_count_kernel<T, false><<<grid, CB, 0, st>>>(a, (const T*)vol);
+    mesh_count_kernel<T><<<grid, CB, 0, st>>>(a, (const T*)vol);
     CTU_CHECK_LAUNCH("mesh count");
     return CTU_OK;
 }

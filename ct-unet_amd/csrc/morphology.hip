@@ -21,11 +21,14 @@
 //
 // Replaces: erode / dilate / ErodeDilate of ctunet/pytorch/transforms.py:97-127,356-377 (SimpleITK on the host; its ball
 // convention is not pinned here, scipy.ndimage's 3x3x3 structures are).
-#include <type_traits>
-
 #include "common.h"
+#include "voxel_rows.h"
 
 namespace {
+
+using ctu_vox::Foreground;
+using ctu_vox::mask16;
+using ctu_vox::store_mask16;
 
 typedef unsigned long long u64;
 
@@ -42,41 +45,8 @@ constexpr int MODE_ERODE = CTU_MORPH_ERODE, MODE_OPEN = CTU_MORPH_OPEN, MODE_CLO
 constexpr int WS_MORPH = CTU_MORPH_WS_MORPH, WS_FILL = CTU_MORPH_WS_FILL, WS_IMPLANT = CTU_MORPH_WS_IMPLANT;
 constexpr uint32_t CODE_ALL = (1u << 27) - 1;
 
-struct None {};                                                // no second input
-
-// ------------------------------------------------------------------------------------------------ foreground bits
-// bit u of the result: voxel p[u] is foreground (u < nv <= 16; the rest 0)
-__device__ __forceinline__ bool is_fg(long long v, int has_label, long long label) { return has_label ? v == label : v != 0; }
-
-__device__ __forceinline__ uint32_t fg_bits16(const uint8_t* p, int nv, int has_label, long long label) {
-    uint32_t b = 0;
-    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) b |= (uint32_t)is_fg((w[j] >> (8 * u)) & 0xff, has_label, label) << (4 * j + u);
-    } else {
-        for (int u = 0; u < nv; ++u) b |= (uint32_t)is_fg(p[u], has_label, label) << u;
-    }
-    return b;
-}
-__device__ __forceinline__ uint32_t fg_bits16(const long long* p, int nv, int has_label, long long label) {
-    typedef long long i64x2 __attribute__((ext_vector_type(2)));
-    uint32_t b = 0;
-    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const i64x2 q = reinterpret_cast<const i64x2*>(p)[j];
-            b |= (uint32_t)is_fg(q.x, has_label, label) << (2 * j) | (uint32_t)is_fg(q.y, has_label, label) << (2 * j + 1);
-        }
-    } else {
-        for (int u = 0; u < nv; ++u) b |= (uint32_t)is_fg(p[u], has_label, label) << u;
-    }
-    return b;
-}
-__device__ __forceinline__ uint32_t fg_bits16(const None*, int, int, long long) { return 0; }
+struct None {};                                                // no second input: no voxel of it is set
+template <class Pred> __device__ __forceinline__ uint32_t mask16(const None*, int, Pred) { return 0; }
 
 // ------------------------------------------------------------------------------------------------ 1. pack
 // thread (row, q): voxels x = 16 q .. 16 q + 15 of one row; lanes 4 j .. 4 j + 3 share word q / 4
@@ -95,8 +65,8 @@ __global__ void __launch_bounds__(SB) morph_pack_kernel(const TA* __restrict__ a
     uint32_t m = 0;
     if (nv) {
         const int64_t off = n * V + row * W + x0;
-        m = fg_bits16(a + off, nv, has_label, label);
-        if constexpr (!std::is_same<TB, None>::value) m &= ~fg_bits16(b + off, nv, 0, 0);
+        m = mask16(a + off, nv, Foreground{has_label, label});
+        m &= ~mask16(b + off, nv, Foreground{0, 0});
     }
     if (border && nv < 16) m |= (0xffffu << nv) & 0xffffu;      // padding bits carry the border value
     u64 w = (u64)m << (16 * (q & 3));
@@ -118,18 +88,7 @@ __global__ void __launch_bounds__(SB) morph_unpack_kernel(const u64* __restrict_
     const int nv = min(W - x0, 16);
     if (nv <= 0) return;
     const uint32_t m = (uint32_t)(bits[(n * rows + row) * WW + (q >> 2)] >> (16 * (q & 3))) & 0xffffu;
-    uint8_t* p = out + n * V + row * W + x0;
-    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-        // 4 bits -> 4 bytes of 0 / 1: bit i lands on bit 8 i, no two partial products share a position
-        uint4 o;
-        o.x = ((m & 0xf) * 0x00204081u) & 0x01010101u;
-        o.y = (((m >> 4) & 0xf) * 0x00204081u) & 0x01010101u;
-        o.z = (((m >> 8) & 0xf) * 0x00204081u) & 0x01010101u;
-        o.w = (((m >> 12) & 0xf) * 0x00204081u) & 0x01010101u;
-        *reinterpret_cast<uint4*>(p) = o;
-    } else {
-        for (int u = 0; u < nv; ++u) p[u] = (m >> u) & 1;
-    }
+    store_mask16(out + n * V + row * W + x0, nv, m);
 }
 
 // ------------------------------------------------------------------------------------------------ 2. steps

@@ -16,21 +16,24 @@
 //   5. final:   sqrt, interpolation, the empty-surface rules, the symmetric / directed combinations.
 // No host synchronisation, allocation or copy: the whole sequence can be captured into a graph.
 //
-// Replaces: nothing in the reference (its only distance metric is utilities.hausdorff, ctunet/utilities.py:62-70, kept
-//           as ctu_hausdorff); evaluation users would call monai / scipy on the CPU.
+// ctu_hausdorff, the metric of the inference tail, is a composition on top: argmax of the prediction into a
+// float label map (ctu_hard_segm), these metrics against the one-hot target, and the HD row copied out.
+//
+// Replaces: hausdorff (monai compute_hausdorff_distance on one_hot(argmax(pred)))  ctunet/utilities.py:62-70, the
+//           reference's only distance metric; for the others evaluation users would call monai / scipy on the CPU.
 #include "common.h"
 #include "edt_line.h"
 
 namespace {
 
-using namespace ctu_edt;             // INF_I, LINE_LDS, DistT, is_inf, dist_inf, line_lanes, edt_line
+using namespace ctu_edt;             // INF_I, LINE_LDS, DistT, is_inf, dist_inf, line_lanes, row_nearest, store16, edt_line
+using namespace ctu_vox;             // InClass, mask16, store_mask16, sides_ok, MAX_SIDE
 
 constexpr int EB = 256;                 // edge_x block: 4 waves, one row per wave
 constexpr int RT = 256;                 // reduce / histogram block
 constexpr int RB_MAX = 256;             // reduce blocks per directed plane
 constexpr int MAXG = 64;                // pairs per group (kernel-argument spacing table)
 constexpr int MAXC = 16;
-constexpr int NONE_POS = 1 << 20;
 
 struct Side {
     const void* p;
@@ -59,53 +62,12 @@ struct SelState {
     uint32_t k[2];
 };
 
-__device__ __forceinline__ uint32_t member_bit(uint8_t v, int c, int oh) { return oh ? (v != 0) : (v == c); }
-__device__ __forceinline__ uint32_t member_bit(float v, int c, int oh) { return oh ? (v != 0.f) : (v == (float)c); }
-__device__ __forceinline__ uint32_t member_bit(long long v, int c, int oh) { return oh ? (v != 0) : (v == c); }
-
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-// 16-bit membership mask of nv (<= 16) x-consecutive voxels starting at element `off` of side s
+// 16-bit membership mask of class c in nv (<= 16) x-consecutive voxels starting at element `off` of side s
 __device__ __forceinline__ uint32_t row_bits(const Side& s, int64_t off, int nv, int c) {
-    uint32_t bits = 0;
-    const int oh = s.onehot;
-    if (s.dtype == CTU_U8) {
-        const uint8_t* p = (const uint8_t*)s.p + off;
-        if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-            const uint4 v = *reinterpret_cast<const uint4*>(p);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) bits |= member_bit((uint8_t)(w[j] >> (8 * b)), c, oh) << (4 * j + b);
-        } else {
-            for (int u = 0; u < nv; ++u) bits |= member_bit(p[u], c, oh) << u;
-        }
-    } else if (s.dtype == CTU_F32) {
-        const float* p = (const float*)s.p + off;
-        if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 v = reinterpret_cast<const f32x4*>(p)[j];
-                bits |= (member_bit(v.x, c, oh) | member_bit(v.y, c, oh) << 1 | member_bit(v.z, c, oh) << 2 |
-                         member_bit(v.w, c, oh) << 3) << (4 * j);
-            }
-        } else {
-            for (int u = 0; u < nv; ++u) bits |= member_bit(p[u], c, oh) << u;
-        }
-    } else {
-        const long long* p = (const long long*)s.p + off;
-        if (nv == 16 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const i64x2 v = reinterpret_cast<const i64x2*>(p)[j];
-                bits |= (member_bit(v.x, c, oh) | member_bit(v.y, c, oh) << 1) << (2 * j);
-            }
-        } else {
-            for (int u = 0; u < nv; ++u) bits |= member_bit(p[u], c, oh) << u;
-        }
-    }
-    return bits;
+    const InClass in{s.onehot, c};
+    if (s.dtype == CTU_U8) return mask16((const uint8_t*)s.p + off, nv, in);
+    if (s.dtype == CTU_F32) return mask16((const float*)s.p + off, nv, in);
+    return mask16((const long long*)s.p + off, nv, in);
 }
 
 // ------------------------------------------------------------------------------------------------ 1. edges + x pass
@@ -156,55 +118,12 @@ __global__ void __launch_bounds__(EB) surf_edge_x_kernel(GroupArgs g, int64_t Vp
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const uint32_t es = e[s];
-            // nearest edge at or left of each voxel: exclusive prefix max over lanes of the lane's last edge
-            int last = es ? x0 + 31 - __clz(es) : -1;
-            int first = es ? x0 + __ffs(es) - 1 : NONE_POS;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int tl = __shfl_up(last, o), tf = __shfl_down(first, o);
-                if (lane >= o) last = max(last, tl);
-                if (lane + o < 64) first = min(first, tf);
-            }
-            int prev_last = __shfl_up(last, 1), next_first = __shfl_down(first, 1);
-            if (lane == 0) prev_last = -1;
-            if (lane == 63) next_first = NONE_POS;
-            if (!nv) continue;
-            const int plane = 2 * il + s;
             T val[16];
-            uint32_t eb[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int x = x0 + u;
-                const uint32_t le = es & ((2u << u) - 1u), re = es >> u;
-                const int lp = le ? x0 + 31 - __clz(le) : prev_last;
-                const int rp = re ? x + __ffs(re) - 1 : next_first;
-                int dmin = NONE_POS;
-                if (lp >= 0) dmin = x - lp;
-                if (rp < NONE_POS) dmin = min(dmin, rp - x);
-                if (dmin == NONE_POS) val[u] = dist_inf<FLT>();
-                else if (FLT) val[u] = (T)(sx2 * (float)(dmin * dmin));
-                else val[u] = (T)(dmin * dmin);
-                eb[u >> 2] |= ((es >> u) & 1u) << (8 * (u & 3));
-            }
-            const int64_t vo = (int64_t)plane * Vp + (int64_t)z * HW + (int64_t)y * W + x0;
-            T* dp = (T*)dist + vo;
-            uint8_t* ep = edges + vo;
-            if (nv == 16 && ((uintptr_t)dp & 15) == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint4 w;
-                    w.x = __builtin_bit_cast(uint32_t, val[4 * j]); w.y = __builtin_bit_cast(uint32_t, val[4 * j + 1]);
-                    w.z = __builtin_bit_cast(uint32_t, val[4 * j + 2]); w.w = __builtin_bit_cast(uint32_t, val[4 * j + 3]);
-                    reinterpret_cast<uint4*>(dp)[j] = w;
-                }
-            } else {
-                for (int u = 0; u < nv; ++u) dp[u] = val[u];
-            }
-            if (nv == 16 && ((uintptr_t)ep & 15) == 0) {
-                *reinterpret_cast<uint4*>(ep) = make_uint4(eb[0], eb[1], eb[2], eb[3]);
-            } else {
-                for (int u = 0; u < nv; ++u) ep[u] = (uint8_t)((es >> u) & 1u);
-            }
+            row_nearest<FLT, false>(es, x0, lane, sx2, val, nullptr);
+            if (!nv) continue;
+            const int64_t vo = (int64_t)(2 * il + s) * Vp + vrow;
+            store16((T*)dist + vo, nv, val);
+            store_mask16(edges + vo, nv, es);
         }
     }
 #pragma unroll
@@ -504,7 +423,7 @@ extern "C" int ctu_surface_metrics(const void* pred, int pred_dtype, int pred_on
     CTU_REQUIRE(pred && target && out && ws, "surface_metrics: null pointer");
     CTU_REQUIRE(dtype_ok(pred_dtype) && dtype_ok(target_dtype), "surface_metrics: unsupported dtype");
     CTU_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "surface_metrics: bad shape");
-    CTU_REQUIRE(D <= 1024 && H <= 1024 && W <= 1024, "surface_metrics: volume side above 1024");
+    CTU_REQUIRE(sides_ok(D, H, W), "surface_metrics: volume side above %d", MAX_SIDE);
     CTU_REQUIRE(Cs >= 1 && Cs <= MAXC && (cls0 == 0 || cls0 == 1) && cls0 + Cs <= C && C <= MAXC + 1,
                 "surface_metrics: bad classes C=%d cls0=%d Cs=%d", C, cls0, Cs);
     CTU_REQUIRE((int64_t)N * Cs <= (1 << 20), "surface_metrics: too many (item, class) pairs");
@@ -542,6 +461,39 @@ extern "C" int ctu_surface_metrics(const void* pred, int pred_dtype, int pred_on
         }
         const int rc = unit ? run_group<false>(g, lay, w, out, st) : run_group<true>(g, lay, w, out, st);
         if (rc != CTU_OK) return rc;
+    }
+    return CTU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ Hausdorff
+namespace {
+// workspace: the float label map of the prediction, the 8 rows of ctu_surface_metrics, its workspace
+size_t hd_seg_bytes(int N, int D, int H, int W) { return align256((size_t)N * D * H * W * sizeof(float)); }
+size_t hd_rows_bytes(int N, int C) { return align256((size_t)8 * N * (C - 1) * sizeof(float)); }
+}  // namespace
+
+extern "C" size_t ctu_hausdorff_ws_bytes(int N, int C, int D, int H, int W) {
+    if (N <= 0 || C < 2 || D <= 0 || H <= 0 || W <= 0) return 0;
+    return hd_seg_bytes(N, D, H, W) + hd_rows_bytes(N, C) + align256(ctu_surface_ws_bytes(N, C - 1, D, H, W));
+}
+
+extern "C" int ctu_hausdorff(const float* pred, const float* target, int N, int C, int D, int H, int W, float* out, void* ws,
+                             void* stream) {
+    CTU_REQUIRE(pred && target && out && ws, "hausdorff: null pointer");
+    CTU_REQUIRE(N > 0 && C >= 2 && C <= 8 && D > 0 && H > 0 && W > 0, "hausdorff: bad shape N=%d C=%d", N, C);
+    CTU_REQUIRE(sides_ok(D, H, W), "hausdorff: volume side above %d", MAX_SIDE);
+    CTU_REQUIRE(N * (C - 1) * 2 <= 65535, "hausdorff: too many (item, class) planes");
+    float* seg = (float*)ws;
+    float* rows = (float*)((uint8_t*)ws + hd_seg_bytes(N, D, H, W));
+    int rc = ctu_hard_segm(pred, N, C, (int64_t)D * H * W, seg, stream);
+    if (rc != CTU_OK) return rc;
+    rc = ctu_surface_metrics(seg, CTU_F32, 0, target, CTU_F32, 1, N, C, 1, C - 1, D, H, W, nullptr, nullptr, -1.0, rows,
+                             (uint8_t*)rows + hd_rows_bytes(N, C), stream);
+    if (rc != CTU_OK) return rc;
+    const size_t pairs = (size_t)N * (C - 1);                         // row 1 of the block: hd
+    if (hipMemcpyAsync(out, rows + pairs, pairs * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+        ctu_set_error("hausdorff: copy failed");
+        return CTU_ELAUNCH;
     }
     return CTU_OK;
 }

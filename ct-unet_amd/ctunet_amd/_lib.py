@@ -247,3 +247,25 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = load().ctu_last_error().decode("utf-8", "replace")
         raise CtuError(f"{what} failed (status {status}): {msg}")
+
+
+# ---- what every wrapper of a volume entry point (metrics, postprocess, mesh) does around its call
+def check_device(module: str, *tensors) -> None:
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{module}: inputs must live on the GPU; this path has no CPU fallback")
+
+
+def as_bytes(t):
+    """The contiguous tensor a kernel reads: bool viewed as uint8, every other dtype as it is."""
+    import torch
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def float_array(values):
+    """A host float array for a ``const float*`` argument (None stays None: the entry point's default)."""
+    if values is None:
+        return None
+    values = list(values)
+    return (C.c_float * len(values))(*values)

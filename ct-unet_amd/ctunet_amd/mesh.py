@@ -224,13 +224,10 @@ def extract_surface(volume: torch.Tensor, level: float = 0.5, spacing=None, orig
     if not volume.is_cuda:
         raise ValueError("mesh: volume must live on the GPU; this path has no CPU fallback")
     lib = _lib.load()
-    src = volume.contiguous()
-    if src.dtype == torch.bool:
-        src = src.view(torch.uint8)
+    src = _lib.as_bytes(volume)
     dt = CTU_F32 if field else (CTU_I64 if src.dtype == torch.int64 else CTU_U8)
     dev = volume.device
-    c_sp = None if sp is None else (ctypes.c_float * 3)(*sp)
-    c_org = None if org is None else (ctypes.c_float * 3)(*org)
+    c_sp, c_org = _lib.float_array(sp), _lib.float_array(org)
     ws = torch.empty(lib.ctu_mesh_ws_bytes(*shape), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
@@ -375,8 +372,7 @@ def smooth(m: Mesh, iterations: int = 10, lamb: float = 0.5, mu: Optional[float]
     src, off, nb = v.contiguous(), off.contiguous(), nb.contiguous()
     fx = None
     if fixed is not None:
-        fx = fixed.contiguous()
-        fx = fx.view(torch.uint8) if fx.dtype == torch.bool else fx
+        fx = _lib.as_bytes(fixed)
     out = torch.empty((V, 3), dtype=torch.float32, device=v.device)
     ws = torch.empty(lib.ctu_mesh_smooth_ws_bytes(V), dtype=torch.uint8, device=v.device)
     with torch.cuda.device(v.device):

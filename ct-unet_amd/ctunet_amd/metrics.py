@@ -7,8 +7,8 @@ metric is derived.  Results are float32 ``[N, C']`` device tensors, C' = the sco
 
 Definitions (the tests restate them on scipy in float64):
 
-- **Surface** of a mask: ``mask & ~binary_erosion(mask)``, 6-neighbourhood, background outside the volume (the surface
-  ``ctu_hausdorff`` uses).
+- **Surface** of a mask: ``mask & ~binary_erosion(mask)``, 6-neighbourhood, background outside the volume
+  (``ctu_hausdorff`` / ``ops.hausdorff`` is the HD row of the same kernels on ``argmax(pred)``).
 - **Directed distances** d(A->B): for each surface voxel of A, the Euclidean distance in physical units to the nearest
   surface voxel of B, i.e. ``scipy.ndimage.distance_transform_edt(~edges_B, sampling=spacing)`` at A's surface voxels.
   P = prediction, G = target.
@@ -107,12 +107,6 @@ def _dtype_code(t: torch.Tensor, allowed, what: str) -> int:
     return codes[t.dtype]
 
 
-def _check_device(*ts) -> None:
-    for t in ts:
-        if not t.is_cuda:
-            raise ValueError("metrics: inputs must live on the GPU; this path has no CPU fallback")
-
-
 def _check_sides(shape) -> None:
     if any(s <= 0 or s > MAX_SIDE for s in shape):
         raise ValueError(f"metrics: every side must lie in [1, {MAX_SIDE}], got {tuple(shape)}")
@@ -125,15 +119,8 @@ def _run(a: torch.Tensor, a_code: int, a_onehot: bool, b: torch.Tensor, b_code: 
     cs = c - cls0
     d, h, w = shape
     lib = _lib.load()
-    a, b = a.contiguous(), b.contiguous()
-    if a.dtype == torch.bool:
-        a = a.view(torch.uint8)
-    if b.dtype == torch.bool:
-        b = b.view(torch.uint8)
-    sp = None
-    if spacing is not None:
-        flat = [v for t in spacing for v in t]
-        sp = (ctypes.c_float * len(flat))(*flat)
+    a, b = _lib.as_bytes(a), _lib.as_bytes(b)
+    sp = None if spacing is None else _lib.float_array(v for t in spacing for v in t)
     tau_arr = (ctypes.c_double * cs)(*tau) if tau is not None else None
     ws = torch.empty(lib.ctu_surface_ws_bytes(n, cs, d, h, w), dtype=torch.uint8, device=a.device)
     out = torch.empty((8, n, cs), dtype=torch.float32, device=a.device)
@@ -169,7 +156,7 @@ def compute_hausdorff_distance(y_pred: torch.Tensor, y: torch.Tensor, include_ba
     pct = _check_percentile(percentile)
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     sp = parse_spacing(spacing, n)
-    _check_device(y_pred, y)
+    _lib.check_device("metrics", y_pred, y)
     out = _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, None, pct)
     if pct is None:
         return out[_HD_DIR if directed else _HD]
@@ -183,7 +170,7 @@ def compute_average_surface_distance(y_pred: torch.Tensor, y: torch.Tensor, incl
     _check_metric(distance_metric)
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     sp = parse_spacing(spacing, n)
-    _check_device(y_pred, y)
+    _lib.check_device("metrics", y_pred, y)
     out = _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, None, None)
     return out[_ASSD if symmetric else _ASD_DIR]
 
@@ -200,7 +187,7 @@ def compute_surface_dice(y_pred: torch.Tensor, y: torch.Tensor, class_thresholds
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     tau = _thresholds(class_thresholds, c - cls0, "class_thresholds")
     sp = parse_spacing(spacing, n)
-    _check_device(y_pred, y)
+    _lib.check_device("metrics", y_pred, y)
     return _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, tau, None)[_NSD]
 
 
@@ -231,7 +218,7 @@ def surface_metrics(pred_labels: torch.Tensor, target_labels: torch.Tensor, num_
     allowed = (torch.uint8, torch.int64)
     ca, cb = _dtype_code(pred_labels, allowed, "pred_labels"), _dtype_code(target_labels, allowed, "target_labels")
     sp = parse_spacing(spacing, n)
-    _check_device(pred_labels, target_labels)
+    _lib.check_device("metrics", pred_labels, target_labels)
     out = _run(pred_labels, ca, False, target_labels, cb, False, n, num_classes, cls0, shape, sp, tau, pct)
     res = {"dice": out[_DICE], "hd": out[_HD], "hd_p": out[_HDP], "assd": out[_ASSD]}
     if tau is not None:

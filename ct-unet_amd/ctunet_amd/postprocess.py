@@ -135,11 +135,6 @@ def _applied(applied_labels, dtype) -> Optional[list]:
     return [int(v) for v in vals]
 
 
-def _check_device(t: torch.Tensor) -> None:
-    if not t.is_cuda:
-        raise ValueError("postprocess: inputs must live on the GPU; this path has no CPU fallback")
-
-
 def _ws(lib, n, shape, device) -> torch.Tensor:
     return torch.empty(lib.ctu_components_ws_bytes(n, *shape), dtype=torch.uint8, device=device)
 
@@ -159,7 +154,7 @@ def label(mask: torch.Tensor, connectivity: int = 3) -> Tuple[torch.Tensor, torc
     """
     n, shape = _volume(mask, "mask", (torch.bool, torch.uint8))
     conn = _connectivity(connectivity)
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     lib = _lib.load()
     m = mask.contiguous()
     m = m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).view(torch.uint8)
@@ -174,7 +169,7 @@ def label(mask: torch.Tensor, connectivity: int = 3) -> Tuple[torch.Tensor, torc
 
 
 def _filter(labels: torch.Tensor, mode: int, param: int, applied, conn: int, n: int, shape) -> torch.Tensor:
-    _check_device(labels)
+    _lib.check_device("postprocess", labels)
     lib = _lib.load()
     src = labels.contiguous()
     out = torch.empty_like(src)
@@ -266,9 +261,7 @@ def _label_arg(label):
 
 def _as_bytes(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
     """The contiguous tensor the kernels read (bool viewed as uint8) and its dtype code."""
-    t = t.contiguous()
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
+    t = _lib.as_bytes(t)
     return t, (CTU_I64 if t.dtype == torch.int64 else CTU_U8)
 
 
@@ -286,7 +279,7 @@ def _morphology(mask, mode: int, structure, iterations, border_value, label) -> 
     it = _iterations(iterations)
     border = _border(border_value)
     has_label, lab = _label_arg(label)
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     lib = _lib.load()
     src, dt = _as_bytes(mask)
     out = _mask_out(mask)
@@ -326,7 +319,7 @@ def binary_fill_holes(mask: torch.Tensor, connectivity: int = 1, label: Optional
     n, shape = _volume(mask, "mask", _MASK_DTYPES)
     conn = _connectivity(connectivity)
     has_label, lab = _label_arg(label)
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     lib = _lib.load()
     src, dt = _as_bytes(mask)
     out = _mask_out(mask)
@@ -366,8 +359,7 @@ def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, ope
         _distance_sides(shape)
         r2 = _radius2(opening_radius, "opening_radius")
         spacing = _sampling(sampling, n)
-    _check_device(full_skull)
-    _check_device(defective_skull)
+    _lib.check_device("postprocess", full_skull, defective_skull)
     if full_skull.device != defective_skull.device:
         raise ValueError("postprocess: full_skull and defective_skull must live on the same GPU")
     if opening_radius is not None:
@@ -436,7 +428,6 @@ def _flag(v, what: str) -> bool:
 
 def _distance(mask, n, shape, kind: int, spacing, has_label: int, lab: int, invert: int, border: int, want_indices: bool,
               r2: float = -1.0):
-    import ctypes
     lib = _lib.load()
     src, dt = _as_bytes(mask)
     dev = mask.device
@@ -448,10 +439,7 @@ def _distance(mask, n, shape, kind: int, spacing, has_label: int, lab: int, inve
     idx = None
     if want_indices:
         idx = torch.empty(tuple(mask.shape[:-3]) + (3,) + tuple(shape), dtype=torch.int32, device=dev)
-    sp = None
-    if not unit:
-        flat = [v for t in spacing for v in t]
-        sp = (ctypes.c_float * len(flat))(*flat)
+    sp = None if unit else _lib.float_array(v for t in spacing for v in t)
     ws = torch.empty(lib.ctu_distance_ws_bytes(n, *shape, kind, int(want_indices)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
@@ -474,7 +462,7 @@ def distance_transform_edt(mask: torch.Tensor, sampling=None, return_distances: 
         _flag(squared, "squared")
     if not (want_d or want_i):
         raise ValueError("postprocess: at least one of return_distances and return_indices must be true")
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     out, idx = _distance(mask, n, shape, _DIST_SQUARED if sq else _DIST_EDT, sp, has_label, lab, 0, 0, want_i)
     if want_d and want_i:
         return out, idx
@@ -488,7 +476,7 @@ def signed_distance(mask: torch.Tensor, sampling=None, label: Optional[int] = No
     _distance_sides(shape)
     sp = _sampling(sampling, n)
     has_label, lab = _label_arg(label)
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     return _distance(mask, n, shape, _DIST_SIGNED, sp, has_label, lab, 0, 0, False)[0]
 
 
@@ -506,7 +494,7 @@ def _ball_op(mask, modes, radius, sampling, label) -> torch.Tensor:
     r2 = _radius2(radius)
     sp = _sampling(sampling, n)
     has_label, lab = _label_arg(label)
-    _check_device(mask)
+    _lib.check_device("postprocess", mask)
     out = _ball(mask, modes[0], r2, sp, has_label, lab)
     for mode in modes[1:]:
         out = _ball(out, mode, r2, sp)

@@ -423,16 +423,19 @@ int ctu_hard_dice_counts(const float* pred, const float* target, int N, int C, i
  * excluded, Euclidean, symmetric, no percentile): out[n][c-1], c = 1..C-1 = max over the surface voxels of either set of
  * the distance to the other set's surface; surface = mask & ~erode(mask) (6-neighbourhood, background outside the
  * volume); the distances come from an exact integer squared-distance transform.  NaN where either surface is empty (the
- * caller maps it, utilities.py:69).  pred / target [N,C,D,H,W]; ws: ctu_hausdorff_ws_bytes() bytes.  PARITY UNPINNED
- * (monai is not in the reference tree); tested against the same definition on scipy.ndimage. */
+ * caller maps it, utilities.py:69).  A composition: ctu_hard_segm(pred) into a float label map, ctu_surface_metrics of it
+ * against the one-hot target at unit spacing, the HD row copied to out; no host sync, capture-safe.  pred / target
+ * [N,C,D,H,W], C in 2..8, every side <= 1024, N*(C-1)*2 <= 65535; ws: ctu_hausdorff_ws_bytes() bytes (the label map, 4
+ * bytes per voxel per item, and ctu_surface_ws_bytes).  PARITY UNPINNED (monai is not in the reference tree); tested
+ * against the same definition on scipy.ndimage. */
 size_t ctu_hausdorff_ws_bytes(int N, int C, int D, int H, int W);
 int ctu_hausdorff(const float* pred, const float* target, int N, int C, int D, int H, int W, float* out, void* ws,
                   void* stream);
 
 /* Surface-distance metrics with voxel spacing (no reference counterpart: ctunet/utilities.py:62-70 has only the voxel-unit
- * maximum kept above; definitions pinned in ctunet_amd/metrics.py).  One (item n, class c) pair per scored class
- * c = cls0 .. cls0+Cs-1 of each item; per side the mask is p[n][c] != 0 for a one-hot tensor [N,C,D,H,W] (onehot = 1) or
- * p[n] == c for a label map [N,D,H,W] (onehot = 0); dtype CTU_U8, CTU_I64 or CTU_F32 per side.
+ * maximum, ctu_hausdorff above, which is one row of these; definitions pinned in ctunet_amd/metrics.py).  One (item n,
+ * class c) pair per scored class c = cls0 .. cls0+Cs-1 of each item; per side the mask is p[n][c] != 0 for a one-hot tensor
+ * [N,C,D,H,W] (onehot = 1) or p[n] == c for a label map [N,D,H,W] (onehot = 0); dtype CTU_U8, CTU_I64 or CTU_F32 per side.
  * spacing: HOST float [N][3] (z, y, x spacing of each item; NULL = unit: exact int32 squared distances), tau: HOST double
  * [Cs] surface-Dice tolerances (NULL: no NSD), percentile in [0, 100] (< 0: none).  out: DEVICE float [8][N*Cs], row r of
  * pair n*Cs + (c-cls0): 0 hard Dice, 1 HD, 2 directed HD (P->G), 3 HD_p, 4 directed HD_p, 5 ASSD (symmetric),

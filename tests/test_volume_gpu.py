@@ -137,3 +137,47 @@ def test_hausdorff_at_patch_size_is_deterministic_and_bounded():
     b = ops.hausdorff(full.unsqueeze(0), flap.unsqueeze(0))
     assert torch.equal(a, b) and 0 < float(a) <= 128 * 3 ** 0.5
     assert float(ops.hausdorff(flap.unsqueeze(0), flap.unsqueeze(0))) == 0.0
+
+
+def _many_pairs_case():
+    """N = 10, C = 8, 6 x 5 x 17: 70 (item, class) pairs, more than one group of 64 pairs in surface.hip.  Runs of labels along
+    x; class 3 never wins the argmax of the prediction, class 5 never occurs in the target."""
+    n, c, shape = 10, 8, (6, 5, 17)
+    g = gen(23)
+    runs = lambda: torch.randint(0, c, (n,) + shape[:2] + (6,), generator=g).repeat_interleave(3, 3)[..., :shape[2]]
+    pl, tl = runs(), runs()
+    tl[tl == 5] = 0
+    pred = 0.05 * torch.rand((n, c) + shape, generator=g) + torch.nn.functional.one_hot(pl, c).movedim(-1, 1).float()
+    pred[:, 3] = -1.0
+    target = torch.nn.functional.one_hot(tl, c).movedim(-1, 1).float().contiguous()
+    return pred, target
+
+
+def test_hausdorff_many_pairs_and_absent_classes():
+    from ctunet_amd import ops
+    pred, target = _many_pairs_case()
+    ref = _hd_scipy(pred, target)
+    absent = np.zeros(ref.shape, bool)
+    absent[:, [3 - 1, 5 - 1]] = True
+    assert np.isnan(ref[absent]).all() and np.isfinite(ref[~absent]).all() and ref.shape == (10, 7)
+    got = ops.hausdorff(pred.cuda(), target.cuda()).cpu().double().numpy()
+    assert np.isnan(got[absent]).all()
+    assert np.allclose(got, ref, rtol=1e-6, atol=0, equal_nan=True)
+
+
+@pytest.mark.parametrize("shape,message", [((1, 9, 2, 2, 2), "hausdorff: bad shape N=1 C=9"),
+                                           ((1, 2, 1, 1, 1025), "hausdorff: volume side above 1024")])
+def test_hausdorff_refuses_what_it_cannot_run(shape, message):
+    """C = 9 and a side of 1025 come back with a negative status before anything is launched: the output and the workspace
+    (which the first kernel of a call would write) keep their fill."""
+    from ctunet_amd import _lib
+    lib = _lib.load()
+    n, c, d, h, w = shape
+    pred, target = torch.zeros(shape).cuda(), torch.zeros(shape).cuda()
+    out = torch.full((n, c - 1), 7.0).cuda()
+    ws = torch.full((max(int(lib.ctu_hausdorff_ws_bytes(n, c, d, h, w)), 4096),), 0x5A, dtype=torch.uint8).cuda()
+    rc = lib.ctu_hausdorff(pred.data_ptr(), target.data_ptr(), n, c, d, h, w, out.data_ptr(), ws.data_ptr(),
+                           torch.cuda.current_stream().cuda_stream)
+    assert rc < 0 and lib.ctu_last_error().decode() == message
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((ws == 0x5A).all())
