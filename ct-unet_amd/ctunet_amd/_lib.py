@@ -139,6 +139,8 @@ SIGNATURES = {
     "ctu_mesh_adjacency_emit": (I, [L, L, L, P, P, P, P]),
     "ctu_mesh_smooth_ws_bytes": (Z, [L]),
     "ctu_mesh_smooth": (I, [P, L, P, P, L, P, I, F, I, F, P, P, P]),
+    "ctu_mesh_voxelize_ws_bytes": (Z, [I, I, I]),
+    "ctu_mesh_voxelize": (I, [P, L, P, L, I, I, I, P, P, I, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

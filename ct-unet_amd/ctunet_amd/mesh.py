@@ -1,11 +1,16 @@
-"""Surface meshes of label volumes and scalar fields on the GPU, their smoothing, and their export as binary STL: the last
-step of the segmentation-to-implant pipeline (``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of
-``csrc/mesh.hip``, ``ctu_mesh_adjacency_*`` / ``ctu_mesh_smooth`` of ``csrc/mesh_smooth.hip``); no CPU fallback.
+"""Surface meshes of label volumes and scalar fields on the GPU, their smoothing, their voxelisation back onto a grid, and
+their export and import as binary STL: the last step of the segmentation-to-implant pipeline and the way back from it
+(``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of ``csrc/mesh.hip``, ``ctu_mesh_adjacency_*`` /
+``ctu_mesh_smooth`` of ``csrc/mesh_smooth.hip``, ``ctu_mesh_voxelize`` of ``csrc/mesh_voxelize.hip``); no CPU fallback.
 
     m = mesh.extract_surface(implant, spacing=(0.8, 0.45, 0.45))      # Mesh: vertices [V,3] (z, y, x) in mm, faces [F,3]
     m = mesh.smooth(m)                                                # Taubin: the staircase goes, the volume stays
     area, volume = mesh.measure(m).tolist()
     mesh.write_stl("implant.stl", m)
+    v = mesh.voxelize(mesh.smooth(m), scan.shape, spacing=(0.8, 0.45, 0.45))      # uint8 [D,H,W] on the scanner's grid
+    metrics.surface_metrics(v, truth, ...)                            # the smoothed implant scored as a volume
+    w = mesh.winding_number(m, scan.shape, spacing=(0.8, 0.45, 0.45))  # int32: outside {0, 1} where a mesh self-intersects
+    other = mesh.read_stl("designed_elsewhere.stl")                    # host Mesh; move both fields with .to("cuda")
 
 ``volume`` is one ``[D,H,W]`` tensor.  Meshes are ragged (V and F depend on the data), so a batch is a Python loop over its
 items.  bool, uint8 and int64 volumes are masks or label maps: inside = ``v != 0``, or ``v == label`` with ``label=``;
@@ -73,7 +78,54 @@ a staircase: every vertex sits at the midpoint of a lattice edge.  ``smooth`` mo
   list afterwards, so the table does not depend on the order of the faces and two calls are bit-equal.
 
 Limits of smoothing: V < 2^31 and 6F < 2^31 (E and every offset fit an int32); anything beyond raises.
+
+**Voxelisation** (``voxelize`` / ``winding_number``; ``tests/mesh_voxelize_ref.py`` restates the rule in numpy): the inverse of
+``extract_surface``, mesh in, volume out, on any grid ``(shape, spacing, origin)``; the mesh need not come from that grid.
+The centre of voxel (i, j, k) is ``origin + (i, j, k) * spacing`` per axis.  A voxel's value is the winding number of the
+mesh around its centre, evaluated with rays along x, one per (z, y) row of the grid; ``voxelize`` is ``winding != 0``.  For
+every mask ``M``, ``voxelize(extract_surface(M), M.shape) == M`` bit for bit, and a float field cut at ``level`` comes back as
+``field > level``: the marching-tetrahedra surface separates the lattice points exactly by their insideness.
+
+- **Arithmetic.**  float64; vertex coordinates are the float32 values widened; the centre n of axis a is
+  ``double(origin_a) + n * double(spacing_a)`` (``spacing`` and ``origin`` are rounded to float32 once, as everywhere in this
+  module); every product, difference, sum and division is rounded on its own (contraction is off on the device).
+- **Faces that are skipped.**  A face with an index outside ``[0, V)`` or a vertex that is not finite is skipped on the
+  device, never read through, and counted; the call then reads the count and raises ``ValueError``.  Otherwise a face with
+  a repeated index contributes nothing, and neither does one whose projected doubled area
+  ``A = (p1_z - p0_z)(p2_y - p0_y) - (p1_y - p0_y)(p2_z - p0_z)`` evaluates to 0 (``p0, p1, p2`` its corners in face order).
+- **Rows of a face.**  A face is tested against the rows whose centre ``p = (z_i, y_j)`` lies in the closed bounding box of
+  its three projected corners (exact float64 comparisons), and against no other.
+- **Containment in projection.**  For each of the three edges (corner q to corner q+1), with ``a`` the endpoint of lower
+  vertex index and ``b`` the other: ``E = (b_z - a_z)(p_y - a_y) - (b_y - a_y)(p_z - a_z)``, and the edge's sign is
+  ``sign(E)``; where ``E == 0`` it is ``sign(-(b_y - a_y))`` and, where that is 0 too, ``sign(b_z - a_z)`` (the ray shifted by
+  (+eps, +eps^2) in (z, y)); where all are 0 the edge projects to a point and the face contributes nothing.  The sign is
+  negated if the face traverses the edge from ``b`` to ``a``.  Two faces that share an edge thereby see bit-identical
+  arithmetic and opposite signs.  The ray crosses the face where the three signs agree, and that common sign is the
+  crossing's weight: +1 where the ray enters through ``extract_surface``'s outward winding, -1 where it leaves.  Rays
+  through vertices and edges are the main case, not an edge case: every vertex of a mask's mesh on an x-directed lattice
+  edge projects exactly onto a row centre.
+- **Depth.**  With ``e1 = p1 - p0``, ``e2 = p2 - p0``, ``n_z = e1_y e2_x - e1_x e2_y`` and ``n_y = e1_x e2_z - e1_z e2_x``:
+  ``x_c = p0_x - (n_z (p_z - p0_z) + n_y (p_y - p0_y)) / A``.  The crossing weighs on every voxel of the row with
+  ``x_k > x_c``, strictly, against the float64 centres above; one behind the row's last centre (or with ``x_c`` NaN) is
+  dropped, one before the first weighs on the whole row.  The device estimates the first such ``k`` (a product with
+  ``1 / spacing``), clamps the estimate in floating point (a vertex at 1e30 never reaches a float-to-int conversion) and
+  corrects it by explicit comparison, so the estimate's rounding never shows.
+- **Value.**  ``winding[i, j, k]`` = the sum of the weights of the row's crossings with ``x_c < x_k``.  A closed, consistently
+  wound mesh without self-intersection gives 1 inside and 0 outside (-1 inside if wound inward); a smoothed mesh that
+  self-intersects shows other values.  For a mesh that is not closed the result is defined by this rule, bounded, and reads
+  or writes nothing out of range; it is not meaningful.
+- **Device.**  One memset of an int32 delta volume, one scatter launch (a lane per face, integer ``atomicAdd`` of the weight at
+  the crossing's first voxel; a face whose box holds more than 16 rows is walked by its whole wave), one scan launch
+  (prefix sums along x).  Integer adds commute, so the result does not depend on the order of the faces or of arrival and
+  two calls are bit-equal.  The read of the refused-face count is the call's one host synchronisation.  Workspace:
+  ``voxelize_workspace_bytes``, 4 bytes per voxel and 256; processing the grid in slabs would shrink it and is the follow-up
+  if 512^3 grids matter.  Limits: every side <= 1024, D*H*W < 2^31, V < 2^31, F < 2^31; anything beyond raises.
+
+``read_stl`` is the host-side inverse of ``write_stl``: binary STL only, the stored corners welded where their three float32
+values are bit-equal, vertices numbered in order of first appearance, faces in file order and winding, normals ignored.
+
 Out of scope: decimation, formats other than binary STL, marching cubes.
+Out of scope of voxelisation: anti-aliased coverage, signed distance to a mesh, mesh repair.
 """
 from __future__ import annotations
 
@@ -384,6 +436,57 @@ def smooth(m: Mesh, iterations: int = 10, lamb: float = 0.5, mu: Optional[float]
     return Mesh(out, f)
 
 
+def voxelize_workspace_bytes(shape) -> int:
+    """Device workspace (bytes) of one ``voxelize`` or ``winding_number`` call onto a (D, H, W) grid: the int32 delta volume
+    (4 bytes per voxel, rounded up to 256) and 256 for the refused-face count; the only allocation besides the result and
+    contiguous copies of non-contiguous inputs."""
+    return int(_lib.load().ctu_mesh_voxelize_ws_bytes(*_shape(shape)))
+
+
+def _voxelize(m, shape, spacing, origin, winding: bool, who: str) -> torch.Tensor:
+    v, f = _check_mesh(m, who)
+    V, F = v.shape[0], f.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"mesh: {who} takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
+    shape = _shape(shape)
+    sp, org = _spacing(spacing), _origin(origin)
+    if not v.is_cuda:
+        raise ValueError(f"mesh: {who} takes a mesh on the GPU; this path has no CPU fallback")
+    dev = v.device
+    dtype = torch.int32 if winding else torch.uint8
+    if F == 0:
+        return torch.zeros(shape, dtype=dtype, device=dev)
+    lib = _lib.load()
+    v, f = v.contiguous(), f.contiguous()
+    out = torch.empty(shape, dtype=dtype, device=dev)
+    ws = torch.empty(lib.ctu_mesh_voxelize_ws_bytes(*shape), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_voxelize(v.data_ptr(), V, f.data_ptr(), F, *shape, _lib.float_array(sp), _lib.float_array(org),
+                                         int(winding), out.data_ptr(), ws.data_ptr(), stream), "mesh_voxelize")
+        bad = int(ws[:8].view(torch.int64).item())                      # the call's one host synchronisation
+    if bad:
+        raise ValueError(f"mesh: a face refers to a vertex that does not exist or is not finite ({bad} of {F} faces hold an "
+                         f"index outside [0, {V}) or a NaN / infinite coordinate)")
+    return out
+
+
+def voxelize(m: Mesh, shape, spacing=None, origin=None) -> torch.Tensor:
+    """uint8 ``[D,H,W]`` on the mesh's device: 1 where the winding number of the mesh around the voxel's centre
+    ``origin + (i, j, k) * spacing`` is not 0, by the module docstring's rule; the inverse of ``extract_surface``.  ``shape``,
+    ``spacing`` and ``origin`` describe the target grid with ``extract_surface``'s conventions (a number or a (z, y, x) triple,
+    default 1 and 0); the grid need not be the one the mesh was extracted on.  One host synchronisation (the refused-face
+    count); a face index outside ``[0, V)`` or a vertex that is not finite raises.  An empty mesh gives zeros without a
+    launch of the kernels."""
+    return _voxelize(m, shape, spacing, origin, False, "voxelize")
+
+
+def winding_number(m: Mesh, shape, spacing=None, origin=None) -> torch.Tensor:
+    """int32 ``[D,H,W]``: the winding numbers ``voxelize`` thresholds, through the same device path: 0 / 1 for a closed
+    outward-wound mesh, 0 / -1 for an inward-wound one, other values where a (smoothed) mesh intersects itself."""
+    return _voxelize(m, shape, spacing, origin, True, "winding_number")
+
+
 def stl_bytes(vertices, faces, header: bytes = b"") -> bytes:
     """The binary STL of host arrays ``vertices [V,3]`` (z, y, x) and ``faces [F,3]``: the 80-byte header, the uint32 count and
     50 bytes per triangle: normal and three corners as little-endian float32 in (x, y, z), then a zero uint16.  The winding
@@ -414,3 +517,39 @@ def write_stl(path, m: Mesh, header: bytes = b"") -> None:
     data = stl_bytes(v.detach().cpu().numpy(), f.detach().cpu().numpy(), header)
     with open(path, "wb") as fh:
         fh.write(data)
+
+
+def read_stl(source) -> Mesh:
+    """The ``Mesh`` of a binary STL file, on the host: ``source`` is a path or a bytes object.  The stored corners are taken as
+    they are (the stored normals are ignored), returned as (z, y, x) columns, and welded where their three float32 values
+    are bit-equal (so -0.0 and 0.0 stay apart); vertices are numbered in order of first appearance, faces keep the file's
+    order and winding.  For a mesh without unreferenced or duplicate vertices ``read_stl(stl_bytes(v, f))`` gives the same
+    triangles back (``v[f]``, bit for bit), and ``(v, f)`` itself where ``v`` is numbered in that order.  A truncated file, a triangle count that does not match the length and the ASCII form raise ``ValueError``."""
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        data = bytes(source)
+    else:
+        with open(source, "rb") as fh:
+            data = fh.read()
+    if len(data) < 84:
+        if data[:5].lower() == b"solid":
+            raise ValueError("mesh: read_stl reads binary STL only; this is the ASCII form (it begins with 'solid')")
+        raise ValueError(f"mesh: a binary STL has an 80-byte header and a 4-byte count; this one is truncated at {len(data)} bytes")
+    nf = int(np.frombuffer(data, dtype="<u4", count=1, offset=80)[0])
+    if len(data) != 84 + 50 * nf:
+        if data[:5].lower() == b"solid":
+            raise ValueError("mesh: read_stl reads binary STL only; this is the ASCII form (it begins with 'solid')")
+        if len(data) < 84 + 50 * nf:
+            raise ValueError(f"mesh: the STL counts {nf} triangles ({84 + 50 * nf} bytes) and is truncated at {len(data)} bytes")
+        raise ValueError(f"mesh: the STL counts {nf} triangles ({84 + 50 * nf} bytes) and holds {len(data)} bytes")
+    rec = np.frombuffer(data, dtype=np.dtype([("n", "<f4", 3), ("p", "<f4", (3, 3)), ("a", "<u2")]), count=nf, offset=84)
+    corners = np.ascontiguousarray(rec["p"].reshape(-1, 3)[:, ::-1]).astype(np.float32)            # (z, y, x)
+    if nf == 0:
+        return Mesh(torch.zeros((0, 3), dtype=torch.float32), torch.zeros((0, 3), dtype=torch.int32))
+    keys = corners.view(np.uint32).reshape(-1, 3)
+    _, first, inverse = np.unique(keys, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                            # unique rows in order of first appearance
+    rank = np.empty(len(order), dtype=np.int64)
+    rank[order] = np.arange(len(order))
+    vertices = corners[first[order]]
+    faces = rank[inverse.reshape(-1)].reshape(-1, 3).astype(np.int32)
+    return Mesh(torch.from_numpy(np.ascontiguousarray(vertices)), torch.from_numpy(faces))

@@ -615,6 +615,20 @@ int ctu_mesh_smooth(const float* vertices, int64_t V, const int32_t* offsets, co
                     const uint8_t* fixed, int iterations, float lambda, int has_mu, float mu, float* out, void* ws,
                     void* stream);
 
+/* Voxelisation of a surface mesh onto a [D,H,W] grid (no reference counterpart; rule pinned in ctunet_amd/mesh.py): the
+ * winding number of the mesh around every voxel centre origin + (i, j, k) * spacing, by rays along x, float64 arithmetic on
+ * the float32 vertices.  vertices: DEVICE float32 [V][3] in (z, y, x); faces: DEVICE int32 [F][3]; spacing, origin: HOST
+ * float [3] in (z, y, x) (NULL: 1 and 0).  out: DEVICE uint8 [D][H][W] (1 where the winding number is not 0) or, with
+ * want_winding != 0, int32 [D][H][W] (the numbers).  A face with an index outside [0, V) or a vertex that is not finite is
+ * skipped, never read through, and counted: the head of ws holds that count as one int64, which the caller reads after
+ * the call (its one synchronisation) and refuses the mesh on.  F = 0: out and the head are cleared, no kernel is launched.
+ *   ws: ctu_mesh_voxelize_ws_bytes() bytes, 0 for an invalid shape: 256 + 4 per voxel (rounded up to 256); 16-byte aligned.
+ * Limits: every side <= 1024, D*H*W < 2^31, V < 2^31, F < 2^31.  Integer atomics only (the sums do not depend on arrival
+ * order); two calls are bitwise equal. */
+size_t ctu_mesh_voxelize_ws_bytes(int D, int H, int W);
+int ctu_mesh_voxelize(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int D, int H, int W,
+                      const float* spacing, const float* origin, int want_winding, void* out, void* ws, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
