@@ -130,6 +130,11 @@ SIGNATURES = {
     "ctu_distance_ws_bytes": (Z, [I, I, I, I, I, I]),
     "ctu_distance_transform": (I, [P, I, I, I, I, I, I, L, I, I, P, I, P, P, F, P, P]),
     "ctu_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P]),
+    "ctu_affine_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P, D, P, P]),
+    "ctu_registration_ws_bytes": (Z, [L]),
+    "ctu_registration_init": (I, [P, L, P, P, P]),
+    "ctu_registration_accumulate": (I, [P, L, P, I, I, I, P, P, D, P, P]),
+    "ctu_registration_update": (I, [L, I, P, P, P, I, P, P]),
     "ctu_mesh_ws_bytes": (Z, [I, I, I]),
     "ctu_mesh_count": (I, [P, I, I, I, I, I, L, F, P, P]),
     "ctu_mesh_emit": (I, [P, I, I, I, I, F, F, P, P, L, L, P, P, P, P]),

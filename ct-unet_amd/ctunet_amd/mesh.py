@@ -487,6 +487,19 @@ def winding_number(m: Mesh, shape, spacing=None, origin=None) -> torch.Tensor:
     return _voxelize(m, shape, spacing, origin, True, "winding_number")
 
 
+def transform(m: Mesh, matrix: torch.Tensor) -> Mesh:
+    """The mesh with every vertex moved through ``matrix`` (float64 [3,4] or [4,4] on the mesh's device, acting on (z, y, x)
+    column vectors: ``registration``'s ``matrix`` / ``inverse``): ``R v + t`` in float64, rounded to float32 once.  The faces
+    are shared, not copied; a matrix with a negative determinant flips the surface's orientation and is not corrected."""
+    v, f = _check_mesh(m, "transform")
+    if not isinstance(matrix, torch.Tensor) or matrix.dtype != torch.float64 or tuple(matrix.shape) not in ((3, 4), (4, 4)):
+        raise ValueError("mesh: transform takes a float64 matrix [3,4] or [4,4]")
+    if matrix.device != v.device:
+        raise ValueError(f"mesh: the matrix lives on {matrix.device}, the mesh on {v.device}")
+    moved = v.to(torch.float64) @ matrix[:3, :3].T + matrix[:3, 3]
+    return Mesh(moved.to(torch.float32), f)
+
+
 def stl_bytes(vertices, faces, header: bytes = b"") -> bytes:
     """The binary STL of host arrays ``vertices [V,3]`` (z, y, x) and ``faces [F,3]``: the 80-byte header, the uint32 count and
     50 bytes per triangle: normal and three corners as little-endian float32 in (x, y, z), then a zero uint16.  The winding

@@ -1269,3 +1269,27 @@ def resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n:
     _lib.check(_lib.load().ctu_resample(x.data_ptr(), RESAMPLE_CODE[x.dtype], mode, num_classes, n, d0, h0, w0, d1, h1, w1,
                                         i0.data_ptr(), wt.data_ptr(), near.data_ptr(), out.data_ptr(), _stream()),
                "resample")
+
+
+def _double3(v):
+    """A host double [3] for a ``const double*`` argument (None stays None: the entry point's default)."""
+    import ctypes
+    return None if v is None else (ctypes.c_double * 3)(*v)
+
+
+def affine_resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n: int, in_shape: Tuple[int, int, int],
+                    out_shape: Tuple[int, int, int], matrix: torch.Tensor, spacing, origin, out_spacing, out_origin,
+                    fill: float) -> None:
+    """out [n, d, h, w] = x [n, D, H, W] pulled through the DEVICE float64 matrix [3,4] / [4,4] (output world -> input world;
+    rule: ctunet_amd/resample.py).  spacing .. out_origin: host (z, y, x) triples or None.  One launch, nothing allocated."""
+    for t, nm in ((x, "input"), (out, "output"), (matrix, "matrix")):
+        if not t.is_cuda:
+            raise RuntimeError(f"ctunet_amd: affine_resample {nm} must live on the GPU (MI355X); this path has no CPU fallback")
+        assert t.is_contiguous(), nm
+    (d0, h0, w0), (d1, h1, w1) = in_shape, out_shape
+    assert x.numel() == n * d0 * h0 * w0 and out.numel() == n * d1 * h1 * w1, "affine_resample shapes"
+    assert matrix.dtype == torch.float64 and matrix.numel() in (12, 16), "affine_resample matrix"
+    _lib.check(_lib.load().ctu_affine_resample(x.data_ptr(), RESAMPLE_CODE[x.dtype], mode, num_classes, n, d0, h0, w0, d1, h1,
+                                               w1, matrix.data_ptr(), _double3(spacing), _double3(origin),
+                                               _double3(out_spacing), _double3(out_origin), float(fill), out.data_ptr(),
+                                               _stream()), "affine_resample")

@@ -47,9 +47,38 @@ A call is one launch: no host synchronisation, no atomics, and with ``out=`` and
 can be captured into a graph; two calls are bit-equal.  A ``Resampler`` uploads its tables once (``.to(device)``, or the
 first call on a device: do that before a capture); ``resample`` keeps the tables of its recent geometries.  D*H*W is
 below 2^31 on either grid; offsets across the batch are 64-bit.
+
+Affine resampling (``ctu_affine_resample`` of ``csrc/affine.hip``) moves a volume through a rigid or affine matrix: into the
+frame of an atlas that ``registration.register`` found, and a result back out::
+
+    y = affine_resample(x, out_to_in, out_shape, spacing=, origin=, out_spacing=, out_origin=, mode="linear", fill=0)
+
+``out_to_in`` is a DEVICE float64 tensor ``[3,4]`` or ``[4,4]`` that maps world coordinates (z, y, x) of the OUTPUT grid to
+world coordinates of the INPUT grid (the pull convention of ``scipy.ndimage.affine_transform``); the world coordinate of
+voxel index ``k`` is ``origin + k * spacing`` per axis, as in ``mesh.extract_surface``.  The kernel reads the matrix from
+device memory: a registration result feeds it without a host synchronisation, and a captured call follows later changes of
+the tensor.  The pinned rule (``tests/affine_ref.py`` restates it), per output voxel with index ``idx``, in float64 with
+every operation rounded on its own::
+
+    w_a = out_origin_a + idx_a * out_spacing_a
+    s_a = ((m_a0 * w_0 + m_a1 * w_1) + m_a2 * w_2) + m_a3
+    u_a = (s_a - origin_a) / spacing_a
+
+- ``"nearest"``: ``n_a = floor(u_a + 0.5)``; ``in[n]``, or ``fill`` where an ``n_a`` lies outside ``[0, size_a)`` or ``u`` is
+  not finite.  uint8, int16 or float32, the same dtype out.
+- ``"linear"``: ``i0_a = floor(u_a)``, ``w_a = float32(u_a - i0_a)``; the eight neighbours ``i0 + {0,1}^3``, one outside the
+  volume reading as ``float32(fill)`` (scipy's ``mode="grid-constant"``); the lerps of the linear rule above, x then y then
+  z.  Where a ``u_a`` lies outside ``[-1, size_a)`` (all eight neighbours outside) or is not finite the output is
+  ``float32(fill)``.  float32, int16 or uint8 in, float32 out.
+- ``"label_linear"``: the label rule above on those eight neighbours; one outside the volume carries the label ``fill``.
+  uint8 (or bool) in and out.
+
+One launch, no workspace, no synchronisation and with ``out=`` no allocation; every read is bounded whatever the matrix holds
+(a NaN matrix gives ``fill`` everywhere).
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 import math
 from numbers import Integral, Real
@@ -58,7 +87,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 MODES = ("nearest", "linear", "label_linear")
 MAX_CLASSES = 16
@@ -128,7 +157,8 @@ def axis_tables(n: int, m: int, a: float):
     return i0.astype(np.int32), (src - i0).astype(np.float32), near.astype(np.int32)
 
 
-def _check_call(x, mode, num_classes, who: str):
+def _check_call(x, mode, num_classes, who: str, dtypes=None):
+    dtypes = _IN_DTYPES if dtypes is None else dtypes
     if not isinstance(mode, str) or mode not in MODES:
         raise ValueError(f"{who}: mode must be one of {', '.join(MODES)}, got {mode!r}")
     if mode == "label_linear":
@@ -142,8 +172,8 @@ def _check_call(x, mode, num_classes, who: str):
         raise TypeError(f"{who}: the input must be a tensor, got {type(x).__name__}")
     if x.dim() < 3:
         raise ValueError(f"{who}: the input needs at least the three dimensions (D, H, W), got shape {tuple(x.shape)}")
-    if x.dtype not in _IN_DTYPES[mode]:
-        raise TypeError(f"{who}: mode {mode!r} takes {', '.join(str(d) for d in _IN_DTYPES[mode])}, got {x.dtype}")
+    if x.dtype not in dtypes[mode]:
+        raise TypeError(f"{who}: mode {mode!r} takes {', '.join(str(d) for d in dtypes[mode])}, got {x.dtype}")
 
 
 class Resampler:
@@ -236,3 +266,82 @@ def resample(x, size=None, *, spacing=None, new_spacing=None, mode: str = "linea
     geometry(in_shape, size, spacing, new_spacing, "resample")           # raises before the cache sees an unhashable value
     r = _cached(in_shape, _key(size), _key(spacing), _key(new_spacing))
     return r._run(x, 0, mode, num_classes, out, "resample")
+
+
+_AFFINE_DTYPES = {
+    "nearest": (torch.uint8, torch.int16, torch.float32),
+    "linear": (torch.float32, torch.int16, torch.uint8),
+    "label_linear": (torch.bool, torch.uint8),
+}
+
+
+def _triple_real(v, what: str, who: str, positive: bool):
+    """A host (z, y, x) float64 triple from a number or a triple; None stays None (the entry point's default)."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        v = v.tolist()
+    if isinstance(v, Real) and not isinstance(v, bool):
+        vals = (v, v, v)
+    else:
+        try:
+            vals = tuple(v)
+        except TypeError:
+            raise TypeError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}") from None
+        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
+            raise TypeError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}")
+    if any(not math.isfinite(s) or (positive and s <= 0) for s in vals):
+        raise ValueError(f"{who}: {what} must be {'positive and ' if positive else ''}finite, got {v!r}")
+    return tuple(float(s) for s in vals)
+
+
+def _check_matrix(m, device, who: str) -> torch.Tensor:
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or tuple(m.shape) not in ((3, 4), (4, 4)):
+        raise TypeError(f"{who}: the matrix must be a float64 tensor [3,4] or [4,4], got "
+                        f"{m.dtype if isinstance(m, torch.Tensor) else type(m).__name__} "
+                        f"{tuple(m.shape) if isinstance(m, torch.Tensor) else ''}")
+    if m.device != device:
+        raise ValueError(f"{who}: the matrix lives on {m.device}, the volume on {device}: the kernel reads it from device memory")
+    return m if m.is_contiguous() else m.contiguous()
+
+
+def affine_resample(x, out_to_in, out_shape, *, spacing=None, origin=None, out_spacing=None, out_origin=None,
+                    mode: str = "linear", num_classes: Optional[int] = None, fill=0, out=None) -> torch.Tensor:
+    """``x [..., D, H, W]`` on the grid ``out_shape`` through the device matrix ``out_to_in`` (module docstring)."""
+    who = "affine_resample"
+    _check_call(x, mode, num_classes, who, _AFFINE_DTYPES)
+    src = _triple_int(tuple(int(s) for s in x.shape[-3:]), "the input grid", who)
+    dst = _triple_int(out_shape, "out_shape", who)
+    sp, org = _triple_real(spacing, "spacing", who, True), _triple_real(origin, "origin", who, False)
+    osp, oorg = _triple_real(out_spacing, "out_spacing", who, True), _triple_real(out_origin, "out_origin", who, False)
+    if isinstance(fill, bool) or not isinstance(fill, Real):
+        raise TypeError(f"{who}: fill must be a number, got {fill!r}")
+    out_dtype = torch.float32 if mode == "linear" else x.dtype
+    fillv = float(fill) + 0.0                                            # -0.0 -> 0.0
+    if out_dtype == torch.float32:
+        if not math.isfinite(fillv) or not math.isfinite(C.c_float(fillv).value):
+            raise ValueError(f"{who}: fill must be finite in float32, got {fill!r}")
+    else:
+        lo, hi = (-32768, 32767) if out_dtype == torch.int16 else ((0, 1) if out_dtype == torch.bool else (0, 255))
+        if fillv != math.floor(fillv) or not lo <= fillv <= hi:
+            raise ValueError(f"{who}: fill must be an integer in {lo}..{hi} for {out_dtype}, got {fill!r}")
+    lead = tuple(x.shape[:-3])
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if n < 1:
+        raise ValueError(f"{who}: the batch is empty, got shape {tuple(x.shape)}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError(f"{who}: out must be a tensor, got {type(out).__name__}")
+        if tuple(out.shape) != lead + dst or out.dtype != out_dtype or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f"{who}: out must be a contiguous {out_dtype} tensor of shape {lead + dst} on {x.device}, "
+                             f"got {out.dtype} {tuple(out.shape)} on {out.device}"
+                             f"{'' if out.is_contiguous() else ', not contiguous'}")
+    if not x.is_cuda:
+        raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
+    m = _check_matrix(out_to_in, x.device, who)
+    if out is None:
+        out = torch.empty(lead + dst, dtype=out_dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        ops.affine_resample(_lib.as_bytes(x), _lib.as_bytes(out), _MODE_CODE[mode], int(num_classes or 0), n, src, dst, m,
+                            sp, org, osp, oorg, fillv)
+    return out

@@ -555,6 +555,56 @@ int ctu_distance_transform(const void* in, int dtype, int N, int D, int H, int W
 int ctu_resample(const void* in, int dtype, int mode, int num_classes, int64_t N, int D, int H, int W, int d, int h, int w,
                  const int32_t* i0, const float* wt, const int32_t* near, void* out, void* stream);
 
+/* Affine resampling of volumes through a matrix in DEVICE memory (no reference counterpart: the reference expects scans
+ * registered to its atlas by a host tool, ctunet/pytorch/datasets.py:22-45; rule pinned in ctunet_amd/resample.py).  in:
+ * DEVICE [N,D,H,W], out: DEVICE [N,d,h,w], both contiguous, a buffer each.  out_to_in: DEVICE double, row-major [3][4] (or
+ * the first three rows of a [4][4]): world (z, y, x) of the OUTPUT grid -> world of the INPUT grid, read by the kernel.
+ * spacing, origin (input grid), out_spacing, out_origin (output grid): HOST double [3] in (z, y, x), NULL = 1 / 0; the world
+ * coordinate of voxel index k is origin + k spacing.  Per output voxel, in float64 with every operation rounded on its own:
+ *   w_a = out_origin_a + idx_a out_spacing_a;  s_a = ((m_a0 w_0 + m_a1 w_1) + m_a2 w_2) + m_a3;  u_a = (s_a - origin_a) / spacing_a
+ *   CTU_RESAMPLE_NEAREST:      in[n], n_a = floor(u_a + 0.5); fill where an n_a lies outside [0, size_a) or u is not finite;
+ *                              dtype CTU_U8, CTU_I16 or CTU_F32, the same dtype out.
+ *   CTU_RESAMPLE_LINEAR:       i0_a = floor(u_a), weight float32(u_a - i0_a), the 8 neighbours i0 + {0,1}^3, one outside the
+ *                              volume reading as float32(fill); ctu_resample's lerps, x then y then z; fill where a u_a lies
+ *                              outside [-1, size_a) or is not finite; dtype CTU_F32, CTU_I16 or CTU_U8, float32 out.
+ *   CTU_RESAMPLE_LABEL_LINEAR: ctu_resample's rule on those 8 neighbours, one outside the volume carrying the label fill;
+ *                              dtype CTU_U8, num_classes in 2..16.
+ * fill must be representable in the output dtype (finite in float32).  One launch per 65535 items, no workspace, no atomics,
+ * no host sync, capture-safe, bitwise reproducible; every read is bounded whatever the matrix holds.  D*H*W < 2^31 on
+ * either grid; offsets across the batch are 64-bit. */
+int ctu_affine_resample(const void* in, int dtype, int mode, int num_classes, int64_t N, int D, int H, int W, int d, int h,
+                        int w, const double* out_to_in, const double* spacing, const double* origin,
+                        const double* out_spacing, const double* out_origin, double fill, void* out, void* stream);
+
+/* Rigid registration of a point set to a distance field: Levenberg-Marquardt on the directed chamfer cost (no reference
+ * counterpart, as above; rule pinned in ctunet_amd/registration.py).  points: DEVICE float32 [P][3], world (z, y, x) of the
+ * moving frame; field: DEVICE float32 [D][H][W], the distance to the fixed object on the fixed grid (spacing, origin: HOST
+ * double [3], NULL = 1 / 0; every side >= 2).  All state lives in ws (ctu_registration_ws_bytes(P) bytes, 0 for P < 1; 8-byte
+ * aligned): a head of 1024 bytes of doubles -- M [16], candidate M_c [16], H [21] (upper triangle, row by row), b [6],
+ * pivot [3], candidate pivot [3], mean of the finite points [3], cost, lambda, inlier count (int64) -- then one slab row of
+ * 32 doubles per block of the accumulation: min(ceil(P / 256), CTU_REG_MAX_BLOCKS) rows of (H [21], b [6], cost, count
+ * (int64), padding).
+ *   init:       the mean and the start state (M = M_c = init, DEVICE double [4][4], NULL = identity; cost = +inf,
+ *               lambda = 1e-3); once per registration.
+ *   accumulate: the sums at M_c about the candidate's pivot into the slab, one row per block, no float atomics;
+ *               max_distance = +inf: no bound.
+ *   update:     iteration `it`: sums the slab in block order, accepts the candidate iff its cost is lower (lambda / 3,
+ *               at least 1e-9; otherwise lambda * 10, at most 1e9), solves (H + lambda diag(H) + 1e-12 I) delta = -b by
+ *               Cholesky and forms the next candidate; with fewer than CTU_REG_MIN_INLIERS inliers, a pivot that is not
+ *               positive or a result that is not finite the candidate stays and the row's flag is -1.  Writes matrix and
+ *               inverse (DEVICE double [4][4]: the accepted matrix, (R^T, -R^T t)) and history[it] = (cost / P, inliers,
+ *               lambda, 1 accepted / 0 rejected / -1), history DEVICE double [history_rows][4].
+ * A registration is init, then (accumulate, update) for it = 0 .. iterations: no host sync, capture-safe, two runs bitwise
+ * equal. */
+#define CTU_REG_MAX_BLOCKS 1024
+#define CTU_REG_MIN_INLIERS 6
+size_t ctu_registration_ws_bytes(int64_t P);
+int ctu_registration_init(const float* points, int64_t P, const double* init, void* ws, void* stream);
+int ctu_registration_accumulate(const float* points, int64_t P, const float* field, int D, int H, int W,
+                                const double* spacing, const double* origin, double max_distance, void* ws, void* stream);
+int ctu_registration_update(int64_t P, int it, double* matrix, double* inverse, double* history, int history_rows, void* ws,
+                            void* stream);
+
 /* Surface meshes of label volumes and scalar fields (no reference counterpart: the reference writes NIfTI volumes only;
  * rule pinned in ctunet_amd/mesh.py): marching tetrahedra on the Kuhn split of the cells of the grid padded by one layer of
  * outside points, welded (shared vertex indices) and closed.  volume: DEVICE contiguous [D,H,W] of dtype CTU_U8 or CTU_I64
