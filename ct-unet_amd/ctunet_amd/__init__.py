@@ -10,6 +10,7 @@ from . import mesh  # noqa: F401
 from . import metrics  # noqa: F401
 from . import optim  # noqa: F401
 from . import postprocess  # noqa: F401
+from . import preprocess  # noqa: F401
 from . import resample  # noqa: F401
 from . import registration  # noqa: F401
 from .inference import Prediction, predict_volume  # noqa: F401
@@ -22,4 +23,5 @@ from .transforms import FlapRecTransform, SaltAndPepper, SkullRandomHole, flap_r
 __all__ = ["UNet", "UNet4b2i3o", "UNet5b2i3o", "UNet4b1i3o", "UNetSP", "UNetSPSmall", "UNetDO", "recAE_v2_fixed",
            "UNet4_2IC", "DynamicLossScale", "predict_volume", "Prediction",
            "SkullRandomHole", "SaltAndPepper", "FlapRecTransform", "flap_rec_transform", "FlapRecWShapePrior2OTrainDataset",
-           "FlapRec2OTrainDataset", "metrics", "postprocess", "resample", "registration", "mesh", "lr_scheduler", "optim"]
+           "FlapRec2OTrainDataset", "metrics", "postprocess", "preprocess", "resample", "registration", "mesh", "lr_scheduler",
+           "optim"]

@@ -146,6 +146,13 @@ SIGNATURES = {
     "ctu_mesh_smooth": (I, [P, L, P, P, L, P, I, F, I, F, P, P, P]),
     "ctu_mesh_voxelize_ws_bytes": (Z, [I, I, I]),
     "ctu_mesh_voxelize": (I, [P, L, P, L, I, I, I, P, P, I, P, P, P]),
+    "ctu_gaussian_ws_bytes": (Z, [L, I, I, I, I]),
+    "ctu_gaussian_filter": (I, [P, I, L, I, I, I, P, P, I, F, P, P, P]),
+    "ctu_minmax_ws_bytes": (Z, [L]),
+    "ctu_finite_minmax": (I, [P, I, L, P, P, P]),
+    "ctu_histogram": (I, [P, I, L, I, P, D, D, P, P]),
+    "ctu_threshold_otsu": (I, [P, I, P, D, D, P, P, P]),
+    "ctu_binarize": (I, [P, I, L, P, D, P, D, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

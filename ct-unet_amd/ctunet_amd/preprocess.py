@@ -1,0 +1,349 @@
+"""CT preprocessing on the GPU: from a scanner's int16 Hounsfield volume to the binary skull that the networks, the
+registration and the implant extraction take.  Gaussian filter, histogram, Otsu's threshold, a range test and their
+composition (``csrc/preprocess.hip``); no CPU fallback.
+
+    smooth = gaussian_filter(scan, 1.0, spacing=(0.8, 0.45, 0.45))            # float32, sigma in mm
+    skull = extract_skull(scan, 300, spacing=(0.8, 0.45, 0.45), sigma=0.5)    # uint8 0 / 1
+    t = threshold_otsu(scan, range=(-200, 3000))                              # float64 0-dim DEVICE tensor, no sync
+    mask = binarize(scan, t)                                                  # reads t on the device
+
+Every volume is contiguous ``[..., D, H, W]`` with all leading dimensions a batch; ``histogram`` and ``binarize`` take a
+tensor of any shape.  Inputs are float32, int16 or uint8 and are converted in the kernel.  ``tests/preprocess_ref.py``
+restates each rule in numpy and every device result is bit-equal to it.
+
+**gaussian_filter** (``scipy.ndimage.gaussian_filter`` up to float32 rounding):
+
+- ``sigma`` is a number or a (z, y, x) triple; with ``spacing`` it is in the spacing's units,
+  ``sigma_vox_a = sigma_a / spacing_a``.  Per axis the radius is ``R_a = int(truncate * sigma_vox_a + 0.5)`` (scipy's).
+- Weights, in float64: ``p_k = exp(-0.5 k^2 / sigma_vox^2)`` for ``k = 0..R``,
+  ``w_k = float32(p_k / (p_0 + 2 sum_{k>=1} p_k))``.  ``sigma = 0`` gives ``R = 0`` and ``w_0 = 1``: the identity.
+- One axis: ``acc = w_0 v[i]``, then for ``k = 1..R`` in order ``acc = acc + w_k (v[i-k] + v[i+k])``; float32, each
+  operation rounded on its own, no fused multiply-add.  The input is converted to float32 first; the axes go x, then y,
+  then z.
+- Outside the axis ``v`` reads, by ``mode``: ``"nearest"`` the clamped index; ``"reflect"`` scipy's reflect,
+  ``d c b a | a b c d | d c b a`` with period ``2 n`` (also where ``R > n``); ``"constant"`` ``float32(cval)``.
+- Limits: ``R_a <= 32``, every side ``<= 1024``, ``D * H * W < 2^31``.  Anything beyond raises.
+
+**histogram** (``numpy.histogram`` with equal bins), int64 ``[bins]`` over the whole tensor, ``bins`` in 2..4096:
+
+- ``range`` is ``(lo, hi)`` host numbers, a float64 ``[2]`` DEVICE tensor, or ``None``: the smallest and largest finite
+  value, found on the device and read by the histogram kernel there (a tensor without a finite value counts nothing).
+- In float64: ``hi == lo`` widens both by 0.5 (numpy's rule); ``scale = bins / (hi - lo)``; a value with
+  ``lo <= v <= hi`` counts in bin ``min(floor((v - lo) * scale), bins - 1)``; values outside, and NaN, are not counted.
+
+**threshold_otsu** (scikit-image's definition, restated: scikit-image is not a dependency and no parity is claimed), on the
+counts ``h`` with ``N = sum h`` and ``S = sum k h_k``:
+
+- exact int64 prefixes ``w1_k = sum_{j<=k} h_j`` and ``s1_k = sum_{j<=k} j h_j`` for ``k = 0..bins-2``;
+- in float64 ``m1 = s1 / w1``, ``m2 = (S - s1) / (N - w1)``, ``var_k = (double(w1) double(N - w1)) ((m1 - m2) (m1 - m2))``,
+  and ``var_k = 0`` where ``w1 = 0`` or ``w1 = N``;
+- ``k*`` is the first maximum: 0 for a constant volume (every ``var_k`` is 0), the bin of the lower value for a volume of
+  two values;
+- the threshold is ``lo + (k* + 0.5) ((hi - lo) / bins)``, a float64 0-dim DEVICE tensor; foreground is ``x > threshold``.
+
+On a head CT the full range separates air from the head; a range such as ``(-200, 3000)`` separates soft tissue from
+bone (on a synthetic three-class volume the restatement gives -904 and 494 HU).
+
+**binarize**: uint8 ``(x > lower) & (x <= upper)``, compared in float64; each bound a number or a 0-dim float64 DEVICE
+tensor (Otsu's result, consumed without a synchronisation); ``upper=None`` is no upper bound.
+
+**extract_skull**: ``gaussian_filter`` (skipped at ``sigma == 0``), ``binarize`` (``threshold="otsu"``: above Otsu's
+threshold of the filtered volume over ``otsu_range``), ``postprocess.keep_largest_connected_component``
+(``components=0`` skips it), ``postprocess.ball_closing`` when ``closing_radius > 0`` (in the units of ``spacing``).
+
+No call synchronises with the host, so each can be captured into a graph (outputs and workspaces are ``torch.empty``
+tensors, which a capture draws from the graph's pool); the only atomics add integers, so two calls are bit-equal.  Bad
+arguments raise ``ValueError`` before anything is launched.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from numbers import Integral, Real
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MODES = ("nearest", "reflect", "constant")
+MAX_RADIUS = 32              # CTU_GAUSS_MAX_RADIUS
+MAX_SIDE = 1024
+MAX_BINS = 4096              # CTU_HISTOGRAM_MAX_BINS
+_DTYPES = (torch.float32, torch.int16, torch.uint8)
+_CODE = {torch.float32: 0, torch.int16: 5, torch.uint8: 3}          # CTU_F32 / CTU_I16 / CTU_U8
+
+
+def _check_input(x, who: str, volume: bool) -> None:
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{who}: the input must be a tensor, got {type(x).__name__}")
+    if x.dtype not in _DTYPES:
+        raise ValueError(f"{who}: the input must be float32, int16 or uint8, got {x.dtype}")
+    if volume and x.dim() < 3:
+        raise ValueError(f"{who}: the input needs at least the three dimensions (D, H, W), got shape {tuple(x.shape)}")
+    if x.numel() < 1:
+        raise ValueError(f"{who}: the input is empty, got shape {tuple(x.shape)}")
+
+
+def _triple(v, what: str, who: str, positive: bool) -> Tuple[float, float, float]:
+    if isinstance(v, Real) and not isinstance(v, bool):
+        vals = (v, v, v)
+    else:
+        try:
+            vals = tuple(v)
+        except TypeError:
+            raise ValueError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}") from None
+        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
+            raise ValueError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}")
+    if any(not math.isfinite(s) or s < 0 or (positive and s <= 0) for s in vals):
+        raise ValueError(f"{who}: {what} must be finite and {'positive' if positive else 'not negative'}, got {v!r}")
+    return tuple(float(s) for s in vals)
+
+
+def _check_out(out, shape, dtype, device, who: str) -> None:
+    if out is None:
+        return
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f"{who}: out must be a tensor, got {type(out).__name__}")
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
+                         f"{out.dtype} {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', not contiguous'}")
+
+
+def _need_gpu(x, who: str) -> None:
+    if not x.is_cuda:
+        raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def gaussian_weights(sigma_vox: float, truncate: float = 4.0) -> np.ndarray:
+    """``w_0..w_R`` (float32) of one axis: the weights of the module docstring."""
+    r = int(truncate * sigma_vox + 0.5)
+    if r == 0:
+        return np.ones(1, np.float32)
+    k = np.arange(0, r + 1, dtype=np.float64)
+    p = np.exp(-0.5 / (np.float64(sigma_vox) * np.float64(sigma_vox)) * k * k)
+    return (p / (p[0] + 2.0 * p[1:].sum())).astype(np.float32)
+
+
+def gaussian_filter(x: torch.Tensor, sigma, *, spacing=None, truncate: float = 4.0, mode: str = "nearest",
+                    cval: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 Gaussian filter of ``x [..., D, H, W]`` (float32, int16 or uint8); the rule is the module docstring's."""
+    who = "gaussian_filter"
+    _check_input(x, who, True)
+    sig = _triple(sigma, "sigma", who, False)
+    if spacing is not None:
+        sp = _triple(spacing, "spacing", who, True)
+        sig = tuple(s / q for s, q in zip(sig, sp))
+    if isinstance(truncate, bool) or not isinstance(truncate, Real) or not math.isfinite(truncate) or truncate < 0:
+        raise ValueError(f"{who}: truncate must be a finite number >= 0, got {truncate!r}")
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"{who}: mode must be one of {', '.join(MODES)}, got {mode!r}")
+    if isinstance(cval, bool) or not isinstance(cval, Real) or not math.isfinite(C.c_float(float(cval)).value):
+        raise ValueError(f"{who}: cval must be finite in float32, got {cval!r}")
+    radius = tuple(int(float(truncate) * s + 0.5) if math.isfinite(float(truncate) * s) else MAX_RADIUS + 1 for s in sig)
+    if any(r > MAX_RADIUS for r in radius):
+        raise ValueError(f"{who}: the radius int(truncate * sigma + 0.5) of an axis may be at most {MAX_RADIUS} voxels, got "
+                         f"{radius} (z, y, x) from sigma {sig} voxels")
+    shape = tuple(int(s) for s in x.shape[-3:])
+    if any(s > MAX_SIDE for s in shape):
+        raise ValueError(f"{who}: every side may be at most {MAX_SIDE}, got {shape}")
+    if shape[0] * shape[1] * shape[2] >= 1 << 31:
+        raise ValueError(f"{who}: a volume must hold fewer than 2^31 voxels, got {shape}")
+    _check_out(out, x.shape, torch.float32, x.device, who)
+    _need_gpu(x, who)
+    weights = np.concatenate([gaussian_weights(s, float(truncate)) for s in sig])
+    assert weights.size == sum(radius) + 3
+    lib = _lib.load()
+    n = x.numel() // (shape[0] * shape[1] * shape[2])
+    src = x.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    nbytes = int(lib.ctu_gaussian_ws_bytes(n, *shape, radius[0]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ctu_gaussian_filter(src.data_ptr(), _CODE[x.dtype], n, *shape, (C.c_int * 3)(*radius),
+                                           (C.c_float * weights.size)(*weights.tolist()), MODES.index(mode), float(cval),
+                                           out.data_ptr(), ws.data_ptr() if nbytes else None, _stream()), who)
+    return out
+
+
+def _range_arg(rng, device, who: str):
+    """(device tensor or None, lo, hi) of a ``range`` argument that is not None."""
+    if isinstance(rng, torch.Tensor):
+        if rng.dtype != torch.float64 or tuple(rng.shape) != (2,):
+            raise ValueError(f"{who}: a range tensor must be float64 [2], got {rng.dtype} {tuple(rng.shape)}")
+        if rng.device != device:
+            raise ValueError(f"{who}: the range tensor lives on {rng.device}, the input on {device}: the kernel reads it "
+                             f"from device memory")
+        return rng.contiguous(), 0.0, 0.0
+    try:
+        lo, hi = rng
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: range must be (lo, hi), a float64 [2] device tensor or None, got {rng!r}") from None
+    if any(isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v) for v in (lo, hi)) or lo > hi:
+        raise ValueError(f"{who}: range must be finite numbers with lo <= hi, got {rng!r}")
+    return None, float(lo), float(hi)
+
+
+def _check_bins(bins, who: str) -> int:
+    if isinstance(bins, bool) or not isinstance(bins, Integral) or not 2 <= bins <= MAX_BINS:
+        raise ValueError(f"{who}: bins must be an integer in 2..{MAX_BINS}, got {bins!r}")
+    return int(bins)
+
+
+def finite_range(x: torch.Tensor) -> torch.Tensor:
+    """float64 ``[2]`` DEVICE tensor: the smallest and the largest finite value of ``x`` (``+inf, -inf`` without one)."""
+    who = "finite_range"
+    _check_input(x, who, False)
+    _need_gpu(x, who)
+    lib = _lib.load()
+    src = x.contiguous()
+    rng = torch.empty(2, dtype=torch.float64, device=x.device)
+    ws = torch.empty(int(lib.ctu_minmax_ws_bytes(src.numel())), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ctu_finite_minmax(src.data_ptr(), _CODE[x.dtype], src.numel(), rng.data_ptr(), ws.data_ptr(),
+                                         _stream()), who)
+    return rng
+
+
+def _histogram(x, bins: int, rng, out, who: str):
+    """The counts and the range they were taken over, as ``(hist, range tensor or None, lo, hi)``."""
+    if rng is None:
+        _need_gpu(x, who)
+        rt, lo, hi = finite_range(x), 0.0, 0.0
+    else:
+        rt, lo, hi = _range_arg(rng, x.device, who)
+    _check_out(out, (bins,), torch.int64, x.device, who)
+    _need_gpu(x, who)
+    lib = _lib.load()
+    src = x.contiguous()
+    if out is None:
+        out = torch.empty(bins, dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ctu_histogram(src.data_ptr(), _CODE[x.dtype], src.numel(), bins,
+                                     None if rt is None else rt.data_ptr(), lo, hi, out.data_ptr(), _stream()), who)
+    return out, rt, lo, hi
+
+
+def histogram(x: torch.Tensor, bins: int = 256, range=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 ``[bins]`` counts of the whole tensor ``x`` over equal bins of ``range`` (module docstring)."""
+    who = "histogram"
+    _check_input(x, who, False)
+    bins = _check_bins(bins, who)
+    if range is not None:
+        _range_arg(range, x.device, who)
+    _check_out(out, (bins,), torch.int64, x.device, who)
+    return _histogram(x, bins, range, out, who)[0]
+
+
+def threshold_otsu(x: Optional[torch.Tensor] = None, *, hist: Optional[torch.Tensor] = None, bins: int = 256, range=None,
+                   return_index: bool = False):
+    """Otsu's threshold (module docstring) of ``x``, or of the counts ``hist`` (int64 ``[bins]``, taken over ``range``,
+    which is required then).  A float64 0-dim DEVICE tensor; with ``return_index`` the pair ``(threshold, k*)``, ``k*`` an
+    int64 0-dim DEVICE tensor."""
+    who = "threshold_otsu"
+    if (x is None) == (hist is None):
+        raise ValueError(f"{who}: give the volume or hist=, not both and not neither")
+    if hist is not None:
+        if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() != 1:
+            raise ValueError(f"{who}: hist must be an int64 [bins] tensor")
+        bins = _check_bins(int(hist.shape[0]), who)
+        if range is None:
+            raise ValueError(f"{who}: hist= needs the range its counts were taken over")
+        rt, lo, hi = _range_arg(range, hist.device, who)
+        _need_gpu(hist, who)
+        h = hist.contiguous()
+    else:
+        _check_input(x, who, False)
+        bins = _check_bins(bins, who)
+        if range is not None:
+            _range_arg(range, x.device, who)
+        h, rt, lo, hi = _histogram(x, bins, range, None, who)
+    lib = _lib.load()
+    thr = torch.empty((), dtype=torch.float64, device=h.device)
+    idx = torch.empty((), dtype=torch.int64, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(lib.ctu_threshold_otsu(h.data_ptr(), bins, None if rt is None else rt.data_ptr(), lo, hi, thr.data_ptr(),
+                                          idx.data_ptr(), _stream()), who)
+    return (thr, idx) if return_index else thr
+
+
+def _bound(b, device, what: str, who: str):
+    """(device tensor or None, value) of a bound of ``binarize``."""
+    if isinstance(b, torch.Tensor):
+        if b.dtype != torch.float64 or b.numel() != 1:
+            raise ValueError(f"{who}: a {what} tensor must hold one float64, got {b.dtype} {tuple(b.shape)}")
+        if b.device != device:
+            raise ValueError(f"{who}: the {what} tensor lives on {b.device}, the input on {device}: the kernel reads it "
+                             f"from device memory")
+        return b, 0.0
+    if isinstance(b, bool) or not isinstance(b, Real) or math.isnan(b):
+        raise ValueError(f"{who}: {what} must be a number or a 0-dim float64 device tensor, got {b!r}")
+    return None, float(b)
+
+
+def binarize(x: torch.Tensor, lower, upper=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 ``(x > lower) & (x <= upper)`` of the shape of ``x``; a bound is a number or a 0-dim float64 DEVICE tensor."""
+    who = "binarize"
+    _check_input(x, who, False)
+    lt, lv = _bound(lower, x.device, "lower", who)
+    ut, uv = (None, math.inf) if upper is None else _bound(upper, x.device, "upper", who)
+    _check_out(out, x.shape, torch.uint8, x.device, who)
+    _need_gpu(x, who)
+    lib = _lib.load()
+    src = x.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ctu_binarize(src.data_ptr(), _CODE[x.dtype], src.numel(), None if lt is None else lt.data_ptr(), lv,
+                                    None if ut is None else ut.data_ptr(), uv, out.data_ptr(), _stream()), who)
+    return out
+
+
+def extract_skull(scan: torch.Tensor, threshold, *, spacing=None, sigma=0.0, otsu_range=None, bins: int = 256,
+                  components: int = 1, closing_radius: float = 0.0) -> torch.Tensor:
+    """The binary skull (uint8 0 / 1) of a CT ``scan [D,H,W]`` or ``[N,D,H,W]``: smoothed by ``sigma`` (units of ``spacing``),
+    ``> threshold`` (a number in the scan's units, or ``"otsu"`` over ``otsu_range``), reduced to its ``components`` largest
+    components (0: all kept) and closed by a ball of ``closing_radius`` (module docstring).  ``threshold`` has no default:
+    the Hounsfield value that counts as bone is the user's clinical choice."""
+    from . import postprocess
+    who = "extract_skull"
+    _check_input(scan, who, True)
+    if scan.dim() not in (3, 4):
+        raise ValueError(f"{who}: scan must be [D,H,W] or [N,D,H,W], got shape {tuple(scan.shape)}")
+    otsu = isinstance(threshold, str)
+    if otsu:
+        if threshold != "otsu":
+            raise ValueError(f"{who}: threshold must be a number or 'otsu', got {threshold!r}")
+        if otsu_range is None:
+            raise ValueError(f"{who}: threshold='otsu' needs otsu_range, e.g. (-200, 3000) to separate soft tissue from "
+                             f"bone: over the full range Otsu separates air from the head")
+        _range_arg(otsu_range, scan.device, who)
+        bins = _check_bins(bins, who)
+    elif isinstance(threshold, bool) or not isinstance(threshold, Real) or math.isnan(threshold):
+        raise ValueError(f"{who}: threshold must be a number or 'otsu', got {threshold!r}")
+    sig = _triple(sigma, "sigma", who, False)
+    if isinstance(components, bool) or not isinstance(components, Integral) or not 0 <= components <= postprocess.MAX_COMPONENTS:
+        raise ValueError(f"{who}: components must lie in 0..{postprocess.MAX_COMPONENTS}, got {components!r}")
+    if (isinstance(closing_radius, bool) or not isinstance(closing_radius, Real) or not math.isfinite(closing_radius)
+            or closing_radius < 0):
+        raise ValueError(f"{who}: closing_radius must be a finite number >= 0, got {closing_radius!r}")
+    if spacing is not None:
+        _triple(spacing, "spacing", who, True)
+    v = scan
+    if any(s > 0 for s in sig):
+        v = gaussian_filter(scan, sig, spacing=spacing)
+    else:
+        _need_gpu(scan, who)
+    t = threshold_otsu(v, bins=bins, range=otsu_range) if otsu else threshold
+    m = binarize(v, t)
+    if components:
+        m = postprocess.keep_largest_connected_component(m, num_components=int(components))
+    if closing_radius > 0:
+        m = postprocess.ball_closing(m, float(closing_radius), sampling=spacing)
+    return m

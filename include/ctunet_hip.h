@@ -679,6 +679,45 @@ size_t ctu_mesh_voxelize_ws_bytes(int D, int H, int W);
 int ctu_mesh_voxelize(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int D, int H, int W,
                       const float* spacing, const float* origin, int want_winding, void* out, void* ws, void* stream);
 
+/* CT preprocessing: from a scanner's volume to a binary skull (no reference counterpart: the reference's datasets load skulls
+ * that were thresholded beforehand, ctunet/pytorch/datasets.py:22-45; rules pinned in ctunet_amd/preprocess.py).  Every input
+ * `in` is a DEVICE contiguous array of dtype CTU_F32, CTU_I16 or CTU_U8, converted in the kernel.  No entry point allocates
+ * or synchronises, each is capture-safe, and two calls are bitwise equal (the only atomics add integers).
+ *   gaussian_filter: in [N,D,H,W] -> out float32 [N,D,H,W], separable, axes in the order x, y, z.  radius: HOST int [3] in
+ *                    (z, y, x), each 0..CTU_GAUSS_MAX_RADIUS; weights: HOST float, w_0..w_R of z, then of y, then of x.  One
+ *                    axis: acc = w_0 v[i]; acc = acc + w_k (v[i-k] + v[i+k]) for k = 1..R, every float32 operation rounded
+ *                    on its own.  mode: what v reads outside the axis (clamp; scipy's reflect, period 2 n; cval).
+ *                    ws: ctu_gaussian_ws_bytes() bytes (0 for an invalid shape or rz = 0), 16-byte aligned: the volume after
+ *                    x and y.  Every side <= 1024, D*H*W < 2^31.
+ *   finite_minmax:   range [2] (DEVICE double) = the smallest and the largest finite element of in [n] (+inf, -inf if none);
+ *                    ws: ctu_minmax_ws_bytes(n) bytes.
+ *   histogram:       hist [bins] (DEVICE int64, cleared by the call) over in [n], bins in 2..CTU_HISTOGRAM_MAX_BINS.  The range
+ *                    is DEVICE double [2] = (lo, hi) when `range` is given, else the HOST values lo <= hi.  In float64:
+ *                    hi == lo widens both by 0.5; scale = bins / (hi - lo); v in [lo, hi] counts in
+ *                    min(floor((v - lo) scale), bins - 1); anything else, NaN included, is not counted.  n < 2^38.
+ *   threshold_otsu:  on hist [bins] with N = sum h, S = sum k h_k and the exact int64 prefixes w1_k, s1_k (k = 0..bins-2):
+ *                    var_k = (double(w1) double(N - w1)) ((m1 - m2) (m1 - m2)), m1 = s1 / w1, m2 = (S - s1) / (N - w1), 0
+ *                    where w1 = 0 or w1 = N; index = the first maximum k*; threshold = lo + (k* + 0.5) ((hi - lo) / bins)
+ *                    with the range as in histogram.  threshold: DEVICE double [1]; index: DEVICE int64 [1] or NULL.
+ *   binarize:        out [n] (uint8 0 / 1) = in > lower && in <= upper, compared in float64.  Each bound is DEVICE double [1]
+ *                    when its pointer is given, else the HOST value (upper = +inf: no upper bound). */
+#define CTU_GAUSS_NEAREST 0
+#define CTU_GAUSS_REFLECT 1
+#define CTU_GAUSS_CONSTANT 2
+#define CTU_GAUSS_MAX_RADIUS 32
+#define CTU_HISTOGRAM_MAX_BINS 4096
+size_t ctu_gaussian_ws_bytes(int64_t N, int D, int H, int W, int rz);
+int ctu_gaussian_filter(const void* in, int dtype, int64_t N, int D, int H, int W, const int* radius, const float* weights,
+                        int mode, float cval, float* out, void* ws, void* stream);
+size_t ctu_minmax_ws_bytes(int64_t n);
+int ctu_finite_minmax(const void* in, int dtype, int64_t n, double* range, void* ws, void* stream);
+int ctu_histogram(const void* in, int dtype, int64_t n, int bins, const double* range, double lo, double hi, int64_t* hist,
+                  void* stream);
+int ctu_threshold_otsu(const int64_t* hist, int bins, const double* range, double lo, double hi, double* threshold,
+                       int64_t* index, void* stream);
+int ctu_binarize(const void* in, int dtype, int64_t n, const double* lower_dev, double lower, const double* upper_dev,
+                 double upper, uint8_t* out, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
