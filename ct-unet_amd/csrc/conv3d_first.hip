@@ -153,18 +153,28 @@ __global__ __launch_bounds__(256) void first_fwd_kernel(FirstP p, int tiles_per_
 // ------------------------------------------------------------------ input gradient: dx[v][ci] = sum g[v - tap + 1][co] W[co][ci][tap]
 template <int CIN, class T>
 __global__ __launch_bounds__(256) void first_bwd_data_kernel(FirstP p, int tiles_per_block) {
-    constexpr int TW = 32, HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW, GS = 12;
+    constexpr int TW = 32, HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW;
     constexpr int NIT = (HV * 2 + 255) / 256;
-    __shared__ __attribute__((aligned(16))) float sG[HV * GS];          // haloed gradient box, 8 channels + 4 pad per voxel
-    __shared__ __attribute__((aligned(16))) float sW[27 * CIN * 8];     // [tap (flipped)][ci][co], read as broadcasts
+    // Haloed gradient box, 8 channels (32 bytes) per voxel with no padding inside a voxel: voxel pw of a w row sits in slot
+    // pw + pw / 4 of RS = 44, so the w quads of a row start 5 slots apart and the d planes 6 * 44 = 0 (mod 8) slots apart.
+    // The 16 lanes one ds_read_b128 cycle serves (quads {0, 1, 6, 7} of one d plane and {2, 3, 4, 5} of the next, both
+    // channel halves) then fall into 8 different slots mod 8 = all 64 banks.  50.7 KB: three blocks per CU, as the grid assumes.
+    constexpr int RS = 44, GS = 8;
+    __shared__ __attribute__((aligned(16))) float sG[HD * HH * RS * GS];
+    __shared__ __attribute__((aligned(16))) float sW[27 * CIN * 8];     // [(kd, kh) row][channel half][ci][kw][4 co], taps flipped
     const int tid = threadIdx.x;
     for (int i = tid; i < 27 * CIN * 8; i += 256) {
-        const int co = i & 7, r = i >> 3, ci = r % CIN, tap = r / CIN;
-        sW[i] = co < p.Co ? p.w[((size_t)co * CIN + ci) * 27 + (26 - tap)] : 0.f;
+        const int c4 = i & 3, kw = (i >> 2) % 3, r = (i >> 2) / 3, ci = r % CIN, hf = (r / CIN) & 1, r9 = (r / CIN) >> 1;
+        const int co = hf * 4 + c4;
+        sW[i] = co < p.Co ? p.w[((size_t)co * CIN + ci) * 27 + (26 - (r9 * 3 + kw))] : 0.f;
     }
-    const int tw = tid & 15, th = (tid >> 4) & 3, td = tid >> 6;
-    const int pbase = (td * HH + th) * HW + tw;
-    const int half = tid & 1;
+    // A lane pair owns four consecutive w outputs of one (d, h) row: the even lane sums gradient channels 0-3, the odd lane
+    // channels 4-7, and the two halves of each output's pairwise tree meet in one cross-lane add.  Per (kd, kh) row a lane reads
+    // the six voxels its four outputs need once (its 16-byte half of each) and its 3 * CIN weight quads.
+    const int half = tid & 1, wq = (tid >> 1) & 7, td = (tid >> 4) & 3, th = tid >> 6;
+    const int pbase = ((td * HH + th) * RS + 5 * wq) * GS + half * 4;
+    // a pair of outputs goes out as one 8-byte store where every row of dx starts 8-byte aligned
+    const bool st2 = (p.W & 1) == 0 && ((uintptr_t)p.out & 7) == 0;
     const int64_t plane = (int64_t)p.D * p.H * p.W;
     int tile = blockIdx.x * tiles_per_block;
     const int tile_end = min(p.ntiles, tile + tiles_per_block);
@@ -189,54 +199,73 @@ __global__ __launch_bounds__(256) void first_bwd_data_kernel(FirstP p, int tiles
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int e = tid + it * 256;
-            if (e < HV * 2) *reinterpret_cast<float4*>(&sG[(e >> 1) * GS + half * 4]) = vg[it];
+            const int v = e >> 1, pw = v % HW;
+            if (e < HV * 2) *reinterpret_cast<float4*>(&sG[((v / HW) * RS + pw + (pw >> 2)) * GS + half * 4]) = vg[it];
         }
         __syncthreads();
         if (tile + 1 < tile_end) load(tile + 1);
         // 8 independent partial sums (one per gradient channel) per output and voxel: no long dependent FMA chain
-        float q0[CIN][8], q1[CIN][8];
+        float q[4][CIN][4];
 #pragma unroll
-        for (int ci = 0; ci < CIN; ++ci)
+        for (int o = 0; o < 4; ++o)
 #pragma unroll
-            for (int c = 0; c < 8; ++c) { q0[ci][c] = 0.f; q1[ci][c] = 0.f; }
+            for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) q[o][ci][c] = 0.f;
+        // the (kd, kh) rows stay rolled: unrolled by 3 the kernel needs 212 registers instead of 144 and a third block no
+        // longer fits a CU (measured slower), fully unrolled it spills
 #pragma unroll 1
-        for (int r9 = 0; r9 < 9; ++r9)                       // (kd, kh) rows stay rolled: full unrolling hoists every LDS load and spills
+        for (int kd = 0; kd < 3; ++kd)
+#pragma unroll 1
+        for (int kh = 0; kh < 3; ++kh) {
+            const float* gp = &sG[pbase + ((kd * HH + kh) * RS) * GS];
+            const float* wr = &sW[(((kd * 3 + kh) * 2 + half) * CIN) * 12];
+            float4 gv[6], wv[CIN][3];
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-            const int tap = r9 * 3 + kw;
-            const int off = (((r9 / 3) * HH + r9 % 3) * HW + kw) * GS;
-            float g0[8], g1[8];
-            *reinterpret_cast<float4*>(&g0[0]) = *reinterpret_cast<const float4*>(&sG[pbase * GS + off]);
-            *reinterpret_cast<float4*>(&g0[4]) = *reinterpret_cast<const float4*>(&sG[pbase * GS + off + 4]);
-            *reinterpret_cast<float4*>(&g1[0]) = *reinterpret_cast<const float4*>(&sG[(pbase + 16) * GS + off]);
-            *reinterpret_cast<float4*>(&g1[4]) = *reinterpret_cast<const float4*>(&sG[(pbase + 16) * GS + off + 4]);
+            for (int j = 0; j < 6; ++j) gv[j] = *reinterpret_cast<const float4*>(gp + (j + (j >> 2)) * GS);
 #pragma unroll
-            for (int ci = 0; ci < CIN; ++ci) {
-                float wv[8];
-                *reinterpret_cast<float4*>(&wv[0]) = *reinterpret_cast<const float4*>(&sW[(tap * CIN + ci) * 8]);
-                *reinterpret_cast<float4*>(&wv[4]) = *reinterpret_cast<const float4*>(&sW[(tap * CIN + ci) * 8 + 4]);
+            for (int ci = 0; ci < CIN; ++ci)
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    q0[ci][c] = fmaf(g0[c], wv[c], q0[ci][c]);
-                    q1[ci][c] = fmaf(g1[c], wv[c], q1[ci][c]);
-                }
-            }
+                for (int kw = 0; kw < 3; ++kw) wv[ci][kw] = *reinterpret_cast<const float4*>(wr + (ci * 3 + kw) * 4);
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw)                   // every partial sum takes its taps in (kd, kh, kw) order
+#pragma unroll
+                for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+                        q[o][ci][0] = fmaf(gv[o + kw].x, wv[ci][kw].x, q[o][ci][0]);
+                        q[o][ci][1] = fmaf(gv[o + kw].y, wv[ci][kw].y, q[o][ci][1]);
+                        q[o][ci][2] = fmaf(gv[o + kw].z, wv[ci][kw].z, q[o][ci][2]);
+                        q[o][ci][3] = fmaf(gv[o + kw].w, wv[ci][kw].w, q[o][ci][3]);
+                    }
         }
-        float a0[CIN], a1[CIN];
+        // ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)): each lane forms its half, the pair's other lane supplies the rest
+        // the even lane finishes and stores outputs 0 and 1, the odd lane outputs 2 and 3
+        float o0[CIN], o1[CIN];
 #pragma unroll
         for (int ci = 0; ci < CIN; ++ci) {
-            a0[ci] = ((q0[ci][0] + q0[ci][1]) + (q0[ci][2] + q0[ci][3])) + ((q0[ci][4] + q0[ci][5]) + (q0[ci][6] + q0[ci][7]));
-            a1[ci] = ((q1[ci][0] + q1[ci][1]) + (q1[ci][2] + q1[ci][3])) + ((q1[ci][4] + q1[ci][5]) + (q1[ci][6] + q1[ci][7]));
+            const float m0 = (q[0][ci][0] + q[0][ci][1]) + (q[0][ci][2] + q[0][ci][3]);
+            const float m1 = (q[1][ci][0] + q[1][ci][1]) + (q[1][ci][2] + q[1][ci][3]);
+            const float m2 = (q[2][ci][0] + q[2][ci][1]) + (q[2][ci][2] + q[2][ci][3]);
+            const float m3 = (q[3][ci][0] + q[3][ci][1]) + (q[3][ci][2] + q[3][ci][3]);
+            const float r0 = __shfl_xor(half ? m0 : m2, 1), r1 = __shfl_xor(half ? m1 : m3, 1);
+            const float k0 = half ? m2 : m0, k1 = half ? m3 : m1;
+            o0[ci] = half ? r0 + k0 : k0 + r0;                // channels 0-3 first, as in the tree
+            o1[ci] = half ? r1 + k1 : k1 + r1;
         }
         int n, d0, h0, w0;
         box_origin(p, tile, TW, n, d0, h0, w0);
-        const int gd = d0 + td, gh = h0 + th;
+        const int gd = d0 + td, gh = h0 + th, gw = w0 + 4 * wq + 2 * half;
         if (gd < p.D && gh < p.H) {
 #pragma unroll
             for (int ci = 0; ci < CIN; ++ci) {
-                float* dst = reinterpret_cast<float*>(p.out) + ((int64_t)n * CIN + ci) * plane + ((int64_t)gd * p.H + gh) * p.W;
-                if (w0 + tw < p.W) dst[w0 + tw] = a0[ci];
-                if (w0 + tw + 16 < p.W) dst[w0 + tw + 16] = a1[ci];
+                float* dst = reinterpret_cast<float*>(p.out) + ((int64_t)n * CIN + ci) * plane + ((int64_t)gd * p.H + gh) * p.W + gw;
+                if (st2) {
+                    if (gw < p.W) *reinterpret_cast<float2*>(dst) = make_float2(o0[ci], o1[ci]);
+                } else {
+                    if (gw < p.W) dst[0] = o0[ci];
+                    if (gw + 1 < p.W) dst[1] = o1[ci];
+                }
             }
         }
         ++tile;

@@ -42,7 +42,7 @@ __device__ __forceinline__ int tap_off(int tap, int H, int W) {
 // from the fine grid, accumulated over the 8 taps, one store).
 // The MFMA operands are swapped (weights as the row operand, voxels as the column operand) so that a
 // lane ends up with 4 CONSECUTIVE output channels of one voxel: the epilogue is one 16-byte store per
-// lane instead of four scattered dword stores.  `tps` taps' weights are staged per barrier pair.
+// lane instead of four scattered dword stores.  `tps` taps' weights make one stage.
 template <int NTT, int MODE>
 __global__ __launch_bounds__(256) void convt2_kernel(CtP p, int tps) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -75,104 +75,161 @@ __global__ __launch_bounds__(256) void convt2_kernel(CtP p, int tps) {
 #pragma unroll
     for (int nt = 0; nt < NTT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    for (int tap0 = 0; tap0 < 8; tap0 += tps) {
-        __syncthreads();
-        // Staging is all latency here (deep levels: a few hundred blocks, one per CU): every batch of loads is issued
-        // together, branch-free (items past the end re-read a valid address and are not stored), then stored.
-        if (MODE == 0 && tap0 == 0) {
-            f32x4 va[GMAX];
+    // Staging is all latency here (deep levels: a few hundred blocks, one per CU), so nothing is fetched when it is needed:
+    // every batch of loads is issued together, branch-free (items past the end re-read a valid address and are not stored),
+    // into registers, one stage ahead of its use, and goes to LDS between two barriers after the MFMAs that read the stage
+    // it replaces (the planned LDS holds one weight stage and one A image, so the second stage lives in registers).
+    const int tot = tps * wfl;                        // floats of one weight stage
+    f32x4 wv[8], vg[GMAX];
+    // packed weights: [tap][g][ntt_total][128]; this block takes tiles by*NTT .. by*NTT+NTT-1.  Chunk c of a stage is the
+    // floats [c * 8192, c * 8192 + 8192): chunk 0 is the one that is fetched ahead, a 128-channel x 128-channel stage has two.
+    auto w_issue = [&](int tap0, int c) {
 #pragma unroll
-            for (int k = 0; k < GMAX; ++k) {
-                const int it = tid + k * 256;
-                const int vl = it / nq, qd = it % nq;
+        for (int k = 0; k < 8; ++k) {
+            const int i1 = tid * 4 + (c * 8 + k) * 1024;
+            const int i = i1 < tot ? i1 : 0;
+            const int tl = i / wfl, rem = i % wfl, g = rem / (NTT * 128), r = rem % (NTT * 128);
+            // (a 32-bit offset: the packed weights are at most 512 KB, and 64-bit address arithmetic costs 8 registers)
+            wv[k] =*reinterpret_cast<const f32x4*>(p.wp + (unsigned)((((tap0 + tl) * ng + g) * p.ntt_total + by * NTT) * 128 + r));
+        }
+    };
+    auto w_store = [&](int c) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i1 = tid * 4 + (c * 8 + k) * 1024;
+            if (i1 < tot) *reinterpret_cast<f32x4*>(&sW[i1]) = wv[k];
+        }
+    };
+    auto w_rest = [&](int tap0) {                     // what chunk 0 does not hold, fetched where it is stored
+        for (int c = 1; c * 8192 < tot; ++c) { w_issue(tap0, c); w_store(c); }
+    };
+    // MODE 0: the block's 64 input voxels; MODE 1: one tap's fine-grid voxels of the block's 64 coarse voxels
+    auto a_issue = [&](int tap) {
+        const int toff = MODE == 1 ? tap_off(tap, p.H, p.W) : 0;
+#pragma unroll
+        for (int k = 0; k < GMAX; ++k) {
+            const int it = tid + k * 256;
+            const int vl = it / nq, qd = it % nq;
+            if (MODE == 0) {
                 const bool ok = it < 64 * nq && v0 + vl < p.nvox;
-                va[k] = *reinterpret_cast<const f32x4*>(p.in + (ok ? (size_t)(v0 + vl) * p.in_cs : (size_t)0) + qd * 4);
+                vg[k] = *reinterpret_cast<const f32x4*>(p.in + (ok ? (size_t)(v0 + vl) * p.in_cs : (size_t)0) + qd * 4);
+            } else {
+                const bool ok = gbase[k] != (size_t)-1;
+                vg[k] = *reinterpret_cast<const f32x4*>(p.in + (ok ? (gbase[k] + toff) * p.in_cs : (size_t)0) + qd * 4);
             }
+        }
+    };
+    auto a_store = [&]() {
 #pragma unroll
-            for (int k = 0; k < GMAX; ++k) {
-                const int it = tid + k * 256;
-                const int vl = it / nq, qd = it % nq;
-                if (it < 64 * nq) {
-                    float4 val = make_float4(va[k][0], va[k][1], va[k][2], va[k][3]);
-                    if (has_xf)
-                        val = xform4(val, *reinterpret_cast<const float4*>(p.in_scale + qd * 4),
-                                     *reinterpret_cast<const float4*>(p.in_shift + qd * 4), p.in_relu);
+        for (int k = 0; k < GMAX; ++k) {
+            const int it = tid + k * 256;
+            const int vl = it / nq, qd = it % nq;
+            if (it < 64 * nq) {
+                if (MODE == 0) {
+                    float4 val = make_float4(vg[k][0], vg[k][1], vg[k][2], vg[k][3]);
+                    if (has_xf)                       // the transform's rows wait in the weight stage's LDS (below)
+                        val = xform4(val, *reinterpret_cast<const float4*>(&sW[qd * 4]),
+                                     *reinterpret_cast<const float4*>(&sW[(nq + qd) * 4]), p.in_relu);
                     if (v0 + vl >= p.nvox) val = make_float4(0.f, 0.f, 0.f, 0.f);
                     *reinterpret_cast<float4*>(&sA[vl * AS + qd * 4]) = val;
-                }
-            }
-        }
-        {
-            // packed weights: [tap][g][ntt_total][128]; this block takes tiles by*NTT .. by*NTT+NTT-1
-            const int tot = tps * wfl;
-            for (int i0 = tid * 4; i0 < tot; i0 += 8 * 1024) {
-                f32x4 wv[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = (i0 + k * 1024 < tot) ? i0 + k * 1024 : i0;
-                    const int tl = i / wfl, rem = i % wfl, g = rem / (NTT * 128), r = rem % (NTT * 128);
-                    wv[k] = *reinterpret_cast<const f32x4*>(p.wp + ((size_t)((tap0 + tl) * ng + g) * p.ntt_total + by * NTT) * 128 + r);
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (i0 + k * 1024 < tot) *reinterpret_cast<f32x4*>(&sW[i0 + k * 1024]) = wv[k];
-            }
-        }
-        if (MODE == 0) __syncthreads();
-        for (int tl = 0; tl < tps; ++tl) {
-            const int tap = tap0 + tl;
-            if (MODE == 1) {
-                // gather this tap's fine-grid voxels (the block's 64 coarse voxels) into sA
-                __syncthreads();
-                const int toff = tap_off(tap, p.H, p.W);
-                f32x4 vg[GMAX];
-#pragma unroll
-                for (int k = 0; k < GMAX; ++k) {
-                    const int qd = (tid + k * 256) % nq;
+                } else {
                     const bool ok = gbase[k] != (size_t)-1;
-                    vg[k] = *reinterpret_cast<const f32x4*>(p.in + (ok ? (gbase[k] + toff) * p.in_cs : (size_t)0) + qd * 4);
-                }
-#pragma unroll
-                for (int k = 0; k < GMAX; ++k) {
-                    const int it = tid + k * 256;
-                    if (it < 64 * nq) {
-                        const int vl = it / nq, qd = it % nq;
-                        const bool ok = gbase[k] != (size_t)-1;
-                        *reinterpret_cast<f32x4*>(&sA[vl * AS + qd * 4]) = ok ? vg[k] : f32x4{0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-                __syncthreads();
-            } else {
-#pragma unroll
-                for (int nt = 0; nt < NTT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            const float* arow = &sA[(wave * 16 + m) * AS + kq * 2];
-            const float* brow = &sW[tl * wfl + kq * 32 + m * 2];
-            for (int g = 0; g < ng; ++g) {
-                const float2 a = *reinterpret_cast<const float2*>(arow + g * 8);
-#pragma unroll
-                for (int nt = 0; nt < NTT; ++nt) {
-                    const float2 b = *reinterpret_cast<const float2*>(brow + (g * NTT + nt) * 128);
-                    // rows = output channels (weights), columns = voxels
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[nt], 0, 0, 0);
+                    *reinterpret_cast<f32x4*>(&sA[vl * AS + qd * 4]) = ok ? vg[k] : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }
-            if (MODE == 0 && vme < p.nvox) {
-                float* orow = p.out + (fme + tap_off(tap, p.H, p.W)) * p.out_cs;
+        }
+    };
+
+    // the bias quads of this lane's output channels (the loop below stores between its loads: it would fetch them per tap)
+    float4 bv[NTT];
 #pragma unroll
-                for (int nt = 0; nt < NTT; ++nt) {
-                    const int co = (by * NTT + nt) * 16 + kq * 4;   // this lane: channels co .. co+3 of voxel vme
-                    if (co < p.nout_p) {
-                        float4 o;
-                        o.x = acc[nt][0] + ((p.bias && co + 0 < p.nbias) ? p.bias[co + 0] : 0.f);
-                        o.y = acc[nt][1] + ((p.bias && co + 1 < p.nbias) ? p.bias[co + 1] : 0.f);
-                        o.z = acc[nt][2] + ((p.bias && co + 2 < p.nbias) ? p.bias[co + 2] : 0.f);
-                        o.w = acc[nt][3] + ((p.bias && co + 3 < p.nbias) ? p.bias[co + 3] : 0.f);
-                        *reinterpret_cast<float4*>(orow + co) = o;
-                    }
+    for (int nt = 0; nt < NTT; ++nt) {
+        const int co = (by * NTT + nt) * 16 + kq * 4;
+        bv[nt].x = (MODE == 0 && p.bias && co + 0 < p.nbias) ? p.bias[co + 0] : 0.f;
+        bv[nt].y = (MODE == 0 && p.bias && co + 1 < p.nbias) ? p.bias[co + 1] : 0.f;
+        bv[nt].z = (MODE == 0 && p.bias && co + 2 < p.nbias) ? p.bias[co + 2] : 0.f;
+        bv[nt].w = (MODE == 0 && p.bias && co + 3 < p.nbias) ? p.bias[co + 3] : 0.f;
+    }
+    // The input transform's scale and shift rows (2 * rin_p floats) pass through the start of the weight stage's LDS, which is
+    // free until the first stage lands: read from global memory where they are used, each item paid a round trip of its own.
+    const bool xf_stage = MODE == 0 && has_xf;
+    float4 xfv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xf_stage && tid < 2 * nq) xfv = *reinterpret_cast<const float4*>((tid < nq ? p.in_scale : p.in_shift - p.rin_p) + tid * 4);
+    a_issue(0);                                       // the A image and the first weight stage travel together
+    w_issue(0, 0);
+    if (xf_stage) {
+        if (tid < 2 * nq) *reinterpret_cast<float4*>(&sW[tid * 4]) = xfv;
+        __syncthreads();
+    }
+    a_store();
+    if (xf_stage) __syncthreads();
+    w_store(0);
+    w_rest(0);
+    __syncthreads();
+    const float* arow = &sA[(wave * 16 + m) * AS + kq * 2];
+    for (int tap = 0; tap < 8; ++tap) {
+        const int tl = tap & (tps - 1);               // tps is a power of two
+        const bool swap_w = tl == tps - 1 && tap < 7;
+        if (tl == 0 && tap + tps < 8) w_issue(tap + tps, 0);     // the next stage's weights fly under this stage's MFMAs
+        if (MODE == 1 && tap < 7) a_issue(tap + 1);             // and so does the next tap's gather
+        if (MODE == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NTT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const float* brow = &sW[tl * wfl + kq * 32 + m * 2];
+        // rows = output channels (weights), columns = voxels; K ascending over the 8-channel groups, .x then .y.  One wave per
+        // SIMD: nobody else covers an LDS read, so the fragments of the next pair of groups are read before this pair's MFMAs.
+        auto frag = [&](int g, float2& fa, float2 (&fb)[NTT]) {
+            fa = *reinterpret_cast<const float2*>(arow + g * 8);
+#pragma unroll
+            for (int nt = 0; nt < NTT; ++nt) fb[nt] = *reinterpret_cast<const float2*>(brow + (g * NTT + nt) * 128);
+        };
+        auto mma = [&](const float2& fa, const float2 (&fb)[NTT]) {
+#pragma unroll
+            for (int nt = 0; nt < NTT; ++nt) {
+                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[nt].x, fa.x, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[nt].y, fa.y, acc[nt], 0, 0, 0);
+            }
+        };
+        const int np = ng >> 1;
+        float2 a0, a1, b0[NTT], b1[NTT], c0, c1, d0[NTT], d1[NTT];           // two register sets, used in turn
+        if (np) { frag(0, a0, b0); frag(1, a1, b1); }
+        int pr = 0;
+        for (; pr + 2 <= np; pr += 2) {
+            frag(2 * pr + 2, c0, d0);
+            frag(2 * pr + 3, c1, d1);
+            mma(a0, b0);
+            mma(a1, b1);
+            const int gn = pr + 2 < np ? 2 * pr + 4 : 2 * pr;     // past the last pair: an earlier one again (inside the stage, unused)
+            frag(gn, a0, b0);
+            frag(gn + 1, a1, b1);
+            mma(c0, d0);
+            mma(c1, d1);
+        }
+        if (pr < np) {                                // an odd number of pairs: the last one is in the first set
+            mma(a0, b0);
+            mma(a1, b1);
+        }
+        if (ng & 1) {                                 // ng = 1, odd ng: the last group
+            frag(ng - 1, a0, b0);
+            mma(a0, b0);
+        }
+        if (MODE == 0 && vme < p.nvox) {
+            float* orow = p.out + (fme + tap_off(tap, p.H, p.W)) * p.out_cs;
+#pragma unroll
+            for (int nt = 0; nt < NTT; ++nt) {
+                const int co = (by * NTT + nt) * 16 + kq * 4;   // this lane: channels co .. co+3 of voxel vme
+                if (co < p.nout_p) {
+                    *reinterpret_cast<float4*>(orow + co) =
+                        make_float4(acc[nt][0] + bv[nt].x, acc[nt][1] + bv[nt].y, acc[nt][2] + bv[nt].z, acc[nt][3] + bv[nt].w);
                 }
             }
+        }
+        if (swap_w || (MODE == 1 && tap < 7)) {
+            __syncthreads();                          // every wave is done with the stage that is replaced
+            if (swap_w) { w_store(0); w_rest(tap + 1); }
+            if (MODE == 1) a_store();
+            __syncthreads();
         }
     }
     if (MODE == 1 && vme < p.nvox) {
