@@ -146,6 +146,10 @@ SIGNATURES = {
     "ctu_mesh_smooth": (I, [P, L, P, P, L, P, I, F, I, F, P, P, P]),
     "ctu_mesh_voxelize_ws_bytes": (Z, [I, I, I]),
     "ctu_mesh_voxelize": (I, [P, L, P, L, I, I, I, P, P, I, P, P, P]),
+    "ctu_mesh_grid_ws_bytes": (Z, [L, L]),
+    "ctu_mesh_grid_build": (I, [P, L, P, L, F, L, P, P, P]),
+    "ctu_mesh_grid_emit": (I, [P, L, L, L, L, P, P, P, P]),
+    "ctu_mesh_distance": (I, [P, L, P, P, L, P, I, I, I, P, L, I, I, I, P, P, F, F, P, P, P, P]),
     "ctu_gaussian_ws_bytes": (Z, [L, I, I, I, I]),
     "ctu_gaussian_filter": (I, [P, I, L, I, I, I, P, P, I, F, P, P, P]),
     "ctu_minmax_ws_bytes": (Z, [L]),

@@ -1,7 +1,8 @@
 """Surface meshes of label volumes and scalar fields on the GPU, their smoothing, their voxelisation back onto a grid, and
 their export and import as binary STL: the last step of the segmentation-to-implant pipeline and the way back from it
 (``ctu_mesh_count`` / ``ctu_mesh_emit`` / ``ctu_mesh_measure`` of ``csrc/mesh.hip``, ``ctu_mesh_adjacency_*`` /
-``ctu_mesh_smooth`` of ``csrc/mesh_smooth.hip``, ``ctu_mesh_voxelize`` of ``csrc/mesh_voxelize.hip``); no CPU fallback.
+``ctu_mesh_smooth`` of ``csrc/mesh_smooth.hip``, ``ctu_mesh_voxelize`` of ``csrc/mesh_voxelize.hip``, ``ctu_mesh_grid_*`` /
+``ctu_mesh_distance`` of ``csrc/mesh_distance.hip``); no CPU fallback.
 
     m = mesh.extract_surface(implant, spacing=(0.8, 0.45, 0.45))      # Mesh: vertices [V,3] (z, y, x) in mm, faces [F,3]
     m = mesh.smooth(m)                                                # Taubin: the staircase goes, the volume stays
@@ -11,6 +12,9 @@ their export and import as binary STL: the last step of the segmentation-to-impl
     metrics.surface_metrics(v, truth, ...)                            # the smoothed implant scored as a volume
     w = mesh.winding_number(m, scan.shape, spacing=(0.8, 0.45, 0.45))  # int32: outside {0, 1} where a mesh self-intersects
     other = mesh.read_stl("designed_elsewhere.stl")                    # host Mesh; move both fields with .to("cuda")
+    moved = mesh.point_distance(mesh.smooth(m).vertices, m).max()      # mm: how far smoothing moved the surface
+    sdf = mesh.distance_field(other, scan.shape, spacing=(0.8, 0.45, 0.45), max_distance=5.0, signed=True)   # mm, < 0 inside
+    metrics.mesh_surface_metrics(m, other, tolerance=1.0)              # HD, HD95, ASSD, NSD between two meshes, in mm
 
 ``volume`` is one ``[D,H,W]`` tensor.  Meshes are ragged (V and F depend on the data), so a batch is a Python loop over its
 items.  bool, uint8 and int64 volumes are masks or label maps: inside = ``v != 0``, or ``v == label`` with ``label=``;
@@ -124,8 +128,50 @@ every mask ``M``, ``voxelize(extract_surface(M), M.shape) == M`` bit for bit, an
 ``read_stl`` is the host-side inverse of ``write_stl``: binary STL only, the stored corners welded where their three float32
 values are bit-equal, vertices numbered in order of first appearance, faces in file order and winding, normals ignored.
 
+**Distance to a mesh** (``build_face_grid`` / ``point_distance`` / ``distance_field``; ``tests/mesh_distance_ref.py`` restates
+the rule in numpy as brute force over all faces): the missing inverse, mesh in, distance out, at any points or on any grid.
+
+- **Distance from a point to a face.**  float64; ``p`` is the query widened (or a grid centre, formed as above), ``a, b, c``
+  the face's corners in face order, float32 widened, all in (z, y, x); ``n = (b - a) x (c - a)``.  The squared distance to a
+  segment ``u-v``: ``t = ((p - u) . (v - u)) / |v - u|^2`` clamped to [0, 1] (a segment of zero length is its endpoint, ``t = 0``),
+  closest point ``q = u + t (v - u)``, ``|p - q|^2``.  The squared distance to the face is the minimum over its three edge segments
+  ``a-b``, ``b-c``, ``c-a`` (the first wins a tie) and, where ``|n|^2 > 0`` and the three edge functions ``((b-a) x (p-a)) . n``,
+  ``((c-b) x (p-b)) . n`` and ``((a-c) x (p-c)) . n`` are all >= 0, also the plane term ``((p-a) . n)^2 / |n|^2`` where it is
+  smaller, with closest point ``p - (((p-a) . n) / |n|^2) n``.  Every product, difference, sum and division is rounded on its
+  own (contraction is off on the device); a dot product is ``(x + y) + z``.  This form is continuous across the edge / interior
+  classification, so a sliver that is classified one way or the other by rounding costs nothing; against the textbook
+  region-based closest-point algorithm it agrees to 1e-16 of the scene's diagonal (``tests/test_mesh_distance_cpu.py``).
+- **Degenerate faces.**  A face with a repeated index, or with collinear corners, is its segments; nothing is skipped for lack
+  of area (``extract_surface`` gives such faces for samples equal to ``level``).
+- **Distance from a point to a mesh.**  The minimum over the faces of the squared distance, ``sqrt`` in float64, rounded to
+  float32 once.  The reported face is the lowest face index among those whose computed squared distance equals the minimum;
+  the reported closest point is that face's closest point rounded to float32.
+- **Refused input.**  A face with an index outside ``[0, V)`` or a vertex that is not finite is never read through; it is
+  counted and the call raises ``ValueError``, as ``voxelize`` does.  A query that is not finite gives NaN, face -1, closest
+  point NaN and touches no face.  With ``F == 0`` every distance is ``+inf`` and every face -1, without a launch of the kernels.
+- **max_distance.**  A positive finite float32, or ``None``.  A query whose squared distance exceeds ``float64(max_distance)^2``
+  gives ``+inf``, face -1 and closest point NaN (``distance_field`` stores ``max_distance`` there: a truncated field), and the
+  search may stop there.  ``None`` is unbounded and exact at any distance; its cost grows with the distance of the query from
+  the mesh.
+- **Face grid.**  ``FaceGrid``: a uniform grid of cubic cells over the bounding box of the vertices the accepted faces use;
+  ``floor(extent / cell_size) + 1`` cells per axis and one cell for an axis of zero extent (a planar mesh, a single triangle,
+  coinciding vertices), at most ``min(2^24, max(65536, 64 F))`` cells.  Every face is listed in every cell its bounding box
+  overlaps: count, scan, fill, with integer atomics only for the counts and the fill cursors, so the order of a cell's list
+  depends on arrival and nothing else does.  One host synchronisation reads the pair count, the cell count and the
+  refused-face count.
+- **Search.**  A lane per query: from the query's cell, clamped into the grid, shells of cells outward.  A cell is skipped, and
+  the search stops at a shell, only where a lower bound of the distance to it exceeds the best squared distance so far (or
+  ``max_distance^2``), strictly; the bound is lowered by 2^-45 of the coordinates' magnitude before it is squared, which
+  covers the rounding of the bound and of the cells' indices, so rounding can only lower it.  Every face that attains the
+  minimum is therefore evaluated, each with the same arithmetic wherever it is met: the result is a function of the rule
+  alone, does not depend on the cell size or on the order of a cell's list, and two calls are bit-equal.
+- **Sign.**  Only grid centres get one: ``distance_field(signed=True)`` takes it from ``winding_number``.
+
+Limits of the distance functions: V, F, Q and the face-cell pairs < 2^31; ``distance_field`` has ``voxelize``'s grid limits.
+
 Out of scope: decimation, formats other than binary STL, marching cubes.
-Out of scope of voxelisation: anti-aliased coverage, signed distance to a mesh, mesh repair.
+Out of scope of voxelisation: anti-aliased coverage, mesh repair.
+Out of scope of the distance functions: the sign at arbitrary points, area-weighted or resampled surface metrics, a BVH.
 """
 from __future__ import annotations
 
@@ -145,6 +191,8 @@ SCAN_BLOCK = 1024          # CTU_MESH_SCAN_BLOCK: more cell rows, (D+1)(H+1), th
 _MEASURE_WS = 16384        # CTU_MESH_MEASURE_WS
 ADJ_SCAN_CHUNK = 4096      # CTU_MESH_ADJ_SCAN_CHUNK: more vertices than this take the adjacency scan's second level
 MAX_ITERATIONS = 10000     # CTU_MESH_SMOOTH_MAX_ITERATIONS
+MAX_CELLS = 1 << 24        # CTU_MESH_GRID_MAX_CELLS: no face grid has more cells
+MIN_CELL_CAP = 1 << 16     # a grid of F faces has at most min(MAX_CELLS, max(MIN_CELL_CAP, 64 F)) cells
 _MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
 _DTYPES = _MASK_DTYPES + (torch.float32,)
 CTU_F32, CTU_U8, CTU_I64 = 0, 3, 4
@@ -161,6 +209,21 @@ class Adjacency(NamedTuple):
     device; the neighbours of vertex i are ``neighbours[offsets[i]:offsets[i+1]]``, ascending."""
     offsets: torch.Tensor
     neighbours: torch.Tensor
+
+
+class FaceGrid(NamedTuple):
+    """The uniform grid of face lists ``point_distance`` and ``distance_field`` search (CSR over the cells in C order):
+    ``offsets`` int32 [cells+1] and ``faces`` int32 [pairs]: the faces whose bounding box overlaps cell c are
+    ``faces[offsets[c]:offsets[c+1]]``, in no particular order; ``corners`` float32 [F,12]: the nine coordinates of every
+    face (a, b, c in (z, y, x)) and three words of padding; ``frame`` float64 [6]: the lower corner of the grid and the
+    cell size per axis; all on the mesh's device.  ``dims``: the cells per axis (nz, ny, nx), and ``cell_size``: the side of
+    a cell, both on the host."""
+    offsets: torch.Tensor
+    faces: torch.Tensor
+    corners: torch.Tensor
+    frame: torch.Tensor
+    dims: tuple
+    cell_size: float
 
 
 def _shape(shape) -> tuple:
@@ -485,6 +548,229 @@ def winding_number(m: Mesh, shape, spacing=None, origin=None) -> torch.Tensor:
     """int32 ``[D,H,W]``: the winding numbers ``voxelize`` thresholds, through the same device path: 0 / 1 for a closed
     outward-wound mesh, 0 / -1 for an inward-wound one, other values where a (smoothed) mesh intersects itself."""
     return _voxelize(m, shape, spacing, origin, True, "winding_number")
+
+
+def _max_cells(F: int) -> int:
+    return min(MAX_CELLS, max(MIN_CELL_CAP, 64 * int(F)))
+
+
+def _cell_size(cell_size):
+    if cell_size is None:
+        return 0.0
+    c = ctypes.c_float(float(cell_size)).value if isinstance(cell_size, Real) and not isinstance(cell_size, bool) else None
+    if c is None or not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"mesh: cell_size must be None or positive and finite in float32, got {cell_size!r}")
+    return c
+
+
+def distance_workspace_bytes(V: int, F: int, cell_size=None) -> int:
+    """The most device memory (bytes) one ``build_face_grid`` call on a contiguous mesh of V vertices and F faces allocates
+    besides the ``FaceGrid`` it returns: the build's workspace ``ctu_mesh_grid_ws_bytes(F, max_cells)``, where ``max_cells =
+    min(2^24, max(65536, 64 F))`` caps the cells of the grid: 256 bytes, 64 per block of 256 faces, 8 per cell of the cap and
+    8 per scan chunk of 4096 cells, each array rounded up to 256.  It does not depend on V or on ``cell_size`` (the cap
+    holds for every size), which are validated and otherwise unused.  The ``FaceGrid`` itself holds 48 bytes per face,
+    4 per cell and 4 per face-cell pair.  ``point_distance`` and ``distance_field`` with ``grid=`` allocate their results
+    and nothing else; without it they build the grid first."""
+    if any(isinstance(n, bool) or not isinstance(n, Integral) for n in (V, F)) or V < 0 or F < 0 or V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"mesh: distance_workspace_bytes takes 0 <= V < 2^31 and 0 <= F < 2^31, got {V!r}, {F!r}")
+    _cell_size(cell_size)
+    if F == 0:
+        return 0
+    return int(_lib.load().ctu_mesh_grid_ws_bytes(int(F), _max_cells(F)))
+
+
+def _empty_grid(dev) -> FaceGrid:
+    return FaceGrid(torch.zeros(2, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                    torch.empty((0, 12), dtype=torch.float32, device=dev),
+                    torch.tensor([0.0, 0.0, 0.0, 1.0, 1.0, 1.0], dtype=torch.float64, device=dev), (1, 1, 1), 1.0)
+
+
+def build_face_grid(m: Mesh, cell_size: Optional[float] = None) -> FaceGrid:
+    """The ``FaceGrid`` of a mesh on the GPU, by the module docstring's rule: what ``point_distance`` and ``distance_field``
+    search, reusable for any number of queries against the same mesh (it holds the faces' coordinates: rebuild it when the
+    vertices move).  ``cell_size``: the side of a cell in the units of the vertices, rounded to float32; ``None``: twice the
+    mean largest extent of a face, which lists a few faces per cell for the meshes ``extract_surface`` gives, doubled until
+    the grid has at most ``min(2^24, max(65536, 64 F))`` cells.  A given ``cell_size`` that needs more cells than that, or any
+    that lists 2^31 face-cell pairs or more, raises ``ValueError`` (a face is listed in every cell its bounding box
+    overlaps, so a cell far smaller than the faces multiplies the pairs).  The result of a query does not depend on
+    ``cell_size``; its speed does.  The call synchronises with the host once, to read the pair count, the cell count and the
+    refused-face count; a face index outside ``[0, V)`` or a vertex that is not finite raises (such faces are listed
+    nowhere and never read through).  A mesh without faces gives an empty one-cell grid without any launch."""
+    v, f = _check_mesh(m, "build_face_grid")
+    V, F = v.shape[0], f.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"mesh: build_face_grid takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
+    size = _cell_size(cell_size)
+    if not v.is_cuda:
+        raise ValueError("mesh: build_face_grid takes a mesh on the GPU; this path has no CPU fallback")
+    dev = v.device
+    if F == 0:
+        return _empty_grid(dev)
+    lib = _lib.load()
+    v, f = v.contiguous(), f.contiguous()
+    cap = _max_cells(F)
+    corners = torch.empty((F, 12), dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.ctu_mesh_grid_ws_bytes(F, cap), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_grid_build(v.data_ptr(), V, f.data_ptr(), F, size, cap, corners.data_ptr(), ws.data_ptr(), stream),
+                   "mesh_grid_build")
+        head = ws[:104].cpu()                                           # the call's one host synchronisation
+        pairs, bad, cells, overflow, nz, ny, nx = head[:56].view(torch.int64).tolist()
+        lo_h = head[56:104].view(torch.float64).tolist()
+        if bad:
+            raise ValueError(f"mesh: a face refers to a vertex that does not exist or is not finite ({bad} of {F} faces hold an "
+                             f"index outside [0, {V}) or a NaN / infinite coordinate)")
+        if overflow:
+            raise ValueError(f"mesh: cell_size={cell_size!r} needs more than {cap} cells for this mesh; choose a larger cell_size")
+        if pairs >= 1 << 31:
+            raise ValueError(f"mesh: the face grid lists {pairs} face-cell pairs; they must stay below 2^31: choose a larger cell_size")
+        offsets = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+        items = torch.empty(pairs, dtype=torch.int32, device=dev)
+        frame = ws[56:104].view(torch.float64).clone()
+        _lib.check(lib.ctu_mesh_grid_emit(corners.data_ptr(), F, cap, cells, pairs, offsets.data_ptr(),
+                                          items.data_ptr() if pairs else None, ws.data_ptr(), stream), "mesh_grid_emit")
+    return FaceGrid(offsets, items, corners, frame, (nz, ny, nx), lo_h[3])
+
+
+def _check_grid(grid, F: int, dev) -> FaceGrid:
+    if not (isinstance(grid, tuple) and len(grid) == 6 and all(isinstance(t, torch.Tensor) for t in grid[:4])):
+        raise ValueError(f"mesh: grid must be a FaceGrid (the result of build_face_grid), got {type(grid).__name__}")
+    off, items, corners, frame, dims, _ = grid
+    if off.dtype != torch.int32 or items.dtype != torch.int32 or off.dim() != 1 or items.dim() != 1:
+        raise ValueError(f"mesh: the grid's offsets and faces must be int32 vectors, got {off.dtype} {tuple(off.shape)} and "
+                         f"{items.dtype} {tuple(items.shape)}")
+    if corners.dtype != torch.float32 or tuple(corners.shape) != (F, 12):
+        raise ValueError(f"mesh: the grid belongs to another mesh: corners must be float32 [{F}, 12], got {corners.dtype} "
+                         f"{tuple(corners.shape)}")
+    if frame.dtype != torch.float64 or tuple(frame.shape) != (6,):
+        raise ValueError(f"mesh: the grid's frame must be float64 [6], got {frame.dtype} {tuple(frame.shape)}")
+    try:
+        dims = tuple(dims)
+    except TypeError:
+        dims = ()
+    if len(dims) != 3 or any(isinstance(n, bool) or not isinstance(n, Integral) or n < 1 for n in dims) \
+            or dims[0] * dims[1] * dims[2] > MAX_CELLS or off.shape[0] != dims[0] * dims[1] * dims[2] + 1:
+        raise ValueError(f"mesh: the grid's dims must be three positive integers with at most {MAX_CELLS} cells and "
+                         f"offsets one entry per cell and one, got dims {grid[4]!r} and {off.shape[0]} offsets")
+    if items.shape[0] >= 1 << 31:
+        raise ValueError(f"mesh: the grid must list fewer than 2^31 face-cell pairs, got {items.shape[0]}")
+    if any(t.device != dev for t in (off, items, corners, frame)):
+        raise ValueError("mesh: the grid must live on the mesh's device")
+    return FaceGrid(off.contiguous(), items.contiguous(), corners.contiguous(), frame.contiguous(), tuple(int(n) for n in dims), grid[5])
+
+
+def _max_distance(max_distance, who: str, required: bool) -> float:
+    if max_distance is None and not required:
+        return 0.0
+    md = None
+    if isinstance(max_distance, Real) and not isinstance(max_distance, bool):
+        md = ctypes.c_float(float(max_distance)).value
+    if md is None or not (math.isfinite(md) and md > 0.0):
+        raise ValueError(f"mesh: {who} takes a max_distance that is positive and finite in float32"
+                         f"{'' if required else ', or None'}, got {max_distance!r}")
+    return md
+
+
+def _query(g: FaceGrid, F: int, points, shape, sp, org, md: float, far: float, want_faces: bool, want_points: bool, dev):
+    lib = _lib.load()
+    Q = points.shape[0] if points is not None else shape[0] * shape[1] * shape[2]
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    faces = torch.empty(Q, dtype=torch.int32, device=dev) if want_faces else None
+    closest = torch.empty((Q, 3), dtype=torch.float32, device=dev) if want_points else None
+    if Q == 0:
+        return dist, faces, closest
+    if F == 0:                                                          # no face: every finite query is infinitely far
+        dist.fill_(far)
+        if points is not None:
+            dist[~torch.isfinite(points).all(dim=1)] = float("nan")
+        if faces is not None:
+            faces.fill_(-1)
+        if closest is not None:
+            closest.fill_(float("nan"))
+        return dist, faces, closest
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.ctu_mesh_distance(g.corners.data_ptr(), F, g.offsets.data_ptr(), g.faces.data_ptr() if g.faces.shape[0] else None,
+                                         g.faces.shape[0], g.frame.data_ptr(), *g.dims,
+                                         points.data_ptr() if points is not None else None, Q if points is not None else 0,
+                                         *(shape if points is None else (0, 0, 0)), _lib.float_array(sp), _lib.float_array(org), md, far,
+                                         dist.data_ptr(), faces.data_ptr() if want_faces else None,
+                                         closest.data_ptr() if want_points else None, stream), "mesh_distance")
+    return dist, faces, closest
+
+
+def point_distance(points: torch.Tensor, m: Mesh, max_distance: Optional[float] = None, return_faces: bool = False,
+                   return_points: bool = False, grid: Optional[FaceGrid] = None, cell_size: Optional[float] = None):
+    """float32 ``[Q]``: the exact distance from every point to the surface of the mesh, by the module docstring's rule.
+    ``points``: float32 ``[Q,3]`` in (z, y, x) on the mesh's device; ``Q == 0`` works.  ``return_faces``: also int32 ``[Q]``,
+    the lowest index among the nearest faces; ``return_points``: also float32 ``[Q,3]``, that face's closest point; the
+    result is then a tuple in that order.  ``max_distance`` (positive, rounded to float32): a point farther away gets
+    ``inf``, face -1 and closest point NaN, and its search stops there; ``None`` is exact at any distance, at a cost that
+    grows with the distance of the point from the mesh (the search visits the cells of the grid shell by shell until a
+    shell lies farther than the best face found).  A point that is not finite gets NaN, -1, NaN; a mesh without faces
+    gives ``inf`` everywhere.  ``grid``: the ``FaceGrid`` of ``build_face_grid(m)`` to reuse; with it the call neither
+    synchronises nor allocates anything besides its results.  Without it the grid is built first (one synchronisation),
+    with ``cell_size``, which changes the speed and never the result."""
+    v, f = _check_mesh(m, "point_distance")
+    V, F = v.shape[0], f.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"mesh: point_distance takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"mesh: points must be a float32 [Q,3] tensor, got {getattr(points, 'dtype', type(points).__name__)} "
+                         f"{tuple(getattr(points, 'shape', ()))}")
+    if points.shape[0] >= 1 << 31:
+        raise ValueError(f"mesh: point_distance takes Q < 2^31 points, got {points.shape[0]}")
+    if points.device != v.device:
+        raise ValueError(f"mesh: the points live on {points.device}, the mesh on {v.device}")
+    md = _max_distance(max_distance, "point_distance", False)
+    if grid is not None and cell_size is not None:
+        raise ValueError("mesh: cell_size belongs to the build; give grid= or cell_size=, not both")
+    _cell_size(cell_size)
+    if grid is not None:
+        grid = _check_grid(grid, F, v.device)
+    if not v.is_cuda:
+        raise ValueError("mesh: point_distance takes a mesh on the GPU; this path has no CPU fallback")
+    g = grid if grid is not None else build_face_grid(m, cell_size)
+    dist, faces, closest = _query(g, F, points.contiguous(), None, None, None, md, float("inf"), bool(return_faces),
+                                  bool(return_points), v.device)
+    out = (dist,) + ((faces,) if return_faces else ()) + ((closest,) if return_points else ())
+    return out[0] if len(out) == 1 else out
+
+
+_REQUIRED = object()
+
+
+def distance_field(m: Mesh, shape, spacing=None, origin=None, max_distance=_REQUIRED, signed: bool = False,
+                   grid: Optional[FaceGrid] = None) -> torch.Tensor:
+    """float32 ``[D,H,W]`` on the mesh's device: the distance from the centre ``origin + (i, j, k) * spacing`` of every voxel
+    to the surface of the mesh, truncated at ``max_distance``, by the module docstring's rule.  ``shape``, ``spacing`` and
+    ``origin`` describe the grid with ``voxelize``'s conventions and limits; the centres are formed in float64 in the kernel
+    as ``voxelize`` forms them, and no list of points is materialised.  ``max_distance`` is required (a whole grid has far
+    voxels, and the search of each stops there): voxels farther away hold ``max_distance``, not ``inf``.  ``signed=True``
+    multiplies by -1 where ``winding_number(m, shape, spacing, origin) != 0``: positive outside, negative inside, the
+    convention of ``postprocess.signed_distance``; it costs that call, its workspace and its synchronisation.  ``grid``: a
+    prebuilt ``FaceGrid``; with it and ``signed=False`` the call neither synchronises nor allocates anything besides the
+    result.  A mesh without faces gives ``max_distance`` everywhere."""
+    v, f = _check_mesh(m, "distance_field")
+    V, F = v.shape[0], f.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"mesh: distance_field takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
+    shape = _shape(shape)
+    sp, org = _spacing(spacing), _origin(origin)
+    if max_distance is _REQUIRED:
+        raise ValueError("mesh: distance_field takes a max_distance (a whole grid has far voxels; the field is truncated there)")
+    md = _max_distance(max_distance, "distance_field", True)
+    if grid is not None:
+        grid = _check_grid(grid, F, v.device)
+    if not v.is_cuda:
+        raise ValueError("mesh: distance_field takes a mesh on the GPU; this path has no CPU fallback")
+    g = grid if grid is not None else build_face_grid(m)
+    dist, _, _ = _query(g, F, None, shape, sp, org, md, md, False, False, v.device)
+    out = dist.view(shape)
+    if signed:
+        out = torch.where(winding_number(m, shape, spacing, origin) != 0, -out, out)
+    return out
 
 
 def transform(m: Mesh, matrix: torch.Tensor) -> Mesh:

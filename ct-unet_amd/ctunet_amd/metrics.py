@@ -226,6 +226,62 @@ def surface_metrics(pred_labels: torch.Tensor, target_labels: torch.Tensor, num_
     return res
 
 
+def _linear_percentile(d: torch.Tensor, pct: float) -> torch.Tensor:
+    """numpy's default ("linear") percentile of a non-empty float64 vector, on the device, without a synchronisation."""
+    s = torch.sort(d).values
+    pos = pct / 100.0 * (s.shape[0] - 1)
+    lo = min(int(math.floor(pos)), s.shape[0] - 1)
+    hi = min(lo + 1, s.shape[0] - 1)
+    t = pos - lo
+    a, b = s[lo], s[hi]
+    return b - (b - a) * (1.0 - t) if t >= 0.5 else a + (b - a) * t   # numpy's two-sided form: exact at t = 0 and t = 1
+
+
+def mesh_surface_metrics(a, b, percentile: Optional[float] = 95.0, tolerance: Optional[float] = None, grid_a=None,
+                         grid_b=None) -> Dict[str, torch.Tensor]:
+    """HD, HD_p, ASSD and NSD between two surface meshes (``mesh.Mesh``, both on one GPU, in the same physical frame), without
+    the round trip through voxels: float32 scalar device tensors ``hd``, ``hd_p`` (NaN with ``percentile=None``), ``assd`` and,
+    when ``tolerance`` is given, ``nsd``.
+
+    The samples are the vertices, unweighted: d(A->B) holds, for every vertex of ``a``, its exact distance to the surface of
+    ``b`` (``mesh.point_distance``: to the nearest point of a face, not to the nearest vertex), and d(B->A) the same the other
+    way.  A mesh with vertices of very uneven density weighs its dense regions more; a vertex that no face uses counts like
+    any other.  From the two vectors the definitions of the module docstring apply with mesh vertices in place of surface
+    voxels: ``hd`` = the larger maximum, ``hd_p`` = the larger of the two numpy "linear" percentiles, ``assd`` = the sum of both
+    vectors over the number of samples, ``nsd`` = the share of samples within ``tolerance``; sums and percentiles in float64,
+    rounded to float32 once.  Empty surfaces (no vertex or no face): ``hd``, ``hd_p`` and ``assd`` are NaN when either is
+    empty, ``nsd`` is NaN when both are and 0 when exactly one is.
+
+    ``grid_a`` / ``grid_b``: the ``mesh.build_face_grid`` of ``a`` / ``b`` to reuse.  The metrics are computed on the device with
+    torch; the call synchronises only where it builds a grid."""
+    from . import mesh as _mesh
+    pct = _check_percentile(percentile)
+    tau = None if tolerance is None else _thresholds(tolerance, 1, "tolerance")[0]
+    va, fa = _mesh._check_mesh(a, "mesh_surface_metrics")
+    vb, fb = _mesh._check_mesh(b, "mesh_surface_metrics")
+    if va.device != vb.device:
+        raise ValueError(f"metrics: the meshes live on different devices: {va.device} and {vb.device}")
+    if not va.is_cuda:
+        raise ValueError("metrics: mesh_surface_metrics takes meshes on the GPU; this path has no CPU fallback")
+    dev = va.device
+    empty_a, empty_b = va.shape[0] == 0 or fa.shape[0] == 0, vb.shape[0] == 0 or fb.shape[0] == 0
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    if empty_a or empty_b:
+        res = {"hd": nan, "hd_p": nan.clone(), "assd": nan.clone()}
+        if tau is not None:
+            res["nsd"] = nan.clone() if empty_a and empty_b else torch.zeros((), dtype=torch.float32, device=dev)
+        return res
+    dab = _mesh.point_distance(va, b, grid=grid_b).to(torch.float64)
+    dba = _mesh.point_distance(vb, a, grid=grid_a).to(torch.float64)
+    n = dab.shape[0] + dba.shape[0]
+    res = {"hd": torch.maximum(dab.max(), dba.max()).to(torch.float32),
+           "hd_p": nan if pct is None else torch.maximum(_linear_percentile(dab, pct), _linear_percentile(dba, pct)).to(torch.float32),
+           "assd": ((dab.sum() + dba.sum()) / n).to(torch.float32)}
+    if tau is not None:
+        res["nsd"] = (((dab <= tau).sum() + (dba <= tau).sum()).to(torch.float64) / n).to(torch.float32)
+    return res
+
+
 def workspace_bytes(n: int, num_scored: int, shape) -> int:
     """Device workspace of one call (bytes) for n items, num_scored classes and a (D, H, W) volume."""
     return int(_lib.load().ctu_surface_ws_bytes(n, num_scored, *shape))

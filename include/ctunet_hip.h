@@ -679,6 +679,41 @@ size_t ctu_mesh_voxelize_ws_bytes(int D, int H, int W);
 int ctu_mesh_voxelize(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int D, int H, int W,
                       const float* spacing, const float* origin, int want_winding, void* out, void* ws, void* stream);
 
+/* Exact distances from points to a surface mesh (no reference counterpart; rule pinned in ctunet_amd/mesh.py): a uniform grid
+ * of face lists over the bounding box of the mesh, and a nearest-triangle query in float64 on the float32 vertices.
+ *   grid_build: vertices DEVICE float32 [V][3] in (z, y, x), faces DEVICE int32 [F][3], F >= 1.  Writes corners DEVICE float32
+ *          [F][12] (the nine coordinates of every face and three words of padding; 16-byte aligned), fixes the grid (cell
+ *          size: cell_size, or with cell_size = 0 twice the mean largest extent of a face, doubled until the grid has at most
+ *          max_cells cells; floor(extent / size) + 1 cells per axis, 1 for an axis without extent), counts the faces of every
+ *          cell its bounding box overlaps and scans the counts.  A face with an index outside [0, V) or a vertex that is not
+ *          finite is refused: counted, listed nowhere, never read through.  The head of ws then holds 13 words the caller
+ *          reads after synchronising (the build's one synchronisation): int64 pairs, refused faces, cells, overflow (1: the
+ *          given cell_size needs more than max_cells cells; the grid is then one cell and must be refused), nz, ny, nx, then
+ *          double lower corner (z, y, x) and cell size (z, y, x): the `frame` of a query.
+ *   grid_emit: with the ws and corners of grid_build: offsets DEVICE int32 [cells + 1], items DEVICE int32 [pairs]: the faces
+ *          of cell c are items[offsets[c] .. offsets[c + 1]), in no particular order.  pairs >= 2^31 is refused.
+ *   ws: ctu_mesh_grid_ws_bytes(F, max_cells) bytes, 0 outside the limits: 256 + 64 per block of 256 faces + 8 max_cells + 8
+ *       per scan chunk of 4096 cells, each array rounded up to 256; 16-byte aligned.  max_cells in 1..CTU_MESH_GRID_MAX_CELLS.
+ *   distance: dist DEVICE float32 [Q] = the distance from every query to the nearest face; face (NULL: none) DEVICE int32 [Q] =
+ *          the lowest index among the nearest faces; closest (NULL: none) DEVICE float32 [Q][3] = that face's closest point.
+ *          Queries: points DEVICE float32 [Q][3], or with points = NULL the Q = D*H*W centres origin + (i, j, k) * spacing of a
+ *          grid (HOST float [3] each, NULL = 1 and 0; every side <= 1024, D*H*W < 2^31) in C order.  max_distance > 0: a query
+ *          farther than that gets far_value, face -1 and closest NaN; 0: unbounded.  A query that is not finite gets NaN, -1,
+ *          NaN.  Every offset is bounded against pairs and every listed face against F before use.  No workspace, no
+ *          synchronisation; capture-safe.
+ * Limits: V, F, pairs, Q < 2^31.  Integer atomics only for counts and fill cursors; float64 with contraction off; the
+ * result does not depend on the cell size and two calls are bitwise equal. */
+#define CTU_MESH_GRID_MAX_CELLS 16777216
+size_t ctu_mesh_grid_ws_bytes(int64_t F, int64_t max_cells);
+int ctu_mesh_grid_build(const float* vertices, int64_t V, const int32_t* faces, int64_t F, float cell_size, int64_t max_cells,
+                        float* corners, void* ws, void* stream);
+int ctu_mesh_grid_emit(const float* corners, int64_t F, int64_t max_cells, int64_t cells, int64_t pairs, int32_t* offsets,
+                       int32_t* items, void* ws, void* stream);
+int ctu_mesh_distance(const float* corners, int64_t F, const int32_t* offsets, const int32_t* items, int64_t pairs,
+                      const double* frame, int nz, int ny, int nx, const float* points, int64_t Q, int D, int H, int W,
+                      const float* spacing, const float* origin, float max_distance, float far_value, float* dist,
+                      int32_t* face, float* closest, void* stream);
+
 /* CT preprocessing: from a scanner's volume to a binary skull (no reference counterpart: the reference's datasets load skulls
  * that were thresholded beforehand, ctunet/pytorch/datasets.py:22-45; rules pinned in ctunet_amd/preprocess.py).  Every input
  * `in` is a DEVICE contiguous array of dtype CTU_F32, CTU_I16 or CTU_U8, converted in the kernel.  No entry point allocates
