@@ -5,6 +5,7 @@
 // results are bitwise reproducible run to run.
 #include "common.h"
 #include "bn_tail.h"
+#include "channel_sum.h"
 
 static thread_local char g_err[512] = "";
 
@@ -22,6 +23,7 @@ extern "C" const char* ctu_arch(void) { return "gfx950"; }
 namespace {
 
 constexpr int EW_BLOCK = 256;
+static_assert(EW_BLOCK == CSUM_BLOCK, "channel_sum.h block size");
 constexpr int FIN_BLOCK = 256;    // threads of the per-channel statistics finalisation
 constexpr int MAX_RED_BLOCKS = 1024;
 
@@ -595,44 +597,20 @@ __global__ __launch_bounds__(EW_BLOCK) void maxpool2_bwd_row_kernel(const T* __r
 }
 
 // ------------------------------------------------------------------ channel sums
+// block bodies in channel_sum.h (the fused up-convolution's projection runs them inside its own launches)
 template <class T>
 __global__ void channel_sum_partial_kernel(const T* __restrict__ x, int cs, int cp, int64_t nvox,
                                            float* __restrict__ partials) {
-    const int nq = cp >> 2;
-    const int tpv = EW_BLOCK / nq;
-    const int qd = threadIdx.x % nq, vl = threadIdx.x / nq;
     __shared__ float red[EW_BLOCK * 4];
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vl < tpv)
-        for (int64_t v = (int64_t)blockIdx.x * tpv + vl; v < nvox; v += (int64_t)gridDim.x * tpv) {
-            const float4 t = ld4<T>(x + v * cs + qd * 4);
-            a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
-        }
-    float* r = &red[threadIdx.x * 4];
-    r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
-    __syncthreads();
-    if (threadIdx.x < cp) {
-        const int c = threadIdx.x, q = c >> 2, j = c & 3;
-        float s = 0.f;
-        for (int l = 0; l < tpv; ++l) s += red[(l * nq + q) * 4 + j];
-        partials[(size_t)blockIdx.x * cp + c] = s;
-    }
+    channel_sum_partial_block<T>(x, cs, cp, nvox, partials, blockIdx.x, gridDim.x, red);
 }
 
 // one block per channel, fixed-order tree -> deterministic
 __global__ void channel_sum_final_kernel(const float* __restrict__ partials, int nb, int cp, float* __restrict__ out,
                                          int C) {
-    const int c = blockIdx.x;
     __shared__ double r[EW_BLOCK];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) s += (double)partials[(size_t)b * cp + c];
-    r[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = EW_BLOCK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = (float)r[0];
+    const float s = channel_sum_final_block(partials, nb, cp, blockIdx.x, r);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // ------------------------------------------------------------------ Adam(amsgrad)

@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "common.h"
 #include "bn_tail.h"
+#include "channel_sum.h"
 
 namespace {
 
@@ -589,10 +590,8 @@ __global__ __launch_bounds__(256, 2) void upconv_fused_bwd_data_kernel(UpDP p, i
 
 // data-gradient weights gathered from the forward packing: wpd[(p*qc + q)][e][n16][kq][n][j] = W_eff[p][tap = e ^ 7][pos][co],
 // pos = n16*16 + n (padded input-channel position), co = q*8 + kq*2 + j
-__global__ void upconv_pack_bwd_kernel(const float* __restrict__ wp, float* __restrict__ wpd, int cin_p, int nout_p) {
+__device__ __forceinline__ float upconv_pack_bwd_value(const float* __restrict__ wp, int idx, int cin_p, int nout_p) {
     const int n16 = (cin_p + 15) >> 4, qc = nout_p >> 3, ntpt = (nout_p + 15) >> 4;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 8 * qc * 8 * n16 * 128) return;
     int r = idx;
     const int j = r & 1; r >>= 1;
     const int n = r & 15; r >>= 4;
@@ -607,7 +606,7 @@ __global__ void upconv_pack_bwd_kernel(const float* __restrict__ wp, float* __re
         const int cf = pos >> 3, kqf = (pos & 7) >> 1, jf = pos & 1;
         v = wp[((((size_t)cf * 8 + par) * 8 + (e ^ 7)) * ntpt + (co >> 4)) * 128 + kqf * 32 + (co & 15) * 2 + jf];
     }
-    wpd[idx] = v;
+    return v;
 }
 
 // ---- composite weights in fragment order: wp[chunk][parity][tap8 = (dz*2+dy)*2+dx][ntp][kq][n][j]
@@ -637,17 +636,22 @@ __global__ void upconv_transpose_kernel(const float* __restrict__ wt, const floa
     }
 }
 
-// Step 2: 8 lanes per (chunk, parity, tap, padded input channel, QUAD of output channels): a W_eff entry = sum over its
-// <= 8 (conv tap, transposed-conv tap) pairs of a C-long dot product; each lane takes every 8th cm (one W3 float4 and one
-// WT scalar per 4 multiply-adds: the kernel is bound by load instructions, not flops), a 3-step shuffle reduction combines
-// the lanes and lane 0 writes the four values straight to their fragment positions
-__global__ void upconv_pack_kernel(const float* __restrict__ wtt, const float* __restrict__ w3t, float* __restrict__ wp,
-                                   int C, int nout_p, const int32_t* __restrict__ cinv, int nchunk, int ntpt) {
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int sub = gidx & 7, idx = gidx >> 3;
+// Step 2: 8 lanes per (chunk, parity, tap, padded input channel, QUAD of output channels), 8 such outputs per wave: a W_eff
+// entry = sum over its <= 8 (conv tap, transposed-conv tap) pairs of a C-long dot product; each lane takes every 8th cm (one
+// W3 float4 and one WT scalar per 4 multiply-adds).  The time is the length of the dependent load + fma chains, so the pairs
+// do not run one after another: wave p of the block's WS_WAVES runs pair p = (iz * ny + iy) * nx + ix of the same 8 outputs
+// (a wave's outputs share parity and tap, hence the pairs; its loads coalesce as before), the sums meet in LDS, wave 0 adds
+// them in pair order -- the (iz, iy, ix) nesting of the serial form -- then a 3-step shuffle reduction combines the lanes
+// and lane 0 writes the four values straight to their fragment positions
+constexpr int WS_WAVES = 8, WS_BLOCK = WS_WAVES * 64;
+__device__ __forceinline__ void upconv_pack_block(const float* __restrict__ wtt, const float* __restrict__ w3t, float* __restrict__ wp,
+                                                  int C, int nout_p, const int32_t* __restrict__ cinv, int nchunk, int ntpt,
+                                                  int bid, float4 (*part)[64]) {
+    const int pr = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane & 7;
+    const int idx = bid * 8 + (lane >> 3);
     const int ncol4 = ntpt * 4;                          // output-channel quads per row of N-tiles
-    if (idx >= nchunk * 8 * 8 * 8 * ncol4) return;      // (whole 8-lane groups leave together)
-    int r = idx;
+    const bool valid = idx < nchunk * 8 * 8 * 8 * ncol4;
+    int r = valid ? idx : 0;
     const int co = (r % ncol4) * 4; r /= ncol4;
     const int r8 = r & 7; r >>= 3;                       // channel inside the chunk (= kq*2 + j)
     const int tap = r & 7; r >>= 3;
@@ -655,31 +659,38 @@ __global__ void upconv_pack_kernel(const float* __restrict__ wtt, const float* _
     const int c = r;
     const int rp = c * 8 + r8;
     const int ci = cinv ? cinv[rp] : (rp < C ? rp : -1);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ci >= 0 && co < nout_p) {                        // (nout_p is a multiple of 8: a quad is inside or outside as a whole)
+    int np = 0;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (valid && ci >= 0 && co < nout_p) {               // (nout_p is a multiple of 8: a quad is inside or outside as a whole)
         int tz[2], az[2], ty[2], ay[2], tx[2], ax[2];
         const int nz = axis_pairs((par >> 2) & 1, (tap >> 2) & 1, tz, az);
         const int ny = axis_pairs((par >> 1) & 1, (tap >> 1) & 1, ty, ay);
         const int nx = axis_pairs(par & 1, tap & 1, tx, ax);
-        for (int iz = 0; iz < nz; ++iz)
-            for (int iy = 0; iy < ny; ++iy)
-                for (int ix = 0; ix < nx; ++ix) {
-                    const float* a = wtt + ((size_t)((az[iz] * 2 + ay[iy]) * 2 + ax[ix]) * C + ci) * C;
-                    const float* b = w3t + (size_t)((tz[iz] * 3 + ty[iy]) * 3 + tx[ix]) * C * nout_p + co;
-                    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        np = nz * ny * nx;
+        const int ix = pr % nx, iy = (pr / nx) % ny, iz = pr / (nx * ny);
+        if (iz < nz) {
+            const float* a = wtt + ((size_t)((az[iz] * 2 + ay[iy]) * 2 + ax[ix]) * C + ci) * C;
+            const float* b = w3t + (size_t)((tz[iz] * 3 + ty[iy]) * 3 + tx[ix]) * C * nout_p + co;
 #pragma unroll 4
-                    for (int cm = sub; cm < C; cm += 8) {
-                        const float av = a[cm];
-                        const float4 bv = *reinterpret_cast<const float4*>(b + (size_t)cm * nout_p);
-                        s.x = fmaf(av, bv.x, s.x); s.y = fmaf(av, bv.y, s.y); s.z = fmaf(av, bv.z, s.z); s.w = fmaf(av, bv.w, s.w);
-                    }
-                    v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w;
-                }
+            for (int cm = sub; cm < C; cm += 8) {
+                const float av = a[cm];
+                const float4 bv = *reinterpret_cast<const float4*>(b + (size_t)cm * nout_p);
+                s.x = fmaf(av, bv.x, s.x); s.y = fmaf(av, bv.y, s.y); s.z = fmaf(av, bv.z, s.z); s.w = fmaf(av, bv.w, s.w);
+            }
+        }
+    }
+    part[pr][lane] = s;
+    __syncthreads();
+    if (pr != 0) return;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = 0; p < np; ++p) {
+        const float4 t = part[p][lane];
+        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
     }
     float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int q = 0; q < 4; ++q) { vv[q] += __shfl_xor(vv[q], 1); vv[q] += __shfl_xor(vv[q], 2); vv[q] += __shfl_xor(vv[q], 4); }
-    if (sub == 0) {
+    if (valid && sub == 0) {
         const int nt = co >> 4, n = co & 15, kq = r8 >> 1, j = r8 & 1;
         float* dst = wp + ((((size_t)c * 8 + par) * 8 + tap) * ntpt + nt) * 128 + kq * 32 + n * 2 + j;
 #pragma unroll
@@ -689,9 +700,7 @@ __global__ void upconv_pack_kernel(const float* __restrict__ wtt, const float* _
 
 // PW forward packing (8 padded output channels) gathered from the standard one:
 // wpw[chunk][par4 = pd*2+ph][tap12 = (dz*2+dy)*3+dxx][kq][n = px*8+co][j] = W_eff[(pd,ph,px)][(dz,dy,dxx-px)] or 0
-__global__ void upconv_pack_pw_kernel(const float* __restrict__ wp, float* __restrict__ wpw, int nchunk) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nchunk * 4 * 12 * 128) return;
+__device__ __forceinline__ float upconv_pack_pw_value(const float* __restrict__ wp, int idx) {
     int r = idx;
     const int j = r & 1; r >>= 1;
     const int n = r & 15; r >>= 4;
@@ -702,25 +711,35 @@ __global__ void upconv_pack_pw_kernel(const float* __restrict__ wp, float* __res
     const int px = n >> 3, co = n & 7, dxx = tap % 3, dzy = tap / 3, jx = dxx - px;
     float v = 0.f;
     if (jx == 0 || jx == 1) v = wp[((size_t)(c * 8 + par4 * 2 + px) * 8 + dzy * 2 + jx) * 128 + kq * 32 + co * 2 + j];
-    wpw[idx] = v;
+    return v;
+}
+
+// The two gathers of the standard packing in one launch: the PW forward packing (npw elements, 0 unless nout_p = 8), then the
+// data-gradient packing (nwpd elements, 0 when the caller wants none).  Every element of both is written, zeros included.
+__global__ void upconv_pack_gather_kernel(const float* __restrict__ wp, float* __restrict__ wpw, int npw, float* __restrict__ wpd,
+                                          int nwpd, int cin_p, int nout_p) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < npw) wpw[idx] = upconv_pack_pw_value(wp, idx);
+    else if (idx - npw < nwpd) wpd[idx - npw] = upconv_pack_bwd_value(wp, idx - npw, cin_p, nout_p);
 }
 
 // b_eff[class 27][nout_p]: class = (cz*3+cy)*3+cx, per axis 0 interior, 1 first fine voxel (t=0 outside), 2 last (t=2 outside).
-// One block: S[t][co] = sum_cm bT[cm] w3t[t][cm][co] into LDS (coalesced over co), then the 27 class sums of valid taps.
-__global__ __launch_bounds__(1024) void upconv_beff_kernel(const float* __restrict__ bt, const float* __restrict__ w3t,
-                                                           float* __restrict__ beff, int C, int nout_p) {
-    __shared__ float S[27 * 64];
-    for (int i = threadIdx.x; i < 27 * nout_p; i += blockDim.x) {
-        const int co = i % nout_p, t = i / nout_p;
+// One block per BEFF_CO output channels co0 ..: S[t][co] = sum_cm bT[cm] w3t[t][cm][co] into LDS (one cm-ordered chain per
+// thread), then the 27 class sums of valid taps in t order.  Needs only the transposes, so it rides along the pack launch.
+constexpr int BEFF_CO = 8;
+__device__ __forceinline__ void upconv_beff_block(const float* __restrict__ bt, const float* __restrict__ w3t, float* __restrict__ beff,
+                                                  int C, int nout_p, int co0, float* S) {
+    for (int i = threadIdx.x; i < 27 * BEFF_CO; i += blockDim.x) {
+        const int co = co0 + i % BEFF_CO, t = i / BEFF_CO;
         const float* b = w3t + (size_t)t * C * nout_p + co;
         float s = 0.f;
-#pragma unroll 4
+#pragma unroll 16                                        // (16 loads in flight per round of the serial chain)
         for (int cm = 0; cm < C; ++cm) s = fmaf(bt[cm], b[(size_t)cm * nout_p], s);
         S[i] = s;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 27 * nout_p; i += blockDim.x) {
-        const int co = i % nout_p, cls = i / nout_p;
+    for (int i = threadIdx.x; i < 27 * BEFF_CO; i += blockDim.x) {
+        const int col = i % BEFF_CO, cls = i / BEFF_CO;
         const int cz = cls / 9, cy = (cls / 3) % 3, cx = cls % 3;
         float v = 0.f;
         for (int t = 0; t < 27; ++t) {
@@ -728,10 +747,26 @@ __global__ __launch_bounds__(1024) void upconv_beff_kernel(const float* __restri
             if ((cz == 1 && tz == 0) || (cz == 2 && tz == 2) || (cy == 1 && ty == 0) || (cy == 2 && ty == 2) ||
                 (cx == 1 && tx == 0) || (cx == 2 && tx == 2))
                 continue;
-            v += S[t * nout_p + co];
+            v += S[t * BEFF_CO + col];
         }
-        beff[i] = v;
+        beff[cls * nout_p + co0 + col] = v;
     }
+}
+
+// Step 2 launch: the first nout_p / BEFF_CO blocks build b_eff (the longest chains: they start first), the rest pack the
+// composite weights
+__global__ __launch_bounds__(WS_BLOCK) void upconv_pack_beff_kernel(const float* __restrict__ wtt, const float* __restrict__ w3t,
+                                                                    float* __restrict__ wp, int C, int nout_p,
+                                                                    const int32_t* __restrict__ cinv, int nchunk, int ntpt,
+                                                                    const float* __restrict__ bt, float* __restrict__ beff) {
+    __shared__ float4 part[WS_WAVES][64];
+    static_assert(27 * BEFF_CO <= WS_WAVES * 64 * 4, "b_eff's S fits the pack's LDS");
+    const int nbeff = nout_p / BEFF_CO;
+    if ((int)blockIdx.x < nbeff) {
+        upconv_beff_block(bt, w3t, beff, C, nout_p, (int)blockIdx.x * BEFF_CO, reinterpret_cast<float*>(part));
+        return;
+    }
+    upconv_pack_block(wtt, w3t, wp, C, nout_p, cinv, nchunk, ntpt, (int)blockIdx.x - nbeff, part);
 }
 
 // ------------------------------------------------------------------ backward w.r.t. the three parameter tensors
@@ -742,12 +777,13 @@ __global__ __launch_bounds__(1024) void upconv_beff_kernel(const float* __restri
 //   dbT[cm]      = sum_t sum_co V[t][co] W3[co,cm,t]
 // V[t][co] = sum of dy over the fine voxels whose conv tap t lies inside the volume (per axis: t=0 excludes the first
 // plane, t=2 the last) -- built from 27 box sums T[sel] (each axis: all / first plane / last plane).
-constexpr int FS_SPLIT = 16;      // blocks per face / edge / corner selection (the full-volume sum goes through ctu_channel_sum)
+constexpr int FS_SPLIT = 16;      // blocks per face / edge / corner selection (the full-volume sum: channel_sum.h's two stages)
 
+// block (sel - 1, split) of the 26 x FS_SPLIT face / edge / corner partial sums.  red: 256 float4 of LDS.
 template <class T>
-__global__ __launch_bounds__(256) void upconv_face_sums_kernel(const T* __restrict__ dy, int cs, int cp, int N, int Df, int Hf,
-                                                               int Wf, float* __restrict__ tpart) {
-    const int sel = blockIdx.x + 1;                               // (sz*3 + sy)*3 + sx, 0 all / 1 first / 2 last; sel 0 is not computed here
+__device__ __forceinline__ void upconv_face_sums_block(const T* __restrict__ dy, int cs, int cp, int N, int Df, int Hf, int Wf,
+                                                       float* __restrict__ tpart, int sel, int split, float4* red) {
+    // sel = (sz*3 + sy)*3 + sx, 0 all / 1 first / 2 last; sel 0 is not computed here
     const int sz = sel / 9, sy = (sel / 3) % 3, sx = sel % 3;
     const int nz = sz ? 1 : Df, ny = sy ? 1 : Hf, nx = sx ? 1 : Wf;
     const int z0 = sz == 2 ? Df - 1 : 0, y0 = sy == 2 ? Hf - 1 : 0, x0 = sx == 2 ? Wf - 1 : 0;
@@ -755,7 +791,7 @@ __global__ __launch_bounds__(256) void upconv_face_sums_kernel(const T* __restri
     const int qd = threadIdx.x % nq;                              // 256 % nq == 0 for cp in {8, 16, 32, 64}
     const int64_t nvox = (int64_t)N * nz * ny * nx;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t v = (int64_t)blockIdx.y * (256 / nq) + threadIdx.x / nq; v < nvox; v += (int64_t)FS_SPLIT * (256 / nq)) {
+    for (int64_t v = (int64_t)split * (256 / nq) + threadIdx.x / nq; v < nvox; v += (int64_t)FS_SPLIT * (256 / nq)) {
         int64_t r = v;
         const int x = x0 + (int)(r % nx); r /= nx;
         const int y = y0 + (int)(r % ny); r /= ny;
@@ -764,7 +800,6 @@ __global__ __launch_bounds__(256) void upconv_face_sums_kernel(const T* __restri
         const float4 g = ld4<T>(dy + ((((size_t)n * Df + z) * Hf + y) * Wf + x) * cs + qd * 4);
         acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
     }
-    __shared__ float4 red[256];
     red[threadIdx.x] = acc;
     __syncthreads();
     for (int o = 128; o >= nq; o >>= 1) {                         // threads with equal quad are nq apart
@@ -776,13 +811,33 @@ __global__ __launch_bounds__(256) void upconv_face_sums_kernel(const T* __restri
         __syncthreads();
     }
     if (threadIdx.x < nq)
-        *reinterpret_cast<float4*>(tpart + ((size_t)sel * FS_SPLIT + blockIdx.y) * cp + threadIdx.x * 4) = red[threadIdx.x];
+        *reinterpret_cast<float4*>(tpart + ((size_t)sel * FS_SPLIT + split) * cp + threadIdx.x * 4) = red[threadIdx.x];
 }
 
-__global__ void upconv_v_kernel(const float* __restrict__ tpart, const float* __restrict__ tall, int cp, float* __restrict__ V) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 27 * cp) return;
-    const int co = idx % cp, t = idx / cp;
+// Everything that only reads the gradient, in one launch: blocks [0, nb) write the full-volume sum's nb partial rows (csp),
+// the 26 * FS_SPLIT blocks after them the face / edge / corner partial sums (tpart)
+template <class T>
+__global__ __launch_bounds__(256) void upconv_sums_kernel(const T* __restrict__ dy, int cs, int cp, int N, int Df, int Hf, int Wf,
+                                                          int64_t fvox, float* __restrict__ csp, int nb, float* __restrict__ tpart) {
+    static_assert(CSUM_BLOCK == 256, "one block size for both ranges");
+    __shared__ float4 red[256];
+    if ((int)blockIdx.x < nb) {
+        channel_sum_partial_block<T>(dy, cs, cp, fvox, csp, blockIdx.x, nb, reinterpret_cast<float*>(red));
+        return;
+    }
+    const int b = (int)blockIdx.x - nb;
+    upconv_face_sums_block<T>(dy, cs, cp, N, Df, Hf, Wf, tpart, b / FS_SPLIT + 1, b % FS_SPLIT, red);
+}
+
+// One block per output channel co: tall[co] = the fp64 tree over the full-volume partial rows, then threads 0..26 build V[t][co]
+__global__ __launch_bounds__(256) void upconv_tall_v_kernel(const float* __restrict__ csp, int nb, const float* __restrict__ tpart,
+                                                            int cp, float* __restrict__ tall, float* __restrict__ V) {
+    __shared__ double r[CSUM_BLOCK];
+    const int co = blockIdx.x;
+    const float ta = channel_sum_final_block(csp, nb, cp, co, r);
+    if (threadIdx.x == 0) tall[co] = ta;
+    if (threadIdx.x >= 27) return;
+    const int t = threadIdx.x, idx = t * cp + co;
     const int tz = t / 9, ty = (t / 3) % 3, tx = t % 3;
     // per axis: tap 0 -> all - first, tap 1 -> all, tap 2 -> all - last
     float v = 0.f;
@@ -794,7 +849,7 @@ __global__ void upconv_v_kernel(const float* __restrict__ tpart, const float* __
                 const int sel = (sz * 3 + sy) * 3 + sx;
                 float s = 0.f;
                 if (sel == 0) {
-                    s = tall[co];
+                    s = ta;
                 } else {
                     const float* src = tpart + (size_t)sel * FS_SPLIT * cp + co;
                     for (int b = 0; b < FS_SPLIT; ++b) s += src[(size_t)b * cp];      // fixed order
@@ -817,48 +872,65 @@ __device__ __forceinline__ int weff_index(int t, int a) {                    // 
     return ((pz * 4 + py * 2 + px) * 8) + (jz * 4 + jy * 2 + jx);
 }
 
-// 8 lanes per output element; grid covers dWT (C*C*8), then dW3 (Co*C*27), then dbT (C).  These sums are a few MFLOP:
-// the time is the number of cache lines a wave touches per load, so (a) the dWT lanes read their c_out runs of dW_eff / W3
-// as float4, (b) the dW3 outputs are dealt in c_out quads, c_out-fastest: a wave's (c_in lane, c_out quad) pairs read contiguous dW_eff
-// rows as float4 (4 multiply-adds per load pair).
-__global__ void upconv_project_kernel(const float* __restrict__ dweff, const float* __restrict__ V, const float* __restrict__ wtt,
-                                      const float* __restrict__ w3t, const float* __restrict__ bt,
-                                      const int32_t* __restrict__ imap, int C, int Co, int cin_p, int nout_p,
-                                      float* __restrict__ dwt, float* __restrict__ dw3, float* __restrict__ dbt) {
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int sub = gidx & 7;
-    int idx = gidx >> 3;
+// Grid: blocks [0, nb1) cover dWT (C*C*8 outputs) and dbT (C) with 8 lanes per output element, the blocks after them dW3: 8
+// lanes per (quad of output channels, cm, t), dealt c_out-quad-fastest (a wave's (c_in lane, c_out quad) pairs read
+// contiguous dW_eff rows as float4, 4 multiply-adds per load pair), 8 such outputs per wave.  These sums are a few MFLOP and
+// their time is the length of the dependent load + fma chains, so chains that do not depend on each other do not run one
+// after another:
+//  - dWT: a lane's 4 chains (t = sub + 8k) read their c_out runs of dW_eff / W3 as float4;
+//  - dW3: wave a of the block's 8 runs the chain of transposed-conv tap a (ci = sub, sub + 8, ...) for the block's 8 outputs;
+//    the sums meet in LDS, wave 0 adds them in the order a = 0..7, adds V bT on lane sub == 0 and finishes with the
+//    xor-1, 2, 4 tree over sub -- the operations and their order of the form that ran the eight chains on one lane.
+__global__ __launch_bounds__(WS_BLOCK) void upconv_project_kernel(const float* __restrict__ dweff, const float* __restrict__ V,
+                                                                  const float* __restrict__ wtt, const float* __restrict__ w3t,
+                                                                  const float* __restrict__ bt, const int32_t* __restrict__ imap,
+                                                                  int C, int Co, int cin_p, int nout_p, int nb1,
+                                                                  float* __restrict__ dwt, float* __restrict__ dw3,
+                                                                  float* __restrict__ dbt) {
     const int coq = (Co + 3) >> 2;                                // output-channel quads of the dW3 part
     const int n1 = C * C * 8, n2 = coq * C * 27, n3 = C;
-    if (idx >= n1 + n2 + n3) return;
-    float v = 0.f;
-    float* dst;
-    if (idx >= n1 && idx < n1 + n2) {                             // dW3[co .. co+3][cm][t], dealt co-quad-fastest
-        const int k = idx - n1;
-        const int co = (k % coq) * 4, cm = (k / coq) % C, t = k / (coq * C);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {                              // 8 independent chains
+    if ((int)blockIdx.x >= nb1) {                                 // dW3[co .. co+3][cm][t], dealt co-quad-fastest
+        __shared__ float4 part[WS_WAVES][64];
+        const int a = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane & 7;
+        const int k = ((int)blockIdx.x - nb1) * 8 + (lane >> 3);
+        const bool valid = k < n2;
+        const int kk = valid ? k : 0;
+        const int co = (kk % coq) * 4, cm = (kk / coq) % C, t = kk / (coq * C);
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (valid) {
             const float* g = dweff + (size_t)weff_index(t, a) * cin_p * nout_p + co;
             const float* w = wtt + (size_t)a * C * C + cm;
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
             for (int ci = sub; ci < C; ci += 8) {
                 const float4 gv = *reinterpret_cast<const float4*>(g + (size_t)(imap ? imap[ci] : ci) * nout_p);
                 const float wv = w[(size_t)ci * C];
                 s.x = fmaf(gv.x, wv, s.x); s.y = fmaf(gv.y, wv, s.y); s.z = fmaf(gv.z, wv, s.z); s.w = fmaf(gv.w, wv, s.w);
             }
-            acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
+        }
+        part[a][lane] = s;
+        __syncthreads();
+        if (a != 0) return;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int aa = 0; aa < 8; ++aa) {                           // the eight chains, a = 0..7 in order
+            const float4 p = part[aa][lane];
+            acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
         }
         float av[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (sub == 0 && co + q < Co) av[q] = fmaf(V[t * nout_p + co + q], bt[cm], av[q]);
             av[q] += __shfl_xor(av[q], 1); av[q] += __shfl_xor(av[q], 2); av[q] += __shfl_xor(av[q], 4);
-            if (sub == 0 && co + q < Co) dw3[((size_t)(co + q) * C + cm) * 27 + t] = av[q];
+            if (valid && sub == 0 && co + q < Co) dw3[((size_t)(co + q) * C + cm) * 27 + t] = av[q];
         }
         return;
     }
+    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int sub = gidx & 7;
+    const int idx = gidx >> 3;
+    if (idx >= n1 + n3) return;
+    float v = 0.f;
+    float* dst;
     if (idx < n1) {                                               // dWT[ci][cm][a]
         const int a = idx & 7, cm = (idx >> 3) % C, ci = idx / (8 * C);
         const int pos = imap ? imap[ci] : ci;
@@ -882,9 +954,10 @@ __global__ void upconv_project_kernel(const float* __restrict__ dweff, const flo
         }
         dst = dwt + idx;
     } else {                                                      // dbT[cm]
-        const int cm = idx - n1 - n2;
+        const int cm = idx - n1;
         for (int t = sub; t < 27; t += 8) {
             const float* w = w3t + ((size_t)t * C + cm) * nout_p;
+#pragma unroll 8                                                  // (one serial chain: at least keep 16 loads in flight)
             for (int co = 0; co < Co; ++co) v = fmaf(V[t * nout_p + co], w[co], v);
         }
         dst = dbt + cm;
@@ -937,8 +1010,21 @@ extern "C" int ctu_upconv_fused_num_blocks(int N, int D, int H, int W, int nout_
 
 extern "C" size_t ctu_upconv_fused_pack_ws_floats(int C, int nout_p) { return (size_t)27 * C * nout_p + (size_t)8 * C * C; }
 
-extern "C" int ctu_upconv_fused_pack(const float* wt, const float* bt, const float* w3, int C, int Co, const int32_t* cinv,
-                                     int cin_p, int nout_p, float* wp, float* beff, float* ws, void* stream) {
+// the gathers of the standard packing wp in one launch: the PW packing wpw (nout_p = 8) and the data-gradient packing wpd,
+// either may be NULL
+static int upconv_pack_gather(const float* wp, int cin_p, int nout_p, float* wpw, float* wpd, hipStream_t st) {
+    const int npw = wpw ? (cin_p / 8) * 4 * 12 * 128 : 0;                          // (a multiple of the block: the ranges split at a block edge)
+    const int nwpd = wpd ? (int)ctu_upconv_fused_bwd_packed_floats(cin_p, nout_p) : 0;
+    if (npw + nwpd == 0) return CTU_OK;
+    upconv_pack_gather_kernel<<<ceil_div(npw + nwpd, 256), 256, 0, st>>>(wp, wpw, npw, wpd, nwpd, cin_p, nout_p);
+    CTU_CHECK_LAUNCH("upconv_fused_pack_gather");
+    return CTU_OK;
+}
+
+// wpd: the data-gradient packing (ctu_upconv_fused_bwd_packed_floats) written by the same launch as the PW packing, or NULL.
+// Three launches: transposes, composite weights + b_eff, gathers.  Every element of wp, beff, ws and wpd is written.
+extern "C" int ctu_upconv_fused_pack_all(const float* wt, const float* bt, const float* w3, int C, int Co, const int32_t* cinv,
+                                         int cin_p, int nout_p, float* wp, float* beff, float* ws, float* wpd, void* stream) {
     CTU_REQUIRE(wt && bt && w3 && wp && beff && ws, "upconv_fused_pack: null pointer");
     CTU_REQUIRE(C > 0 && Co > 0 && Co <= nout_p && cin_p % 8 == 0 && nout_p % 8 == 0 && (cinv || C <= cin_p),
                 "upconv_fused_pack: C=%d Co=%d cin_p=%d nout_p=%d", C, Co, cin_p, nout_p);
@@ -950,17 +1036,16 @@ extern "C" int ctu_upconv_fused_pack(const float* wt, const float* bt, const flo
     const int ntr = 27 * C * nout_p + 8 * C * C;
     upconv_transpose_kernel<<<ceil_div(ntr, 256), 256, 0, st>>>(wt, w3, wtt, w3t, C, Co, nout_p);
     CTU_CHECK_LAUNCH("upconv_fused_transpose");
-    const int total = (cin_p / 8) * 8 * 8 * 8 * ntpt * 4 * 8;            // 8 lanes per quad of packed elements
-    upconv_pack_kernel<<<ceil_div(total, 256), 256, 0, st>>>(wtt, w3t, wp, C, nout_p, cinv, cin_p / 8, ntpt);
+    const int quads = (cin_p / 8) * 8 * 8 * 8 * ntpt * 4;                // 8 quads of packed elements per block
+    upconv_pack_beff_kernel<<<nout_p / BEFF_CO + ceil_div(quads, 8), WS_BLOCK, 0, st>>>(wtt, w3t, wp, C, nout_p, cinv, cin_p / 8,
+                                                                                         ntpt, bt, beff);
     CTU_CHECK_LAUNCH("upconv_fused_pack");
-    if (nout_p == 8) {
-        const int tpw = (cin_p / 8) * 4 * 12 * 128;
-        upconv_pack_pw_kernel<<<ceil_div(tpw, 256), 256, 0, st>>>(wp, wp + up_std_packed(cin_p, nout_p), cin_p / 8);
-        CTU_CHECK_LAUNCH("upconv_fused_pack_pw");
-    }
-    upconv_beff_kernel<<<1, 1024, 0, st>>>(bt, w3t, beff, C, nout_p);
-    CTU_CHECK_LAUNCH("upconv_fused_beff");
-    return CTU_OK;
+    return upconv_pack_gather(wp, cin_p, nout_p, nout_p == 8 ? wp + up_std_packed(cin_p, nout_p) : nullptr, wpd, st);
+}
+
+extern "C" int ctu_upconv_fused_pack(const float* wt, const float* bt, const float* w3, int C, int Co, const int32_t* cinv,
+                                     int cin_p, int nout_p, float* wp, float* beff, float* ws, void* stream) {
+    return ctu_upconv_fused_pack_all(wt, bt, w3, C, Co, cinv, cin_p, nout_p, wp, beff, ws, nullptr, stream);
 }
 
 extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
@@ -1000,7 +1085,6 @@ extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const
 }
 
 extern "C" int ctu_channel_sum_num_blocks(int64_t nvox);
-extern "C" int ctu_channel_sum(const float* x, int cs, int cp, int64_t nvox, float* partials, float* out, int C, void* stream);
 
 extern "C" size_t ctu_upconv_fused_project_ws_floats(int nout_p, int64_t fine_nvox) {
     return (size_t)27 * FS_SPLIT * nout_p + (size_t)27 * nout_p + nout_p + (size_t)ctu_channel_sum_num_blocks(fine_nvox) * nout_p;
@@ -1009,8 +1093,6 @@ extern "C" size_t ctu_upconv_fused_project_ws_floats(int nout_p, int64_t fine_nv
 // dweff: [8][8][cin_p][nout_p] from ctu_upconv_fused_wgrad; gout: fine-grid gradient w.r.t. the fused op's RAW output
 // [N,2D,2H,2W,g_cs]; pack_ws: the scratch ctu_upconv_fused_pack filled this step (transposed weights); imap: logical input
 // channel -> padded position (NULL = identity).  Outputs in torch layouts: dwt [C][C][2][2][2], dbt [C], dw3 [Co][C][3][3][3].
-extern "C" int ctu_lp_channel_sum(int dtype, const void* x, int cs, int cp, int64_t nvox, float* partials, float* out, int C, void* stream);
-
 // dtype 0: gout is fp32; CTU_BF16 / CTU_F16: a 16-bit gradient tensor (the 16-bit path's ctu_lp_upconv_fused_project)
 static int upconv_project_impl(int dtype, const float* dweff, const void* gout, int g_cs, int nout_p, int N, int D, int H, int W,
                                const float* bt, const float* pack_ws, const int32_t* imap, int C, int Co, int cin_p,
@@ -1025,23 +1107,23 @@ static int upconv_project_impl(int dtype, const float* dweff, const void* gout, 
     float* tall = V + (size_t)27 * nout_p;
     float* csp = tall + nout_p;
     const int64_t fvox = (int64_t)N * 8 * D * H * W;
-    int rc;
+    // launch 1: the partial rows of the full-volume sum (ctu_channel_sum's, same row count) and the face / edge / corner sums
+    const int nb = ctu_channel_sum_num_blocks(fvox);
+    const int nsum = nb + 26 * FS_SPLIT;
     if (dtype == 0) {
-        rc = ctu_channel_sum((const float*)gout, g_cs, nout_p, fvox, csp, tall, nout_p, stream);          // full-volume sum per channel
-        if (rc != CTU_OK) return rc;
-        upconv_face_sums_kernel<float><<<dim3(26, FS_SPLIT), 256, 0, st>>>((const float*)gout, g_cs, nout_p, N, 2 * D, 2 * H, 2 * W, tpart);
+        upconv_sums_kernel<float><<<nsum, 256, 0, st>>>((const float*)gout, g_cs, nout_p, N, 2 * D, 2 * H, 2 * W, fvox, csp, nb, tpart);
     } else {
-        rc = ctu_lp_channel_sum(dtype, gout, g_cs, nout_p, fvox, csp, tall, nout_p, stream);
-        if (rc != CTU_OK) return rc;
-        CTU_DISPATCH_LP(dtype, upconv_face_sums_kernel<T><<<dim3(26, FS_SPLIT), 256, 0, st>>>((const T*)gout, g_cs, nout_p, N, 2 * D, 2 * H, 2 * W, tpart));
+        CTU_DISPATCH_LP(dtype, upconv_sums_kernel<T><<<nsum, 256, 0, st>>>((const T*)gout, g_cs, nout_p, N, 2 * D, 2 * H, 2 * W, fvox, csp, nb, tpart));
     }
-    CTU_CHECK_LAUNCH("upconv_face_sums");
-    upconv_v_kernel<<<ceil_div(27 * nout_p, 64), 64, 0, st>>>(tpart, tall, nout_p, V);
-    CTU_CHECK_LAUNCH("upconv_v");
+    CTU_CHECK_LAUNCH("upconv_sums");
+    // launch 2: per channel the fp64 tree over the rows, then V
+    upconv_tall_v_kernel<<<nout_p, 256, 0, st>>>(csp, nb, tpart, nout_p, tall, V);
+    CTU_CHECK_LAUNCH("upconv_tall_v");
     const float* w3t = pack_ws;
     const float* wtt = pack_ws + (size_t)27 * C * nout_p;
-    const int total = (C * C * 8 + ((Co + 3) / 4) * C * 27 + C) * 8;
-    upconv_project_kernel<<<ceil_div(total, 256), 256, 0, st>>>(dweff, V, wtt, w3t, bt, imap, C, Co, cin_p, nout_p, dwt, dw3, dbt);
+    const int nb1 = ceil_div((C * C * 8 + C) * 8, WS_BLOCK);              // dWT + dbT: 8 lanes per output
+    const int nb2 = ceil_div(((Co + 3) / 4) * C * 27, 8);                  // dW3: 8 quads of outputs per block
+    upconv_project_kernel<<<nb1 + nb2, WS_BLOCK, 0, st>>>(dweff, V, wtt, w3t, bt, imap, C, Co, cin_p, nout_p, nb1, dwt, dw3, dbt);
     CTU_CHECK_LAUNCH("upconv_project");
     return CTU_OK;
 }
@@ -1065,10 +1147,7 @@ extern "C" size_t ctu_upconv_fused_bwd_packed_floats(int cin_p, int nout_p) {
 
 extern "C" int ctu_upconv_fused_pack_bwd(const float* wp, int cin_p, int nout_p, float* wpd, void* stream) {
     CTU_REQUIRE(wp && wpd && cin_p % 8 == 0 && nout_p % 8 == 0, "upconv_fused_pack_bwd: bad argument");
-    const int total = (int)ctu_upconv_fused_bwd_packed_floats(cin_p, nout_p);
-    upconv_pack_bwd_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)stream>>>(wp, wpd, cin_p, nout_p);
-    CTU_CHECK_LAUNCH("upconv_fused_pack_bwd");
-    return CTU_OK;
+    return upconv_pack_gather(wp, cin_p, nout_p, nullptr, wpd, (hipStream_t)stream);
 }
 
 extern "C" int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin, int gin_cs,

@@ -102,6 +102,7 @@ SIGNATURES = {
     "ctu_upconv_fused_num_blocks": (I, [I, I, I, I, I]),
     "ctu_upconv_fused_pack_ws_floats": (Z, [I, I]),
     "ctu_upconv_fused_pack": (I, [P, P, P, I, I, P, I, I, P, P, P, P]),
+    "ctu_upconv_fused_pack_all": (I, [P, P, P, I, I, P, I, I, P, P, P, P, P]),
     "ctu_upconv_fused_fwd": (I, [P, I, I, P, P, I, P, P, P, I, I, P, I, I, I, I, P, P]),
     "ctu_upconv_fused_wgrad_ws_floats": (Z, [I, I, I, I, I, I]),
     "ctu_upconv_fused_wgrad": (I, [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, P]),

@@ -273,11 +273,12 @@ class UNetEngine:
         hit = self._up_cache.get(prefix)
         if hit is None or hit[0] != ver or hit[3] != (x.cp, out.cp, self.dtype) or torch.cuda.is_current_stream_capturing():
             same = hit is not None and hit[3] == (x.cp, out.cp, self.dtype)
-            wp, beff, pws = ops.upconv_fused_pack(wt, bt, w3, cinv, x.cp, out.cp, (hit[1], hit[2], hit[4]) if same else None)
             if lp:
+                wp, beff, pws = ops.upconv_fused_pack(wt, bt, w3, cinv, x.cp, out.cp, (hit[1], hit[2], hit[4]) if same else None)
                 wpd = ops.lp_upconv_fused_pack(wp, x.cp, self.dtype, hit[5] if same else None)      # forward + data-gradient fragments
-            else:
-                wpd = ops.upconv_fused_pack_bwd(wp, x.cp, out.cp, hit[5] if same else None)          # same weights, data-gradient order
+            else:                          # the same weights in data-gradient order come out of the pack's own gather launch
+                wp, beff, pws, wpd = ops.upconv_fused_pack_all(wt, bt, w3, cinv, x.cp, out.cp,
+                                                               (hit[1], hit[2], hit[4], hit[5]) if same else None)
             self._up_cache[prefix] = (ver, wp, beff, (x.cp, out.cp, self.dtype), pws, wpd)
         else:
             wp, beff, wpd = hit[1], hit[2], hit[5]

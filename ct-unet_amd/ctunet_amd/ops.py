@@ -864,20 +864,36 @@ def upconv_fused_supported(dims, k: int, cin_p: int, nout_p: int) -> bool:
 def upconv_fused_pack(wt: torch.Tensor, bt: torch.Tensor, w3: torch.Tensor, cinv, cin_p: int, nout_p: int,
                       into=None):
     """Composite weights (fragment order) and the 27 border-class biases of ConvTranspose3d(C,C,2,2) -> Conv3d(C,Co,3).
-    into = (wp, beff): re-pack in place (stable pointers for graph replay)."""
+    into = (wp, beff, ws): re-pack in place (stable pointers for graph replay)."""
+    return _upconv_pack(wt, bt, w3, cinv, cin_p, nout_p, into, False)
+
+
+def upconv_fused_pack_all(wt: torch.Tensor, bt: torch.Tensor, w3: torch.Tensor, cinv, cin_p: int, nout_p: int,
+                          into=None):
+    """upconv_fused_pack and upconv_fused_pack_bwd in one call (three launches): returns (wp, beff, ws, wpd).
+    into = (wp, beff, ws, wpd): re-pack in place."""
+    return _upconv_pack(wt, bt, w3, cinv, cin_p, nout_p, into, True)
+
+
+def _upconv_pack(wt, bt, w3, cinv, cin_p, nout_p, into, with_wpd: bool):
     lib = _lib.load()
     c, co = wt.shape[0], w3.shape[0]
     assert wt.shape == (c, c, 2, 2, 2) and w3.shape == (co, c, 3, 3, 3) and bt.shape == (c,)
     if into is not None:
-        wp, beff, ws = into
+        bufs = tuple(into)
+        assert len(bufs) == 3 + with_wpd
     else:
-        wp = torch.empty(lib.ctu_upconv_fused_packed_floats(cin_p, nout_p), dtype=torch.float32, device=wt.device)
-        beff = torch.empty((27, nout_p), dtype=torch.float32, device=wt.device)
-        ws = torch.empty(lib.ctu_upconv_fused_pack_ws_floats(c, nout_p), dtype=torch.float32, device=wt.device)
-    _lib.check(lib.ctu_upconv_fused_pack(wt.detach().contiguous().data_ptr(), bt.detach().contiguous().data_ptr(),
-                                         w3.detach().contiguous().data_ptr(), c, co, _ptr(cinv), cin_p, nout_p, wp.data_ptr(),
-                                         beff.data_ptr(), ws.data_ptr(), _stream()), "upconv_fused_pack")
-    return wp, beff, ws
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=wt.device)
+        bufs = (new(lib.ctu_upconv_fused_packed_floats(cin_p, nout_p)), new((27, nout_p)),
+                new(lib.ctu_upconv_fused_pack_ws_floats(c, nout_p)))
+        if with_wpd:
+            bufs += (new(lib.ctu_upconv_fused_bwd_packed_floats(cin_p, nout_p)),)
+    wp, beff, ws = bufs[:3]
+    _lib.check(lib.ctu_upconv_fused_pack_all(wt.detach().contiguous().data_ptr(), bt.detach().contiguous().data_ptr(),
+                                             w3.detach().contiguous().data_ptr(), c, co, _ptr(cinv), cin_p, nout_p, wp.data_ptr(),
+                                             beff.data_ptr(), ws.data_ptr(), bufs[3].data_ptr() if with_wpd else None, _stream()),
+               "upconv_fused_pack")
+    return bufs
 
 
 def upconv_fused_num_blocks(dims, nout_p: int) -> int:

@@ -363,6 +363,9 @@ int ctu_skip_add(const float* a, int a_cs, const float* a_scale, const float* a_
  *   ctu_upconv_fused_pack: wt [C][C][2][2][2], bt [C], w3 [Co][C][3][3][3] (torch layouts) -> wp (packed_floats)
  *     and beff [27][nout_p]; cinv maps padded input positions to logical channels (concat layout), NULL = identity;
  *     ws = pack_ws_floats scratch (transposed copies of the two weight tensors).
+ *   ctu_upconv_fused_pack_all: the same plus wpd (ctu_upconv_fused_pack_bwd's data-gradient packing, bwd_packed_floats; NULL =
+ *     none) in three launches -- transposes, composite weights + beff, gathers (PW packing + wpd).  Every element of every
+ *     output is written on every call.
  *   ctu_upconv_fused_fwd: in = COARSE activations [N,D,H,W,in_cs] with the lazy BatchNorm transform, out = RAW
  *     fine-grid output [N,2D,2H,2W,out_cs]; stats = num_blocks rows of [2][nout_p] partial sums for ctu_bn_finalize. */
 int ctu_upconv_fused_supported(int k, int D, int H, int W, int cin_p, int nout_p);
@@ -371,6 +374,8 @@ int ctu_upconv_fused_num_blocks(int N, int D, int H, int W, int nout_p);
 size_t ctu_upconv_fused_pack_ws_floats(int C, int nout_p);
 int ctu_upconv_fused_pack(const float* wt, const float* bt, const float* w3, int C, int Co, const int32_t* cinv,
                           int cin_p, int nout_p, float* wp, float* beff, float* ws, void* stream);
+int ctu_upconv_fused_pack_all(const float* wt, const float* bt, const float* w3, int C, int Co, const int32_t* cinv,
+                              int cin_p, int nout_p, float* wp, float* beff, float* ws, float* wpd, void* stream);
 int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                          int in_relu, const float* wp, const float* beff, float* out, int out_cs, int nout_p,
                          float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail, void* stream);
