@@ -695,6 +695,184 @@ __global__ void adam_amsgrad_dev_kernel(AdamTable tb, const float* __restrict__ 
     adam_amsgrad_body<true>(tb, step, 0.f, beta1, beta2, omb1, omb2, eps, wd, decoupled, skip, dlr, gcoef);
 }
 
+// ------------------------------------------------------------------ SGD and RMSprop
+// torch.optim.SGD / torch.optim.RMSprop over a pointer table, launched like the Adam kernels (table by value, 64 tensors a
+// launch, adam_step_inc_kernel in front).  One kernel per rule serves the host and the device learning rate: dlr != NULL
+// reads it as (float)dlr[0], rounded where the host call rounds its argument.  A state slot the options do not use is
+// NULL and never dereferenced.  Arithmetic is fp32 in the order written; the weight decay is the one fused multiply-add.
+struct OptArgs {
+    const float* step;                  // device step counter, already incremented for this step (unless it is skipped)
+    const double* dlr;                  // NULL: lr below
+    const float* gcoef;                 // NULL or the clip coefficient
+    const float* skip;                  // NULL or the overflow flag
+    float lr, wd, mu;
+    float omd;                          // SGD: 1 - dampening;  RMSprop: 1 - alpha (formed in double on the host, as torch does)
+    float alpha, eps;                   // RMSprop
+    int nesterov, centered, maximize;
+};
+
+struct SgdTable {
+    float* p[ADAM_MAXT];
+    const float* g[ADAM_MAXT];
+    float* buf[ADAM_MAXT];
+    int64_t n[ADAM_MAXT];
+};
+
+struct RmsTable {
+    float* p[ADAM_MAXT];
+    const float* g[ADAM_MAXT];
+    float* sq[ADAM_MAXT];
+    float* buf[ADAM_MAXT];
+    float* ga[ADAM_MAXT];
+    int64_t n[ADAM_MAXT];
+};
+
+// what the element rules read besides the tensors, resolved once per thread
+struct OptScalars {
+    float lr, coef;
+    bool clip, first;
+};
+
+__device__ __forceinline__ OptScalars opt_scalars(const OptArgs& a) {
+    OptScalars s;
+    s.lr = a.dlr ? (float)a.dlr[0] : a.lr;
+    s.clip = a.gcoef != nullptr;
+    s.coef = s.clip ? a.gcoef[0] : 1.f;
+    s.first = a.step[0] == 1.f;         // the first APPLIED step: a skipped one left the counter at 0
+    return s;
+}
+
+__device__ __forceinline__ float opt_grad(float g, float p, const OptArgs& a, const OptScalars& s) {
+#pragma clang fp contract(off)
+    if (s.clip) g = g * s.coef;
+    if (a.maximize) g = -g;
+    if (a.wd != 0.f) g = fmaf(a.wd, p, g);         // one rounding, as torch's add(alpha=wd) on the GPU and the Adam kernel:
+    return g;                                      // where g cancels to ~0, RMSprop's g / avg follows its last bit
+}
+
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, const OptArgs& a, const OptScalars& s) {
+#pragma clang fp contract(off)
+    g = opt_grad(g, p, a, s);
+    if (a.mu != 0.f) {
+        buf = s.first ? g : a.mu * buf + a.omd * g;
+        g = a.nesterov ? g + a.mu * buf : buf;
+    }
+    p = p - s.lr * g;
+}
+
+__device__ __forceinline__ void rms_elem(float& p, float g, float& sq, float& buf, float& ga, const OptArgs& a,
+                                         const OptScalars& s) {
+#pragma clang fp contract(off)
+    g = opt_grad(g, p, a, s);
+    sq = a.alpha * sq + a.omd * g * g;
+    float avg;
+    if (a.centered) {
+        ga = ga + a.omd * (g - ga);
+        avg = sqrtf(sq - ga * ga) + a.eps;
+    } else {
+        avg = sqrtf(sq) + a.eps;
+    }
+    if (a.mu > 0.f) {
+        buf = a.mu * buf + g / avg;
+        p = p - s.lr * buf;
+    } else {
+        p = p - s.lr * (g / avg);
+    }
+}
+
+// How one tensor's n elements split into a scalar head, 16-byte groups and a scalar tail.  Pointers are only 4-byte aligned
+// (a parameter may be a view at an odd float offset of its storage): the vector body exists when every pointer in use sits
+// at the same offset within 16 bytes, so that one head aligns them all; otherwise the whole tensor goes the scalar way.
+struct OptSpan {
+    int64_t head, n4;
+};
+
+__device__ __forceinline__ OptSpan opt_span(int64_t n, const void* p, const void* g, const void* s0, const void* s1,
+                                            const void* s2) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p) & 15;
+    bool same = (reinterpret_cast<uintptr_t>(g) & 15) == a;
+    if (s0) same = same && (reinterpret_cast<uintptr_t>(s0) & 15) == a;
+    if (s1) same = same && (reinterpret_cast<uintptr_t>(s1) & 15) == a;
+    if (s2) same = same && (reinterpret_cast<uintptr_t>(s2) & 15) == a;
+    OptSpan sp;
+    if (!same) { sp.head = n; sp.n4 = 0; return sp; }
+    const int64_t h = (int64_t)(((16 - a) & 15) >> 2);
+    sp.head = h < n ? h : n;
+    sp.n4 = (n - sp.head) >> 2;
+    return sp;
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void sgd_kernel(SgdTable tb, OptArgs a) {
+    if (a.skip && a.skip[0] != 0.f) return;
+    const OptScalars s = opt_scalars(a);
+    const int t = blockIdx.y;
+    const int64_t n = tb.n[t];
+    float* __restrict__ p = tb.p[t];
+    const float* __restrict__ g = tb.g[t];
+    float* __restrict__ b = a.mu != 0.f ? tb.buf[t] : nullptr;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const OptSpan sp = opt_span(n, p, g, b, nullptr, nullptr);
+    auto scalar = [&](int64_t i) {
+        float pv = p[i], bv = b ? b[i] : 0.f;
+        sgd_elem(pv, g[i], bv, a, s);
+        if (b) b[i] = bv;
+        p[i] = pv;
+    };
+    for (int64_t i = tid; i < sp.head; i += nthr) scalar(i);
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p + sp.head);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + sp.head);
+    float4* __restrict__ b4 = b ? reinterpret_cast<float4*>(b + sp.head) : nullptr;
+    for (int64_t q = tid; q < sp.n4; q += nthr) {
+        float4 pv = p4[q], bv = b4 ? b4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gv = g4[q];
+        sgd_elem(pv.x, gv.x, bv.x, a, s); sgd_elem(pv.y, gv.y, bv.y, a, s);
+        sgd_elem(pv.z, gv.z, bv.z, a, s); sgd_elem(pv.w, gv.w, bv.w, a, s);
+        if (b4) b4[q] = bv;
+        p4[q] = pv;
+    }
+    for (int64_t i = sp.head + (sp.n4 << 2) + tid; i < n; i += nthr) scalar(i);
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void rmsprop_kernel(RmsTable tb, OptArgs a) {
+    if (a.skip && a.skip[0] != 0.f) return;
+    const OptScalars s = opt_scalars(a);
+    const int t = blockIdx.y;
+    const int64_t n = tb.n[t];
+    float* __restrict__ p = tb.p[t];
+    const float* __restrict__ g = tb.g[t];
+    float* __restrict__ sq = tb.sq[t];
+    float* __restrict__ b = a.mu > 0.f ? tb.buf[t] : nullptr;
+    float* __restrict__ ga = a.centered ? tb.ga[t] : nullptr;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const OptSpan sp = opt_span(n, p, g, sq, b, ga);
+    auto scalar = [&](int64_t i) {
+        float pv = p[i], sv = sq[i], bv = b ? b[i] : 0.f, av = ga ? ga[i] : 0.f;
+        rms_elem(pv, g[i], sv, bv, av, a, s);
+        sq[i] = sv;
+        if (b) b[i] = bv;
+        if (ga) ga[i] = av;
+        p[i] = pv;
+    };
+    for (int64_t i = tid; i < sp.head; i += nthr) scalar(i);
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p + sp.head);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + sp.head);
+    float4* __restrict__ s4 = reinterpret_cast<float4*>(sq + sp.head);
+    float4* __restrict__ b4 = b ? reinterpret_cast<float4*>(b + sp.head) : nullptr;
+    float4* __restrict__ a4 = ga ? reinterpret_cast<float4*>(ga + sp.head) : nullptr;
+    for (int64_t q = tid; q < sp.n4; q += nthr) {
+        float4 pv = p4[q], sv = s4[q], bv = b4 ? b4[q] : z4, av = a4 ? a4[q] : z4;
+        const float4 gv = g4[q];
+        rms_elem(pv.x, gv.x, sv.x, bv.x, av.x, a, s); rms_elem(pv.y, gv.y, sv.y, bv.y, av.y, a, s);
+        rms_elem(pv.z, gv.z, sv.z, bv.z, av.z, a, s); rms_elem(pv.w, gv.w, sv.w, bv.w, av.w, a, s);
+        s4[q] = sv;
+        if (b4) b4[q] = bv;
+        if (a4) a4[q] = av;
+        p4[q] = pv;
+    }
+    for (int64_t i = sp.head + (sp.n4 << 2) + tid; i < n; i += nthr) scalar(i);
+}
+
 // ------------------------------------------------------------------ global gradient norm and clip coefficient
 // torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite=False) over a pointer table, in two launches and in a
 // fixed order: per-thread double sums of g*g, a fixed-order tree per block, one float partial per block (stage one);
@@ -1210,6 +1388,86 @@ extern "C" int ctu_adam_amsgrad_dev(void* const* ptrs, const int64_t* sizes, int
                                                                   (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
                                                                   (float)weight_decay, decoupled, skip_flag, grad_coef);
         CTU_CHECK_LAUNCH("adam_amsgrad_dev");
+    }
+    return CTU_OK;
+}
+
+namespace {
+// the shared argument checks of ctu_sgd / ctu_rmsprop: nothing is launched unless every tensor passes.  need[k]: slot k of
+// a tensor's K pointers must be non-null (an unused state slot may be NULL).
+int opt_check(const char* what, void* const* ptrs, const int64_t* sizes, int n, const float* step, int K, const bool* need) {
+    CTU_REQUIRE(ptrs && sizes && n > 0 && step, "%s: bad argument", what);
+    for (int t = 0; t < n; ++t) {
+        CTU_REQUIRE(sizes[t] >= 0, "%s: negative size at %d", what, t);
+        for (int k = 0; k < K; ++k) {
+            void* q = ptrs[(size_t)t * K + k];
+            CTU_REQUIRE(q || !need[k], "%s: null tensor pointer at %d (slot %d)", what, t, k);
+            CTU_REQUIRE(((uintptr_t)q & 3) == 0, "%s: tensor %d (slot %d) is not 4-byte aligned", what, t, k);
+        }
+    }
+    return CTU_OK;
+}
+
+inline int opt_grid_x(int64_t mx) {
+    int64_t gx = ceil_div64(mx, EW_BLOCK * 4);
+    return gx > 128 ? 128 : (gx < 1 ? 1 : (int)gx);
+}
+}  // namespace
+
+extern "C" int ctu_sgd(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr_dev, double lr,
+                       double momentum, double dampening, double weight_decay, int nesterov, int maximize,
+                       const float* grad_coef, const float* skip_flag, void* stream) {
+    const bool need[3] = {true, true, momentum != 0.0};
+    if (int rc = opt_check("sgd", ptrs, sizes, n, step, 3, need)) return rc;
+    CTU_REQUIRE(!nesterov || (momentum != 0.0 && dampening == 0.0),
+                "sgd: Nesterov momentum requires a momentum and zero dampening (momentum=%g dampening=%g)", momentum, dampening);
+    OptArgs a = {};
+    a.step = step; a.dlr = lr_dev; a.gcoef = grad_coef; a.skip = skip_flag;
+    a.lr = (float)lr; a.wd = (float)weight_decay; a.mu = (float)momentum; a.omd = (float)(1.0 - dampening);
+    a.nesterov = nesterov != 0; a.maximize = maximize != 0;
+    hipStream_t st = (hipStream_t)stream;
+    adam_step_inc_kernel<<<1, 1, 0, st>>>(step, skip_flag);
+    CTU_CHECK_LAUNCH("adam_step_inc");
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
+        const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
+        SgdTable tb;
+        int64_t mx = 1;
+        for (int t = 0; t < nt; ++t) {
+            void* const* q = ptrs + (size_t)(t0 + t) * 3;
+            tb.p[t] = (float*)q[0]; tb.g[t] = (const float*)q[1]; tb.buf[t] = (float*)q[2]; tb.n[t] = sizes[t0 + t];
+            if (tb.n[t] > mx) mx = tb.n[t];
+        }
+        sgd_kernel<<<dim3(opt_grid_x(mx), nt), EW_BLOCK, 0, st>>>(tb, a);
+        CTU_CHECK_LAUNCH("sgd");
+    }
+    return CTU_OK;
+}
+
+extern "C" int ctu_rmsprop(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr_dev, double lr,
+                           double alpha, double eps, double weight_decay, double momentum, int centered, int maximize,
+                           const float* grad_coef, const float* skip_flag, void* stream) {
+    const bool need[5] = {true, true, true, momentum != 0.0, centered != 0};
+    if (int rc = opt_check("rmsprop", ptrs, sizes, n, step, 5, need)) return rc;
+    OptArgs a = {};
+    a.step = step; a.dlr = lr_dev; a.gcoef = grad_coef; a.skip = skip_flag;
+    a.lr = (float)lr; a.wd = (float)weight_decay; a.mu = (float)momentum; a.omd = (float)(1.0 - alpha);
+    a.alpha = (float)alpha; a.eps = (float)eps;
+    a.centered = centered != 0; a.maximize = maximize != 0;
+    hipStream_t st = (hipStream_t)stream;
+    adam_step_inc_kernel<<<1, 1, 0, st>>>(step, skip_flag);
+    CTU_CHECK_LAUNCH("adam_step_inc");
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAXT) {
+        const int nt = (n - t0) < ADAM_MAXT ? (n - t0) : ADAM_MAXT;
+        RmsTable tb;
+        int64_t mx = 1;
+        for (int t = 0; t < nt; ++t) {
+            void* const* q = ptrs + (size_t)(t0 + t) * 5;
+            tb.p[t] = (float*)q[0]; tb.g[t] = (const float*)q[1]; tb.sq[t] = (float*)q[2]; tb.buf[t] = (float*)q[3];
+            tb.ga[t] = (float*)q[4]; tb.n[t] = sizes[t0 + t];
+            if (tb.n[t] > mx) mx = tb.n[t];
+        }
+        rmsprop_kernel<<<dim3(opt_grid_x(mx), nt), EW_BLOCK, 0, st>>>(tb, a);
+        CTU_CHECK_LAUNCH("rmsprop");
     }
     return CTU_OK;
 }

@@ -228,6 +228,8 @@ SIGNATURES = {
     "ctu_grad_norm_num_blocks": (I, [P, I]),
     "ctu_grad_clip_coef": (I, [P, P, I, F, P, P, P, P]),
     "ctu_plateau_update": (I, [P, P, P, P, I, I, D, I, D, I, D, D, P]),
+    "ctu_sgd": (I, [P, P, I, P, P, D, D, D, D, I, I, P, P, P]),
+    "ctu_rmsprop": (I, [P, P, I, P, P, D, D, D, D, D, I, I, P, P, P]),
 }
 
 _lib = None

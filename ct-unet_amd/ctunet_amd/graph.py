@@ -14,10 +14,10 @@ launched on a side stream behind an event and runs UNDER segment k+1; the last s
 which waits for every bucket.  Only the last, smallest bucket's collective is exposed.  Without it the same step body
 is one graph: the chain without bucket boundaries.
 
-Train controls: with an ``optim.Adam(device_lr=True)`` every call uploads a changed ``group["lr"]`` before the
-replay, so host schedulers and manual edits take effect; ``scheduler=`` (``lr_scheduler.ReduceLROnPlateau``) is stepped
-with the total loss INSIDE the captured step, right behind the optimizer: the reference's per-batch
-``scheduler.step(pt_loss)`` without its host sync.
+Train controls: with an ``optim.Adam(device_lr=True)`` (or ``optim.SGD`` / ``optim.RMSprop``) every call
+uploads a changed ``group["lr"]`` before the replay, so host schedulers and manual edits take effect; ``scheduler=``
+(``lr_scheduler.ReduceLROnPlateau``) is stepped with the total loss INSIDE the captured step, right behind the optimizer:
+the reference's per-batch ``scheduler.step(pt_loss)`` without its host sync.
 """
 from __future__ import annotations
 
@@ -72,7 +72,8 @@ class _Segmenter:
 
 
 class GraphedTrainStep:
-    """model: a ctunet_amd model on the GPU; optimizer: ctunet_amd.optim.Adam/AdamW (or torch.optim with capturable=True).
+    """model: a ctunet_amd model on the GPU; optimizer: ctunet_amd.optim.Adam/AdamW/SGD/RMSprop (or torch.optim with
+    capturable=True).
     ``x.grad`` is not filled: the input gradient kernels run (``input_requires_grad``), their result is not kept."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, example_input: torch.Tensor,
@@ -92,8 +93,8 @@ class GraphedTrainStep:
         scaler = getattr(model, "loss_scaler", None)
         if scaler is not None and not hasattr(optimizer, "guard"):
             raise RuntimeError("GraphedTrainStep: a model with dynamic loss scaling needs an optimizer that reads the device "
-                               "overflow flag (ctunet_amd.optim.Adam / AdamW); loss_scaler.step(optimizer) would need a host "
-                               "sync inside the captured step")
+                               "overflow flag (ctunet_amd.optim.Adam / AdamW / SGD / RMSprop); loss_scaler.step(optimizer) "
+                               "would need a host sync inside the captured step")
         if hasattr(optimizer, "guard"):
             optimizer.guard(model)             # fp16: an overflowed step is skipped inside the replayed graph too
         if scaler is not None:                 # (dynamic: its state must exist on the GPU before anything is captured)

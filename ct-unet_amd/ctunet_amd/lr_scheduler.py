@@ -28,9 +28,9 @@ class ReduceLROnPlateau:
         if not isinstance(optimizer, torch.optim.Optimizer):
             raise TypeError(f"{type(optimizer).__name__} is not an Optimizer")
         if not (getattr(optimizer, "device_lr", False) and hasattr(optimizer, "sync_lr")):
-            raise ValueError("ctunet_amd.lr_scheduler.ReduceLROnPlateau needs a ctunet_amd.optim.Adam / AdamW built with "
-                             "device_lr=True (the kernel writes the learning rate the optimizer's kernel reads); use "
-                             "torch.optim.lr_scheduler.ReduceLROnPlateau for any other optimizer")
+            raise ValueError("ctunet_amd.lr_scheduler.ReduceLROnPlateau needs a ctunet_amd.optim.Adam / AdamW / SGD / RMSprop "
+                             "built with device_lr=True (the kernel writes the learning rate the optimizer's kernel reads); "
+                             "use torch.optim.lr_scheduler.ReduceLROnPlateau for any other optimizer")
         groups = optimizer.param_groups
         if isinstance(min_lr, (list, tuple)):
             if len(min_lr) != len(groups):

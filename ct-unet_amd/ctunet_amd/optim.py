@@ -16,6 +16,14 @@ Opt-in train controls that stay on the device, so a replayed graph follows them 
 reads; ``group["lr"]`` stays the Python float every torch scheduler edits, and ``sync_lr()`` uploads it when it changed.
 ``max_grad_norm=x`` clips the global gradient norm as ``clip_grad_norm_(model.parameters(), x)`` does: two launches
 form the norm and the coefficient, the Adam launch multiplies each gradient by it.
+
+``SGD`` and ``RMSprop`` (the reference's other two optimizers, Model.py:528-541) are the same construction over
+``ctu_sgd`` / ``ctu_rmsprop``: torch's hyper-parameter names, defaults, constructor errors and state entries
+(``momentum_buffer``; ``square_avg``, ``momentum_buffer``, ``grad_avg``, ``step``), so a ``torch.optim`` state dict loads
+into them and back, and every control above -- overflow guard, device learning rate, clipping, graph capture.  The
+shared counter shows in SGD's first step: ``momentum_buffer = grad`` happens on the group's first APPLIED step (an
+overflowed first step leaves it to the next one, as ``GradScaler.step`` leaves torch's state empty); a parameter that
+receives its first gradient later starts from a zero buffer instead.
 """
 from __future__ import annotations
 
@@ -27,17 +35,15 @@ import torch
 from . import _lib
 
 
-class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=True,
-                 decoupled_weight_decay=False, device_lr=False, max_grad_norm=None):
-        if not amsgrad:
-            raise NotImplementedError("ctunet_amd.optim.Adam implements the amsgrad variant the reference uses")
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
-            raise ValueError("invalid Adam hyper-parameter")
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError(f"ctunet_amd.optim.Adam: max_grad_norm must be positive, got {max_grad_norm}")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=True,
-                                      decoupled_weight_decay=decoupled_weight_decay))
+class _Fused(torch.optim.Optimizer):
+    """What every fused optimizer shares: the control protocol ``graph.py``, ``lr_scheduler.py``, ``loss_scale.py``,
+    ``checkpoint.py`` and ``trainer.py`` reach by duck typing, and the step around one group's launch.  A subclass names
+    itself (``_NAME``, for messages), lists one tensor's pointers (``_slots``, creating its state) and launches
+    (``_launch``)."""
+
+    _NAME = "Adam"
+
+    def _init_controls(self, device_lr, max_grad_norm) -> None:
         # fp16 training: a float32[1] device flag (model.overflow_flag()) that the backward sets when a loss-scaled gradient
         # overflowed; a step that sees it set changes nothing (torch.amp.GradScaler.step's found_inf), also inside a replayed
         # HIP graph.  None: every step is applied.
@@ -50,7 +56,12 @@ class Adam(torch.optim.Optimizer):
         self._clip_coef = None
         self._clip_ws = None
 
-    def guard(self, model) -> "Adam":
+    @classmethod
+    def _check_max_grad_norm(cls, max_grad_norm) -> None:
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"ctunet_amd.optim.{cls._NAME}: max_grad_norm must be positive, got {max_grad_norm}")
+
+    def guard(self, model):
         """Skip every step whose float16 backward overflowed (``model.overflow_flag()``); no-op for fp32 / bf16 models.
         Dynamic loss scaling (``model.loss_scaler``): the flag is the scaler's ``found_inf``, and every ``step()`` also
         launches ``loss_scaler.update()`` behind its own kernels.  The scaler is looked up on the model at each step, so
@@ -85,8 +96,9 @@ class Adam(torch.optim.Optimizer):
             if lr_t is not None and lr_t.device == dev and group.get("lr_shadow") == lr:
                 continue
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("ctunet_amd.optim.Adam: the device learning rate must be in place before a graph capture "
-                                   "(run one eager step or call sync_lr() first, and edit group['lr'] between replays only)")
+                raise RuntimeError(f"ctunet_amd.optim.{self._NAME}: the device learning rate must be in place before a graph "
+                                   "capture (run one eager step or call sync_lr() first, and edit group['lr'] between replays "
+                                   "only)")
             if lr_t is None:
                 group["lr_t"] = torch.full((1,), lr, dtype=torch.float64, device=dev)
             elif lr_t.device != dev:
@@ -117,8 +129,8 @@ class Adam(torch.optim.Optimizer):
         dev = grads[0].device
         if self._clip_ws is None or self._clip_ws.numel() < need or self._clip_ws.device != dev:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("ctunet_amd.optim.Adam: the clipping workspace is allocated by the first eager step; run "
-                                   "one before capturing a graph (GraphedTrainStep's warm-up does)")
+                raise RuntimeError(f"ctunet_amd.optim.{self._NAME}: the clipping workspace is allocated by the first eager "
+                                   "step; run one before capturing a graph (GraphedTrainStep's warm-up does)")
             self._clip_ws = torch.empty(need, dtype=torch.float32, device=dev)
             if self.last_grad_norm is None or self.last_grad_norm.device != dev:
                 self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -128,6 +140,19 @@ class Adam(torch.optim.Optimizer):
                                           self.last_grad_norm.data_ptr(), self._clip_coef.data_ptr(),
                                           torch.cuda.current_stream().cuda_stream), "grad_clip_coef")
         return self._clip_coef
+
+    # ------------------------------------------------------------------ what a subclass provides
+    def _first_count(self, live) -> float:
+        """The value a group's step counter starts from when the group carries none."""
+        return 0.0
+
+    def _slots(self, group, p, g, st) -> List[int]:
+        """The device pointers of one tensor in the entry point's order; creates the state entries that are missing."""
+        raise NotImplementedError
+
+    def _launch(self, lib, group, pa, sa, n, lr_ptr, coef_ptr, skip_ptr, stream) -> None:
+        """One group's update; ``lr_ptr`` is None for the host learning rate ``group["lr"]``."""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -148,48 +173,34 @@ class Adam(torch.optim.Optimizer):
                 continue
             for p in live:
                 if not p.is_cuda or p.dtype != torch.float32:
-                    raise RuntimeError("ctunet_amd.optim.Adam: parameters must be float32 on the GPU (no CPU fallback)")
+                    raise RuntimeError(f"ctunet_amd.optim.{self._NAME}: parameters must be float32 on the GPU (no CPU "
+                                       "fallback)")
             work.append((group, live, [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in live]))
         coef = None
         if self.max_grad_norm is not None and work:
             coef = self._clip(lib, [g for _, _, grads in work for g in grads])      # ONE norm over all groups
         for group, live, grads in work:
             if "step_t" not in group:
-                group["step_t"] = torch.zeros(1, dtype=torch.float32, device=live[0].device)
+                group["step_t"] = torch.full((1,), self._first_count(live), dtype=torch.float32, device=live[0].device)
             elif group["step_t"].device != live[0].device:
                 # load_state_dict casts per-parameter state to the parameter's device but leaves param_groups values
                 # where the checkpoint had them (map_location="cpu"): the kernel must never see a host pointer
                 group["step_t"] = group["step_t"].to(live[0].device)
             ptrs, sizes = [], []
             for p, g in zip(live, grads):
-                st = self.state[p]
-                if not st:
-                    st["step"] = group["step_t"]                    # shared device counter (torch keeps one per tensor)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                ptrs += [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                         st["max_exp_avg_sq"].data_ptr()]
+                ptrs += self._slots(group, p, g, self.state[p])
                 sizes.append(p.numel())
             n = len(live)
-            pa = (C.c_void_p * (5 * n))(*ptrs)
+            pa = (C.c_void_p * len(ptrs))(*ptrs)
             sa = (C.c_int64 * n)(*sizes)
-            b1, b2 = group["betas"]
-            stream = torch.cuda.current_stream().cuda_stream
-            if not self.device_lr:
-                _lib.check(lib.ctu_adam_amsgrad(pa, sa, n, group["step_t"].data_ptr(), float(group["lr"]), float(b1),
-                                                float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                int(bool(group["decoupled_weight_decay"])),
-                                                None if skip is None else skip.data_ptr(), stream), "adam_amsgrad")
-            else:
+            lr_ptr = None
+            if self.device_lr:
                 if "lr_t" not in group or group["lr_t"].device != live[0].device:
-                    raise RuntimeError("ctunet_amd.optim.Adam: the device learning rate must be in place before a graph "
-                                       "capture (run one eager step or call sync_lr() first)")
-                _lib.check(lib.ctu_adam_amsgrad_dev(pa, sa, n, group["step_t"].data_ptr(), group["lr_t"].data_ptr(),
-                                                    float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                    int(bool(group["decoupled_weight_decay"])),
-                                                    None if coef is None else coef.data_ptr(),
-                                                    None if skip is None else skip.data_ptr(), stream), "adam_amsgrad_dev")
+                    raise RuntimeError(f"ctunet_amd.optim.{self._NAME}: the device learning rate must be in place before a "
+                                       "graph capture (run one eager step or call sync_lr() first)")
+                lr_ptr = group["lr_t"].data_ptr()
+            self._launch(lib, group, pa, sa, n, lr_ptr, None if coef is None else coef.data_ptr(),
+                         None if skip is None else skip.data_ptr(), torch.cuda.current_stream().cuda_stream)
             # the kernel wrote the parameters through raw pointers: tell autograd / every (version-keyed) cache of
             # derived data -- the engine's MFMA-ordered weight copies -- that they changed
             torch.autograd.graph.increment_version(live)
@@ -199,8 +210,135 @@ class Adam(torch.optim.Optimizer):
         return loss
 
 
+def _zeros(p):
+    return torch.zeros_like(p, memory_format=torch.preserve_format)
+
+
+class Adam(_Fused):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=True,
+                 decoupled_weight_decay=False, device_lr=False, max_grad_norm=None):
+        if not amsgrad:
+            raise NotImplementedError("ctunet_amd.optim.Adam implements the amsgrad variant the reference uses")
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("invalid Adam hyper-parameter")
+        self._check_max_grad_norm(max_grad_norm)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=True,
+                                      decoupled_weight_decay=decoupled_weight_decay))
+        self._init_controls(device_lr, max_grad_norm)
+
+    def _slots(self, group, p, g, st):
+        if not st:
+            st["step"] = group["step_t"]                    # shared device counter (torch keeps one per tensor)
+            st["exp_avg"] = _zeros(p)
+            st["exp_avg_sq"] = _zeros(p)
+            st["max_exp_avg_sq"] = _zeros(p)
+        return [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                st["max_exp_avg_sq"].data_ptr()]
+
+    def _launch(self, lib, group, pa, sa, n, lr_ptr, coef_ptr, skip_ptr, stream):
+        b1, b2 = group["betas"]
+        hyper = (float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                 int(bool(group["decoupled_weight_decay"])))
+        if lr_ptr is None:
+            _lib.check(lib.ctu_adam_amsgrad(pa, sa, n, group["step_t"].data_ptr(), float(group["lr"]), *hyper, skip_ptr,
+                                            stream), "adam_amsgrad")
+        else:
+            _lib.check(lib.ctu_adam_amsgrad_dev(pa, sa, n, group["step_t"].data_ptr(), lr_ptr, *hyper, coef_ptr, skip_ptr,
+                                                stream), "adam_amsgrad_dev")
+
+
 class AdamW(Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=True, device_lr=False,
                  max_grad_norm=None):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, decoupled_weight_decay=True, device_lr=device_lr,
                          max_grad_norm=max_grad_norm)
+
+
+class SGD(_Fused):
+    """``torch.optim.SGD`` (momentum, dampening, weight decay, Nesterov, maximize) in one launch per 64 tensors."""
+
+    _NAME = "SGD"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 device_lr=False, max_grad_norm=None):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._check_max_grad_norm(max_grad_norm)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov, maximize=maximize))
+        self._init_controls(device_lr, max_grad_norm)
+
+    def _first_count(self, live):
+        # momentum buffers without a counter: a torch.optim.SGD state dict was loaded, and its first step is behind it
+        return 1.0 if any("momentum_buffer" in self.state[p] for p in live) else 0.0
+
+    def _slots(self, group, p, g, st):
+        buf = None
+        if group["momentum"] != 0:
+            if st.get("momentum_buffer") is None:
+                st["momentum_buffer"] = _zeros(p)           # the kernel's first applied step overwrites it with the gradient
+            buf = st["momentum_buffer"].data_ptr()
+        return [p.data_ptr(), g.data_ptr(), buf]
+
+    def _launch(self, lib, group, pa, sa, n, lr_ptr, coef_ptr, skip_ptr, stream):
+        _lib.check(lib.ctu_sgd(pa, sa, n, group["step_t"].data_ptr(), lr_ptr, float(group["lr"]), float(group["momentum"]),
+                               float(group["dampening"]), float(group["weight_decay"]), int(bool(group["nesterov"])),
+                               int(bool(group.get("maximize", False))), coef_ptr, skip_ptr, stream), "sgd")
+
+
+class RMSprop(_Fused):
+    """``torch.optim.RMSprop`` (alpha, eps, weight decay, momentum, centered, maximize) in one launch per 64 tensors."""
+
+    _NAME = "RMSprop"
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, *,
+                 maximize=False, device_lr=False, max_grad_norm=None):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if alpha < 0.0:
+            raise ValueError(f"Invalid alpha value: {alpha}")
+        self._check_max_grad_norm(max_grad_norm)
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum,
+                                      centered=centered, maximize=maximize))
+        self._init_controls(device_lr, max_grad_norm)
+
+    def _first_count(self, live):
+        # a loaded torch.optim.RMSprop state dict keeps one count per tensor: the group's counter continues from it
+        for p in live:
+            if "step" in self.state[p]:
+                return float(self.state[p]["step"])
+        return 0.0
+
+    def _slots(self, group, p, g, st):
+        if st.get("step") is not group["step_t"]:
+            st["step"] = group["step_t"]                    # shared device counter (torch keeps one per tensor)
+        if "square_avg" not in st:
+            st["square_avg"] = _zeros(p)
+        buf = ga = None
+        if group["momentum"] > 0:
+            if "momentum_buffer" not in st:
+                st["momentum_buffer"] = _zeros(p)
+            buf = st["momentum_buffer"].data_ptr()
+        if group["centered"]:
+            if "grad_avg" not in st:
+                st["grad_avg"] = _zeros(p)
+            ga = st["grad_avg"].data_ptr()
+        return [p.data_ptr(), g.data_ptr(), st["square_avg"].data_ptr(), buf, ga]
+
+    def _launch(self, lib, group, pa, sa, n, lr_ptr, coef_ptr, skip_ptr, stream):
+        _lib.check(lib.ctu_rmsprop(pa, sa, n, group["step_t"].data_ptr(), lr_ptr, float(group["lr"]), float(group["alpha"]),
+                                   float(group["eps"]), float(group["weight_decay"]), float(group["momentum"]),
+                                   int(bool(group["centered"])), int(bool(group.get("maximize", False))), coef_ptr,
+                                   skip_ptr, stream), "rmsprop")

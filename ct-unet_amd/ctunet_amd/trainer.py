@@ -60,13 +60,22 @@ class StepRunner:
         # per-batch float(loss) for the scheduler
         dev_lr = bool(p.get("device_lr", False))
         ctl = dict(device_lr=True, max_grad_norm=p.get("max_grad_norm")) if dev_lr else {}
-        if dev_lr and not (name in ("adam", "adamw") or getattr(name, "device_lr", False)):
+        # fused_optimizer (opt-in ini key): 'sgd' / 'rmsprop' build the fused classes, which take the controls above and
+        # skip overflowed float16 steps on the device; 'adam' / 'adamw' are fused either way
+        fused = bool(p.get("fused_optimizer", False))
+        if dev_lr and not (name in ("adam", "adamw") or (fused and name in ("sgd", "rmsprop"))
+                           or getattr(name, "device_lr", False)):
             raise ValueError(f"ctunet_amd: device_lr needs the fused optimizer ('adam' or 'adamw'), not '{name}': "
-                             "torch.optim optimizers take their learning rate from the host")
+                             "torch.optim optimizers take their learning rate from the host (fused_optimizer=True builds "
+                             "the fused 'sgd' / 'rmsprop')")
         if name == "adam":                      # fused multi-tensor kernels (same update rule as optim.Adam(amsgrad=True))
             p["optimizer"] = _optim.Adam(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True, **ctl)
         elif name == "adamw":
             p["optimizer"] = _optim.AdamW(net.parameters(), lr=lr, weight_decay=wd, amsgrad=True, **ctl)
+        elif name == "rmsprop" and fused:
+            p["optimizer"] = _optim.RMSprop(net.parameters(), lr=lr, weight_decay=wd, momentum=p.get("momentum", 0) or 0, **ctl)
+        elif name == "sgd" and fused:
+            p["optimizer"] = _optim.SGD(net.parameters(), lr=lr, momentum=p.get("momentum", 0) or 0, weight_decay=wd, **ctl)
         elif name == "rmsprop":
             p["optimizer"] = torch.optim.RMSprop(net.parameters(), lr=lr, weight_decay=wd, momentum=p.get("momentum", 0) or 0)
         elif name == "sgd":

@@ -1047,6 +1047,38 @@ int ctu_grad_clip_coef(void* const* gptrs, const int64_t* sizes, int n, float ma
 int ctu_plateau_update(const float* metric, double* lr, double* state, int32_t* counters, int mode_max, int threshold_rel,
                        double factor, int patience, double threshold, int cooldown, double min_lr, double eps, void* stream);
 
+/* --------------------------------------------------------------- SGD and RMSprop ---- */
+/* torch.optim.SGD and torch.optim.RMSprop over a list of float32 tensors with the device-side train controls of
+ * ctu_adam_amsgrad_dev: one step-counter launch plus one launch per 64 tensors, graph-capturable, fp32 arithmetic in the
+ * order written below (g + wd*p is one fused multiply-add, as in ctu_adam_amsgrad; nothing else is contracted).
+ *   ptrs ....... HOST array of K*n DEVICE pointers, K per tensor: {param, grad, momentum_buffer} for ctu_sgd (K = 3),
+ *                {param, grad, square_avg, momentum_buffer, grad_avg} for ctu_rmsprop (K = 5).  4-byte alignment is
+ *                enough (a view at an odd float offset); 16-byte accesses are used where a tensor's pointers share their
+ *                offset within 16 bytes.  A state slot the options do not use (momentum == 0, not centered) may be NULL and
+ *                is never dereferenced.
+ *   sizes ...... HOST int64[n], elements per tensor (0 allowed).
+ *   step ....... DEVICE float[1], incremented by this call before it is used: it counts the APPLIED steps, this one included.
+ *   lr_dev, lr . lr_dev != NULL: DEVICE double[1], lr = (float)lr_dev[0], rounded where the host call rounds `lr`;
+ *                NULL: the host argument.  Both give bit-equal results at the same rate.
+ *   grad_coef .. NULL or DEVICE float[1]: every gradient value is multiplied by it first (ctu_grad_clip_coef's coefficient).
+ *   skip_flag .. NULL or DEVICE float[1]; non-zero = nothing is written: no parameter, no state, no step counter.
+ * ctu_sgd, per element:      g = coef*grad;  if maximize: g = -g;  if wd != 0: g = g + wd*p
+ *                            if momentum != 0:  buf = g on the first applied step (step[0] == 1), which a skipped first
+ *                                               step leaves to the next one;  buf = momentum*buf + (1-dampening)*g after it;
+ *                                               g = g + momentum*buf if nesterov, else buf
+ *                            p = p - lr*g
+ * ctu_rmsprop, per element:  g as above;  sq = alpha*sq + (1-alpha)*g*g
+ *                            centered: ga = ga + (1-alpha)*(g - ga), avg = sqrtf(sq - ga*ga) + eps;  else avg = sqrtf(sq) + eps
+ *                            momentum > 0: buf = momentum*buf + g/avg, p = p - lr*buf;  else p = p - lr*(g/avg)
+ * Refused before any launch (non-zero status): null ptrs / sizes / step, n <= 0, a negative size, a null param or grad, a
+ * null state pointer the options need, a pointer that is not 4-byte aligned, nesterov without momentum or with dampening. */
+int ctu_sgd(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr_dev, double lr, double momentum,
+            double dampening, double weight_decay, int nesterov, int maximize, const float* grad_coef,
+            const float* skip_flag, void* stream);
+int ctu_rmsprop(void* const* ptrs, const int64_t* sizes, int n, float* step, const double* lr_dev, double lr, double alpha,
+                double eps, double weight_decay, double momentum, int centered, int maximize, const float* grad_coef,
+                const float* skip_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
