@@ -85,7 +85,8 @@ class FlapRecWShapePrior2OTrainDataset(Dataset):
     skulls: a list of [D,H,W] tensors or one [M,D,H,W] tensor, float32 or uint8, on the host or the device (host items
     are copied to the device per item); atlas: [D,H,W].  transform: a ``transforms.FlapRecTransform`` (default: the
     module's ``flap_rec_transform``, with the reference's decaying noise density); its hole must be double-output.
-    The transform runs as ONE fused pass per item; every call advances its device sample counter."""
+    The transform runs as ONE fused pass per item (after the warp of its ``spatial`` step, when it has one, as
+    ``transforms.cranioplasty_transform`` does); every call advances its device sample counters."""
 
     def __init__(self, skulls, atlas=None, transform=None, append_atlas: bool = True, device="cuda"):
         from . import transforms as T
@@ -100,7 +101,7 @@ class FlapRecWShapePrior2OTrainDataset(Dataset):
         if self.append_atlas and atlas is None:
             raise ValueError("ctunet_amd: append_atlas needs an atlas [D,H,W]")
         self.atlas = atlas.to(self.device, torch.float32).contiguous() if self.append_atlas else None
-        self.transform = T.FlapRecTransform(base.hole, base.noise, self.atlas)   # shares the hole / noise state
+        self.transform = T.FlapRecTransform(base.hole, base.noise, self.atlas, base.spatial)   # shares their state
 
     def __len__(self):
         return len(self.skulls)

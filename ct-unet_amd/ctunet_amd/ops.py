@@ -1309,3 +1309,43 @@ def affine_resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: 
                                                w1, matrix.data_ptr(), _double3(spacing), _double3(origin),
                                                _double3(out_spacing), _double3(out_origin), float(fill), out.data_ptr(),
                                                _stream()), "affine_resample")
+
+
+SPATIAL_RECORD = 26                              # CTU_SPATIAL_RECORD of ctunet_hip.h
+SPATIAL_MIN_POINTS, SPATIAL_MAX_POINTS = 4, 12   # CTU_SPATIAL_MIN_POINTS / CTU_SPATIAL_MAX_POINTS
+
+
+def _spatial_buffers(n: int, grid: Tuple[int, int, int], record: torch.Tensor, control: torch.Tensor) -> None:
+    for t, nm, numel in ((record, "record", n * SPATIAL_RECORD), (control, "control", n * 3 * grid[0] * grid[1] * grid[2])):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == numel, f"spatial {nm}"
+
+
+def spatial_draw(n: int, shape: Tuple[int, int, int], spacing, seq: torch.Tensor, seed: int, flip_mask: int, flip_p: float,
+                 affine_p: float, elastic_p: float, ranges, grid: Tuple[int, int, int], locked: int, record: torch.Tensor,
+                 control: torch.Tensor) -> None:
+    """record float64 [N, SPATIAL_RECORD] and control float64 [N, 3, Gz, Gy, Gx] of N samples, drawn from the device counter
+    seq (layout and rule: ctunet_hip.h, transforms.py).  ranges: the 11 host doubles of ctu_spatial_draw.  One launch."""
+    import ctypes
+    _spatial_buffers(n, grid, record, control)
+    assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1 and len(ranges) == 11
+    _lib.check(_lib.load().ctu_spatial_draw(n, shape[0], shape[1], shape[2], _double3(spacing), seq.data_ptr(), seed,
+                                            flip_mask, float(flip_p), float(affine_p), float(elastic_p),
+                                            (ctypes.c_double * 11)(*ranges), grid[0], grid[1], grid[2], locked,
+                                            record.data_ptr(), control.data_ptr(), _stream()), "spatial_draw")
+
+
+def spatial_warp(x: torch.Tensor, out: torch.Tensor, spacing, grid: Tuple[int, int, int], record: torch.Tensor,
+                 control: torch.Tensor, seq: torch.Tensor) -> None:
+    """out [N,C,D,H,W] = x warped by the samples' records and control grids (uint8 or float32, nearest, fill 0); advances
+    the device counter seq by N.  One launch, nothing allocated."""
+    for t, nm in ((x, "input"), (out, "output")):
+        if not t.is_cuda:
+            raise RuntimeError(f"ctunet_amd: spatial_warp {nm} must live on the GPU (MI355X); this path has no CPU fallback")
+        assert t.is_contiguous() and t.dim() == 5, nm
+    assert x.dtype in (torch.uint8, torch.float32) and out.dtype == x.dtype and out.shape == x.shape, "spatial_warp tensors"
+    n, c, d, h, w = x.shape
+    _spatial_buffers(n, grid, record, control)
+    assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1
+    _lib.check(_lib.load().ctu_spatial_warp(x.data_ptr(), RESAMPLE_CODE[x.dtype], n, c, d, h, w, _double3(spacing), grid[0],
+                                            grid[1], grid[2], record.data_ptr(), control.data_ptr(), seq.data_ptr(),
+                                            out.data_ptr(), _stream()), "spatial_warp")

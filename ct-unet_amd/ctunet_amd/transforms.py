@@ -43,15 +43,53 @@ Arithmetic: c_diam = ((0.25 + 0.75 u) size) 0.25 and nd' = U nd, every float32 o
 Results are float32: the network input [N, C, D, H, W] (channel 1 = atlas when given) and one-hot targets
 [N, 2, D, H, W] (full skull, flap; or the flap alone) -- the reference's sample schema after its dataset's one_hot
 (ctunet/pytorch/datasets.py:195-235).
+
+RandomSpatial (csrc/spatial.hip; tests/spatial_ref.py restates it): the random flip, slight elastic deformation and random
+zoom / shift / rotation that the docstring of the reference's ``cranioplasty_transform`` (173-228) lists before the flap
+extraction, as ONE nearest-neighbour gather with fill 0.  The parameters carry torchio's names; the rule is this package's
+own (torchio's random streams and resampling cannot be reproduced here, and no parity with it is claimed).  Axes are
+(z, y, x); all C channels of a sample share one warp.  For output voxel o of a sample, in float64, every operation rounded
+on its own (no contraction), with n the grid (D, H, W) and sp the spacing in mm:
+  1. world:   w_a = o_a sp_a
+  2. affine:  s_a = ((M_a0 w_0 + M_a1 w_1) + M_a2 w_2) + M_a3       (resample.affine_resample's form, origins 0)
+              M = [L | c - L c + t],  L = Rz(az) Ry(ay) Rx(ax) diag(scale),  c_a = ((n_a - 1) 0.5) sp_a, where, on vectors
+              (z, y, x) and with the angle in radians = degrees * 0.017453292519943295,
+                Rz = [[1,0,0],[0,cos,-sin],[0,sin,cos]]  Ry = [[cos,0,sin],[0,1,0],[-sin,0,cos]]  Rx = [[cos,-sin,0],[sin,cos,0],[0,0,1]]
+              every 3x3 product entry is ((a_0 b_0 + a_1 b_1) + a_2 b_2), L = ((Rz Ry) Rx) with column j times scale_j, and
+              M_a3 = (c_a - ((L_a0 c_0 + L_a1 c_1) + L_a2 c_2)) + t_a.  Not applied: M is the exact identity.
+  3. elastic: q = s + e(s) (not applied: q = s).  Per axis, G control points, m = G - 3:
+                g = (s / (n sp)) m, then g = g if g >= 0 else 0 (NaN -> 0), then g = g if g <= m else m
+                i = min(floor(g), m - 1),  f = g - i,  f2 = f f,  f3 = f2 f,  h = 1 - f
+                B0 = ((h h) h) / 6   B1 = ((3 f3 - 6 f2) + 4) / 6   B2 = ((((-3 f3) + 3 f2) + 3 f) + 1) / 6   B3 = f3 / 6
+              e_c = sum over l, then m, then n (x innermost) from 0, one accumulator per component c, of
+                    ((Bz_l By_m) Bx_n) phi_c[iz + l, iy + m, ix + n]
+  4. flip:    for each flipped axis  q_a = ((n_a - 1) sp_a) - q_a
+  5. sample:  u_a = q_a / sp_a,  k_a = floor(u_a + 0.5);  out = x[k] where every 0 <= k_a < n_a, else 0 (a non-finite u
+              fails the comparison, and every read sits behind it).
+This is the pull form of "flip, then elastic, then affine" applied to the image.
+Draws: Philox as above, key = the instance's seed, seq = its device sample counter + n.  All draws are consumed whether or
+not a step is applied; step X is applied iff u_X < p_X (float64 comparison of the exact u).  Stream 0, (c0 -> words):
+  0 -> (u_flip z, u_flip y, u_flip x, u_affine)      axis a flips iff a is in flip_axes and u_flip a < flip_p
+  1 -> (u_elastic, scale z, scale y, scale x)        scale = lo + u (hi - lo)
+  2 -> (angle z, angle y, angle x, -)                angle = (2 u - 1) degrees_a     (degrees, about axis a)
+  3 -> (t z, t y, t x, -)                            t = (2 u - 1) translation_a     (mm)
+Stream 1: c0 = the control point's flat index (iz Gy + iy) Gx + ix, words 0..2 = its z, y, x displacement
+phi_c = (2 u - 1) max_displacement_c; the ``locked_borders`` outer layers on every side are 0.
+The draw kernel records, per sample, float64 [26]: 0-2 flip flags, 3 affine applied, 4 elastic applied, 5-7 scales, 8-10
+angles, 11-13 translations, 14-25 M row-major -- and the control grid [N, 3, Gz, Gy, Gx]; M uses the device's sin / cos, so
+the restatement takes the recorded M for the voxel rule and tests bound M against NumPy's separately.
 """
 from __future__ import annotations
 
+import math
 import os
+from numbers import Real
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
+from .resample import _triple_real
 
 SHAPES = ("sphere", "box", "flap")
 _RECORD_FIELDS = ("apply", "count", "k", "cz", "cy", "cx", "size", "shape", "c_diam", "cut", "noise_applied", "nd")
@@ -315,17 +353,174 @@ class SaltAndPepper(_Recorded):
         return sample
 
 
+def _triple_nonneg(v, what: str) -> Tuple[float, float, float]:
+    t = _triple_real(v, what, "RandomSpatial", False)
+    if t is None or any(s < 0 for s in t):
+        raise ValueError(f"RandomSpatial: {what} must be a non-negative number or (z, y, x) triple, got {v!r}")
+    return t
+
+
+class RandomSpatial:
+    """Random flip, elastic deformation and affine map of a batch in one gather pass on the device (module docstring, the
+    "RandomSpatial" rule).  ``apply`` is the device batch form; ``sample`` dicts get "image" (and "target" where present)
+    warped by the same draw.  Two launches per call, no host sync: it can be captured in a graph after one warm call."""
+
+    def __init__(self, flip_axes=(0,), flip_p=0.5, scales=(0.9, 1.1), degrees=15, translation=(10, 10, 15), affine_p=0.5,
+                 num_control_points=7, max_displacement=7.5, locked_borders=2, elastic_p=0.5, spacing=(1, 1, 1),
+                 seed: Optional[int] = None):
+        axes = (flip_axes,) if isinstance(flip_axes, int) and not isinstance(flip_axes, bool) else tuple(flip_axes)
+        if any(isinstance(a, bool) or not isinstance(a, int) or not 0 <= a <= 2 for a in axes) or len(set(axes)) != len(axes):
+            raise ValueError(f"RandomSpatial: flip_axes must be distinct axes out of (0, 1, 2) = (z, y, x), got {flip_axes!r}")
+        self.flip_axes = axes
+        self.flip_p, self.affine_p = _check_p(flip_p, "flip_p"), _check_p(affine_p, "affine_p")
+        self.elastic_p = _check_p(elastic_p, "elastic_p")
+        try:
+            lo, hi = scales
+        except (TypeError, ValueError):
+            raise TypeError(f"RandomSpatial: scales must be a (low, high) pair, got {scales!r}") from None
+        if any(isinstance(v, bool) or not isinstance(v, Real) for v in (lo, hi)):
+            raise TypeError(f"RandomSpatial: scales must be a (low, high) pair of numbers, got {scales!r}")
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
+            raise ValueError(f"RandomSpatial: scales must satisfy 0 < low <= high < inf, got {scales!r}")
+        self.scales = (float(lo), float(hi))
+        self.degrees = _triple_nonneg(degrees, "degrees")
+        self.translation = _triple_nonneg(translation, "translation")
+        self.max_displacement = _triple_nonneg(max_displacement, "max_displacement")
+        g = num_control_points
+        g = (g, g, g) if isinstance(g, int) and not isinstance(g, bool) else g
+        try:
+            g = tuple(g)
+        except TypeError:
+            raise TypeError(f"RandomSpatial: num_control_points must be an int or a (z, y, x) triple, got {g!r}") from None
+        if len(g) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in g):
+            raise TypeError(f"RandomSpatial: num_control_points must be an int or a (z, y, x) triple of ints, got {g!r}")
+        if any(not ops.SPATIAL_MIN_POINTS <= v <= ops.SPATIAL_MAX_POINTS for v in g):
+            raise ValueError(f"RandomSpatial: num_control_points must lie in {ops.SPATIAL_MIN_POINTS}.."
+                             f"{ops.SPATIAL_MAX_POINTS} per axis, got {g!r}")
+        self.num_control_points = g
+        if isinstance(locked_borders, bool) or locked_borders not in (0, 1, 2):
+            raise ValueError(f"RandomSpatial: locked_borders must be 0, 1 or 2, got {locked_borders!r}")
+        if any(2 * locked_borders >= v for v in g):
+            raise ValueError(f"RandomSpatial: locked_borders={locked_borders} leaves no free control point of {g}")
+        self.locked_borders = int(locked_borders)
+        self.spacing = _triple_real(spacing, "spacing", "RandomSpatial", True)
+        if self.spacing is None:
+            raise TypeError("RandomSpatial: spacing must be a number or a (z, y, x) triple")
+        self._rng = _DeviceRng(seed)
+        self._record: Optional[torch.Tensor] = None
+        self._control: Optional[torch.Tensor] = None
+
+    @property
+    def seed(self) -> int:
+        return self._rng.seed
+
+    def to(self, device) -> "RandomSpatial":
+        self._rng.to(device)
+        return self
+
+    def state_dict(self) -> Dict:
+        c, _ = self._rng.state()
+        return {"seed": self._rng.seed, "counter": c}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        self._rng.seed = _seed(sd["seed"])
+        self._rng.load(sd["counter"], None)
+
+    def _buffers(self, n: int, device: torch.device):
+        """The record and the control grid of a batch of n: kept between calls, so a steady call allocates nothing."""
+        if self._record is None or self._record.shape[0] != n or self._record.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd: call the transform once with this batch size before capturing it in a graph")
+            self._record = torch.empty((n, ops.SPATIAL_RECORD), dtype=torch.float64, device=device)
+            self._control = torch.empty((n, 3) + self.num_control_points, dtype=torch.float64, device=device)
+        return self._record, self._control
+
+    def apply(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [N,C,D,H,W] uint8 / float32 on the GPU -> the warped batch, same dtype and shape (out: caller-supplied, not x)."""
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"RandomSpatial: expected a torch.Tensor, got {type(x).__name__}")
+        if x.dim() != 5 or x.numel() == 0:
+            raise ValueError(f"RandomSpatial: x must be a non-empty [N,C,D,H,W] batch, got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"RandomSpatial: x must be uint8 or float32, got {x.dtype}")
+        if out is not None:
+            if not isinstance(out, torch.Tensor):
+                raise TypeError(f"RandomSpatial: out must be a tensor, got {type(out).__name__}")
+            if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+                raise ValueError(f"RandomSpatial: out must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on "
+                                 f"{x.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if not x.is_cuda:
+            raise ValueError("RandomSpatial: x must live on the GPU (MI355X); this path has no CPU fallback")
+        x = x.contiguous()
+        nbytes = x.numel() * x.element_size()
+        if out is not None and out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("RandomSpatial: out overlaps x; the gather cannot run in place")
+        n, _, d, h, w = x.shape
+        self._rng.to(x.device)
+        record, control = self._buffers(n, x.device)
+        if out is None:
+            out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            ops.spatial_draw(n, (d, h, w), self.spacing, self._rng.counter, self._rng.seed,
+                             sum(1 << a for a in self.flip_axes), self.flip_p, self.affine_p, self.elastic_p,
+                             self.scales + self.degrees + self.translation + self.max_displacement,
+                             self.num_control_points, self.locked_borders, record, control)
+            ops.spatial_warp(x, out, self.spacing, self.num_control_points, record, control, self._rng.counter)
+        return out
+
+    @property
+    def last_params(self) -> List[Dict]:
+        """Per-sample records of the last call (one read-back): flip (z, y, x), affine, elastic (the steps applied), scales,
+        degrees, translation (the drawn values, used or not) and matrix (M, float64 [3, 4])."""
+        if self._record is None:
+            raise RuntimeError("ctunet_amd: the transform has not been called yet")
+        out = []
+        for r in self._record.cpu():
+            out.append({"flip": tuple(bool(v) for v in r[0:3]), "affine": bool(r[3]), "elastic": bool(r[4]),
+                        "scales": tuple(r[5:8].tolist()), "degrees": tuple(r[8:11].tolist()),
+                        "translation": tuple(r[11:14].tolist()), "matrix": r[14:26].reshape(3, 4).clone()})
+        return out
+
+    @property
+    def last_control(self) -> torch.Tensor:
+        """The control displacements (mm) of the last call, float64 [N, 3, Gz, Gy, Gx] on the host (one read-back)."""
+        if self._control is None:
+            raise RuntimeError("ctunet_amd: the transform has not been called yet")
+        return self._control.cpu()
+
+    def __call__(self, sample: Dict) -> Dict:
+        img = sample["image"]
+        if not isinstance(img, torch.Tensor):
+            raise TypeError(f"Expected 'torch.Tensor'. Got {type(img)}.")
+        is_batch = img.dim() == 4
+        tg = sample.get("target")
+        tgs = [] if tg is None else (list(tg) if isinstance(tg, (tuple, list)) else [tg])
+        vols = [img] + tgs                                   # one channel each: the same draw warps them all
+        kind = torch.uint8 if all(v.dtype in (torch.uint8, torch.bool) for v in vols) else torch.float32
+        b = torch.stack([(v if is_batch else v.unsqueeze(0)).to("cuda").to(kind) for v in vols], 1)
+        out = self.apply(b)
+        res = [out[:, i].to(v.dtype) if is_batch else out[0, i].to(v.dtype) for i, v in enumerate(vols)]
+        sample["image"] = res[0]
+        if tg is not None:
+            sample["target"] = tuple(res[1:]) if isinstance(tg, (tuple, list)) else res[1]
+        return sample
+
+
 class FlapRecTransform(_Recorded):
     """``hole`` then ``noise`` in ONE fused pass, bit-equal to applying them in sequence (each keeps its own seed, counter
     and density); ``atlas`` [D,H,W] float32 becomes channel 1 of the network input, as the shape-prior datasets append it."""
 
-    def __init__(self, hole: SkullRandomHole, noise: Optional[SaltAndPepper] = None, atlas: Optional[torch.Tensor] = None):
-        if not isinstance(hole, SkullRandomHole) or not (noise is None or isinstance(noise, SaltAndPepper)):
-            raise TypeError("FlapRecTransform(hole: SkullRandomHole, noise: SaltAndPepper | None, atlas=None)")
+    def __init__(self, hole: SkullRandomHole, noise: Optional[SaltAndPepper] = None, atlas: Optional[torch.Tensor] = None,
+                 spatial: Optional[RandomSpatial] = None):
+        if not isinstance(hole, SkullRandomHole) or not (noise is None or isinstance(noise, SaltAndPepper)) \
+                or not (spatial is None or isinstance(spatial, RandomSpatial)):
+            raise TypeError("FlapRecTransform(hole: SkullRandomHole, noise: SaltAndPepper | None, atlas=None, "
+                            "spatial: RandomSpatial | None)")
         if noise is not None and (noise.keyws[:1] != ("image",) or noise.apply_to != (True,) + (False,) * (len(noise.apply_to) - 1)):
             raise ValueError("FlapRecTransform: the fused noise applies to the image only (apply_to=(True, False))")
-        self.hole, self.noise = hole, noise
+        self.hole, self.noise, self.spatial = hole, noise, spatial
         self.atlas = None if atlas is None else atlas.float().contiguous()
+        self._warped: Optional[torch.Tensor] = None
 
     def to(self, device) -> "FlapRecTransform":
         self.hole.to(device)
@@ -333,20 +528,41 @@ class FlapRecTransform(_Recorded):
             self.noise.to(device)
         if self.atlas is not None:
             self.atlas = self.atlas.to(device)
+        if self.spatial is not None:
+            self.spatial.to(device)
         return self
 
     def state_dict(self) -> Dict:
-        return {"hole": self.hole.state_dict(), "noise": None if self.noise is None else self.noise.state_dict()}
+        sd = {"hole": self.hole.state_dict(), "noise": None if self.noise is None else self.noise.state_dict()}
+        if self.spatial is not None:
+            sd["spatial"] = self.spatial.state_dict()
+        return sd
 
     def load_state_dict(self, sd: Dict) -> None:
         self.hole.load_state_dict(sd["hole"])
         if self.noise is not None:
             self.noise.load_state_dict(sd["noise"])
+        if self.spatial is not None and sd.get("spatial") is not None:
+            self.spatial.load_state_dict(sd["spatial"])
+
+    def _warp(self, skulls: torch.Tensor) -> torch.Tensor:
+        """The skulls' uint8 casts warped by ``spatial`` into a uint8 buffer kept between calls."""
+        skulls = _batch(skulls, "skulls")
+        if skulls.dtype != torch.uint8:
+            skulls = skulls.to(torch.uint8)                 # the value of a voxel is its uint8 cast (truncation)
+        if self._warped is None or self._warped.shape != skulls.shape or self._warped.device != skulls.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd: call the transform once with this shape before capturing it in a graph")
+            self._warped = torch.empty_like(skulls)
+        return self.spatial.apply(skulls, out=self._warped)
 
     def apply(self, skulls: torch.Tensor, x: Optional[torch.Tensor] = None,
               targets: Optional[Sequence[torch.Tensor]] = None):
         """skulls [N,1,D,H,W] -> (x [N,C,D,H,W], one-hot targets), float32, written into x / targets when given (e.g.
-        ``GraphedTrainStep.x`` / ``.targets``)."""
+        ``GraphedTrainStep.x`` / ``.targets``).  With ``spatial`` the skulls are warped first; the full-skull target is the
+        warped skull and the atlas channel is not warped."""
+        if self.spatial is not None:
+            skulls = self._warp(skulls)
         if self.atlas is not None and self.atlas.device != skulls.device:
             self.atlas = self.atlas.to(skulls.device)
         return _run(self.hole, self.noise, skulls, self.atlas, x, targets)
@@ -356,7 +572,10 @@ class FlapRecTransform(_Recorded):
         return self.hole._params            # the records of the last call of its hole (fused or not)
 
     def __call__(self, sample: Dict) -> Dict:
-        """The reference's Compose([hole, noise]) on a sample dict: float32 image, uint8 target(s); no atlas."""
+        """The reference's Compose([hole, noise]) on a sample dict: float32 image, uint8 target(s); no atlas.  With
+        ``spatial`` the image is warped first."""
+        if self.spatial is not None:
+            sample = dict(sample, image=self.spatial({"image": sample["image"]})["image"])
         sample = self.hole(sample)
         img = sample["image"]
         if self.noise is not None:
@@ -367,3 +586,13 @@ class FlapRecTransform(_Recorded):
 
 
 flap_rec_transform = FlapRecTransform(SkullRandomHole(double_output=True), SaltAndPepper(p=.5, noise_density=.05))
+
+cranioplasty_transform = FlapRecTransform(SkullRandomHole(p=0.9, double_output=True), SaltAndPepper(p=1, noise_density=.05),
+                                          spatial=RandomSpatial(flip_axes=(0,)))
+"""The pipeline the docstring of the reference's ``cranioplasty_transform`` (ctunet/pytorch/transforms.py:173-228)
+describes, with its numbers: flip of axis 0 (p = .5), elastic deformation (7 control points, 7.5 mm, 2 locked layers,
+p = .5), affine (scales .9-1.1, 15 degrees, translation (10, 10, 15) mm, p = .5), the flap extraction (p = .9) and salt and
+pepper noise (p = 1, density .05).  Differences: no erode / dilate step; the warp follows this module's RandomSpatial rule,
+not torchio's; voxel spacing is (1, 1, 1) mm unless a RandomSpatial with another ``spacing`` is used; and the reference's
+function itself cannot run (it calls ``erode_dilate`` and ``skull_random_hole``, which do not exist, and uses the
+``SaltAndPepper`` class as a function), so there is no behaviour to match, only this described pipeline."""
