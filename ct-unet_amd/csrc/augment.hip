@@ -2,38 +2,22 @@
 // SaltAndPepper (random zeroed / set voxels) for a batch of N skulls, in three launches and without atomics or host syncs,
 // so the whole transform replays inside a captured graph and is bitwise reproducible:
 //   ctu_flap_count  bone voxels per (sample, chunk of CTU_FLAP_CHUNK voxels in C order)
-//   ctu_flap_draw   one block per sample: the per-sample scalars from Philox4x32-10 and the k-th bone voxel (the centre)
+//   ctu_flap_draw   one block per sample: the per-sample scalars from Philox4x32-10 (philox.h) and the k-th bone voxel
 //   ctu_flap_apply  one fused streaming pass: hole mask, noise, network input (+ atlas channel) and one-hot targets
 // The rules (shapes, RNG streams, record layout) are pinned in ctunet_amd/transforms.py and include/ctunet_hip.h.
 //
 // Replaces: ctunet/pytorch/transforms.py:13-95 (SaltAndPepper, SkullRandomHole) and ctunet/utilities.py:127-178 (shape_3d),
 //           ctunet/pytorch/transforms.py:241-300 (random_blank_patch), run per sample in NumPy on the host there.
 #include "common.h"
+#include "philox.h"
 
 namespace {
+
+using namespace ctu_rng;
 
 constexpr int AB = 256;
 constexpr int REC = CTU_FLAP_RECORD;
 
-// Philox4x32-10 (Salmon et al., SC'11): counter c, key k
-__device__ __forceinline__ uint4 philox(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__device__ __forceinline__ uint4 philox_seq(uint32_t c0, uint32_t stream, int64_t seq, uint32_t k0, uint32_t k1) {
-    return philox(make_uint4(c0, stream, (uint32_t)(uint64_t)seq, (uint32_t)((uint64_t)seq >> 32)), k0, k1);
-}
-
-// u = (r >> 8) 2^-24 in [0, 1), exact in float32
-__device__ __forceinline__ float unif(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }
 // lo + floor(r (hi - lo) / 2^32): uniform integer in [lo, hi) for hi - lo <= 2^32
 __device__ __forceinline__ int64_t draw_int(uint32_t r, int64_t lo, uint64_t span) {
     return lo + (int64_t)(((uint64_t)r * span) >> 32);
@@ -133,8 +117,8 @@ __global__ void __launch_bounds__(AB) flap_draw_kernel(DrawArgs a) {
             const int nsh = a.shapes & 3;
             const int shape = (a.shapes >> (2 + 2 * (int)draw_int(r.w, 0, (uint64_t)nsh))) & 3;
             // c_diam = U(0.25, 1) size / 4, every operation rounded separately (no contraction)
-            const float cd = __fmul_rn(__fmul_rn(__fadd_rn(0.25f, __fmul_rn(0.75f, unif(r2.x))), (float)size), 0.25f);
-            rec[0] = unif(r.x) < a.p_hole;
+            const float cd = __fmul_rn(__fmul_rn(__fadd_rn(0.25f, __fmul_rn(0.75f, unif_f32(r2.x))), (float)size), 0.25f);
+            rec[0] = unif_f32(r.x) < a.p_hole;
             rec[1] = (int32_t)total;
             rec[2] = (int32_t)k;
             rec[6] = size;
@@ -178,11 +162,11 @@ __global__ void __launch_bounds__(AB) flap_draw_kernel(DrawArgs a) {
         const uint4 q = philox_seq(0, 0, seq, a.nk0, a.nk1);
         float nd = a.noise_nd[0];
         if (a.decay) {                                // nd_j = U_j nd_{j-1} over the samples before this one, in order
-            for (int j = 0; j <= n; ++j) nd = __fmul_rn(unif(philox_seq(0, 0, s0 + j, a.nk0, a.nk1).y), nd);
+            for (int j = 0; j <= n; ++j) nd = __fmul_rn(unif_f32(philox_seq(0, 0, s0 + j, a.nk0, a.nk1).y), nd);
         } else {
-            nd = __fmul_rn(unif(q.y), nd);
+            nd = __fmul_rn(unif_f32(q.y), nd);
         }
-        rec[10] = unif(q.x) < a.p_noise;
+        rec[10] = unif_f32(q.x) < a.p_noise;
         rec[11] = __float_as_int(nd);
         rec[12] = __float_as_int(__fmul_rn(nd, __fsub_rn(1.0f, a.salt_ratio)));
         rec[13] = __float_as_int(__fmul_rn(nd, a.salt_ratio));
@@ -291,7 +275,7 @@ __global__ void __launch_bounds__(AB) flap_apply_kernel(ApplyArgs a) {
             const float t0 = __int_as_float(rec[12]), t1 = __int_as_float(rec[13]);
             const uint32_t w1[4] = {r1.x, r1.y, r1.z, r1.w}, w2[4] = {r2.x, r2.y, r2.z, r2.w};
 #pragma unroll
-            for (int l = 0; l < 4; ++l) img[l] = (img[l] != 0.f && !(unif(w1[l]) <= t0)) || unif(w2[l]) <= t1 ? 1.f : 0.f;
+            for (int l = 0; l < 4; ++l) img[l] = (img[l] != 0.f && !(unif_f32(w1[l]) <= t0)) || unif_f32(w2[l]) <= t1 ? 1.f : 0.f;
         }
         float* xo = a.x + (int64_t)n * a.C * V + zyx;
         float* fo = a.full ? a.full + (int64_t)n * 2 * V + zyx : nullptr;

@@ -61,10 +61,17 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// limits of the label-map entry points (components, morphology): grid.y carries N, item-local voxel indices are int32
-static inline bool geometry_ok(int N, int D, int H, int W) {
-    return N > 0 && N <= 65535 && D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < ((int64_t)1 << 31);
+// host-side argument predicates of the volume entry points.  A voxel grid: every side >= 1, item-local indices are int32
+static inline bool grid_ok(int D, int H, int W) { return D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < ((int64_t)1 << 31); }
+// ... of the entry points whose grid.y carries N
+static inline bool geometry_ok(int N, int D, int H, int W) { return N > 0 && N <= 65535 && grid_ok(D, H, W); }
+// n finite numbers; three positive finite steps.  NaN fails every comparison
+static inline bool finite_n(const double* v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!(v[i] >= -1.7e308 && v[i] <= 1.7e308)) return false;
+    return true;
 }
+static inline bool steps_ok(const double v[3]) { return v[0] > 0.0 && v[1] > 0.0 && v[2] > 0.0 && finite_n(v, 3); }
 
 // grid of a persistent kernel (a block loops over tpb boxes): at most `cap` blocks, the boxes spread evenly over them.  The
 // cap is what differs between kernels (resident blocks per CU x 256 CUs, divided by the grid's other axes).

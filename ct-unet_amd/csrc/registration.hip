@@ -367,7 +367,7 @@ extern "C" int ctu_registration_accumulate(const float* points, int64_t P, const
                                            void* stream) {
     CTU_REQUIRE(points && field && ws, "registration_accumulate: null pointer");
     CTU_REQUIRE(P >= 1, "registration_accumulate: P must be at least 1, got %lld", (long long)P);
-    CTU_REQUIRE(D >= 2 && H >= 2 && W >= 2 && (int64_t)D * H * W < ((int64_t)1 << 31),
+    CTU_REQUIRE(D >= 2 && H >= 2 && W >= 2 && grid_ok(D, H, W),
                 "registration_accumulate: bad field shape %dx%dx%d (every side >= 2, D*H*W < 2^31)", D, H, W);
     CTU_REQUIRE(max_distance >= 0.0, "registration_accumulate: max_distance must be >= 0 (+inf: no bound)");
     CTU_REQUIRE((uintptr_t)ws % 8 == 0, "registration_accumulate: the workspace must be 8-byte aligned");
@@ -376,9 +376,9 @@ extern "C" int ctu_registration_accumulate(const float* points, int64_t P, const
     for (int i = 0; i < 3; ++i) {
         a.sp[i] = spacing ? spacing[i] : 1.0;
         a.org[i] = origin ? origin[i] : 0.0;
-        CTU_REQUIRE(a.sp[i] > 0.0 && a.sp[i] <= 1.7e308, "registration_accumulate: spacing must be positive and finite");
-        CTU_REQUIRE(a.org[i] >= -1.7e308 && a.org[i] <= 1.7e308, "registration_accumulate: origin must be finite");
     }
+    CTU_REQUIRE(steps_ok(a.sp), "registration_accumulate: spacing must be positive and finite");
+    CTU_REQUIRE(finite_n(a.org, 3), "registration_accumulate: origin must be finite");
     reg_accumulate_kernel<<<num_blocks(P), RB, 0, (hipStream_t)stream>>>(a, points, P, field, (const State*)ws,
                                                                         (double*)((char*)ws + HEAD));
     CTU_CHECK_LAUNCH("registration_accumulate");

@@ -2,11 +2,11 @@
 // map applied to a batch of volumes in ONE nearest-neighbour gather pass (rule: ctunet_amd/transforms.py, "RandomSpatial";
 // tests/spatial_ref.py restates it).  Two launches, no atomics, no host synchronisation, so a call replays inside a graph:
 //   ctu_spatial_draw  one block per sample: the per-sample record (flags, scalars, the 3x4 matrix M) and the control
-//                     displacements [3][Gz][Gy][Gx] from Philox4x32-10 and the instance's DEVICE sample counter
+//                     displacements [3][Gz][Gy][Gx] from Philox4x32-10 (philox.h) and the instance's DEVICE sample counter
 //   ctu_spatial_warp  out[n][c][o] = in[n][c][k(o)] for all C channels of a sample, k from the record and the control grid
-// The warp kernel takes affine_kernel's output tiling (affine.hip): a block of 256 threads owns 4 planes x 4 rows x 16
-// chunks, a chunk being the 16 bytes one thread stores on the 16-byte grid of its output row; the clipped chunks at a row's
-// two ends are stored voxel by voxel.  The sample's control grid (3 G^3 doubles, 8.2 KB at G = 7, 41.5 KB at G = 12) is
+// The warp kernel's output is tiled by chunk_tile.h: a block of 256 threads owns 4 planes x 4 rows x 16 chunks, a chunk
+// being the 16 bytes one thread stores on the 16-byte grid of its output row; a later channel's rows may sit on another
+// grid, so its store tests the address.  The sample's control grid (3 G^3 doubles, 8.2 KB at G = 7, 41.5 KB at G = 12) is
 // staged in LDS once per block, and only when the sample's elastic flag is set -- a branch that is uniform over the block.
 // The source index of a voxel is computed once and reused for every channel.  Every read of the volume sits behind the
 // comparison that declares its index inside it, and every read of the LDS grid uses an index clamped to the grid, so no
@@ -15,40 +15,23 @@
 //
 // Replaces: the flip / elastic / affine steps of ctunet/pytorch/transforms.py:173-228 (cranioplasty_transform), which the
 //           reference takes from torchio on the host; the rule here is the port's own.
+#include "chunk_tile.h"
 #include "common.h"
+#include "philox.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SB = 256;
-constexpr int LXN = 16;                         // chunks of a tile along x
-constexpr int TY = 4, TZ = 4;                   // rows and planes of a tile: LXN * TY * TZ = SB, one chunk per thread
+using namespace ctu_tile;
+using namespace ctu_rng;
+
 constexpr int REC = CTU_SPATIAL_RECORD;
 constexpr int GMIN = CTU_SPATIAL_MIN_POINTS, GMAX = CTU_SPATIAL_MAX_POINTS;
 constexpr int MAXC = 64;                        // channels per sample
 
-// Philox4x32-10 (Salmon et al., SC'11), as augment.hip has it
-__device__ __forceinline__ uint4 philox(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__device__ __forceinline__ uint4 philox_seq(uint32_t c0, uint32_t stream, int64_t seq, uint32_t k0, uint32_t k1) {
-    return philox(make_uint4(c0, stream, (uint32_t)(uint64_t)seq, (uint32_t)((uint64_t)seq >> 32)), k0, k1);
-}
-
-// u = (r >> 8) 2^-24 in [0, 1), exact
-__device__ __forceinline__ double unif(uint32_t r) { return (double)(r >> 8) * 5.9604644775390625e-08; }
 // (2 u - 1) a
-__device__ __forceinline__ double sym(uint32_t r, double a) { return (2.0 * unif(r) - 1.0) * a; }
+__device__ __forceinline__ double sym(uint32_t r, double a) { return (2.0 * unif_f64(r) - 1.0) * a; }
 
 // ---------------------------------------------------------------------------------------------------------------- draw
 struct DrawArgs {
@@ -93,12 +76,12 @@ __global__ void __launch_bounds__(SB) spatial_draw_kernel(DrawArgs a) {
     const uint4 r0 = philox_seq(0, 0, seq, a.k0, a.k1), r1 = philox_seq(1, 0, seq, a.k0, a.k1);
     const uint4 r2 = philox_seq(2, 0, seq, a.k0, a.k1), r3 = philox_seq(3, 0, seq, a.k0, a.k1);
     const uint32_t fl[3] = {r0.x, r0.y, r0.z}, sc[3] = {r1.y, r1.z, r1.w}, an[3] = {r2.x, r2.y, r2.z}, tr[3] = {r3.x, r3.y, r3.z};
-    const bool affine = unif(r0.w) < a.p_affine;
+    const bool affine = unif_f64(r0.w) < a.p_affine;
     double scale[3], t[3], cs[3], sn[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        rec[i] = ((a.flip_mask >> i) & 1) && unif(fl[i]) < a.p_flip ? 1.0 : 0.0;
-        scale[i] = a.s_lo + unif(sc[i]) * (a.s_hi - a.s_lo);
+        rec[i] = ((a.flip_mask >> i) & 1) && unif_f64(fl[i]) < a.p_flip ? 1.0 : 0.0;
+        scale[i] = a.s_lo + unif_f64(sc[i]) * (a.s_hi - a.s_lo);
         const double deg = sym(an[i], a.deg[i]);
         t[i] = sym(tr[i], a.tr[i]);
         const double rad = deg * 0.017453292519943295;
@@ -109,7 +92,7 @@ __global__ void __launch_bounds__(SB) spatial_draw_kernel(DrawArgs a) {
         rec[11 + i] = t[i];
     }
     rec[3] = affine ? 1.0 : 0.0;
-    rec[4] = unif(r1.x) < a.p_elastic ? 1.0 : 0.0;
+    rec[4] = unif_f64(r1.x) < a.p_elastic ? 1.0 : 0.0;
     double* M = rec + 14;
     if (affine) {
         // rotations about z, y, x of vectors (z, y, x): each leaves its own component alone
@@ -146,8 +129,6 @@ struct WarpArgs {
     int N;
 };
 
-template <class T> struct alignas(16) Chunk { T v[16 / sizeof(T)]; };
-
 // NaN fails both comparisons
 __device__ __forceinline__ bool within(double v, int n) { return v >= 0.0 && v < (double)n; }
 
@@ -163,7 +144,6 @@ __device__ __forceinline__ void bspline(double f, double B[4]) {
 template <class T>
 __global__ void __launch_bounds__(SB) spatial_warp_kernel(WarpArgs a, const T* __restrict__ in, T* __restrict__ out) {
     constexpr int VX = 16 / (int)sizeof(T);
-    constexpr int TXO = LXN * VX;
     extern __shared__ __attribute__((aligned(16))) double phi[];                // [3][Gz][Gy][Gx] of this sample
     const int n = blockIdx.y;
     if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) a.seq[0] += a.N;       // the draw kernel has read it
@@ -175,21 +155,16 @@ __global__ void __launch_bounds__(SB) spatial_warp_kernel(WarpArgs a, const T* _
         for (int i = threadIdx.x; i < 3 * g3; i += SB) phi[i] = ctl[i];
         __syncthreads();
     }
-    int bi = blockIdx.x;
-    const int tx = bi % a.ntx;
-    bi /= a.ntx;
-    const int ty = bi % a.nty, tz = bi / a.nty;
-    const int X0 = tx * TXO, Y0 = ty * TY, Z0 = tz * TZ;
-    const int lane = threadIdx.x % LXN, rs = threadIdx.x / LXN;
-    const int yy = Y0 + rs % TY, zz = Z0 + rs / TY;
+    const Origin t = origin<T>(a.ntx, a.nty);
+    int yy, zz;
+    row_of(t, yy, zz);
     if (yy >= a.H || zz >= a.D) return;
     const int64_t V = (int64_t)a.D * a.H * a.W;
     const T* item = in + (int64_t)n * a.C * V;
     T* orow = out + (int64_t)n * a.C * V + ((int64_t)zz * a.H + yy) * a.W;
-    const int e = (int)(((uintptr_t)(orow + X0) / sizeof(T)) % VX);
-    const int cx = X0 + lane * VX - e;
-    const int xa = max(cx, 0), xb = min(cx + VX, a.W);
-    if (xa >= xb) return;
+    const Span s = chunk_of(orow, t.X0, a.W);
+    if (s.xa >= s.xb) return;
+    const int cx = s.cx;
 
     double m[12];
 #pragma unroll
@@ -263,41 +238,20 @@ __global__ void __launch_bounds__(SB) spatial_warp_kernel(WarpArgs a, const T* _
 #pragma unroll
         for (int v = 0; v < VX; ++v) res.v[v] = src[v] >= 0 ? ch[src[v]] : (T)0;
         // a later channel's rows sit on another 16-byte grid when V sizeof(T) is no multiple of 16
-        if (xb - xa == VX && (uintptr_t)(oc + cx) % 16 == 0) {
-            *reinterpret_cast<Chunk<T>*>(oc + cx) = res;
-        } else {
-#pragma unroll
-            for (int v = 0; v < VX; ++v)
-                if (cx + v >= xa && cx + v < xb) oc[cx + v] = res.v[v];
-        }
+        store(oc, s, res, (uintptr_t)(oc + cx) % 16 == 0);
     }
 }
 
 template <class T>
 int launch(WarpArgs a, const void* in, void* out, hipStream_t st) {
-    constexpr int VX = 16 / (int)sizeof(T);
-    constexpr int TXO = LXN * VX;
-    // rows whose chunks all start at a tile's X0 need no tile column for the shifted remainder
-    const bool aligned = a.W % VX == 0 && (uintptr_t)out % 16 == 0;
-    a.ntx = ceil_div(a.W + (aligned ? 0 : VX - 1), TXO);
-    a.nty = ceil_div(a.H, TY);
-    const dim3 grid((unsigned)(a.ntx * a.nty * ceil_div(a.D, TZ)), (unsigned)a.N);
+    const Tiles tl = tiles(a.D, a.H, a.W, out, sizeof(T));
+    a.ntx = tl.ntx;
+    a.nty = tl.nty;
+    const dim3 grid((unsigned)tl.blocks, (unsigned)a.N);
     const size_t lds = (size_t)3 * a.G[0] * a.G[1] * a.G[2] * sizeof(double);   // <= 41472 B
     spatial_warp_kernel<T><<<grid, SB, lds, st>>>(a, (const T*)in, (T*)out);
     CTU_CHECK_LAUNCH("spatial_warp");
     return CTU_OK;
-}
-
-bool steps_ok(const double* v) {
-    for (int i = 0; i < 3; ++i)
-        if (!(v[i] > 0.0) || v[i] > 1.7e308) return false;
-    return true;
-}
-
-bool finite_n(const double* v, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!(v[i] >= -1.7e308 && v[i] <= 1.7e308)) return false;
-    return true;
 }
 
 bool prob_ok(double p) { return p >= 0.0 && p <= 1.0; }

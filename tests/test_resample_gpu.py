@@ -106,6 +106,21 @@ def test_label_linear_is_the_rule(case, k):
     _same_bits(rs.resample(x.to(DEV), size, mode="label_linear", num_classes=k), R.label_linear(x.numpy(), size, a, k))
 
 
+def test_label_linear_int64_stray_beyond_32_bits():
+    """2**32 + 1 is no class; a comparison through a 32-bit cast would read it as label 1."""
+    from ctunet_amd import resample as rs
+    (shape, size), k = CASES["odd"], 3
+    _, a = R.scales(shape, size)
+    rng = np.random.default_rng(40)
+    x = rng.integers(0, k, shape)
+    stray = rng.random(shape) < 0.2
+    x[stray] = 2 ** 32 + 1
+    want = R.label_linear(x, size, a, k)
+    assert np.array_equal(want, R.label_linear(np.where(stray, -1, x), size, a, k))
+    assert np.count_nonzero(want != R.label_linear(np.where(stray, 1, x), size, a, k)) > 100      # of 2080
+    _same_bits(rs.resample(torch.from_numpy(x).to(DEV), size, mode="label_linear", num_classes=k), want)
+
+
 def test_spacing_mode_is_the_rule():
     from ctunet_amd import resample as rs
     shape, s, t = (21, 40, 37), (0.8, 0.45, 0.45), (1.0, 0.7, 0.31)
