@@ -993,7 +993,9 @@ int ctu_lp_head_bwd_bn_dscale(int dtype, const void* in, int in_cs, int cin_p, c
 /* Every tensor of a list scaled in place by s (one launch): un-scaling of loss-scaled fp16 gradients.
  * ptrs: HOST array of n DEVICE float pointers, sizes: HOST int64[n].  nonfinite_flag: NULL or a DEVICE float[1] that is set
  * to 1 when any scaled value is inf / NaN (the fp16 backward overflowed; the caller zeroes it per step and hands it to
- * ctu_adam_amsgrad as skip_flag, what torch.amp.GradScaler does with found_inf). */
+ * ctu_adam_amsgrad as skip_flag, what torch.amp.GradScaler does with found_inf).
+ * Refused before any launch (CTU_EINVAL; no tensor of the list is touched, ctu_unscale_tensors likewise): null ptrs /
+ * sizes, n <= 0, and for ANY tensor of the list a null pointer, a negative size or a pointer that is not 4-byte aligned. */
 int ctu_scale_tensors(void* const* ptrs, const int64_t* sizes, int n, float s, float* nonfinite_flag, void* stream);
 /* Dynamic loss scaling (float16), the device-resident form of torch.amp.GradScaler; every operand is DEVICE memory, so
  * the calls work unchanged inside a replayed graph.
@@ -1034,7 +1036,11 @@ int ctu_channel_sum(const float* x, int cs, int cp, int64_t nvox, float* partial
  * max_exp_avg_sq} (copied into the kernel arguments, 64 tensors per launch); sizes: HOST int64[n].
  * step: DEVICE float[1] step counter, incremented by this call before it is used (so a captured graph
  * keeps advancing the bias corrections).  decoupled != 0: AdamW weight decay.  skip_flag: NULL or a DEVICE float[1];
- * non-zero = skip this update entirely (parameters, moments and the step counter untouched): an overflowed fp16 step. */
+ * non-zero = skip this update entirely (parameters, moments and the step counter untouched): an overflowed fp16 step.
+ * Refused before any launch (CTU_EINVAL; neither the step counter nor any tensor is touched): null ptrs / sizes / step,
+ * n <= 0, and for ANY tensor of the list a null pointer in one of its five slots, a negative size or a pointer that is
+ * not 4-byte aligned.  The rule of every entry point that takes a tensor list (ctu_adam_amsgrad_dev, ctu_sgd, ctu_rmsprop,
+ * ctu_grad_clip_coef, ctu_scale_tensors, ctu_unscale_tensors): the whole list is checked first. */
 int ctu_adam_amsgrad(void* const* ptrs, const int64_t* sizes, int n, float* step,
                      double lr, double beta1, double beta2, double eps, double weight_decay,
                      int decoupled, const float* skip_flag, void* stream);
@@ -1046,13 +1052,15 @@ int ctu_adam_amsgrad(void* const* ptrs, const int64_t* sizes, int n, float* step
  *                              where the host call rounds its argument).  grad_coef: NULL or a DEVICE float[1]; every
  *                              gradient value is multiplied by it (one IEEE multiply) before weight decay, what
  *                              clip_grad_norm_ does to p.grad.  With grad_coef NULL or *grad_coef == 1 the result is
- *                              bit-equal to ctu_adam_amsgrad at the same learning rate.
+ *                              bit-equal to ctu_adam_amsgrad at the same learning rate.  Refuses what ctu_adam_amsgrad
+ *                              refuses, and a null lr, before any launch.
  *   ctu_grad_norm_num_blocks . number of floats ctu_grad_clip_coef needs in partials_ws for these sizes (0: bad argument)
  *   ctu_grad_clip_coef ....... global 2-norm of n gradient tensors (gptrs: HOST array of n DEVICE float pointers, 4-byte
  *                              aligned; sizes: HOST int64[n]) and torch's clip coefficient:
  *                              norm_out[0] = (float)sqrt(sum g*g), summed in double in a fixed order;
  *                              coef_out[0] = min(1, max_norm / (norm + 1e-6f)) in float32, NaN if the norm is NaN and 0 if
- *                              it is inf (clip_grad_norm_ with error_if_nonfinite=False).
+ *                              it is inf (clip_grad_norm_ with error_if_nonfinite=False).  A null or misaligned pointer
+ *                              or a negative size anywhere in the list is refused before any launch.
  *   ctu_plateau_update ....... torch.optim.lr_scheduler.ReduceLROnPlateau.step((double)metric[0]) for one parameter group
  *                              on one thread, in double.  lr: DEVICE double[1]; state: DEVICE double[1] = best (the host
  *                              seeds +inf for min mode, -inf for max mode); counters: DEVICE int32[4] = {num_bad_epochs,

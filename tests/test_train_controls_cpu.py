@@ -167,6 +167,43 @@ def test_bad_arguments_are_refused_without_a_launch():
     assert lib.ctu_grad_norm_num_blocks(None, 1) == 0 and lib.ctu_grad_norm_num_blocks(one, 0) == 0
 
 
+def _table_calls(lib):
+    """(entry point's message prefix, pointers per tensor, call(ptrs, sizes, n)) for every entry point that takes a tensor
+    list; every other argument is valid, so only the list can be refused."""
+    adam = (0.9, 0.999, 1e-8, 0.0, 0)
+    return [
+        (b"adam_amsgrad:", 5, lambda p, s, n: lib.ctu_adam_amsgrad(p, s, n, 64, 1e-3, *adam, None, None)),
+        (b"adam_amsgrad_dev:", 5, lambda p, s, n: lib.ctu_adam_amsgrad_dev(p, s, n, 64, 64, *adam, None, None, None)),
+        (b"sgd:", 3, lambda p, s, n: lib.ctu_sgd(p, s, n, 64, None, 0.1, 0.9, 0.0, 0.0, 0, 0, None, None, None)),
+        (b"rmsprop:", 5, lambda p, s, n: lib.ctu_rmsprop(p, s, n, 64, None, 0.01, 0.99, 1e-8, 0.0, 0.9, 1, 0, None, None, None)),
+        (b"grad_clip_coef:", 1, lambda p, s, n: lib.ctu_grad_clip_coef(p, s, n, 1.0, 64, 64, 64, None)),
+        (b"scale_tensors:", 1, lambda p, s, n: lib.ctu_scale_tensors(p, s, n, 0.5, None, None)),
+        (b"unscale_tensors:", 1, lambda p, s, n: lib.ctu_unscale_tensors(p, s, n, 64, 64, None)),
+    ]
+
+
+@pytest.mark.parametrize("fault", ["null", "negative-size", "misaligned"])
+def test_a_bad_tensor_in_the_second_chunk_refuses_the_whole_list(fault):
+    """65 tensors, the last one bad: CTU_EINVAL (-1) names the entry point and tensor 64.  Without a GPU a launch of the first
+    64 tensors or of the step counter would have answered CTU_ELAUNCH (-2) instead: nothing was launched."""
+    from ctunet_amd import _lib
+    lib = _lib.load()
+    n = 65
+    for name, k, call in _table_calls(lib):
+        ptrs = [64] * (k * n)
+        sizes = [4] * n
+        if fault == "null":
+            ptrs[64 * k + k - 1] = None                                  # the tensor's last slot: required in every call above
+        elif fault == "misaligned":
+            ptrs[64 * k + k - 1] = 66
+        else:
+            sizes[64] = -1
+        rc = call((C.c_void_p * len(ptrs))(*ptrs), (C.c_int64 * n)(*sizes), n)
+        msg = lib.ctu_last_error()
+        assert rc == -1, (name, fault, rc, msg)
+        assert msg.startswith(name) and b"64" in msg, (name, fault, msg)
+
+
 def test_workspace_size_follows_the_launch_plan():
     """One partial per block: per 64-tensor chunk, (blocks along the largest tensor, at most 64) x tensors."""
     from ctunet_amd import _lib
