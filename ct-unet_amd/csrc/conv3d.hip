@@ -15,6 +15,7 @@
 #include "common.h"
 #include "pack.h"
 #include "bn_tail.h"
+#include "wgrad_reduce.h"
 
 #ifndef CTU_K3S_OCC
 #define CTU_K3S_OCC 2
@@ -1675,36 +1676,8 @@ template <int SM, int SN>
 __global__ __launch_bounds__(1024) void conv3d_wgrad_k3s_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
                                                                       int Co, int Ci, const int32_t* __restrict__ cinv,
                                                                       int cin_p, int n_ci_g, int gx) {
-    constexpr int QN = (SM == 2 && SN == 2) ? 1 : ((SM == 1 && SN == 1) ? 3 : 2);
-    constexpr int NMF = 9 * QN;
-    constexpr int CM = 16 / SM, CN = 16 / SN;
     __shared__ float red[RPARTS][64];
-    const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int el = blockIdx.x * 64 + e;
-    const int pair = blockIdx.y;
-    float s = 0.f;
-    if (el < NMF * 256) {
-        const float* src = ws + (size_t)pair * gx * (NMF * 256) + el;
-        for (int k = part; k < gx; k += RPARTS) s += src[(size_t)k * (NMF * 256)];
-    }
-    red[part][e] = s;
-    __syncthreads();
-    if (part != 0 || el >= NMF * 256) return;
-    const float tot = red_total(red, e);
-    const int t = el >> 8, i = (el >> 4) & 15, j = el & 15;
-    const int r = t / QN, q = t % QN;
-    const int sm = (SM == 2) ? i / 8 : 0, cil = (SM == 2) ? i % 8 : i;
-    const int sn = (SN == 2) ? j / 8 : 0, col = (SN == 2) ? j % 8 : j;
-    int kw;
-    bool ok = true;
-    if (SM == 1 && SN == 1) kw = q;
-    else if (SM == 2 && SN == 2) { kw = sm + sn; ok = !(sm == 0 && sn == 1); }
-    else if (SN == 2) { if (q == 0) { kw = 0; ok = sn == 0; } else kw = 1 + sn; }
-    else { if (q == 0) kw = sm; else { kw = 2; ok = sm == 1; } }
-    const int cig = pair % n_ci_g, cog = pair / n_ci_g;
-    const int cip = cig * CM + cil, co = cog * CN + col;
-    const int ci = (cip < cin_p) ? (cinv ? cinv[cip] : (cip < Ci ? cip : -1)) : -1;
-    if (ok && ci >= 0 && co < Co) dw[((size_t)co * Ci + ci) * 27 + r * 3 + kw] = tot;
+    wgrad_k3s_reduce_block<SM, SN>(ws, dw, Co, Ci, cinv, cin_p, n_ci_g, gx, blockIdx.x, blockIdx.y, threadIdx.x, red);
 }
 
 // lazy BatchNorm backward inside the k = 3 weight-gradient kernel: full boxes and full channel tiles only
@@ -2384,11 +2357,20 @@ extern "C" size_t ctu_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int k, 
     return slabs > bsum ? slabs : bsum;
 }
 
+// job: non-NULL = the caller reduces the slabs later (ctu_bn_bwd_finalize_jobs / ctu_wgrad_reduce_jobs)
 template <int SM, int SN>
-static int launch_wgrad_k3s(const WgP& p, const WgPlan& r, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st) {
+static int launch_wgrad_k3s(const WgP& p, const WgPlan& r, float* dw, int Co, int Ci, const int32_t* cinv, hipStream_t st,
+                            ctu_wgrad_job* job) {
     if (p.lz_y) conv3d_wgrad_k3s_kernel<SM, SN, 0, true><<<dim3(r.grid.gx, r.pairs), 256, 0, st>>>(p, r.grid.tpb);
     else conv3d_wgrad_k3s_kernel<SM, SN><<<dim3(r.grid.gx, r.pairs), 256, 0, st>>>(p, r.grid.tpb);
     CTU_CHECK_LAUNCH("conv3d_wgrad_k3s");
+    if (job) {
+        job->kind = WGJ_K3S + (SM - 1) * 2 + (SN - 1);
+        job->ws = p.ws; job->dw = dw; job->db = nullptr; job->cinv = cinv;
+        job->Co = Co; job->Ci = Ci; job->cin_p = p.cin_p; job->n_ci_g = p.n_ci_t; job->gx = r.grid.gx; job->pairs = r.pairs;
+        job->nmf = r.nmf;
+        return CTU_OK;
+    }
     conv3d_wgrad_k3s_reduce_kernel<SM, SN><<<dim3(ceil_div(r.nmf * 256, 64), r.pairs), 64 * RPARTS, 0, st>>>(
         p.ws, dw, Co, Ci, cinv, p.cin_p, p.n_ci_t, r.grid.gx);
     CTU_CHECK_LAUNCH("conv3d_wgrad_k3s_reduce");
@@ -2423,18 +2405,40 @@ struct LazyBn { const float* y; const float* scale; const float* shift; const fl
 static int conv3d_wgrad_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                              int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Co,
                              int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W, int k, const LazyBn* lz,
-                             void* stream);
+                             ctu_wgrad_job* job, void* stream);
 
 extern "C" int ctu_conv3d_wgrad(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                                 int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Co,
                                 int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W, int k,
                                 void* stream) {
     return conv3d_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, cout_p, dw, dbias, Co, Ci, cinv, ws,
-                             N, D, H, W, k, nullptr, stream);
+                             N, D, H, W, k, nullptr, nullptr, stream);
+}
+
+extern "C" int ctu_conv3d_wgrad_slabs(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                      int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Co,
+                                      int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W, int k,
+                                      ctu_wgrad_job* job, void* stream) {
+    CTU_REQUIRE(job, "conv3d_wgrad_slabs: null job");
+    return conv3d_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, cout_p, dw, dbias, Co, Ci, cinv, ws,
+                             N, D, H, W, k, nullptr, job, stream);
 }
 
 extern "C" int ctu_conv3d_wgrad_bn_supported(int N, int D, int H, int W, int k, int cin_p, int cout_p) {
     return (N > 0 && k3s_lazy_ok(D, H, W, k, cin_p, cout_p)) ? 1 : 0;
+}
+
+static int conv3d_wgrad_bn_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                int in_relu, const float* ga, int g_cs, int cout_p, const float* y,
+                                const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
+                                float* dw, int Co, int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W,
+                                int k, ctu_wgrad_job* job, void* stream) {
+    CTU_REQUIRE(y && bn_scale && bn_shift && coef && gy_out, "conv3d_wgrad_bn: null pointer");
+    CTU_REQUIRE(k3s_lazy_ok(D, H, W, k, cin_p, cout_p), "conv3d_wgrad_bn: geometry not supported (ask ctu_conv3d_wgrad_bn_supported)");
+    CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0 && gy_out != ga, "conv3d_wgrad_bn: y / gy_out alignment, gy_out must not alias ga");
+    const LazyBn lz = {y, bn_scale, bn_shift, coef, gy_out, cout_p};
+    return conv3d_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, cout_p, dw, nullptr, Co, Ci, cinv, ws,
+                             N, D, H, W, k, &lz, job, stream);
 }
 
 extern "C" int ctu_conv3d_wgrad_bn(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
@@ -2442,18 +2446,24 @@ extern "C" int ctu_conv3d_wgrad_bn(const float* in, int in_cs, int cin_p, const 
                                    const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
                                    float* dw, int Co, int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W,
                                    int k, void* stream) {
-    CTU_REQUIRE(y && bn_scale && bn_shift && coef && gy_out, "conv3d_wgrad_bn: null pointer");
-    CTU_REQUIRE(k3s_lazy_ok(D, H, W, k, cin_p, cout_p), "conv3d_wgrad_bn: geometry not supported (ask ctu_conv3d_wgrad_bn_supported)");
-    CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0 && gy_out != ga, "conv3d_wgrad_bn: y / gy_out alignment, gy_out must not alias ga");
-    const LazyBn lz = {y, bn_scale, bn_shift, coef, gy_out, cout_p};
-    return conv3d_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, cout_p, dw, nullptr, Co, Ci, cinv, ws,
-                             N, D, H, W, k, &lz, stream);
+    return conv3d_wgrad_bn_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, cout_p, y, bn_scale, bn_shift, coef,
+                                gy_out, dw, Co, Ci, cinv, ws, N, D, H, W, k, nullptr, stream);
+}
+
+extern "C" int ctu_conv3d_wgrad_bn_slabs(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                         int in_relu, const float* ga, int g_cs, int cout_p, const float* y,
+                                         const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
+                                         float* dw, int Co, int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W,
+                                         int k, ctu_wgrad_job* job, void* stream) {
+    CTU_REQUIRE(job, "conv3d_wgrad_bn_slabs: null job");
+    return conv3d_wgrad_bn_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, cout_p, y, bn_scale, bn_shift, coef,
+                                gy_out, dw, Co, Ci, cinv, ws, N, D, H, W, k, job, stream);
 }
 
 static int conv3d_wgrad_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                              int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Co,
                              int Ci, const int32_t* cinv, float* ws, int N, int D, int H, int W, int k, const LazyBn* lz,
-                             void* stream) {
+                             ctu_wgrad_job* job, void* stream) {
     CTU_REQUIRE(k == 3 || k == 5, "conv3d_wgrad: k=%d unsupported (3 or 5)", k);
     CTU_REQUIRE(in && gout && dw && ws, "conv3d_wgrad: null pointer");
     CTU_REQUIRE(cin_p % 8 == 0 && cout_p % 8 == 0 && cin_p > 0 && cout_p > 0, "conv3d_wgrad: padded channels");
@@ -2471,12 +2481,14 @@ static int conv3d_wgrad_impl(const float* in, int in_cs, int cin_p, const float*
     p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     p.ntiles = r.ntiles; p.n_ci_t = r.n_ci_g; p.n_co_t = r.n_co_t;
     int rc;
+    if (job) *job = ctu_wgrad_job{};                 // kind 0: reduced here (every route but k3s without a bias gradient)
+    if (dbias) job = nullptr;                        // the bias gradient's channel sum reuses ws right away
     if (r.kind == WG_K3S) {
         // persistent, software-pipelined kernel; 8-channel sides use (shift, channel) MFMA tiles
-        if (r.sm == 2 && r.sn == 2) rc = launch_wgrad_k3s<2, 2>(p, r, dw, Co, Ci, cinv, st);
-        else if (r.sn == 2) rc = launch_wgrad_k3s<1, 2>(p, r, dw, Co, Ci, cinv, st);
-        else if (r.sm == 2) rc = launch_wgrad_k3s<2, 1>(p, r, dw, Co, Ci, cinv, st);
-        else rc = launch_wgrad_k3s<1, 1>(p, r, dw, Co, Ci, cinv, st);
+        if (r.sm == 2 && r.sn == 2) rc = launch_wgrad_k3s<2, 2>(p, r, dw, Co, Ci, cinv, st, job);
+        else if (r.sn == 2) rc = launch_wgrad_k3s<1, 2>(p, r, dw, Co, Ci, cinv, st, job);
+        else if (r.sm == 2) rc = launch_wgrad_k3s<2, 1>(p, r, dw, Co, Ci, cinv, st, job);
+        else rc = launch_wgrad_k3s<1, 1>(p, r, dw, Co, Ci, cinv, st, job);
     } else if (r.kind == WG_K5S) {
         CTU_REQUIRE((int64_t)((4 + 2 * 2) * H + 8) * W * in_cs * 4 < (int64_t)1 << 31, "conv3d_wgrad: volume too large for 32-bit offsets");
         if (r.sm == 2 && r.sn == 2) rc = launch_wgrad_k5s<2, 2>(p, r, dw, Co, Ci, cinv, st);

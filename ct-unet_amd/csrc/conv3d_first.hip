@@ -11,6 +11,7 @@
 #include <type_traits>
 #include "common.h"
 #include "bn_tail.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -397,32 +398,8 @@ __global__ __launch_bounds__(256) void first_wgrad_kernel(FirstP p, int tiles_pe
 template <int CIN>
 __global__ __launch_bounds__(1024) void first_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Co,
                                                                  int gx) {
-    constexpr int MTN = (27 * CIN + 15) / 16;
-    __shared__ float red[16][64];
-    const int e = threadIdx.x & 63, part = threadIdx.x >> 6;          // 1024 threads: 16 slab groups x 64 elements
-    const int el = blockIdx.x * 64 + e;
-    float s = 0.f;
-    if (el < MTN * 256) {
-        // 4 independent chains per thread (coalesced 256-byte rows of 4 slabs in flight), combined in a fixed order
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int k = part;
-        for (; k + 48 < gx; k += 64) {
-            s0 += ws[(size_t)k * (MTN * 256) + el];
-            s1 += ws[(size_t)(k + 16) * (MTN * 256) + el];
-            s2 += ws[(size_t)(k + 32) * (MTN * 256) + el];
-            s3 += ws[(size_t)(k + 48) * (MTN * 256) + el];
-        }
-        for (; k < gx; k += 16) s0 += ws[(size_t)k * (MTN * 256) + el];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[part][e] = s;
-    __syncthreads();
-    if (part != 0 || el >= MTN * 256) return;
-    float tot = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) tot += red[q][e];
-    const int r = el >> 4, co = el & 15, tap = r / CIN, ci = r % CIN;
-    if (r < 27 * CIN && co < Co) dw[((size_t)co * CIN + ci) * 27 + tap] = tot;
+    __shared__ float red[RPARTS][64];
+    first_wgrad_reduce_block<CIN>(ws, dw, Co, gx, blockIdx.x, threadIdx.x, red);
 }
 
 // resident blocks per CU of the three kernels (x 256 CUs: the cap of their persistent grids)
@@ -486,7 +463,7 @@ struct FirstLazy { const float* y; const float* scale; const float* shift; const
 
 template <class T>
 int first_wgrad_impl(const float* x, int cin, const T* g, int g_cs, float* dw, int Co, float* ws, int N, int D, int H, int W,
-                     const FirstLazy* lz, void* stream) {
+                     const FirstLazy* lz, void* stream, ctu_wgrad_job* job = nullptr) {
     CTU_REQUIRE(x && g && dw && ws, "conv3d_first_wgrad: null pointer");
     CTU_REQUIRE((cin == 1 || cin == 2) && Co >= 1 && Co <= 8 && g_cs >= 8 && g_cs % 4 == 0 && ((uintptr_t)g & (4 * sizeof(T) - 1)) == 0,
                 "conv3d_first_wgrad: bad argument");
@@ -500,15 +477,20 @@ int first_wgrad_impl(const float* x, int cin, const T* g, int g_cs, float* dw, i
             if (lz) first_wgrad_kernel<1, T, true><<<gx, 256, 0, st>>>(p, tpb);
             else first_wgrad_kernel<1, T><<<gx, 256, 0, st>>>(p, tpb);
         } else first_wgrad_kernel<1, T><<<gx, 256, 0, st>>>(p, tpb);
-        first_wgrad_reduce_kernel<1><<<ceil_div(2 * 256, 64), 1024, 0, st>>>(ws, dw, Co, gx);
+        if (!job) first_wgrad_reduce_kernel<1><<<ceil_div(2 * 256, 64), 1024, 0, st>>>(ws, dw, Co, gx);
     } else {
         if constexpr (std::is_same<T, float>::value) {
             if (lz) first_wgrad_kernel<2, T, true><<<gx, 256, 0, st>>>(p, tpb);
             else first_wgrad_kernel<2, T><<<gx, 256, 0, st>>>(p, tpb);
         } else first_wgrad_kernel<2, T><<<gx, 256, 0, st>>>(p, tpb);
-        first_wgrad_reduce_kernel<2><<<ceil_div(4 * 256, 64), 1024, 0, st>>>(ws, dw, Co, gx);
+        if (!job) first_wgrad_reduce_kernel<2><<<ceil_div(4 * 256, 64), 1024, 0, st>>>(ws, dw, Co, gx);
     }
     CTU_CHECK_LAUNCH("conv3d_first_wgrad");
+    if (job) {                                     // the caller reduces the slabs later (ctu_bn_bwd_finalize_jobs / ctu_wgrad_reduce_jobs)
+        *job = ctu_wgrad_job{};
+        job->kind = WGJ_FIRST + (cin - 1);
+        job->ws = ws; job->dw = dw; job->Co = Co; job->Ci = cin; job->gx = gx; job->pairs = 1; job->nmf = (27 * cin + 15) / 16;
+    }
     return CTU_OK;
 }
 
@@ -548,6 +530,21 @@ extern "C" int ctu_conv3d_first_wgrad_bn(const float* x, int cin, const float* g
     CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0, "conv3d_first_wgrad_bn: 16-byte alignment");
     const FirstLazy lz = {y, bn_scale, bn_shift, coef, gy_out};
     return first_wgrad_impl<float>(x, cin, ga, g_cs, dw, Co, ws, N, D, H, W, &lz, stream);
+}
+extern "C" int ctu_conv3d_first_wgrad_slabs(const float* x, int cin, const float* g, int g_cs, float* dw, int Co, float* ws, int N,
+                                            int D, int H, int W, ctu_wgrad_job* job, void* stream) {
+    CTU_REQUIRE(job, "conv3d_first_wgrad_slabs: null job");
+    return first_wgrad_impl<float>(x, cin, g, g_cs, dw, Co, ws, N, D, H, W, nullptr, stream, job);
+}
+extern "C" int ctu_conv3d_first_wgrad_bn_slabs(const float* x, int cin, const float* ga, int g_cs, const float* y,
+                                               const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
+                                               float* dw, int Co, float* ws, int N, int D, int H, int W, ctu_wgrad_job* job,
+                                               void* stream) {
+    CTU_REQUIRE(job, "conv3d_first_wgrad_bn_slabs: null job");
+    CTU_REQUIRE(y && bn_scale && bn_shift && coef && gy_out && gy_out != ga, "conv3d_first_wgrad_bn: null pointer / gy_out aliases ga");
+    CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0, "conv3d_first_wgrad_bn: 16-byte alignment");
+    const FirstLazy lz = {y, bn_scale, bn_shift, coef, gy_out};
+    return first_wgrad_impl<float>(x, cin, ga, g_cs, dw, Co, ws, N, D, H, W, &lz, stream, job);
 }
 extern "C" int ctu_lp_conv3d_first_wgrad(int dtype, const float* x, int cin, const void* g, int g_cs, float* dw, int Co, float* ws,
                                          int N, int D, int H, int W, void* stream) {

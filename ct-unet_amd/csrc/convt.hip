@@ -9,6 +9,7 @@
 // The op is HBM-bound (the 8x larger output stream), see DESIGN.md.
 #include "common.h"
 #include "pack.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -388,29 +389,8 @@ __global__ __launch_bounds__(1024) void convt2_wgrad_reduce_kernel(const float* 
                                                                    float* __restrict__ dw, float* __restrict__ dbias, int Ci,
                                                                    int Co, const int32_t* __restrict__ imap, int n_ci_t,
                                                                    int gx) {
-    constexpr int CA = 16 * MI, CG = 16 * NJ, SL = 8 * MI * NJ * 256;
     __shared__ float red[RPARTS][64];
-    const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int idx = blockIdx.x * 64 + e;
-    float s = 0.f;
-    const int ndw = Ci * Co * 8;
-    const bool ok = idx < ndw, okb = dbias && idx >= ndw && idx < ndw + Co;
-    int co = 0, ci = 0, tap = 0;
-    if (ok) {
-        co = idx % Co; ci = (idx / Co) % Ci; tap = idx / (Co * Ci);
-        const int cip = imap ? imap[ci] : ci;      // logical -> padded position
-        const int cig = cip / CA, cog = co / CG, x = (cip % CA) >> 4, y = (co % CG) >> 4;
-        const float* src = ws + ((size_t)(cog * n_ci_t + cig) * gx) * SL + ((tap * MI + x) * NJ + y) * 256 + (cip & 15) * 16 + (co & 15);
-        for (int k = part; k < gx; k += RPARTS) s += src[(size_t)k * SL];
-    } else if (okb) {
-        co = idx - ndw;
-        const float* src = wsb + ((size_t)(co / CG) * gx) * CG + co % CG;
-        for (int k = part; k < gx; k += RPARTS) s += src[(size_t)k * CG];
-    }
-    red[part][e] = s;
-    __syncthreads();
-    if (part == 0 && ok) dw[((size_t)ci * Co + co) * 8 + tap] = red_total(red, e);
-    if (part == 0 && okb) dbias[co] = red_total(red, e);
+    convt2_wgrad_reduce_block<MI, NJ>(ws, wsb, dw, dbias, Ci, Co, imap, n_ci_t, gx, blockIdx.x, threadIdx.x, red);
 }
 
 // ------------------------------------------------------------------ launch plans (host only)
@@ -554,19 +534,28 @@ extern "C" size_t ctu_convt2_wgrad_ws_floats(int N, int D, int H, int W, int cin
 
 template <int MI, int NJ>
 static int launch_ct_wgrad(CtWgP p, float* dw, float* dbias, int Ci, int Co, const int32_t* imap, int n_co_t, int gx,
-                           hipStream_t st) {
+                           hipStream_t st, ctu_wgrad_job* job) {
     float* wsb = p.ws + (size_t)p.n_ci_t * n_co_t * gx * 8 * MI * NJ * 256;
     convt2_wgrad_kernel<MI, NJ><<<dim3(gx, p.n_ci_t * n_co_t), 256, 0, st>>>(p, dbias ? wsb : nullptr);
     CTU_CHECK_LAUNCH("convt2_wgrad");
+    if (job) {                                     // the caller reduces the slabs later (wsb = ws + pairs * gx * slab floats)
+        *job = ctu_wgrad_job{};
+        job->kind = WGJ_CONVT + (MI - 1) * 2 + (NJ - 1);
+        job->ws = p.ws; job->dw = dw; job->db = dbias; job->cinv = imap;
+        job->Co = Co; job->Ci = Ci; job->cin_p = p.cin_p; job->n_ci_g = p.n_ci_t; job->gx = gx; job->pairs = p.n_ci_t * n_co_t;
+        job->nmf = 8 * MI * NJ;
+        return CTU_OK;
+    }
     convt2_wgrad_reduce_kernel<MI, NJ><<<ceil_div(Ci * Co * 8 + Co, 64), 64 * RPARTS, 0, st>>>(p.ws, wsb, dw, dbias, Ci, Co, imap,
                                                                                            p.n_ci_t, gx);
     CTU_CHECK_LAUNCH("convt2_wgrad_reduce");
     return CTU_OK;
 }
 
-extern "C" int ctu_convt2_wgrad(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
-                                int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Ci,
-                                int Co, const int32_t* imap, float* ws, int N, int D, int H, int W, void* stream) {
+static int convt2_wgrad_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                             int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Ci,
+                             int Co, const int32_t* imap, float* ws, int N, int D, int H, int W, ctu_wgrad_job* job,
+                             void* stream) {
     CTU_REQUIRE(in && gout && dw && ws, "convt2_wgrad: null pointer");
     CTU_REQUIRE(cin_p % 8 == 0 && cout_p % 8 == 0 && cin_p > 0 && cout_p > 0, "convt2_wgrad: padded channels");
     CTU_REQUIRE(in_cs >= cin_p && in_cs % 4 == 0 && g_cs >= cout_p && g_cs % 4 == 0, "convt2_wgrad: bad stride");
@@ -579,10 +568,26 @@ extern "C" int ctu_convt2_wgrad(const float* in, int in_cs, int cin_p, const flo
     const CtWgPlan r = ct_wgrad_plan(p.nvox, cin_p, cout_p);
     p.ntiles = r.ntiles; p.n_ci_t = r.n_ci_t;
     const int mi = r.mi, nj = r.nj, n_co_t = r.n_co_t, gx = r.gx;
-    if (mi == 1 && nj == 1) return launch_ct_wgrad<1, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
-    if (mi == 1) return launch_ct_wgrad<1, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
-    if (nj == 1) return launch_ct_wgrad<2, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
-    return launch_ct_wgrad<2, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st);
+    if (mi == 1 && nj == 1) return launch_ct_wgrad<1, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st, job);
+    if (mi == 1) return launch_ct_wgrad<1, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st, job);
+    if (nj == 1) return launch_ct_wgrad<2, 1>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st, job);
+    return launch_ct_wgrad<2, 2>(p, dw, dbias, Ci, Co, imap, n_co_t, gx, st, job);
+}
+
+extern "C" int ctu_convt2_wgrad(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Ci,
+                                int Co, const int32_t* imap, float* ws, int N, int D, int H, int W, void* stream) {
+    return convt2_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, cout_p, dw, dbias, Ci, Co, imap, ws,
+                             N, D, H, W, nullptr, stream);
+}
+
+extern "C" int ctu_convt2_wgrad_slabs(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                      int in_relu, const float* gout, int g_cs, int cout_p, float* dw, float* dbias, int Ci,
+                                      int Co, const int32_t* imap, float* ws, int N, int D, int H, int W, ctu_wgrad_job* job,
+                                      void* stream) {
+    CTU_REQUIRE(job, "convt2_wgrad_slabs: null job");
+    return convt2_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, cout_p, dw, dbias, Ci, Co, imap, ws,
+                             N, D, H, W, job, stream);
 }
 
 // Host-only plan queries (no GPU): the instantiation a call of this geometry launches, or NULL where the call is refused.

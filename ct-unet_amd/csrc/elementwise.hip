@@ -6,6 +6,7 @@
 #include "common.h"
 #include "bn_tail.h"
 #include "channel_sum.h"
+#include "wgrad_reduce.h"
 
 static thread_local char g_err[512] = "";
 
@@ -23,6 +24,7 @@ extern "C" const char* ctu_arch(void) { return "gfx950"; }
 namespace {
 
 constexpr int EW_BLOCK = 256;
+static_assert(EW_BLOCK == FINALIZE_BLOCK, "wgrad_reduce.h block size");
 static_assert(EW_BLOCK == CSUM_BLOCK, "channel_sum.h block size");
 constexpr int FIN_BLOCK = 256;    // threads of the per-channel statistics finalisation
 constexpr int MAX_RED_BLOCKS = 1024;
@@ -183,54 +185,33 @@ __global__ void bn_relu_bwd_reduce_kernel(const T* __restrict__ y, int y_cs, con
     if (tail.counter) bn_bwd_tail(tail, partials, gridDim.x, cp, gridDim.x);
 }
 
-// coef[0..cp) = k0 = gamma*invstd ; coef[cp..2cp) = k1 = dbeta/n ; coef[2cp..3cp) = k2 = dgamma/n ; and the same backward
-// as one affine map of the raw output (bn_bwd_lazy4, common.h): coef[3cp..4cp) = A = -k0 k2 invstd,
-// coef[4cp..5cp) = B = -k0 (k1 - k2 mean invstd)
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ partials, int nb, int C, int cp, double count,
-                                       const float* __restrict__ gamma, const float* __restrict__ invstd,
-                                       float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                       float* __restrict__ coef, const float* __restrict__ mean,
-                                       float* __restrict__ rmean, float* __restrict__ rvar, float momentum, float eps,
-                                       long long* __restrict__ nbt) {
-    const int c = blockIdx.x;
-    if (nbt && rmean && c == 0 && threadIdx.x == 0) nbt[0] += 1;                      // the replayed update counts too
-    float g_ = 0.f, is_ = 0.f, mu_ = 0.f, rm0 = 0.f, rv0 = 0.f;                      // (prefetched: see bn_finalize_kernel)
-    if (threadIdx.x == 0 && c < C) {
-        g_ = gamma[c]; is_ = invstd[c]; mu_ = mean[c];
-        if (rmean) { rm0 = rmean[c]; rv0 = rvar[c]; }
+// coef rows and arithmetic: bn_bwd_finalize_block (wgrad_reduce.h); one block per padded channel
+__global__ void bn_bwd_finalize_kernel(BnBwdFinArgs f) {
+    __shared__ double sm[2 * (EW_BLOCK / 64)];
+    bn_bwd_finalize_block(f, blockIdx.x, threadIdx.x, sm);
+}
+
+// Pending weight-gradient slab reductions in one launch of 64 * RPARTS-thread blocks: block b of job j runs at
+// start[j] + b.  FIN: the first f.cp blocks are bn_bwd_finalize_kernel's instead (their first EW_BLOCK threads) -- the
+// reductions ride in spare blocks of a launch the backward chain needs anyway.  The two kinds of blocks exchange nothing.
+struct WgJobTable { ctu_wgrad_job job[CTU_WGRAD_JOBS_MAX]; int start[CTU_WGRAD_JOBS_MAX + 1]; int n; };
+
+template <bool FIN>
+__global__ __launch_bounds__(64 * RPARTS) void wgrad_reduce_jobs_kernel(BnBwdFinArgs f, WgJobTable t) {
+    __shared__ float red[RPARTS][64];
+    __shared__ double sm[2 * (EW_BLOCK / 64)];
+    int b = blockIdx.x;
+    if (FIN) {
+        if (b < f.cp) { bn_bwd_finalize_block(f, b, threadIdx.x, sm); return; }
+        b -= f.cp;
     }
-    double s1 = 0.0, s2 = 0.0;
-    if (c < C) {
-#pragma unroll 4
-        for (int b = threadIdx.x; b < nb; b += EW_BLOCK) {
-            s1 += (double)partials[(size_t)b * 2 * cp + c];
-            s2 += (double)partials[(size_t)b * 2 * cp + cp + c];
-        }
-    }
-    block_sum2<EW_BLOCK>(s1, s2);
-    if (threadIdx.x == 0) {
-        if (c < C) {
-            dbeta[c] = (float)s1;
-            dgamma[c] = (float)s2;
-            const float k0 = g_ * is_, k1 = (float)(s1 / count), k2 = (float)(s2 / count);
-            coef[c] = k0;
-            coef[cp + c] = k1;
-            coef[2 * cp + c] = k2;
-            coef[3 * cp + c] = -k0 * k2 * is_;
-            coef[4 * cp + c] = -k0 * (k1 - k2 * mu_ * is_);
-            if (rmean) {
-                // the running-stat update torch.utils.checkpoint's recompute repeats in backward (models.py:232-255):
-                // same batch statistics as the forward update; the biased variance is recovered from invstd
-                const double istd = (double)is_;
-                double var = 1.0 / (istd * istd) - (double)eps;
-                if (var < 0.0) var = 0.0;
-                const float unb = (float)(var * (count / (count > 1.0 ? count - 1.0 : 1.0)));
-                rmean[c] = (1.f - momentum) * rm0 + momentum * mu_;
-                rvar[c] = (1.f - momentum) * rv0 + momentum * unb;
-            }
-        } else {
-            coef[c] = 0.f; coef[cp + c] = 0.f; coef[2 * cp + c] = 0.f; coef[3 * cp + c] = 0.f; coef[4 * cp + c] = 0.f;
-        }
+    int j = 0;
+    while (j + 1 < t.n && b >= t.start[j + 1]) ++j;
+    switch (j) {                                   // (constant indices: the table stays in the kernel-argument registers)
+    case 0: wgrad_job_block(t.job[0], b - t.start[0], threadIdx.x, red); break;
+    case 1: wgrad_job_block(t.job[1], b - t.start[1], threadIdx.x, red); break;
+    case 2: wgrad_job_block(t.job[2], b - t.start[2], threadIdx.x, red); break;
+    default: wgrad_job_block(t.job[3], b - t.start[3], threadIdx.x, red); break;
     }
 }
 
@@ -837,17 +818,86 @@ extern "C" int ctu_lp_bn_relu_bwd_reduce(int dtype, const void* y, int y_cs, con
                                                              nvox, partials, tail, stream));
 }
 
+// the job table of a merged launch: the non-empty jobs and their block ranges; *nblocks = blocks of all of them
+static int wgrad_job_table(const ctu_wgrad_job* jobs, int njobs, WgJobTable* t, int* nblocks, const char* what) {
+    CTU_REQUIRE(njobs >= 0 && njobs <= CTU_WGRAD_JOBS_MAX, "%s: njobs=%d (0 .. %d)", what, njobs, CTU_WGRAD_JOBS_MAX);
+    CTU_REQUIRE(njobs == 0 || jobs, "%s: null job table", what);
+    *t = WgJobTable{};
+    int n = 0, total = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const ctu_wgrad_job& j = jobs[i];
+        if (j.kind == 0) continue;
+        CTU_REQUIRE(j.kind > 0 && j.kind < WGJ_KINDS, "%s: job %d has unknown kind %d", what, i, j.kind);
+        CTU_REQUIRE(j.ws && j.dw, "%s: job %d: null pointer", what, i);
+        CTU_REQUIRE(((uintptr_t)j.ws & 3) == 0 && ((uintptr_t)j.dw & 3) == 0 && ((uintptr_t)j.db & 3) == 0 && ((uintptr_t)j.cinv & 3) == 0,
+                    "%s: job %d: pointers must be 4-byte aligned", what, i);
+        CTU_REQUIRE(j.Co > 0 && j.Ci > 0 && j.gx > 0 && j.pairs > 0 && j.nmf > 0 && j.nmf <= 32 && j.pairs <= 65535,
+                    "%s: job %d: bad geometry", what, i);
+        CTU_REQUIRE(j.kind >= WGJ_FIRST || (j.n_ci_g > 0 && j.cin_p > 0), "%s: job %d: bad channel groups", what, i);
+        CTU_REQUIRE(j.kind < WGJ_CONVT || (j.n_ci_g > 0 && (int64_t)j.Ci * j.Co * 8 + j.Co < (1LL << 31)), "%s: job %d: bad ConvTranspose job", what, i);
+        t->job[n] = j;
+        t->start[n] = total;
+        total += wgrad_job_blocks(j);
+        ++n;
+    }
+    for (int i = n; i <= CTU_WGRAD_JOBS_MAX; ++i) t->start[i] = total;
+    t->n = n;
+    *nblocks = total;
+    return CTU_OK;
+}
+
+static int bn_bwd_fin_args(BnBwdFinArgs* f, const float* partials, int nb, int C, int cp, double count, const float* gamma,
+                           const float* invstd, float* dgamma, float* dbeta, float* coef, const float* mean,
+                           float* running_mean, float* running_var, float momentum, float eps,
+                           long long* num_batches_tracked) {
+    CTU_REQUIRE(partials && gamma && invstd && dgamma && dbeta && coef && mean, "bn_bwd_finalize: null pointer");
+    CTU_REQUIRE((running_mean == nullptr) == (running_var == nullptr) && (!running_mean || mean),
+                "bn_bwd_finalize: the running-stat replay needs mean, running_mean and running_var together");
+    *f = BnBwdFinArgs{partials, gamma, invstd, mean, dgamma, dbeta, coef, running_mean, running_var, num_batches_tracked,
+                      count, momentum, eps, nb, C, cp};
+    return CTU_OK;
+}
+
 extern "C" int ctu_bn_bwd_finalize(const float* partials, int nb, int C, int cp, double count, const float* gamma,
                                    const float* invstd, float* dgamma, float* dbeta, float* coef, const float* mean,
                                    float* running_mean, float* running_var, float momentum, float eps,
                                    long long* num_batches_tracked, void* stream) {
-    CTU_REQUIRE(partials && gamma && invstd && dgamma && dbeta && coef && mean, "bn_bwd_finalize: null pointer");
-    CTU_REQUIRE((running_mean == nullptr) == (running_var == nullptr) && (!running_mean || mean),
-                "bn_bwd_finalize: the running-stat replay needs mean, running_mean and running_var together");
-    bn_bwd_finalize_kernel<<<cp, EW_BLOCK, 0, (hipStream_t)stream>>>(partials, nb, C, cp, count, gamma, invstd, dgamma,
-                                                                    dbeta, coef, mean, running_mean, running_var,
-                                                                    momentum, eps, num_batches_tracked);
+    BnBwdFinArgs f;
+    const int rc = bn_bwd_fin_args(&f, partials, nb, C, cp, count, gamma, invstd, dgamma, dbeta, coef, mean, running_mean,
+                                   running_var, momentum, eps, num_batches_tracked);
+    if (rc != CTU_OK) return rc;
+    bn_bwd_finalize_kernel<<<cp, EW_BLOCK, 0, (hipStream_t)stream>>>(f);
     CTU_CHECK_LAUNCH("bn_bwd_finalize");
+    return CTU_OK;
+}
+
+extern "C" int ctu_bn_bwd_finalize_jobs(const float* partials, int nb, int C, int cp, double count, const float* gamma,
+                                        const float* invstd, float* dgamma, float* dbeta, float* coef, const float* mean,
+                                        float* running_mean, float* running_var, float momentum, float eps,
+                                        long long* num_batches_tracked, const ctu_wgrad_job* jobs, int njobs, void* stream) {
+    BnBwdFinArgs f;
+    int rc = bn_bwd_fin_args(&f, partials, nb, C, cp, count, gamma, invstd, dgamma, dbeta, coef, mean, running_mean,
+                             running_var, momentum, eps, num_batches_tracked);
+    if (rc != CTU_OK) return rc;
+    CTU_REQUIRE(cp > 0 && C <= cp && nb >= 0, "bn_bwd_finalize_jobs: C=%d cp=%d nb=%d", C, cp, nb);
+    WgJobTable t;
+    int nblocks = 0;
+    rc = wgrad_job_table(jobs, njobs, &t, &nblocks, "bn_bwd_finalize_jobs");
+    if (rc != CTU_OK) return rc;
+    if (nblocks == 0) bn_bwd_finalize_kernel<<<cp, EW_BLOCK, 0, (hipStream_t)stream>>>(f);      // exactly ctu_bn_bwd_finalize
+    else wgrad_reduce_jobs_kernel<true><<<cp + nblocks, 64 * RPARTS, 0, (hipStream_t)stream>>>(f, t);
+    CTU_CHECK_LAUNCH("bn_bwd_finalize_jobs");
+    return CTU_OK;
+}
+
+extern "C" int ctu_wgrad_reduce_jobs(const ctu_wgrad_job* jobs, int njobs, void* stream) {
+    WgJobTable t;
+    int nblocks = 0;
+    const int rc = wgrad_job_table(jobs, njobs, &t, &nblocks, "wgrad_reduce_jobs");
+    if (rc != CTU_OK) return rc;
+    if (nblocks == 0) return CTU_OK;
+    wgrad_reduce_jobs_kernel<false><<<nblocks, 64 * RPARTS, 0, (hipStream_t)stream>>>(BnBwdFinArgs{}, t);
+    CTU_CHECK_LAUNCH("wgrad_reduce_jobs");
     return CTU_OK;
 }
 

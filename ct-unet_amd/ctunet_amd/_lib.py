@@ -44,6 +44,15 @@ class BnBwdTail(C.Structure):
                 ("momentum", C.c_float), ("eps", C.c_float), ("C", C.c_int)]
 
 
+class WgradJob(C.Structure):
+    """ctu_wgrad_job of include/ctunet_hip.h."""
+    _fields_ = [("ws", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("cinv", C.c_void_p), ("kind", C.c_int),
+                ("Co", C.c_int), ("Ci", C.c_int), ("cin_p", C.c_int), ("n_ci_g", C.c_int), ("gx", C.c_int),
+                ("pairs", C.c_int), ("nmf", C.c_int)]
+
+
+WGRAD_JOBS_MAX = 4       # CTU_WGRAD_JOBS_MAX
+
 # name -> (restype, argtypes); mirrors include/ctunet_hip.h one to one
 SIGNATURES = {
     "ctu_last_error": (C.c_char_p, []),
@@ -76,6 +85,13 @@ SIGNATURES = {
     "ctu_bn_relu_bwd_reduce": (I, [P, I, P, I, I, P, P, P, P, L, P, P, P]),
     "ctu_bn_bwd_finalize": (I, [P, I, I, I, D, P, P, P, P, P, P, P, P, F, F, P, P]),
     "ctu_bn_relu_bwd_apply": (I, [P, I, P, I, I, P, P, P, P, P, L, P]),
+    "ctu_conv3d_wgrad_slabs": (I, [P, I, I, P, P, I, P, I, I, P, P, I, I, P, P, I, I, I, I, I, P, P]),
+    "ctu_conv3d_wgrad_bn_slabs": (I, [P, I, I, P, P, I, P, I, I, P, P, P, P, P, P, I, I, P, P, I, I, I, I, I, P, P]),
+    "ctu_conv3d_first_wgrad_slabs": (I, [P, I, P, I, P, I, P, I, I, I, I, P, P]),
+    "ctu_conv3d_first_wgrad_bn_slabs": (I, [P, I, P, I, P, P, P, P, P, P, I, P, I, I, I, I, P, P]),
+    "ctu_convt2_wgrad_slabs": (I, [P, I, I, P, P, I, P, I, I, P, P, I, I, P, P, I, I, I, I, P, P]),
+    "ctu_bn_bwd_finalize_jobs": (I, [P, I, I, I, D, P, P, P, P, P, P, P, P, F, F, P, P, I, P]),
+    "ctu_wgrad_reduce_jobs": (I, [P, I, P]),
     "ctu_maxpool2_fwd": (I, [P, I, I, P, P, I, P, I, I, I, I, I, P]),
     "ctu_maxpool2_bwd": (I, [P, I, I, P, P, I, P, I, P, I, I, I, I, I, I, P]),
     "ctu_maxpool2_bwd_bn_num_blocks": (I, [I, I, I, I, I]),

@@ -49,6 +49,10 @@ LAZY_BN_LP = os.environ.get("CTUNET_LAZY_BN_LP", "0") != "0"
 # the launch that writes a BatchNorm's partial rows also finalizes them (its last block: ctu_bn_tail / ctu_bn_bwd_tail)
 # instead of a separate ctu_bn_finalize / ctu_bn_bwd_finalize launch (CTUNET_BN_TAIL=0: the separate launches)
 BN_TAIL = os.environ.get("CTUNET_BN_TAIL", "0") != "0"
+# fp32: a weight gradient's slab reduction is not launched behind its kernel but rides in spare blocks of the next
+# BatchNorm-backward finalize launch (ops.WgradJobs; nothing reads dW before the optimizer or a gradient exchange) -- one
+# dependent launch less per conv layer on the backward chain (CTUNET_DEFER_WGRAD_REDUCE=0: reduce behind each kernel)
+DEFER_WGRAD_REDUCE = os.environ.get("CTUNET_DEFER_WGRAD_REDUCE", "1") != "0"
 
 
 @dataclass
@@ -90,6 +94,32 @@ class _ConvRec:
     imap: Optional[torch.Tensor]
     bias: bool
     first: Optional[torch.Tensor] = None      # the NCDHW network input, when the direct C_in <= 2 kernels ran the stage
+
+
+class _WgradWs:
+    """The weight-gradient workspace(s) of one backward pass and its pending slab reductions (ops.WgradJobs; None: every
+    weight gradient reduces at once, one workspace).  A pending reduction reads its workspace after later launches, and a
+    decoder block's ConvTranspose weight gradient comes before the next finalize launch has run it -- so two workspaces,
+    alternating per weight-gradient call."""
+
+    def __init__(self, floats: int, device, defer: bool):
+        self.jobs = ops.WgradJobs() if defer else None
+        self.bufs = [torch.empty(floats, dtype=torch.float32, device=device) for _ in range(2 if defer else 1)]
+        self.i = 0
+
+    def take(self) -> torch.Tensor:
+        """The workspace of the next weight-gradient call: one that no pending reduction reads."""
+        self.i = (self.i + 1) % len(self.bufs)
+        ws = self.bufs[self.i]
+        if self.jobs is not None:
+            if self.jobs.uses(ws):               # (more than two weight gradients since the last finalize launch)
+                self.jobs.flush()
+            assert not self.jobs.uses(ws)
+        return ws
+
+    def flush(self) -> None:
+        if self.jobs is not None:
+            self.jobs.flush()
 
 
 class UNetEngine:
@@ -451,13 +481,14 @@ class UNetEngine:
             ent = self._gy_bufs[id(ga.buf)] = (ga.buf, torch.empty_like(ga.buf))
         return CL(ent[1], ga.c0, ga.cp)
 
-    def _conv_bn_bwd(self, P, rec: _ConvRec, ga: CL, gin: Optional[CL], grads: Dict[str, torch.Tensor], ws, part,
+    def _conv_bn_bwd(self, P, rec: _ConvRec, ga: CL, gin: Optional[CL], grads: Dict[str, torch.Tensor], ws: _WgradWs, part,
                      pre_reduced: Optional[int] = None, finalized=None, up_in: Optional[CL] = None):
         """ga: gradient w.r.t. the ACTIVATED output (overwritten with the raw-output gradient unless the BatchNorm backward
         is folded into the weight-gradient kernel, ops.conv3d_wgrad_bn: then the raw-output gradient goes to a second buffer).
         gin: where to write the gradient w.r.t. this conv's activated input (None: not needed).
         up_in: rec is a fused up-convolution and this is its coarse input -- only the BatchNorm part runs here; returns what
-        the caller hands to ops.upconv_fused_wgrad(lazy=...) (None: ga already holds the raw-output gradient)."""
+        the caller hands to ops.upconv_fused_wgrad(lazy=...) (None: ga already holds the raw-output gradient).
+        ws: the pass's weight-gradient workspaces; the slab reductions pending there ride on this layer's finalize launch."""
         k = self.plan.k
         can = LAZY_BN and ga.cs == rec.y.cs and (not ga.lp or LAZY_BN_LP)
         if up_in is not None:
@@ -467,26 +498,28 @@ class UNetEngine:
             lazy = can and not rec.bias and not ga.lp
         else:
             lazy = can and not rec.bias and rec.x is not None and ops.conv3d_wgrad_bn_supported(ga.dims, k, rec.x.cp, ga.cp, self.dtype)
+        jobs = ws.jobs
         res = ops.bn_relu_bwd(rec.y, ga, rec.vec, P[rec.bn + ".weight"].detach(), rec.cout, part, self._replay(P, rec),
-                              pre_reduced, self._counter(rec.bn, "bwd", ga.buf.device), finalized, lazy)
+                              pre_reduced, self._counter(rec.bn, "bwd", ga.buf.device), finalized, lazy, jobs)
         grads[rec.bn + ".weight"], grads[rec.bn + ".bias"] = res[0], res[1]
         if up_in is not None:
             return (rec.y, rec.vec, res[2], self._gy_like(ga)) if lazy else None
         if rec.first is not None:                  # direct C_in <= 2 kernels; gin is a request flag here
             if lazy:
                 gy = self._gy_like(ga)
-                grads[rec.conv + ".weight"] = ops.conv_first_wgrad_bn(rec.first, ga, rec.y, rec.vec, res[2], gy, rec.cout, ws)
+                grads[rec.conv + ".weight"] = ops.conv_first_wgrad_bn(rec.first, ga, rec.y, rec.vec, res[2], gy, rec.cout,
+                                                                      ws.take(), jobs)
                 ga = gy
             else:
-                grads[rec.conv + ".weight"] = ops.conv_first_wgrad(rec.first, ga, rec.cout, ws)
+                grads[rec.conv + ".weight"] = ops.conv_first_wgrad(rec.first, ga, rec.cout, ws.take(), jobs)
             return ops.conv_first_bwd_data(ga, P[rec.conv + ".weight"].detach(), rec.cin) if gin is not None else None
         if lazy:
             gy = self._gy_like(ga)
             grads[rec.conv + ".weight"] = ops.conv3d_wgrad_bn(rec.x, ga, rec.y, rec.vec, res[2], gy, rec.cout, rec.cin, k,
-                                                             rec.imap, ws)
+                                                             rec.imap, ws.take(), jobs)
             ga = gy
         elif rec.x is not None:                    # (None: fused up-convolution, its weight gradients come from the caller)
-            dw, dbias = ops.conv3d_wgrad(rec.x, ga, rec.cout, rec.cin, k, rec.imap, ws, rec.bias)
+            dw, dbias = ops.conv3d_wgrad(rec.x, ga, rec.cout, rec.cin, k, rec.imap, ws.take(), rec.bias, jobs)
             grads[rec.conv + ".weight"] = dw
             if rec.bias:
                 grads[rec.conv + ".bias"] = dbias
@@ -539,6 +572,8 @@ class UNetEngine:
             scaling) and hand them to the gradient exchange."""
             new = [(nm, g) for nm, g in grads.items() if nm not in emitted and g is not None]
             emitted.update(nm for nm, _ in new)
+            if sync is not None or dyn is not None or gs != 1.0:
+                ws.flush()                       # what reads the gradients here needs the pending slab reductions done
             unscale([g for _, g in new])
             if sync is not None:
                 sync.push(new)
@@ -559,7 +594,7 @@ class UNetEngine:
         for dsk in ctx["dskip"]:
             part_n = max(part_n, ops.maxpool_bwd_bn_blocks(dsk.dims, dsk.cp) * 2 * dsk.cp)
         part_n = max(part_n, ops.head_bwd_blocks(ctx["head_in"].dims) * 2 * pad8(plan.dec[-1].cout))
-        ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
+        ws = _WgradWs(ws_n, dev, DEFER_WGRAD_REDUCE and self.dtype == torch.float32 and ops.TIMER is None)
         part = torch.empty(part_n, dtype=torch.float32, device=dev)
 
         # the second running-stat update that torch.utils.checkpoint's recompute performs
@@ -647,7 +682,7 @@ class UNetEngine:
             else:
                 g_up = CL(torch.empty_like(up.buf), 0, up.cp)
                 self._conv_bn_bwd(P, r1, g_u1, g_up, grads, ws, part)
-                dwt, dbt = ops.convt_wgrad(x_in, g_up, ct, ct, imap_t, ws)
+                dwt, dbt = ops.convt_wgrad(x_in, g_up, ct, ct, imap_t, ws.take(), ws.jobs)
                 grads[f"{blk.prefix}.0.weight"], grads[f"{blk.prefix}.0.bias"] = dwt, dbt
                 wpd = self._packed(f"{blk.prefix}.0", wt, "convt", cinv_t, g_up.cp, x_in.cp, 1)
                 ops.convt_bwd_data(g_up, wpd, gin)
@@ -691,6 +726,7 @@ class UNetEngine:
             else:
                 self._conv_bn_bwd(P, r1, g_d1, None, grads, ws, part)
             emit()
+        ws.flush()                               # the first layer's reduction: no finalize launch follows it
         emit()
         unscale([dx])
         if sync is not None:

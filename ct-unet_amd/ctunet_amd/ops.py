@@ -237,6 +237,48 @@ class _timed:
             TIMER.end(tag, flops, nbytes, self.t0, detail)
 
 
+class WgradJobs:
+    """The fp32 weight-gradient slab reductions a backward pass has not launched yet (ctu_wgrad_job): nothing reads dW
+    before the optimizer, so a weight-gradient call given ``jobs=`` leaves its reduction here, and the next bn_relu_bwd that
+    launches a BatchNorm-backward finalize runs the pending ones in spare blocks of that launch.  flush() reduces what is
+    pending in one launch of its own.  Each entry keeps its workspace and outputs alive until it has been launched."""
+
+    def __init__(self):
+        self.items = []                          # (WgradJob, (ws, dw, db, ...))
+
+    def __len__(self) -> int:
+        return len(self.items)
+
+    def uses(self, ws: torch.Tensor) -> bool:
+        """Does a pending reduction still read this workspace?"""
+        return any(keep[0] is ws for _, keep in self.items)
+
+    def add(self, job, ws: torch.Tensor, *outs) -> None:
+        if not job.kind:                         # the entry reduced immediately (a route without a deferred form)
+            return
+        if len(self.items) == _lib.WGRAD_JOBS_MAX:
+            self.flush()
+        self.items.append((job, (ws,) + outs))
+
+    def take(self):
+        """(ctypes job array, count) of the pending reductions, which the caller launches now."""
+        n = len(self.items)
+        arr = (_lib.WgradJob * max(n, 1))(*(j for j, _ in self.items))
+        self.items = []
+        return arr, n
+
+    def flush(self) -> None:
+        if self.items:
+            arr, n = self.take()
+            _lib.check(_lib.load().ctu_wgrad_reduce_jobs(arr, n, _stream()), "wgrad_reduce_jobs")
+
+
+def _deferred(jobs: Optional[WgradJobs], code: int = 0) -> bool:
+    """Does a weight-gradient call leave its slab reduction in ``jobs``?  fp32 only, and not while launches are bracketed
+    (the "(+slab reduce)" brackets of the stage table time the reduction with its kernel)."""
+    return jobs is not None and not code and TIMER is None
+
+
 @dataclass
 class CL:
     buf: torch.Tensor                       # [N, D, H, W, cs] contiguous fp32
@@ -419,12 +461,19 @@ def _wgrad_setup(x: CL, g: CL, co: int, ci: int, k: int, ws: torch.Tensor):
 
 
 def conv3d_wgrad(x: CL, g: CL, co: int, ci: int, k: int, cinv: Optional[torch.Tensor], ws: torch.Tensor,
-                 want_bias: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                 want_bias: bool, jobs: Optional[WgradJobs] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """jobs: leave the slab reduction pending there (WgradJobs) instead of launching it."""
     n, d, h, w = x.dims
     code = x.lp
     dw, timed = _wgrad_setup(x, g, co, ci, k, ws)
     # the fp32 kernel's reduction writes the bias gradient too; the 16-bit one leaves it to a channel_sum launch
     db = torch.empty(co, dtype=torch.float32, device=x.buf.device) if want_bias and not code else None
+    if _deferred(jobs, code):
+        job = _lib.WgradJob()
+        _dual(0, "conv3d_wgrad_slabs", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
+              dw.data_ptr(), _ptr(db), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, ctypes.byref(job), _stream())
+        jobs.add(job, ws, dw, cinv)
+        return dw, db
     with timed:
         _dual(code, "conv3d_wgrad", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
               dw.data_ptr(), *(() if code else (_ptr(db),)), co, ci, _ptr(cinv), ws.data_ptr(), n, d, h, w, k, _stream())
@@ -440,14 +489,21 @@ def conv3d_wgrad_bn_supported(dims, k: int, cin_p: int, cout_p: int, dtype=torch
 
 
 def conv3d_wgrad_bn(x: CL, ga: CL, y: CL, vec: torch.Tensor, coef: torch.Tensor, gy: CL, co: int, ci: int, k: int,
-                    cinv: Optional[torch.Tensor], ws: torch.Tensor) -> torch.Tensor:
+                    cinv: Optional[torch.Tensor], ws: torch.Tensor, jobs: Optional[WgradJobs] = None) -> torch.Tensor:
     """Weight gradient with the layer's BatchNorm + ReLU backward folded in: ga = gradient w.r.t. the ACTIVATED output, y =
     the raw conv output, vec = its [4, cp] BatchNorm vectors, coef = bn_relu_bwd(lazy=True)'s rows; gy (same buffer shape
-    and channel offset as ga) receives the raw-output gradient for the data-gradient kernel."""
+    and channel offset as ga) receives the raw-output gradient for the data-gradient kernel.  jobs: as in conv3d_wgrad."""
     n, d, h, w = x.dims
     assert ga.dims == x.dims and y.dims == x.dims and gy.dims == x.dims and ga.dtype == x.dtype == y.dtype == gy.dtype
     assert y.cs == ga.cs == gy.cs and y.cp == ga.cp == gy.cp and gy.buf.data_ptr() != ga.buf.data_ptr()
     dw, timed = _wgrad_setup(x, ga, co, ci, k, ws)
+    if _deferred(jobs, x.lp):
+        job = _lib.WgradJob()
+        _dual(0, "conv3d_wgrad_bn_slabs", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), ga.ptr, ga.cs, ga.cp,
+              y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ci, _ptr(cinv),
+              ws.data_ptr(), n, d, h, w, k, ctypes.byref(job), _stream())
+        jobs.add(job, ws, dw, cinv)
+        return dw
     with timed:
         _dual(x.lp, "conv3d_wgrad_bn", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), ga.ptr, ga.cs, ga.cp,
               y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ci, _ptr(cinv),
@@ -519,7 +575,7 @@ def conv_first_bwd_data(g: CL, w: torch.Tensor, cin: int) -> torch.Tensor:
     return dx
 
 
-def conv_first_wgrad(x: torch.Tensor, g: CL, co: int, ws: torch.Tensor) -> torch.Tensor:
+def conv_first_wgrad(x: torch.Tensor, g: CL, co: int, ws: torch.Tensor, jobs: Optional[WgradJobs] = None) -> torch.Tensor:
     n, cin, d, h, w_ = x.shape
     lib = _lib.load()
     if (g.lp and g.cp == 8 and n * d * h * w_ >= FIRST_WGRAD_MFMA_MIN_VOX
@@ -532,6 +588,12 @@ def conv_first_wgrad(x: torch.Tensor, g: CL, co: int, ws: torch.Tensor) -> torch
         return conv3d_wgrad(x8, g, co, cin, 3, None, ws if ws.numel() >= need else torch.empty(need, device=x.device), False)[0]
     assert ws.numel() >= lib.ctu_conv3d_first_wgrad_ws_floats(n, d, h, w_, cin)
     dw = torch.empty((co, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    if _deferred(jobs, g.lp):
+        job = _lib.WgradJob()
+        _dual(0, "conv3d_first_wgrad_slabs", x.data_ptr(), cin, g.ptr, g.cs, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_,
+              ctypes.byref(job), _stream())
+        jobs.add(job, ws, dw)
+        return dw
     with _timed_first_wgrad(cin, co, n * d * h * w_):
         _dual(g.lp, "conv3d_first_wgrad", x.data_ptr(), cin, g.ptr, g.cs, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream())
     return dw
@@ -542,13 +604,19 @@ def _timed_first_wgrad(cin: int, co: int, vox: int) -> _timed:
 
 
 def conv_first_wgrad_bn(x: torch.Tensor, ga: CL, y: CL, vec: torch.Tensor, coef: torch.Tensor, gy: CL, co: int,
-                        ws: torch.Tensor) -> torch.Tensor:
+                        ws: torch.Tensor, jobs: Optional[WgradJobs] = None) -> torch.Tensor:
     """conv_first_wgrad with the BatchNorm + ReLU backward folded in (see conv3d_wgrad_bn); fp32 only."""
     n, cin, d, h, w_ = x.shape
     lib = _lib.load()
     assert not ga.lp and y.cs == ga.cs == gy.cs and ga.cp == 8 and gy.buf.data_ptr() != ga.buf.data_ptr()
     assert ws.numel() >= lib.ctu_conv3d_first_wgrad_ws_floats(n, d, h, w_, cin)
     dw = torch.empty((co, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    if _deferred(jobs):
+        job = _lib.WgradJob()
+        _dual(0, "conv3d_first_wgrad_bn_slabs", x.data_ptr(), cin, ga.ptr, ga.cs, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(),
+              coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, ctypes.byref(job), _stream())
+        jobs.add(job, ws, dw)
+        return dw
     with _timed_first_wgrad(cin, co, n * d * h * w_):
         _lib.check(lib.ctu_conv3d_first_wgrad_bn(x.data_ptr(), cin, ga.ptr, ga.cs, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(),
                                                  coef.data_ptr(), gy.ptr, dw.data_ptr(), co, ws.data_ptr(), n, d, h, w_, _stream()),
@@ -593,19 +661,23 @@ def bn_eval_affine(gamma, beta, rmean, rvar, eps, c, cp):
 
 def bn_relu_bwd(y: CL, ga: CL, vec: torch.Tensor, gamma: torch.Tensor, c: int, partials: torch.Tensor,
                 replay=None, pre_reduced: Optional[int] = None, counter: Optional[torch.Tensor] = None, finalized=None,
-                lazy: bool = False):
+                lazy: bool = False, jobs: Optional[WgradJobs] = None):
     """In place: ga <- gradient w.r.t. the raw conv output y.  Returns (dgamma, dbeta).
     replay = (running_mean, running_var, momentum, eps[, num_batches_tracked]): also apply the running-stat update a
     second time (the one torch.utils.checkpoint's recompute performs in backward, models.py:232-255).
     counter: the reduction launch finalizes itself (ctu_bn_bwd_tail) instead of a ctu_bn_bwd_finalize launch.
     finalized = (dgb, coef): the kernel that produced ga already reduced AND finalized (maxpool_bwd / head_bwd with fin=).
     lazy: reduce and finalize only -- ga stays the gradient w.r.t. the ACTIVATED output and the weight-gradient kernel
-    applies the backward while it stages ga (conv3d_wgrad_bn / upconv_fused_wgrad_bn); returns (dgamma, dbeta, coef)."""
+    applies the backward while it stages ga (conv3d_wgrad_bn / upconv_fused_wgrad_bn); returns (dgamma, dbeta, coef).
+    jobs: pending weight-gradient slab reductions (WgradJobs) -- they run in spare blocks of the finalize launch; where this
+    call launches no finalize of its own (counter / finalized), in one launch of theirs.  Empty afterwards either way."""
     lib = _lib.load()
     nvox = y.nvox
     cp = y.cp
     sc, sh, mu, istd = (vec[i].data_ptr() for i in range(4))
     st = _stream()
+    if jobs is not None and (finalized is not None or (counter is not None and pre_reduced is None)):
+        jobs.flush()
     if finalized is not None:
         dgb, coef = finalized
         if lazy:
@@ -622,9 +694,13 @@ def bn_relu_bwd(y: CL, ga: CL, vec: torch.Tensor, gamma: torch.Tensor, c: int, p
               _tail_arg(tail), st)
     if tail is None:
         rm, rv, mom, eps, nbt = _replay_args(replay)
-        _lib.check(lib.ctu_bn_bwd_finalize(partials.data_ptr(), nb, c, cp, float(nvox), gamma.data_ptr(), istd,
-                                           dgb[0].data_ptr(), dgb[1].data_ptr(), coef.data_ptr(), mu, _ptr(rm), _ptr(rv),
-                                           mom, eps, None if nbt is None else nbt.data_ptr(), st), "bn_bwd_finalize")
+        fin = (partials.data_ptr(), nb, c, cp, float(nvox), gamma.data_ptr(), istd, dgb[0].data_ptr(), dgb[1].data_ptr(),
+               coef.data_ptr(), mu, _ptr(rm), _ptr(rv), mom, eps, None if nbt is None else nbt.data_ptr())
+        if jobs:
+            arr, n = jobs.take()
+            _lib.check(lib.ctu_bn_bwd_finalize_jobs(*fin, arr, n, st), "bn_bwd_finalize_jobs")
+        else:
+            _lib.check(lib.ctu_bn_bwd_finalize(*fin, st), "bn_bwd_finalize")
     if lazy:
         return dgb[0], dgb[1], coef
     _dual(y.lp, "bn_relu_bwd_apply", y.ptr, y.cs, ga.ptr, ga.cs, cp, sc, sh, mu, istd, coef.data_ptr(), nvox, st)
@@ -720,8 +796,17 @@ def convt_bwd_data(gout: CL, wp: torch.Tensor, gin: CL) -> None:
               _stream())
 
 
-def convt_wgrad(x: CL, g: CL, ci: int, co: int, imap, ws: torch.Tensor):
+def convt_wgrad(x: CL, g: CL, ci: int, co: int, imap, ws: torch.Tensor, jobs: Optional[WgradJobs] = None):
     n, d, h, w = x.dims
+    if _deferred(jobs, x.lp):
+        assert ws.numel() >= convt_wgrad_ws(x.dims, x.cp, g.cp, x.dtype)
+        dw = torch.empty((ci, co, 2, 2, 2), dtype=torch.float32, device=x.buf.device)
+        db = torch.empty(co, dtype=torch.float32, device=x.buf.device)
+        job = _lib.WgradJob()
+        _dual(0, "convt2_wgrad_slabs", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, g.cp,
+              dw.data_ptr(), db.data_ptr(), ci, co, _ptr(imap), ws.data_ptr(), n, d, h, w, ctypes.byref(job), _stream())
+        jobs.add(job, ws, dw, db, imap)
+        return dw, db
     with _convt_bracket("convt2_wgrad", x, x.cp, g.cp, x.dims):
         assert not x.lp or g.dtype == x.dtype
         assert ws.numel() >= convt_wgrad_ws(x.dims, x.cp, g.cp, x.dtype)

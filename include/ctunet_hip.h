@@ -244,6 +244,55 @@ int ctu_bn_relu_bwd_apply(const float* y, int y_cs, float* ga, int g_cs, int cp,
                           const float* scale, const float* shift, const float* mean,
                           const float* invstd, const float* coef, int64_t nvox, void* stream);
 
+/* ------------------------------------- deferred weight-gradient slab reductions ---- */
+/* Nothing reads dW before the optimizer (or a gradient exchange), so the small launch that reduces a weight-gradient
+ * kernel's per-block slabs need not sit on the backward chain.  The *_slabs entries below run the weight-gradient kernel
+ * exactly as ctu_conv3d_wgrad / ctu_conv3d_wgrad_bn / ctu_conv3d_first_wgrad(_bn) / ctu_convt2_wgrad do (same plan, grid,
+ * workspace layout, kernel) and, instead of launching the reduction, describe it in *job (HOST memory).  The caller hands
+ * the pending jobs, at most CTU_WGRAD_JOBS_MAX of them, to
+ *   ctu_bn_bwd_finalize_jobs ... ctu_bn_bwd_finalize's arguments + jobs: ONE launch whose first cp blocks finalize the
+ *                                BatchNorm backward and whose other blocks run the jobs' reductions (the two kinds of
+ *                                blocks exchange nothing); njobs = 0: exactly ctu_bn_bwd_finalize
+ *   ctu_wgrad_reduce_jobs ...... one launch for the pending jobs alone (njobs = 0: nothing)
+ * Every float is the one the immediate entry writes (same kernels' block bodies, same summation order).  Until its job has
+ * run, ws must not be written and dw / dbias hold nothing.  A route without a deferred form (k = 5, the generic k = 3
+ * kernel, a conv bias gradient, whose channel sum reuses ws) reduces immediately and returns job->kind = 0, which the two
+ * calls skip.  The fields are filled by the *_slabs entries and are not meant to be edited. */
+#define CTU_WGRAD_JOBS_MAX 4
+typedef struct ctu_wgrad_job {
+    const float* ws;                                  /* the slabs */
+    float* dw; float* db;                             /* db: ConvTranspose bias gradient or NULL */
+    const int32_t* cinv;                              /* conv: cinv, ConvTranspose: imap (NULL = identity) */
+    int kind;                                         /* 0 = empty */
+    int Co, Ci, cin_p, n_ci_g, gx, pairs, nmf;
+} ctu_wgrad_job;
+int ctu_conv3d_wgrad_slabs(const float* in, int in_cs, int cin_p,
+                           const float* in_scale, const float* in_shift, int in_relu,
+                           const float* gout, int g_cs, int cout_p,
+                           float* dw, float* dbias, int Co, int Ci, const int32_t* cinv,
+                           float* ws, int N, int D, int H, int W, int k, ctu_wgrad_job* job, void* stream);
+int ctu_conv3d_wgrad_bn_slabs(const float* in, int in_cs, int cin_p,
+                              const float* in_scale, const float* in_shift, int in_relu,
+                              const float* ga, int g_cs, int cout_p, const float* y,
+                              const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
+                              float* dw, int Co, int Ci, const int32_t* cinv,
+                              float* ws, int N, int D, int H, int W, int k, ctu_wgrad_job* job, void* stream);
+int ctu_conv3d_first_wgrad_slabs(const float* x, int cin, const float* g, int g_cs, float* dw, int Co,
+                                 float* ws, int N, int D, int H, int W, ctu_wgrad_job* job, void* stream);
+int ctu_conv3d_first_wgrad_bn_slabs(const float* x, int cin, const float* ga, int g_cs, const float* y, const float* bn_scale,
+                                    const float* bn_shift, const float* coef, float* gy_out, float* dw, int Co, float* ws,
+                                    int N, int D, int H, int W, ctu_wgrad_job* job, void* stream);
+int ctu_convt2_wgrad_slabs(const float* in, int in_cs, int cin_p, const float* in_scale,
+                           const float* in_shift, int in_relu, const float* gout, int g_cs,
+                           int cout_p, float* dw, float* dbias, int Ci, int Co,
+                           const int32_t* imap, float* ws, int N, int D, int H, int W, ctu_wgrad_job* job, void* stream);
+int ctu_bn_bwd_finalize_jobs(const float* partials, int nb, int C, int cp, double count,
+                             const float* gamma, const float* invstd,
+                             float* dgamma, float* dbeta, float* coef, const float* mean,
+                             float* running_mean, float* running_var, float momentum, float eps,
+                             long long* num_batches_tracked, const ctu_wgrad_job* jobs, int njobs, void* stream);
+int ctu_wgrad_reduce_jobs(const ctu_wgrad_job* jobs, int njobs, void* stream);
+
 /* -------------------------------------------------------------- MaxPool3d ---- */
 /* nn.MaxPool3d(2, stride 2) (models.py:190-191,233,469-470) of a = A(in); writes the
  * pooled ACTIVATED values (no transform needed downstream). */
