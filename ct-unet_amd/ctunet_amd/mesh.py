@@ -183,7 +183,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .metrics import parse_spacing
 
 MAX_SIDE = 1024
@@ -195,7 +195,13 @@ MAX_CELLS = 1 << 24        # CTU_MESH_GRID_MAX_CELLS: no face grid has more cell
 MIN_CELL_CAP = 1 << 16     # a grid of F faces has at most min(MAX_CELLS, max(MIN_CELL_CAP, 64 F)) cells
 _MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
 _DTYPES = _MASK_DTYPES + (torch.float32,)
-CTU_F32, CTU_U8, CTU_I64 = 0, 3, 4
+assert (MAX_SIDE + 1) ** 3 < 1 << 31          # the side limit keeps the cells (D+1)(H+1)(W+1) of the padded grid below 2^31
+_GRID = _args.Grid(shape="mesh: the shape must be a (D, H, W) triple, got {v!r}",
+                   integers="mesh: the shape must be a (D, H, W) triple of integers, got {v!r}",
+                   side=f"mesh: every side must lie in 1..{MAX_SIDE}, got {{vals}}", max_side=MAX_SIDE, max_voxels=None)
+_ORIGIN = _args.Triple(shape="mesh: origin must be a number or a (z, y, x) triple, got {v!r}",
+                       value="mesh: origin must be finite in float32, got {v!r}", float32=True)
+_ON_GPU = "mesh: {} takes a mesh on the GPU; this path has no CPU fallback"
 
 
 class Mesh(NamedTuple):
@@ -226,50 +232,14 @@ class FaceGrid(NamedTuple):
     cell_size: float
 
 
-def _shape(shape) -> tuple:
-    try:
-        vals = tuple(shape)
-    except TypeError:
-        raise ValueError(f"mesh: the shape must be a (D, H, W) triple, got {shape!r}") from None
-    if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Integral) for s in vals):
-        raise ValueError(f"mesh: the shape must be a (D, H, W) triple of integers, got {shape!r}")
-    if any(s < 1 or s > MAX_SIDE for s in vals):
-        raise ValueError(f"mesh: every side must lie in 1..{MAX_SIDE}, got {vals}")
-    if (vals[0] + 1) * (vals[1] + 1) * (vals[2] + 1) >= 1 << 31:
-        raise ValueError(f"mesh: (D+1)(H+1)(W+1) must stay below 2^31, got {vals}")
-    return tuple(int(s) for s in vals)
-
-
 def _spacing(spacing):
-    try:
-        sp = parse_spacing(spacing, 1)
-    except ValueError as e:
-        raise ValueError(str(e).replace("metrics: spacing", "mesh: spacing")) from e
+    sp = parse_spacing(spacing, 1, "mesh: spacing")
     if sp is not None and len(sp) == 1 and isinstance(spacing, (list, tuple)) and len(spacing) == 1:
         raise ValueError(f"mesh: spacing must be a number or a (z, y, x) triple, got {spacing!r}")
     if sp is not None and any(not math.isfinite(v) or ctypes.c_float(v).value <= 0.0
                               or not math.isfinite(ctypes.c_float(v).value) for v in sp[0]):
         raise ValueError(f"mesh: spacing must be positive and finite in float32, got {spacing!r}")
     return None if sp is None else sp[0]
-
-
-def _origin(origin):
-    if origin is None:
-        return None
-    if isinstance(origin, torch.Tensor):
-        origin = origin.tolist()
-    if isinstance(origin, Real) and not isinstance(origin, bool):
-        vals = [origin] * 3
-    else:
-        try:
-            vals = list(origin)
-        except TypeError:
-            raise ValueError(f"mesh: origin must be a number or a (z, y, x) triple, got {origin!r}") from None
-    if len(vals) != 3 or any(isinstance(v, bool) or not isinstance(v, Real) for v in vals):
-        raise ValueError(f"mesh: origin must be a number or a (z, y, x) triple, got {origin!r}")
-    if any(not math.isfinite(ctypes.c_float(float(v)).value) for v in vals):
-        raise ValueError(f"mesh: origin must be finite in float32, got {origin!r}")
-    return [float(v) for v in vals]
 
 
 def _number(v, what: str) -> float:
@@ -296,7 +266,7 @@ def _check_mesh(m, who: str):
 def workspace_bytes(shape) -> int:
     """Device workspace (bytes) of one ``extract_surface`` call on a (D, H, W) volume: 5 bytes per cell of the padded grid
     (rows of W+1 cells rounded up to 16), 12 per cell row and 256; the only allocation besides the mesh itself."""
-    return int(_lib.load().ctu_mesh_ws_bytes(*_shape(shape)))
+    return int(_lib.load().ctu_mesh_ws_bytes(*_args.grid(shape, _GRID)))
 
 
 def extract_surface(volume: torch.Tensor, level: float = 0.5, spacing=None, origin=None, label: Optional[int] = None,
@@ -313,10 +283,10 @@ def extract_surface(volume: torch.Tensor, level: float = 0.5, spacing=None, orig
         raise ValueError("mesh: volume must be one [D,H,W] tensor (loop over a batch: meshes are ragged)")
     if volume.dtype not in _DTYPES:
         raise ValueError(f"mesh: volume must be one of {', '.join(str(d) for d in _DTYPES)}, got {volume.dtype}")
-    shape = _shape(tuple(volume.shape))
+    shape = _args.grid(tuple(volume.shape), _GRID)
     field = volume.dtype == torch.float32
     lev = _number(level, "level")
-    sp, org = _spacing(spacing), _origin(origin)
+    sp, org = _spacing(spacing), _args.triple(origin, _ORIGIN)
     if field:
         if label is not None:
             raise ValueError("mesh: label belongs to bool / uint8 / int64 volumes; a float32 field is cut at level")
@@ -336,43 +306,35 @@ def extract_surface(volume: torch.Tensor, level: float = 0.5, spacing=None, orig
             raise ValueError(f"mesh: label must be an integer of the map's range, got {label!r}")
         else:
             has_label, lab = 1, int(label)
-    if not volume.is_cuda:
-        raise ValueError("mesh: volume must live on the GPU; this path has no CPU fallback")
+    _lib.check_device("mesh: volume must live on the GPU; this path has no CPU fallback", volume)
     lib = _lib.load()
     src = _lib.as_bytes(volume)
-    dt = CTU_F32 if field else (CTU_I64 if src.dtype == torch.int64 else CTU_U8)
+    dt = _lib.DTYPE_CODE[src.dtype]
     dev = volume.device
     c_sp, c_org = _lib.float_array(sp), _lib.float_array(org)
     ws = torch.empty(lib.ctu_mesh_ws_bytes(*shape), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_count(src.data_ptr(), dt, *shape, has_label, lab, lev, ws.data_ptr(), stream), "mesh_count")
+    with _lib.on(dev) as run:
+        run("ctu_mesh_count", src.data_ptr(), dt, *shape, has_label, lab, lev, ws.data_ptr())
         nv, nf = ws[:16].view(torch.int64).tolist()                     # the call's one host synchronisation
         if nv >= 1 << 31 or nf >= 1 << 31:
             raise ValueError(f"mesh: the surface has {nv} vertices and {nf} faces; both must stay below 2^31")
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        _lib.check(lib.ctu_mesh_emit(src.data_ptr(), dt, *shape, lev, fill, c_sp, c_org, nv, nf,
-                                     vertices.data_ptr() if nv else None, faces.data_ptr() if nf else None, ws.data_ptr(),
-                                     stream), "mesh_emit")
+        run("ctu_mesh_emit", src.data_ptr(), dt, *shape, lev, fill, c_sp, c_org, nv, nf, vertices.data_ptr() if nv else None,
+            faces.data_ptr() if nf else None, ws.data_ptr())
     return Mesh(vertices, faces)
 
 
 def _measure(m, want_normals: bool, who: str):
     v, f = _check_mesh(m, who)
-    if not v.is_cuda:
-        raise ValueError(f"mesh: {who} takes a mesh on the GPU; this path has no CPU fallback")
-    lib = _lib.load()
+    _lib.check_device(_ON_GPU.format(who), v)
     v, f = v.contiguous(), f.contiguous()
     out = torch.empty(2, dtype=torch.float64, device=v.device)
     normals = torch.empty((f.shape[0], 3), dtype=torch.float32, device=v.device) if want_normals else None
     ws = torch.empty(_MEASURE_WS, dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_measure(v.data_ptr() if v.shape[0] else None, v.shape[0],
-                                        f.data_ptr() if f.shape[0] else None, f.shape[0], out.data_ptr(),
-                                        normals.data_ptr() if want_normals and f.shape[0] else None, ws.data_ptr(), stream),
-                   "mesh_measure")
+    with _lib.on(v.device) as run:
+        run("ctu_mesh_measure", v.data_ptr() if v.shape[0] else None, v.shape[0], f.data_ptr() if f.shape[0] else None,
+            f.shape[0], out.data_ptr(), normals.data_ptr() if want_normals and f.shape[0] else None, ws.data_ptr())
     return out, normals
 
 
@@ -402,8 +364,7 @@ def adjacency(m: Mesh) -> Adjacency:
     on the device, never read through).  An empty mesh gives all-zero offsets and E = 0 without any launch."""
     v, f = _check_mesh(m, "adjacency")
     V, F = _check_sizes(v, f, "adjacency")
-    if not v.is_cuda:
-        raise ValueError("mesh: adjacency takes a mesh on the GPU; this path has no CPU fallback")
+    _lib.check_device(_ON_GPU.format("adjacency"), v)
     return _build_adjacency(f, V, F)
 
 
@@ -415,15 +376,13 @@ def _build_adjacency(f: torch.Tensor, V: int, F: int) -> Adjacency:
     f = f.contiguous()
     ws = torch.empty(lib.ctu_mesh_adjacency_ws_bytes(V, F), dtype=torch.uint8, device=dev)
     offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_adjacency_build(f.data_ptr(), V, F, offsets.data_ptr(), ws.data_ptr(), stream), "mesh_adjacency_build")
+    with _lib.on(dev) as run:
+        run("ctu_mesh_adjacency_build", f.data_ptr(), V, F, offsets.data_ptr(), ws.data_ptr())
         ne, bad = ws[:16].view(torch.int64).tolist()                    # the call's one host synchronisation
         if bad:
             raise ValueError(f"mesh: a face refers to a vertex that does not exist ({bad} of {F} faces hold an index outside [0, {V}))")
         neighbours = torch.empty(ne, dtype=torch.int32, device=dev)
-        _lib.check(lib.ctu_mesh_adjacency_emit(V, F, ne, offsets.data_ptr(), neighbours.data_ptr() if ne else None, ws.data_ptr(),
-                                               stream), "mesh_adjacency_emit")
+        run("ctu_mesh_adjacency_emit", V, F, ne, offsets.data_ptr(), neighbours.data_ptr() if ne else None, ws.data_ptr())
     return Adjacency(offsets, neighbours)
 
 
@@ -480,8 +439,7 @@ def smooth(m: Mesh, iterations: int = 10, lamb: float = 0.5, mu: Optional[float]
             raise ValueError(f"mesh: neighbours must have fewer than 2^31 entries, got {nb.shape[0]}")
         if off.device != v.device or nb.device != v.device:
             raise ValueError("mesh: the adjacency must live on the mesh's device")
-    if not v.is_cuda:
-        raise ValueError("mesh: smooth takes a mesh on the GPU; this path has no CPU fallback")
+    _lib.check_device(_ON_GPU.format("smooth"), v)
     off, nb = adjacency if adjacency is not None else _build_adjacency(f, V, F)
     lib = _lib.load()
     src, off, nb = v.contiguous(), off.contiguous(), nb.contiguous()
@@ -490,12 +448,10 @@ def smooth(m: Mesh, iterations: int = 10, lamb: float = 0.5, mu: Optional[float]
         fx = _lib.as_bytes(fixed)
     out = torch.empty((V, 3), dtype=torch.float32, device=v.device)
     ws = torch.empty(lib.ctu_mesh_smooth_ws_bytes(V), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_smooth(src.data_ptr() if V else None, V, off.data_ptr(), nb.data_ptr() if nb.shape[0] else None,
-                                       nb.shape[0], fx.data_ptr() if fx is not None and V else None, int(iterations), lam,
-                                       int(mu32 is not None), 0.0 if mu32 is None else mu32, out.data_ptr() if V else None,
-                                       ws.data_ptr(), stream), "mesh_smooth")
+    with _lib.on(v.device) as run:
+        run("ctu_mesh_smooth", src.data_ptr() if V else None, V, off.data_ptr(), nb.data_ptr() if nb.shape[0] else None,
+            nb.shape[0], fx.data_ptr() if fx is not None and V else None, int(iterations), lam, int(mu32 is not None),
+            0.0 if mu32 is None else mu32, out.data_ptr() if V else None, ws.data_ptr())
     return Mesh(out, f)
 
 
@@ -503,7 +459,7 @@ def voxelize_workspace_bytes(shape) -> int:
     """Device workspace (bytes) of one ``voxelize`` or ``winding_number`` call onto a (D, H, W) grid: the int32 delta volume
     (4 bytes per voxel, rounded up to 256) and 256 for the refused-face count; the only allocation besides the result and
     contiguous copies of non-contiguous inputs."""
-    return int(_lib.load().ctu_mesh_voxelize_ws_bytes(*_shape(shape)))
+    return int(_lib.load().ctu_mesh_voxelize_ws_bytes(*_args.grid(shape, _GRID)))
 
 
 def _voxelize(m, shape, spacing, origin, winding: bool, who: str) -> torch.Tensor:
@@ -511,10 +467,9 @@ def _voxelize(m, shape, spacing, origin, winding: bool, who: str) -> torch.Tenso
     V, F = v.shape[0], f.shape[0]
     if V >= 1 << 31 or F >= 1 << 31:
         raise ValueError(f"mesh: {who} takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
-    shape = _shape(shape)
-    sp, org = _spacing(spacing), _origin(origin)
-    if not v.is_cuda:
-        raise ValueError(f"mesh: {who} takes a mesh on the GPU; this path has no CPU fallback")
+    shape = _args.grid(shape, _GRID)
+    sp, org = _spacing(spacing), _args.triple(origin, _ORIGIN)
+    _lib.check_device(_ON_GPU.format(who), v)
     dev = v.device
     dtype = torch.int32 if winding else torch.uint8
     if F == 0:
@@ -523,10 +478,9 @@ def _voxelize(m, shape, spacing, origin, winding: bool, who: str) -> torch.Tenso
     v, f = v.contiguous(), f.contiguous()
     out = torch.empty(shape, dtype=dtype, device=dev)
     ws = torch.empty(lib.ctu_mesh_voxelize_ws_bytes(*shape), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_voxelize(v.data_ptr(), V, f.data_ptr(), F, *shape, _lib.float_array(sp), _lib.float_array(org),
-                                         int(winding), out.data_ptr(), ws.data_ptr(), stream), "mesh_voxelize")
+    with _lib.on(dev) as run:
+        run("ctu_mesh_voxelize", v.data_ptr(), V, f.data_ptr(), F, *shape, _lib.float_array(sp), _lib.float_array(org),
+            int(winding), out.data_ptr(), ws.data_ptr())
         bad = int(ws[:8].view(torch.int64).item())                      # the call's one host synchronisation
     if bad:
         raise ValueError(f"mesh: a face refers to a vertex that does not exist or is not finite ({bad} of {F} faces hold an "
@@ -601,8 +555,7 @@ def build_face_grid(m: Mesh, cell_size: Optional[float] = None) -> FaceGrid:
     if V >= 1 << 31 or F >= 1 << 31:
         raise ValueError(f"mesh: build_face_grid takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
     size = _cell_size(cell_size)
-    if not v.is_cuda:
-        raise ValueError("mesh: build_face_grid takes a mesh on the GPU; this path has no CPU fallback")
+    _lib.check_device(_ON_GPU.format("build_face_grid"), v)
     dev = v.device
     if F == 0:
         return _empty_grid(dev)
@@ -611,10 +564,8 @@ def build_face_grid(m: Mesh, cell_size: Optional[float] = None) -> FaceGrid:
     cap = _max_cells(F)
     corners = torch.empty((F, 12), dtype=torch.float32, device=dev)
     ws = torch.empty(lib.ctu_mesh_grid_ws_bytes(F, cap), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_grid_build(v.data_ptr(), V, f.data_ptr(), F, size, cap, corners.data_ptr(), ws.data_ptr(), stream),
-                   "mesh_grid_build")
+    with _lib.on(dev) as run:
+        run("ctu_mesh_grid_build", v.data_ptr(), V, f.data_ptr(), F, size, cap, corners.data_ptr(), ws.data_ptr())
         head = ws[:104].cpu()                                           # the call's one host synchronisation
         pairs, bad, cells, overflow, nz, ny, nx = head[:56].view(torch.int64).tolist()
         lo_h = head[56:104].view(torch.float64).tolist()
@@ -628,8 +579,8 @@ def build_face_grid(m: Mesh, cell_size: Optional[float] = None) -> FaceGrid:
         offsets = torch.empty(cells + 1, dtype=torch.int32, device=dev)
         items = torch.empty(pairs, dtype=torch.int32, device=dev)
         frame = ws[56:104].view(torch.float64).clone()
-        _lib.check(lib.ctu_mesh_grid_emit(corners.data_ptr(), F, cap, cells, pairs, offsets.data_ptr(),
-                                          items.data_ptr() if pairs else None, ws.data_ptr(), stream), "mesh_grid_emit")
+        run("ctu_mesh_grid_emit", corners.data_ptr(), F, cap, cells, pairs, offsets.data_ptr(),
+            items.data_ptr() if pairs else None, ws.data_ptr())
     return FaceGrid(offsets, items, corners, frame, (nz, ny, nx), lo_h[3])
 
 
@@ -673,7 +624,6 @@ def _max_distance(max_distance, who: str, required: bool) -> float:
 
 
 def _query(g: FaceGrid, F: int, points, shape, sp, org, md: float, far: float, want_faces: bool, want_points: bool, dev):
-    lib = _lib.load()
     Q = points.shape[0] if points is not None else shape[0] * shape[1] * shape[2]
     dist = torch.empty(Q, dtype=torch.float32, device=dev)
     faces = torch.empty(Q, dtype=torch.int32, device=dev) if want_faces else None
@@ -689,14 +639,12 @@ def _query(g: FaceGrid, F: int, points, shape, sp, org, md: float, far: float, w
         if closest is not None:
             closest.fill_(float("nan"))
         return dist, faces, closest
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_mesh_distance(g.corners.data_ptr(), F, g.offsets.data_ptr(), g.faces.data_ptr() if g.faces.shape[0] else None,
-                                         g.faces.shape[0], g.frame.data_ptr(), *g.dims,
-                                         points.data_ptr() if points is not None else None, Q if points is not None else 0,
-                                         *(shape if points is None else (0, 0, 0)), _lib.float_array(sp), _lib.float_array(org), md, far,
-                                         dist.data_ptr(), faces.data_ptr() if want_faces else None,
-                                         closest.data_ptr() if want_points else None, stream), "mesh_distance")
+    with _lib.on(dev) as run:
+        run("ctu_mesh_distance", g.corners.data_ptr(), F, g.offsets.data_ptr(), g.faces.data_ptr() if g.faces.shape[0] else None,
+            g.faces.shape[0], g.frame.data_ptr(), *g.dims, points.data_ptr() if points is not None else None,
+            Q if points is not None else 0, *(shape if points is None else (0, 0, 0)), _lib.float_array(sp),
+            _lib.float_array(org), md, far, dist.data_ptr(), faces.data_ptr() if want_faces else None,
+            closest.data_ptr() if want_points else None)
     return dist, faces, closest
 
 
@@ -729,8 +677,7 @@ def point_distance(points: torch.Tensor, m: Mesh, max_distance: Optional[float] 
     _cell_size(cell_size)
     if grid is not None:
         grid = _check_grid(grid, F, v.device)
-    if not v.is_cuda:
-        raise ValueError("mesh: point_distance takes a mesh on the GPU; this path has no CPU fallback")
+    _lib.check_device(_ON_GPU.format("point_distance"), v)
     g = grid if grid is not None else build_face_grid(m, cell_size)
     dist, faces, closest = _query(g, F, points.contiguous(), None, None, None, md, float("inf"), bool(return_faces),
                                   bool(return_points), v.device)
@@ -756,15 +703,14 @@ def distance_field(m: Mesh, shape, spacing=None, origin=None, max_distance=_REQU
     V, F = v.shape[0], f.shape[0]
     if V >= 1 << 31 or F >= 1 << 31:
         raise ValueError(f"mesh: distance_field takes V < 2^31 vertices and F < 2^31 faces, got V = {V}, F = {F}")
-    shape = _shape(shape)
-    sp, org = _spacing(spacing), _origin(origin)
+    shape = _args.grid(shape, _GRID)
+    sp, org = _spacing(spacing), _args.triple(origin, _ORIGIN)
     if max_distance is _REQUIRED:
         raise ValueError("mesh: distance_field takes a max_distance (a whole grid has far voxels; the field is truncated there)")
     md = _max_distance(max_distance, "distance_field", True)
     if grid is not None:
         grid = _check_grid(grid, F, v.device)
-    if not v.is_cuda:
-        raise ValueError("mesh: distance_field takes a mesh on the GPU; this path has no CPU fallback")
+    _lib.check_device(_ON_GPU.format("distance_field"), v)
     g = grid if grid is not None else build_face_grid(m)
     dist, _, _ = _query(g, F, None, shape, sp, org, md, md, False, False, v.device)
     out = dist.view(shape)

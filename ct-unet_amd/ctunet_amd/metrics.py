@@ -39,38 +39,39 @@ from . import _lib
 
 MAX_CLASSES = 16
 MAX_SIDE = 1024
-CTU_F32, CTU_U8, CTU_I64 = 0, 3, 4
+_ON_GPU = "metrics: inputs must live on the GPU; this path has no CPU fallback"
 # rows of the kernel's output block
 _DICE, _HD, _HD_DIR, _HDP, _HDP_DIR, _ASSD, _ASD_DIR, _NSD = range(8)
 
 
 def _positive(v, what: str) -> float:
     if isinstance(v, bool) or not isinstance(v, Real):
-        raise ValueError(f"metrics: {what} must be a real number, got {v!r}")
+        raise ValueError(f"{what} must be a real number, got {v!r}")
     v = float(v)
     if not (math.isfinite(v) and v > 0.0):
-        raise ValueError(f"metrics: {what} must be positive and finite, got {v!r}")
+        raise ValueError(f"{what} must be positive and finite, got {v!r}")
     return v
 
 
-def parse_spacing(spacing, n: int) -> Optional[List[List[float]]]:
-    """None -> None (unit spacing); one number, a (D, H, W) triple or N triples -> N lists of three positive floats."""
+def parse_spacing(spacing, n: int, what: str = "metrics: spacing") -> Optional[List[List[float]]]:
+    """None -> None (unit spacing); one number, a (D, H, W) triple or N triples -> N lists of three positive floats.
+    ``what`` names the argument in a refusal (``postprocess`` and ``mesh`` parse their own through this)."""
     if spacing is None:
         return None
     if isinstance(spacing, torch.Tensor):
         spacing = spacing.tolist()
     if isinstance(spacing, Real) and not isinstance(spacing, bool):
-        s = _positive(spacing, "spacing")
+        s = _positive(spacing, what)
         return [[s, s, s] for _ in range(n)]
     if not isinstance(spacing, (list, tuple)) and not hasattr(spacing, "__len__"):
-        raise ValueError(f"metrics: spacing must be a number, a 3-sequence or N 3-sequences, got {spacing!r}")
+        raise ValueError(f"{what} must be a number, a 3-sequence or N 3-sequences, got {spacing!r}")
     items = list(spacing)
     if len(items) == 3 and all(isinstance(v, Real) for v in items):
-        t = [_positive(v, "spacing") for v in items]
+        t = [_positive(v, what) for v in items]
         return [list(t) for _ in range(n)]
     if len(items) == n and all(hasattr(v, "__len__") and len(v) == 3 for v in items):
-        return [[_positive(v, "spacing") for v in t] for t in items]
-    raise ValueError(f"metrics: spacing must be a number, a (D, H, W) triple or {n} such triples, got {spacing!r}")
+        return [[_positive(v, what) for v in t] for t in items]
+    raise ValueError(f"{what} must be a number, a (D, H, W) triple or {n} such triples, got {spacing!r}")
 
 
 def _check_metric(distance_metric) -> None:
@@ -101,10 +102,9 @@ def _thresholds(values, cs: int, what: str) -> List[float]:
 
 
 def _dtype_code(t: torch.Tensor, allowed, what: str) -> int:
-    codes = {torch.float32: CTU_F32, torch.uint8: CTU_U8, torch.bool: CTU_U8, torch.int64: CTU_I64}
     if t.dtype not in allowed:
         raise ValueError(f"metrics: {what} must be one of {', '.join(str(a) for a in allowed)}, got {t.dtype}")
-    return codes[t.dtype]
+    return _lib.DTYPE_CODE[t.dtype]
 
 
 def _check_sides(shape) -> None:
@@ -115,20 +115,16 @@ def _check_sides(shape) -> None:
 def _run(a: torch.Tensor, a_code: int, a_onehot: bool, b: torch.Tensor, b_code: int, b_onehot: bool, n: int, c: int,
          cls0: int, shape, spacing, tau, percentile) -> torch.Tensor:
     """float32 [8, n, Cs] rows of the kernel's output block (see include/ctunet_hip.h)."""
-    import ctypes
     cs = c - cls0
     d, h, w = shape
     lib = _lib.load()
     a, b = _lib.as_bytes(a), _lib.as_bytes(b)
     sp = None if spacing is None else _lib.float_array(v for t in spacing for v in t)
-    tau_arr = (ctypes.c_double * cs)(*tau) if tau is not None else None
     ws = torch.empty(lib.ctu_surface_ws_bytes(n, cs, d, h, w), dtype=torch.uint8, device=a.device)
     out = torch.empty((8, n, cs), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_surface_metrics(a.data_ptr(), a_code, int(a_onehot), b.data_ptr(), b_code, int(b_onehot), n, c,
-                                           cls0, cs, d, h, w, sp, tau_arr, -1.0 if percentile is None else percentile,
-                                           out.data_ptr(), ws.data_ptr(), stream), "surface_metrics")
+    with _lib.on(a.device) as run:
+        run("ctu_surface_metrics", a.data_ptr(), a_code, int(a_onehot), b.data_ptr(), b_code, int(b_onehot), n, c, cls0, cs,
+            d, h, w, sp, _lib.double_array(tau), -1.0 if percentile is None else percentile, out.data_ptr(), ws.data_ptr())
     return out
 
 
@@ -156,7 +152,7 @@ def compute_hausdorff_distance(y_pred: torch.Tensor, y: torch.Tensor, include_ba
     pct = _check_percentile(percentile)
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     sp = parse_spacing(spacing, n)
-    _lib.check_device("metrics", y_pred, y)
+    _lib.check_device(_ON_GPU, y_pred, y)
     out = _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, None, pct)
     if pct is None:
         return out[_HD_DIR if directed else _HD]
@@ -170,7 +166,7 @@ def compute_average_surface_distance(y_pred: torch.Tensor, y: torch.Tensor, incl
     _check_metric(distance_metric)
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     sp = parse_spacing(spacing, n)
-    _lib.check_device("metrics", y_pred, y)
+    _lib.check_device(_ON_GPU, y_pred, y)
     out = _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, None, None)
     return out[_ASSD if symmetric else _ASD_DIR]
 
@@ -187,7 +183,7 @@ def compute_surface_dice(y_pred: torch.Tensor, y: torch.Tensor, class_thresholds
     n, c, cls0, ca, cb = _onehot_inputs(y_pred, y, include_background)
     tau = _thresholds(class_thresholds, c - cls0, "class_thresholds")
     sp = parse_spacing(spacing, n)
-    _lib.check_device("metrics", y_pred, y)
+    _lib.check_device(_ON_GPU, y_pred, y)
     return _run(y_pred, ca, True, y, cb, True, n, c, cls0, y.shape[2:], sp, tau, None)[_NSD]
 
 
@@ -218,7 +214,7 @@ def surface_metrics(pred_labels: torch.Tensor, target_labels: torch.Tensor, num_
     allowed = (torch.uint8, torch.int64)
     ca, cb = _dtype_code(pred_labels, allowed, "pred_labels"), _dtype_code(target_labels, allowed, "target_labels")
     sp = parse_spacing(spacing, n)
-    _lib.check_device("metrics", pred_labels, target_labels)
+    _lib.check_device(_ON_GPU, pred_labels, target_labels)
     out = _run(pred_labels, ca, False, target_labels, cb, False, n, num_classes, cls0, shape, sp, tau, pct)
     res = {"dice": out[_DICE], "hd": out[_HD], "hd_p": out[_HDP], "assd": out[_ASSD]}
     if tau is not None:
@@ -261,8 +257,7 @@ def mesh_surface_metrics(a, b, percentile: Optional[float] = 95.0, tolerance: Op
     vb, fb = _mesh._check_mesh(b, "mesh_surface_metrics")
     if va.device != vb.device:
         raise ValueError(f"metrics: the meshes live on different devices: {va.device} and {vb.device}")
-    if not va.is_cuda:
-        raise ValueError("metrics: mesh_surface_metrics takes meshes on the GPU; this path has no CPU fallback")
+    _lib.check_device("metrics: mesh_surface_metrics takes meshes on the GPU; this path has no CPU fallback", va)
     dev = va.device
     empty_a, empty_b = va.shape[0] == 0 or fa.shape[0] == 0, vb.shape[0] == 0 or fb.shape[0] == 0
     nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)

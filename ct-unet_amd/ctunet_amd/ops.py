@@ -1350,8 +1350,7 @@ def flap_apply(skulls: torch.Tensor, atlas: Optional[torch.Tensor], params: torc
 
 
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_LABEL_LINEAR = 0, 1, 2          # CTU_RESAMPLE_* of ctunet_hip.h
-# dtype codes of ctu_resample (CTU_F32 / CTU_U8 / CTU_I64 / CTU_I16 / CTU_I32); bool travels as uint8
-RESAMPLE_CODE = {torch.float32: 0, torch.uint8: 3, torch.bool: 3, torch.int64: 4, torch.int16: 5, torch.int32: 6}
+RESAMPLE_CODE = _lib.DTYPE_CODE              # the dtype codes of ctu_resample
 
 
 def resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n: int, in_shape: Tuple[int, int, int],
@@ -1372,12 +1371,6 @@ def resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n:
                "resample")
 
 
-def _double3(v):
-    """A host double [3] for a ``const double*`` argument (None stays None: the entry point's default)."""
-    import ctypes
-    return None if v is None else (ctypes.c_double * 3)(*v)
-
-
 def affine_resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: int, n: int, in_shape: Tuple[int, int, int],
                     out_shape: Tuple[int, int, int], matrix: torch.Tensor, spacing, origin, out_spacing, out_origin,
                     fill: float) -> None:
@@ -1391,9 +1384,9 @@ def affine_resample(x: torch.Tensor, out: torch.Tensor, mode: int, num_classes: 
     assert x.numel() == n * d0 * h0 * w0 and out.numel() == n * d1 * h1 * w1, "affine_resample shapes"
     assert matrix.dtype == torch.float64 and matrix.numel() in (12, 16), "affine_resample matrix"
     _lib.check(_lib.load().ctu_affine_resample(x.data_ptr(), RESAMPLE_CODE[x.dtype], mode, num_classes, n, d0, h0, w0, d1, h1,
-                                               w1, matrix.data_ptr(), _double3(spacing), _double3(origin),
-                                               _double3(out_spacing), _double3(out_origin), float(fill), out.data_ptr(),
-                                               _stream()), "affine_resample")
+                                               w1, matrix.data_ptr(), _lib.double_array(spacing), _lib.double_array(origin),
+                                               _lib.double_array(out_spacing), _lib.double_array(out_origin), float(fill),
+                                               out.data_ptr(), _stream()), "affine_resample")
 
 
 SPATIAL_RECORD = 26                              # CTU_SPATIAL_RECORD of ctunet_hip.h
@@ -1410,12 +1403,11 @@ def spatial_draw(n: int, shape: Tuple[int, int, int], spacing, seq: torch.Tensor
                  control: torch.Tensor) -> None:
     """record float64 [N, SPATIAL_RECORD] and control float64 [N, 3, Gz, Gy, Gx] of N samples, drawn from the device counter
     seq (layout and rule: ctunet_hip.h, transforms.py).  ranges: the 11 host doubles of ctu_spatial_draw.  One launch."""
-    import ctypes
     _spatial_buffers(n, grid, record, control)
     assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1 and len(ranges) == 11
-    _lib.check(_lib.load().ctu_spatial_draw(n, shape[0], shape[1], shape[2], _double3(spacing), seq.data_ptr(), seed,
+    _lib.check(_lib.load().ctu_spatial_draw(n, shape[0], shape[1], shape[2], _lib.double_array(spacing), seq.data_ptr(), seed,
                                             flip_mask, float(flip_p), float(affine_p), float(elastic_p),
-                                            (ctypes.c_double * 11)(*ranges), grid[0], grid[1], grid[2], locked,
+                                            _lib.double_array(ranges), grid[0], grid[1], grid[2], locked,
                                             record.data_ptr(), control.data_ptr(), _stream()), "spatial_draw")
 
 
@@ -1431,6 +1423,6 @@ def spatial_warp(x: torch.Tensor, out: torch.Tensor, spacing, grid: Tuple[int, i
     n, c, d, h, w = x.shape
     _spatial_buffers(n, grid, record, control)
     assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1
-    _lib.check(_lib.load().ctu_spatial_warp(x.data_ptr(), RESAMPLE_CODE[x.dtype], n, c, d, h, w, _double3(spacing), grid[0],
-                                            grid[1], grid[2], record.data_ptr(), control.data_ptr(), seq.data_ptr(),
+    _lib.check(_lib.load().ctu_spatial_warp(x.data_ptr(), RESAMPLE_CODE[x.dtype], n, c, d, h, w, _lib.double_array(spacing),
+                                            grid[0], grid[1], grid[2], record.data_ptr(), control.data_ptr(), seq.data_ptr(),
                                             out.data_ptr(), _stream()), "spatial_warp")

@@ -77,6 +77,7 @@ is copied to the host to form its 27-bit code, which synchronises and is refused
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from numbers import Integral, Real
 from typing import Optional, Sequence, Tuple
@@ -84,6 +85,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .metrics import parse_spacing
 
 MAX_APPLIED = 16
 MAX_COMPONENTS = 8
@@ -91,7 +93,7 @@ MAX_ITERATIONS = 64
 _ERODE, _DILATE, _OPEN, _CLOSE = 0, 1, 2, 3
 _WS_MORPH, _WS_FILL, _WS_IMPLANT = 0, 1, 2
 _MASK_DTYPES = (torch.bool, torch.uint8, torch.int64)
-CTU_U8, CTU_I64 = 3, 4
+_ON_GPU = "postprocess: inputs must live on the GPU; this path has no CPU fallback"
 _LARGEST, _MIN_SIZE = 0, 1
 
 
@@ -139,13 +141,6 @@ def _ws(lib, n, shape, device) -> torch.Tensor:
     return torch.empty(lib.ctu_components_ws_bytes(n, *shape), dtype=torch.uint8, device=device)
 
 
-def _host_labels(vals):
-    import ctypes
-    if not vals:
-        return None, 0
-    return (ctypes.c_int64 * len(vals))(*vals), len(vals)
-
-
 def label(mask: torch.Tensor, connectivity: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
     """Connected components of a bool or uint8 mask [D,H,W] or [N,D,H,W] (nonzero = foreground).
 
@@ -154,32 +149,28 @@ def label(mask: torch.Tensor, connectivity: int = 3) -> Tuple[torch.Tensor, torc
     """
     n, shape = _volume(mask, "mask", (torch.bool, torch.uint8))
     conn = _connectivity(connectivity)
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     lib = _lib.load()
     m = mask.contiguous()
     m = m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).view(torch.uint8)
     labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
     num = torch.empty(n, dtype=torch.int32, device=mask.device)
     ws = _ws(lib, n, shape, mask.device)
-    with torch.cuda.device(mask.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_label_components(m.data_ptr(), CTU_U8, n, *shape, conn, None, 0, labels.data_ptr(),
-                                            num.data_ptr(), ws.data_ptr(), stream), "label_components")
+    with _lib.on(mask.device) as run:
+        run("ctu_label_components", m.data_ptr(), _lib.DTYPE_CODE[m.dtype], n, *shape, conn, None, 0, labels.data_ptr(),
+            num.data_ptr(), ws.data_ptr())
     return labels, num
 
 
 def _filter(labels: torch.Tensor, mode: int, param: int, applied, conn: int, n: int, shape) -> torch.Tensor:
-    _lib.check_device("postprocess", labels)
+    _lib.check_device(_ON_GPU, labels)
     lib = _lib.load()
     src = labels.contiguous()
     out = torch.empty_like(src)
-    al, nal = _host_labels(applied)
     ws = _ws(lib, n, shape, labels.device)
-    code = CTU_U8 if src.dtype == torch.uint8 else CTU_I64
-    with torch.cuda.device(labels.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_filter_components(src.data_ptr(), code, n, *shape, conn, al, nal, mode, param, out.data_ptr(),
-                                             ws.data_ptr(), stream), "filter_components")
+    with _lib.on(labels.device) as run:
+        run("ctu_filter_components", src.data_ptr(), _lib.DTYPE_CODE[src.dtype], n, *shape, conn,
+            _lib.array(C.c_int64, applied or None), len(applied or ()), mode, param, out.data_ptr(), ws.data_ptr())
     return out
 
 
@@ -259,12 +250,6 @@ def _label_arg(label):
     return 1, int(label)
 
 
-def _as_bytes(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
-    """The contiguous tensor the kernels read (bool viewed as uint8) and its dtype code."""
-    t = _lib.as_bytes(t)
-    return t, (CTU_I64 if t.dtype == torch.int64 else CTU_U8)
-
-
 def _mask_out(src: torch.Tensor) -> torch.Tensor:
     return torch.empty(src.shape, dtype=torch.uint8, device=src.device)
 
@@ -279,15 +264,14 @@ def _morphology(mask, mode: int, structure, iterations, border_value, label) -> 
     it = _iterations(iterations)
     border = _border(border_value)
     has_label, lab = _label_arg(label)
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     lib = _lib.load()
-    src, dt = _as_bytes(mask)
+    src = _lib.as_bytes(mask)
     out = _mask_out(mask)
     ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_MORPH), dtype=torch.uint8, device=mask.device)
-    with torch.cuda.device(mask.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_binary_morphology(src.data_ptr(), dt, n, *shape, mode, code, it, border, has_label, lab,
-                                             out.data_ptr(), ws.data_ptr(), stream), "binary_morphology")
+    with _lib.on(mask.device) as run:
+        run("ctu_binary_morphology", src.data_ptr(), _lib.DTYPE_CODE[src.dtype], n, *shape, mode, code, it, border, has_label,
+            lab, out.data_ptr(), ws.data_ptr())
     return _finish(out, mask)
 
 
@@ -319,15 +303,14 @@ def binary_fill_holes(mask: torch.Tensor, connectivity: int = 1, label: Optional
     n, shape = _volume(mask, "mask", _MASK_DTYPES)
     conn = _connectivity(connectivity)
     has_label, lab = _label_arg(label)
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     lib = _lib.load()
-    src, dt = _as_bytes(mask)
+    src = _lib.as_bytes(mask)
     out = _mask_out(mask)
     ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_FILL), dtype=torch.uint8, device=mask.device)
-    with torch.cuda.device(mask.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_fill_holes(src.data_ptr(), dt, n, *shape, conn, has_label, lab, out.data_ptr(), ws.data_ptr(),
-                                      stream), "fill_holes")
+    with _lib.on(mask.device) as run:
+        run("ctu_fill_holes", src.data_ptr(), _lib.DTYPE_CODE[src.dtype], n, *shape, conn, has_label, lab, out.data_ptr(),
+            ws.data_ptr())
     return _finish(out, mask)
 
 
@@ -359,7 +342,7 @@ def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, ope
         _distance_sides(shape)
         r2 = _radius2(opening_radius, "opening_radius")
         spacing = _sampling(sampling, n)
-    _lib.check_device("postprocess", full_skull, defective_skull)
+    _lib.check_device(_ON_GPU, full_skull, defective_skull)
     if full_skull.device != defective_skull.device:
         raise ValueError("postprocess: full_skull and defective_skull must live on the same GPU")
     if opening_radius is not None:
@@ -370,14 +353,12 @@ def extract_implant(full_skull: torch.Tensor, defective_skull: torch.Tensor, ope
             m = binary_fill_holes(m, 1)
         return keep_largest_connected_component(m, connectivity=conn, num_components=int(num_components))
     lib = _lib.load()
-    a, da = _as_bytes(full_skull)
-    b, db = _as_bytes(defective_skull)
+    a, b = _lib.as_bytes(full_skull), _lib.as_bytes(defective_skull)
     out = _mask_out(full_skull)
     ws = torch.empty(lib.ctu_morphology_ws_bytes(n, *shape, _WS_IMPLANT), dtype=torch.uint8, device=full_skull.device)
-    with torch.cuda.device(full_skull.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_implant_mask(a.data_ptr(), da, b.data_ptr(), db, n, *shape, code, it, int(bool(fill_holes)), conn,
-                                        int(num_components), out.data_ptr(), ws.data_ptr(), stream), "implant_mask")
+    with _lib.on(full_skull.device) as run:
+        run("ctu_implant_mask", a.data_ptr(), _lib.DTYPE_CODE[a.dtype], b.data_ptr(), _lib.DTYPE_CODE[b.dtype], n, *shape, code,
+            it, int(bool(fill_holes)), conn, int(num_components), out.data_ptr(), ws.data_ptr())
     return out
 
 
@@ -400,13 +381,8 @@ def _distance_sides(shape) -> None:
 
 def _sampling(sampling, n: int):
     """None for unit sampling (the exact int32 path), else N (z, y, x) triples."""
-    from .metrics import parse_spacing
-    import ctypes
-    try:
-        sp = parse_spacing(sampling, n)
-    except ValueError as e:
-        raise ValueError(str(e).replace("metrics: spacing", "postprocess: sampling")) from e
-    if sp is None or all(ctypes.c_float(v).value == 1.0 for t in sp for v in t):
+    sp = parse_spacing(sampling, n, "postprocess: sampling")
+    if sp is None or all(C.c_float(v).value == 1.0 for t in sp for v in t):
         return None
     return sp
 
@@ -429,7 +405,7 @@ def _flag(v, what: str) -> bool:
 def _distance(mask, n, shape, kind: int, spacing, has_label: int, lab: int, invert: int, border: int, want_indices: bool,
               r2: float = -1.0):
     lib = _lib.load()
-    src, dt = _as_bytes(mask)
+    src = _lib.as_bytes(mask)
     dev = mask.device
     unit = spacing is None
     if kind == _DIST_BALL:
@@ -441,11 +417,9 @@ def _distance(mask, n, shape, kind: int, spacing, has_label: int, lab: int, inve
         idx = torch.empty(tuple(mask.shape[:-3]) + (3,) + tuple(shape), dtype=torch.int32, device=dev)
     sp = None if unit else _lib.float_array(v for t in spacing for v in t)
     ws = torch.empty(lib.ctu_distance_ws_bytes(n, *shape, kind, int(want_indices)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_distance_transform(src.data_ptr(), dt, n, *shape, has_label, lab, invert, border, sp, kind,
-                                              out.data_ptr(), idx.data_ptr() if want_indices else None, r2, ws.data_ptr(),
-                                              stream), "distance_transform")
+    with _lib.on(dev) as run:
+        run("ctu_distance_transform", src.data_ptr(), _lib.DTYPE_CODE[src.dtype], n, *shape, has_label, lab, invert, border, sp,
+            kind, out.data_ptr(), idx.data_ptr() if want_indices else None, r2, ws.data_ptr())
     return out, idx
 
 
@@ -462,7 +436,7 @@ def distance_transform_edt(mask: torch.Tensor, sampling=None, return_distances: 
         _flag(squared, "squared")
     if not (want_d or want_i):
         raise ValueError("postprocess: at least one of return_distances and return_indices must be true")
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     out, idx = _distance(mask, n, shape, _DIST_SQUARED if sq else _DIST_EDT, sp, has_label, lab, 0, 0, want_i)
     if want_d and want_i:
         return out, idx
@@ -476,7 +450,7 @@ def signed_distance(mask: torch.Tensor, sampling=None, label: Optional[int] = No
     _distance_sides(shape)
     sp = _sampling(sampling, n)
     has_label, lab = _label_arg(label)
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     return _distance(mask, n, shape, _DIST_SIGNED, sp, has_label, lab, 0, 0, False)[0]
 
 
@@ -494,7 +468,7 @@ def _ball_op(mask, modes, radius, sampling, label) -> torch.Tensor:
     r2 = _radius2(radius)
     sp = _sampling(sampling, n)
     has_label, lab = _label_arg(label)
-    _lib.check_device("postprocess", mask)
+    _lib.check_device(_ON_GPU, mask)
     out = _ball(mask, modes[0], r2, sp, has_label, lab)
     for mode in modes[1:]:
         out = _ball(out, mode, r2, sp)

@@ -60,19 +60,25 @@ from __future__ import annotations
 import ctypes as C
 import math
 from numbers import Integral, Real
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MODES = ("nearest", "reflect", "constant")
 MAX_RADIUS = 32              # CTU_GAUSS_MAX_RADIUS
 MAX_SIDE = 1024
 MAX_BINS = 4096              # CTU_HISTOGRAM_MAX_BINS
 _DTYPES = (torch.float32, torch.int16, torch.uint8)
-_CODE = {torch.float32: 0, torch.int16: 5, torch.uint8: 3}          # CTU_F32 / CTU_I16 / CTU_U8
+_NOT_NEGATIVE = _args.Triple(shape="{who}: {what} must be a number or a (z, y, x) triple, got {v!r}",
+                             value="{who}: {what} must be finite and not negative, got {v!r}", sign=_args.NOT_NEGATIVE,
+                             optional=False, tensors=False)
+_POSITIVE = _NOT_NEGATIVE._replace(value="{who}: {what} must be finite and positive, got {v!r}", sign=_args.POSITIVE)
+# MAX_SIDE^3 is below 2^31, so the sides bound the voxels too
+_GRID = _args.Grid(side=f"{{who}}: every side may be at most {MAX_SIDE}, got {{vals}}", max_side=MAX_SIDE, max_voxels=None)
+_ON_GPU = "{}: the input must live on the GPU; this path has no CPU fallback"
 
 
 def _check_input(x, who: str, volume: bool) -> None:
@@ -84,40 +90,6 @@ def _check_input(x, who: str, volume: bool) -> None:
         raise ValueError(f"{who}: the input needs at least the three dimensions (D, H, W), got shape {tuple(x.shape)}")
     if x.numel() < 1:
         raise ValueError(f"{who}: the input is empty, got shape {tuple(x.shape)}")
-
-
-def _triple(v, what: str, who: str, positive: bool) -> Tuple[float, float, float]:
-    if isinstance(v, Real) and not isinstance(v, bool):
-        vals = (v, v, v)
-    else:
-        try:
-            vals = tuple(v)
-        except TypeError:
-            raise ValueError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}") from None
-        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
-            raise ValueError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}")
-    if any(not math.isfinite(s) or s < 0 or (positive and s <= 0) for s in vals):
-        raise ValueError(f"{who}: {what} must be finite and {'positive' if positive else 'not negative'}, got {v!r}")
-    return tuple(float(s) for s in vals)
-
-
-def _check_out(out, shape, dtype, device, who: str) -> None:
-    if out is None:
-        return
-    if not isinstance(out, torch.Tensor):
-        raise ValueError(f"{who}: out must be a tensor, got {type(out).__name__}")
-    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
-        raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
-                         f"{out.dtype} {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', not contiguous'}")
-
-
-def _need_gpu(x, who: str) -> None:
-    if not x.is_cuda:
-        raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gaussian_weights(sigma_vox: float, truncate: float = 4.0) -> np.ndarray:
@@ -135,9 +107,9 @@ def gaussian_filter(x: torch.Tensor, sigma, *, spacing=None, truncate: float = 4
     """float32 Gaussian filter of ``x [..., D, H, W]`` (float32, int16 or uint8); the rule is the module docstring's."""
     who = "gaussian_filter"
     _check_input(x, who, True)
-    sig = _triple(sigma, "sigma", who, False)
+    sig = _args.triple(sigma, _NOT_NEGATIVE, who=who, what="sigma")
     if spacing is not None:
-        sp = _triple(spacing, "spacing", who, True)
+        sp = _args.triple(spacing, _POSITIVE, who=who, what="spacing")
         sig = tuple(s / q for s, q in zip(sig, sp))
     if isinstance(truncate, bool) or not isinstance(truncate, Real) or not math.isfinite(truncate) or truncate < 0:
         raise ValueError(f"{who}: truncate must be a finite number >= 0, got {truncate!r}")
@@ -149,13 +121,9 @@ def gaussian_filter(x: torch.Tensor, sigma, *, spacing=None, truncate: float = 4
     if any(r > MAX_RADIUS for r in radius):
         raise ValueError(f"{who}: the radius int(truncate * sigma + 0.5) of an axis may be at most {MAX_RADIUS} voxels, got "
                          f"{radius} (z, y, x) from sigma {sig} voxels")
-    shape = tuple(int(s) for s in x.shape[-3:])
-    if any(s > MAX_SIDE for s in shape):
-        raise ValueError(f"{who}: every side may be at most {MAX_SIDE}, got {shape}")
-    if shape[0] * shape[1] * shape[2] >= 1 << 31:
-        raise ValueError(f"{who}: a volume must hold fewer than 2^31 voxels, got {shape}")
-    _check_out(out, x.shape, torch.float32, x.device, who)
-    _need_gpu(x, who)
+    shape = _args.grid(x.shape[-3:], _GRID, who=who)
+    _args.check_out(out, x.shape, torch.float32, x.device, who)
+    _lib.check_device(_ON_GPU.format(who), x)
     weights = np.concatenate([gaussian_weights(s, float(truncate)) for s in sig])
     assert weights.size == sum(radius) + 3
     lib = _lib.load()
@@ -165,10 +133,10 @@ def gaussian_filter(x: torch.Tensor, sigma, *, spacing=None, truncate: float = 4
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     nbytes = int(lib.ctu_gaussian_ws_bytes(n, *shape, radius[0]))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    with torch.cuda.device(x.device):
-        _lib.check(lib.ctu_gaussian_filter(src.data_ptr(), _CODE[x.dtype], n, *shape, (C.c_int * 3)(*radius),
-                                           (C.c_float * weights.size)(*weights.tolist()), MODES.index(mode), float(cval),
-                                           out.data_ptr(), ws.data_ptr() if nbytes else None, _stream()), who)
+    with _lib.on(x.device) as run:
+        run("ctu_gaussian_filter", src.data_ptr(), _lib.DTYPE_CODE[x.dtype], n, *shape, _lib.array(C.c_int, radius),
+            _lib.float_array(weights.tolist()), MODES.index(mode), float(cval), out.data_ptr(),
+            ws.data_ptr() if nbytes else None, what=who)
     return out
 
 
@@ -200,33 +168,31 @@ def finite_range(x: torch.Tensor) -> torch.Tensor:
     """float64 ``[2]`` DEVICE tensor: the smallest and the largest finite value of ``x`` (``+inf, -inf`` without one)."""
     who = "finite_range"
     _check_input(x, who, False)
-    _need_gpu(x, who)
+    _lib.check_device(_ON_GPU.format(who), x)
     lib = _lib.load()
     src = x.contiguous()
     rng = torch.empty(2, dtype=torch.float64, device=x.device)
     ws = torch.empty(int(lib.ctu_minmax_ws_bytes(src.numel())), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.ctu_finite_minmax(src.data_ptr(), _CODE[x.dtype], src.numel(), rng.data_ptr(), ws.data_ptr(),
-                                         _stream()), who)
+    with _lib.on(x.device) as run:
+        run("ctu_finite_minmax", src.data_ptr(), _lib.DTYPE_CODE[x.dtype], src.numel(), rng.data_ptr(), ws.data_ptr(), what=who)
     return rng
 
 
 def _histogram(x, bins: int, rng, out, who: str):
     """The counts and the range they were taken over, as ``(hist, range tensor or None, lo, hi)``."""
     if rng is None:
-        _need_gpu(x, who)
+        _lib.check_device(_ON_GPU.format(who), x)
         rt, lo, hi = finite_range(x), 0.0, 0.0
     else:
         rt, lo, hi = _range_arg(rng, x.device, who)
-    _check_out(out, (bins,), torch.int64, x.device, who)
-    _need_gpu(x, who)
-    lib = _lib.load()
+    _args.check_out(out, (bins,), torch.int64, x.device, who)
+    _lib.check_device(_ON_GPU.format(who), x)
     src = x.contiguous()
     if out is None:
         out = torch.empty(bins, dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.ctu_histogram(src.data_ptr(), _CODE[x.dtype], src.numel(), bins,
-                                     None if rt is None else rt.data_ptr(), lo, hi, out.data_ptr(), _stream()), who)
+    with _lib.on(x.device) as run:
+        run("ctu_histogram", src.data_ptr(), _lib.DTYPE_CODE[x.dtype], src.numel(), bins,
+            None if rt is None else rt.data_ptr(), lo, hi, out.data_ptr(), what=who)
     return out, rt, lo, hi
 
 
@@ -237,7 +203,7 @@ def histogram(x: torch.Tensor, bins: int = 256, range=None, out: Optional[torch.
     bins = _check_bins(bins, who)
     if range is not None:
         _range_arg(range, x.device, who)
-    _check_out(out, (bins,), torch.int64, x.device, who)
+    _args.check_out(out, (bins,), torch.int64, x.device, who)
     return _histogram(x, bins, range, out, who)[0]
 
 
@@ -256,7 +222,7 @@ def threshold_otsu(x: Optional[torch.Tensor] = None, *, hist: Optional[torch.Ten
         if range is None:
             raise ValueError(f"{who}: hist= needs the range its counts were taken over")
         rt, lo, hi = _range_arg(range, hist.device, who)
-        _need_gpu(hist, who)
+        _lib.check_device(_ON_GPU.format(who), hist)
         h = hist.contiguous()
     else:
         _check_input(x, who, False)
@@ -264,12 +230,11 @@ def threshold_otsu(x: Optional[torch.Tensor] = None, *, hist: Optional[torch.Ten
         if range is not None:
             _range_arg(range, x.device, who)
         h, rt, lo, hi = _histogram(x, bins, range, None, who)
-    lib = _lib.load()
     thr = torch.empty((), dtype=torch.float64, device=h.device)
     idx = torch.empty((), dtype=torch.int64, device=h.device)
-    with torch.cuda.device(h.device):
-        _lib.check(lib.ctu_threshold_otsu(h.data_ptr(), bins, None if rt is None else rt.data_ptr(), lo, hi, thr.data_ptr(),
-                                          idx.data_ptr(), _stream()), who)
+    with _lib.on(h.device) as run:
+        run("ctu_threshold_otsu", h.data_ptr(), bins, None if rt is None else rt.data_ptr(), lo, hi, thr.data_ptr(),
+            idx.data_ptr(), what=who)
     return (thr, idx) if return_index else thr
 
 
@@ -293,15 +258,14 @@ def binarize(x: torch.Tensor, lower, upper=None, out: Optional[torch.Tensor] = N
     _check_input(x, who, False)
     lt, lv = _bound(lower, x.device, "lower", who)
     ut, uv = (None, math.inf) if upper is None else _bound(upper, x.device, "upper", who)
-    _check_out(out, x.shape, torch.uint8, x.device, who)
-    _need_gpu(x, who)
-    lib = _lib.load()
+    _args.check_out(out, x.shape, torch.uint8, x.device, who)
+    _lib.check_device(_ON_GPU.format(who), x)
     src = x.contiguous()
     if out is None:
         out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.ctu_binarize(src.data_ptr(), _CODE[x.dtype], src.numel(), None if lt is None else lt.data_ptr(), lv,
-                                    None if ut is None else ut.data_ptr(), uv, out.data_ptr(), _stream()), who)
+    with _lib.on(x.device) as run:
+        run("ctu_binarize", src.data_ptr(), _lib.DTYPE_CODE[x.dtype], src.numel(), None if lt is None else lt.data_ptr(), lv,
+            None if ut is None else ut.data_ptr(), uv, out.data_ptr(), what=who)
     return out
 
 
@@ -327,19 +291,19 @@ def extract_skull(scan: torch.Tensor, threshold, *, spacing=None, sigma=0.0, ots
         bins = _check_bins(bins, who)
     elif isinstance(threshold, bool) or not isinstance(threshold, Real) or math.isnan(threshold):
         raise ValueError(f"{who}: threshold must be a number or 'otsu', got {threshold!r}")
-    sig = _triple(sigma, "sigma", who, False)
+    sig = _args.triple(sigma, _NOT_NEGATIVE, who=who, what="sigma")
     if isinstance(components, bool) or not isinstance(components, Integral) or not 0 <= components <= postprocess.MAX_COMPONENTS:
         raise ValueError(f"{who}: components must lie in 0..{postprocess.MAX_COMPONENTS}, got {components!r}")
     if (isinstance(closing_radius, bool) or not isinstance(closing_radius, Real) or not math.isfinite(closing_radius)
             or closing_radius < 0):
         raise ValueError(f"{who}: closing_radius must be a finite number >= 0, got {closing_radius!r}")
     if spacing is not None:
-        _triple(spacing, "spacing", who, True)
+        _args.triple(spacing, _POSITIVE, who=who, what="spacing")
     v = scan
     if any(s > 0 for s in sig):
         v = gaussian_filter(scan, sig, spacing=spacing)
     else:
-        _need_gpu(scan, who)
+        _lib.check_device(_ON_GPU.format(who), scan)
     t = threshold_otsu(v, bins=bins, range=otsu_range) if otsu else threshold
     m = binarize(v, t)
     if components:

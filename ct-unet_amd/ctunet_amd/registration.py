@@ -50,7 +50,6 @@ and two calls are bit-equal.  ``RegistrationResult.report()`` is the one read-ba
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from numbers import Integral, Real
 from typing import NamedTuple, Optional
@@ -58,7 +57,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_BLOCKS = 1024                      # CTU_REG_MAX_BLOCKS of ctunet_hip.h
 _HEAD_DOUBLES = 128                    # the workspace head: 1024 bytes
@@ -83,27 +82,16 @@ class RegistrationResult(NamedTuple):
                     accepted=int((h[:, 3] == 1).sum()), status=-1 if last[3] < 0 else 0, iterations=int(h.shape[0] - 1))
 
 
-def _triple(v, what: str, positive: bool):
-    if v is None:
-        return None
-    if isinstance(v, torch.Tensor):
-        v = v.tolist()
-    if isinstance(v, Real) and not isinstance(v, bool):
-        vals = (v, v, v)
-    else:
-        try:
-            vals = tuple(v)
-        except TypeError:
-            raise ValueError(f"registration: {what} must be a number or a (z, y, x) triple, got {v!r}") from None
-    if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
-        raise ValueError(f"registration: {what} must be a number or a (z, y, x) triple, got {v!r}")
-    if any(not math.isfinite(s) or (positive and s <= 0) for s in vals):
-        raise ValueError(f"registration: {what} must be {'positive and ' if positive else ''}finite, got {v!r}")
-    return tuple(float(s) for s in vals)
+_REAL = _args.Triple(shape="registration: {what} must be a number or a (z, y, x) triple, got {v!r}",
+                     value="registration: {what} must be finite, got {v!r}")
+_REAL_POSITIVE = _REAL._replace(value="registration: {what} must be positive and finite, got {v!r}", sign=_args.POSITIVE)
+_ON_GPU = "registration: {} must live on the GPU; this path has no CPU fallback"
 
 
-def _double3(v):
-    return None if v is None else (C.c_double * 3)(*v)
+def _frame(spacing, origin, prefix: str = ""):
+    """The host (z, y, x) triples of a grid's ``spacing`` and ``origin`` arguments; None stays None."""
+    return (_args.triple(spacing, _REAL_POSITIVE, what=prefix + "spacing"),
+            _args.triple(origin, _REAL, what=prefix + "origin"))
 
 
 def _bound(max_distance) -> float:
@@ -164,9 +152,8 @@ def register_points(points: torch.Tensor, field: torch.Tensor, *, spacing=None, 
     if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
         raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
     bound = _bound(max_distance)
-    sp, org = _triple(spacing, "spacing", True), _triple(origin, "origin", False)
-    if not points.is_cuda or not field.is_cuda:
-        raise ValueError("registration: points and field must live on the GPU; this path has no CPU fallback")
+    sp, org = _frame(spacing, origin)
+    _lib.check_device(_ON_GPU.format("points and field"), points, field)
     if points.device != field.device:
         raise ValueError(f"registration: points live on {points.device}, the field on {field.device}")
     dev = points.device
@@ -176,17 +163,12 @@ def register_points(points: torch.Tensor, field: torch.Tensor, *, spacing=None, 
     ws = _workspace(P, dev, workspace)
     out = torch.empty((32 + 4 * rows,), dtype=torch.float64, device=dev)
     matrix, inverse, history = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:].view(rows, 4)
-    lib = _lib.load()
-    c_sp, c_org = _double3(sp), _double3(org)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_registration_init(pts.data_ptr(), P, None if init is None else init.data_ptr(), ws.data_ptr(),
-                                             stream), "registration_init")
+    c_sp, c_org = _lib.double_array(sp), _lib.double_array(org)
+    with _lib.on(dev) as run:
+        run("ctu_registration_init", pts.data_ptr(), P, None if init is None else init.data_ptr(), ws.data_ptr())
         for it in range(rows):
-            _lib.check(lib.ctu_registration_accumulate(pts.data_ptr(), P, fld.data_ptr(), *fld.shape, c_sp, c_org, bound,
-                                                       ws.data_ptr(), stream), "registration_accumulate")
-            _lib.check(lib.ctu_registration_update(P, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(), rows,
-                                                   ws.data_ptr(), stream), "registration_update")
+            run("ctu_registration_accumulate", pts.data_ptr(), P, fld.data_ptr(), *fld.shape, c_sp, c_org, bound, ws.data_ptr())
+            run("ctu_registration_update", P, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(), rows, ws.data_ptr())
     return RegistrationResult(matrix, inverse, history, P)
 
 
@@ -197,21 +179,17 @@ def accumulate(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, 
     summed in block order as the update kernel sums them."""
     _check_inputs(points, field)
     bound = _bound(max_distance)
-    sp, org = _triple(spacing, "spacing", True), _triple(origin, "origin", False)
-    if not points.is_cuda or not field.is_cuda:
-        raise ValueError("registration: points and field must live on the GPU; this path has no CPU fallback")
+    sp, org = _frame(spacing, origin)
+    _lib.check_device(_ON_GPU.format("points and field"), points, field)
     dev = points.device
     matrix = _check_init(matrix, dev)
     pts, fld = points.contiguous(), field.contiguous()
     P = int(pts.shape[0])
     ws = _workspace(P, dev, None)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ctu_registration_init(pts.data_ptr(), P, None if matrix is None else matrix.data_ptr(), ws.data_ptr(),
-                                             stream), "registration_init")
-        _lib.check(lib.ctu_registration_accumulate(pts.data_ptr(), P, fld.data_ptr(), *fld.shape, _double3(sp), _double3(org),
-                                                   bound, ws.data_ptr(), stream), "registration_accumulate")
+    with _lib.on(dev) as run:
+        run("ctu_registration_init", pts.data_ptr(), P, None if matrix is None else matrix.data_ptr(), ws.data_ptr())
+        run("ctu_registration_accumulate", pts.data_ptr(), P, fld.data_ptr(), *fld.shape, _lib.double_array(sp),
+            _lib.double_array(org), bound, ws.data_ptr())
     host = ws.cpu().numpy().view(np.float64)
     slab = host[_HEAD_DOUBLES:].reshape(-1, _ROW)
     tot = np.zeros(28)
@@ -226,11 +204,6 @@ def _mask(t, what: str):
         raise ValueError(f"registration: {what} must be one bool or uint8 [D,H,W] mask")
 
 
-def _on_gpu(*masks):
-    if not all(t.is_cuda for t in masks):
-        raise ValueError("registration: the masks must live on the GPU; this path has no CPU fallback")
-
-
 def _world(index: torch.Tensor, spacing, origin) -> torch.Tensor:
     """float64 world coordinates origin + k spacing of int64 voxel indices [P,3]."""
     sp = torch.tensor(spacing or (1.0, 1.0, 1.0), dtype=torch.float64, device=index.device)
@@ -242,8 +215,8 @@ def surface_points(mask: torch.Tensor, spacing=None, origin=None) -> torch.Tenso
     """float32 [P,3] world coordinates (z, y, x) of the surface voxels ``mask & ~binary_erosion(mask)``, in C order."""
     from . import postprocess
     _mask(mask, "mask")
-    sp, org = _triple(spacing, "spacing", True), _triple(origin, "origin", False)
-    _on_gpu(mask)
+    sp, org = _frame(spacing, origin)
+    _lib.check_device(_ON_GPU.format("the masks"), mask)
     m = mask != 0
     surf = m & ~(postprocess.binary_erosion(m) != 0)
     return _world(torch.nonzero(surf), sp, org).to(torch.float32)
@@ -256,14 +229,13 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
     from . import postprocess
     _mask(moving_mask, "moving_mask")
     _mask(fixed_mask, "fixed_mask")
-    msp, morg = _triple(moving_spacing, "moving_spacing", True), _triple(moving_origin, "moving_origin", False)
-    fsp, forg = _triple(fixed_spacing, "fixed_spacing", True), _triple(fixed_origin, "fixed_origin", False)
+    (msp, morg), (fsp, forg) = _frame(moving_spacing, moving_origin, "moving_"), _frame(fixed_spacing, fixed_origin, "fixed_")
     if isinstance(init, str):
         if init != "centroid":
             raise ValueError(f"registration: init must be 'centroid' or a float64 [4,4] tensor, got {init!r}")
     elif init is not None:
         init = _check_init(init, moving_mask.device)
-    _on_gpu(moving_mask, fixed_mask)
+    _lib.check_device(_ON_GPU.format("the masks"), moving_mask, fixed_mask)
     if moving_mask.device != fixed_mask.device:
         raise ValueError("registration: the two masks must live on the same device")
     points = surface_points(moving_mask, msp, morg)

@@ -82,12 +82,12 @@ import ctypes as C
 import functools
 import math
 from numbers import Integral, Real
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _args, _lib, ops
 
 MODES = ("nearest", "linear", "label_linear")
 MAX_CLASSES = 16
@@ -97,52 +97,33 @@ _IN_DTYPES = {
     "label_linear": (torch.bool, torch.uint8, torch.int64),
 }
 _MODE_CODE = {"nearest": ops.RESAMPLE_NEAREST, "linear": ops.RESAMPLE_LINEAR, "label_linear": ops.RESAMPLE_LABEL_LINEAR}
-
-
-def _triple_int(v, what: str, who: str) -> Tuple[int, int, int]:
-    try:
-        vals = tuple(v)
-    except TypeError:
-        raise TypeError(f"{who}: {what} must be a (D, H, W) triple of positive integers, got {v!r}") from None
-    if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Integral) for s in vals):
-        raise TypeError(f"{who}: {what} must be a (D, H, W) triple of positive integers, got {v!r}")
-    if any(s < 1 for s in vals):
-        raise ValueError(f"{who}: every side of {what} must be >= 1, got {v!r}")
-    if vals[0] * vals[1] * vals[2] >= 1 << 31:
-        raise ValueError(f"{who}: {what} must hold fewer than 2^31 voxels, got {v!r}")
-    return tuple(int(s) for s in vals)
-
-
-def _triple_spacing(v, what: str, who: str) -> Tuple[float, float, float]:
-    if isinstance(v, Real) and not isinstance(v, bool):
-        vals = (v, v, v)
-    else:
-        try:
-            vals = tuple(v)
-        except TypeError:
-            raise TypeError(f"{who}: {what} must be a positive number or a (D, H, W) triple, got {v!r}") from None
-        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
-            raise TypeError(f"{who}: {what} must be a positive number or a (D, H, W) triple, got {v!r}")
-    if any(not math.isfinite(s) or s <= 0 for s in vals):
-        raise ValueError(f"{who}: {what} must be positive and finite, got {v!r}")
-    return tuple(float(s) for s in vals)
+_GRID_SHAPE = "{who}: {what} must be a (D, H, W) triple of positive integers, got {v!r}"
+_GRID = _args.Grid(shape=_GRID_SHAPE, integers=_GRID_SHAPE, side="{who}: every side of {what} must be >= 1, got {v!r}",
+                   voxels="{who}: {what} must hold fewer than 2^31 voxels, got {v!r}", shape_error=TypeError)
+_SPACING = _args.Triple(shape="{who}: {what} must be a positive number or a (D, H, W) triple, got {v!r}",
+                        value="{who}: {what} must be positive and finite, got {v!r}", sign=_args.POSITIVE,
+                        shape_error=TypeError, optional=False, tensors=False)
+# the frame of an affine resampling: host (z, y, x) float64 triples; None stays None (the entry point's default)
+_REAL = _args.Triple(shape="{who}: {what} must be a number or a (z, y, x) triple, got {v!r}",
+                     value="{who}: {what} must be finite, got {v!r}", shape_error=TypeError)
+_REAL_POSITIVE = _REAL._replace(value="{who}: {what} must be positive and finite, got {v!r}", sign=_args.POSITIVE)
 
 
 def geometry(in_shape, size=None, spacing=None, new_spacing=None, who: str = "resample"):
     """``(in_shape, out_shape, a)`` of the module docstring's geometry: ``a`` the per-axis float64 scale of the tables."""
-    n = _triple_int(in_shape, "the input grid", who)
+    n = _args.grid(in_shape, _GRID, who=who, what="the input grid")
     if (spacing is None) != (new_spacing is None):
         raise ValueError(f"{who}: spacing and new_spacing go together (with or without size); got only one of them")
     if size is None and spacing is None:
         raise ValueError(f"{who}: give size, or spacing and new_spacing")
-    m = None if size is None else _triple_int(size, "size", who)
+    m = None if size is None else _args.grid(size, _GRID, who=who, what="size")
     if spacing is not None:
-        s = _triple_spacing(spacing, "spacing", who)
-        t = _triple_spacing(new_spacing, "new_spacing", who)
+        s = _args.triple(spacing, _SPACING, who=who, what="spacing")
+        t = _args.triple(new_spacing, _SPACING, who=who, what="new_spacing")
         a = tuple(tj / sj for sj, tj in zip(s, t))
         if m is None:
-            m = _triple_int(tuple(max(1, int(math.floor(nj * sj / tj + 0.5))) for nj, sj, tj in zip(n, s, t)),
-                            "the output grid", who)
+            m = _args.grid(tuple(max(1, int(math.floor(nj * sj / tj + 0.5))) for nj, sj, tj in zip(n, s, t)), _GRID,
+                           who=who, what="the output grid")
     else:
         a = tuple(nj / mj for nj, mj in zip(n, m))
     return n, m, a
@@ -176,6 +157,15 @@ def _check_call(x, mode, num_classes, who: str, dtypes=None):
         raise TypeError(f"{who}: mode {mode!r} takes {', '.join(str(d) for d in dtypes[mode])}, got {x.dtype}")
 
 
+def _lead(x, who: str):
+    """The leading dimensions of ``x [..., D, H, W]`` and the number of volumes they hold."""
+    lead = tuple(x.shape[:-3])
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if n < 1:
+        raise ValueError(f"{who}: the batch is empty, got shape {tuple(x.shape)}")
+    return lead, n
+
+
 class Resampler:
     """The tables of one change of grid, ``in_shape -> out_shape``, and of its inverse; uploaded once per device.
 
@@ -186,8 +176,8 @@ class Resampler:
     def __init__(self, in_shape, out_shape=None, in_spacing=None, out_spacing=None, _who: str = "Resampler"):
         self.in_shape, self.out_shape, a = geometry(in_shape, out_shape, in_spacing, out_spacing, _who)
         spaced = in_spacing is not None
-        self.in_spacing = _triple_spacing(in_spacing, "spacing", _who) if spaced else None
-        self.out_spacing = _triple_spacing(out_spacing, "new_spacing", _who) if spaced else None
+        self.in_spacing = _args.triple(in_spacing, _SPACING, who=_who, what="spacing") if spaced else None
+        self.out_spacing = _args.triple(out_spacing, _SPACING, who=_who, what="new_spacing") if spaced else None
         if spaced:
             inv = tuple(s / t for s, t in zip(self.in_spacing, self.out_spacing))
         else:
@@ -219,24 +209,14 @@ class Resampler:
         src, dst = (self.in_shape, self.out_shape) if direction == 0 else (self.out_shape, self.in_shape)
         if tuple(x.shape[-3:]) != src:
             raise ValueError(f"{who}: the input's grid is {tuple(x.shape[-3:])}, this Resampler maps {src} -> {dst}")
-        lead = tuple(x.shape[:-3])
-        n = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        if n < 1:
-            raise ValueError(f"{who}: the batch is empty, got shape {tuple(x.shape)}")
+        lead, n = _lead(x, who)
         out_dtype = torch.float32 if mode == "linear" else x.dtype
-        if out is not None:
-            if not isinstance(out, torch.Tensor):
-                raise TypeError(f"{who}: out must be a tensor, got {type(out).__name__}")
-            if tuple(out.shape) != lead + dst or out.dtype != out_dtype or out.device != x.device or not out.is_contiguous():
-                raise ValueError(f"{who}: out must be a contiguous {out_dtype} tensor of shape {lead + dst} on {x.device}, "
-                                 f"got {out.dtype} {tuple(out.shape)} on {out.device}"
-                                 f"{'' if out.is_contiguous() else ', not contiguous'}")
-        if not x.is_cuda:
-            raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
+        _args.check_out(out, lead + dst, out_dtype, x.device, who, TypeError)
+        _lib.check_device(f"{who}: the input must live on the GPU; this path has no CPU fallback", x)
         tables = self._tables(x.device)[direction]
         if out is None:
             out = torch.empty(lead + dst, dtype=out_dtype, device=x.device)
-        with torch.cuda.device(x.device):
+        with torch.cuda.device(x.device.index):                # the index spares torch the parsing of a device
             ops.resample(x.contiguous(), out, _MODE_CODE[mode], int(num_classes or 0), n, src, dst, tables)
         return out
 
@@ -275,26 +255,6 @@ _AFFINE_DTYPES = {
 }
 
 
-def _triple_real(v, what: str, who: str, positive: bool):
-    """A host (z, y, x) float64 triple from a number or a triple; None stays None (the entry point's default)."""
-    if v is None:
-        return None
-    if isinstance(v, torch.Tensor):
-        v = v.tolist()
-    if isinstance(v, Real) and not isinstance(v, bool):
-        vals = (v, v, v)
-    else:
-        try:
-            vals = tuple(v)
-        except TypeError:
-            raise TypeError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}") from None
-        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Real) for s in vals):
-            raise TypeError(f"{who}: {what} must be a number or a (z, y, x) triple, got {v!r}")
-    if any(not math.isfinite(s) or (positive and s <= 0) for s in vals):
-        raise ValueError(f"{who}: {what} must be {'positive and ' if positive else ''}finite, got {v!r}")
-    return tuple(float(s) for s in vals)
-
-
 def _check_matrix(m, device, who: str) -> torch.Tensor:
     if not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or tuple(m.shape) not in ((3, 4), (4, 4)):
         raise TypeError(f"{who}: the matrix must be a float64 tensor [3,4] or [4,4], got "
@@ -310,10 +270,12 @@ def affine_resample(x, out_to_in, out_shape, *, spacing=None, origin=None, out_s
     """``x [..., D, H, W]`` on the grid ``out_shape`` through the device matrix ``out_to_in`` (module docstring)."""
     who = "affine_resample"
     _check_call(x, mode, num_classes, who, _AFFINE_DTYPES)
-    src = _triple_int(tuple(int(s) for s in x.shape[-3:]), "the input grid", who)
-    dst = _triple_int(out_shape, "out_shape", who)
-    sp, org = _triple_real(spacing, "spacing", who, True), _triple_real(origin, "origin", who, False)
-    osp, oorg = _triple_real(out_spacing, "out_spacing", who, True), _triple_real(out_origin, "out_origin", who, False)
+    src = _args.grid(tuple(int(s) for s in x.shape[-3:]), _GRID, who=who, what="the input grid")
+    dst = _args.grid(out_shape, _GRID, who=who, what="out_shape")
+    sp = _args.triple(spacing, _REAL_POSITIVE, who=who, what="spacing")
+    org = _args.triple(origin, _REAL, who=who, what="origin")
+    osp = _args.triple(out_spacing, _REAL_POSITIVE, who=who, what="out_spacing")
+    oorg = _args.triple(out_origin, _REAL, who=who, what="out_origin")
     if isinstance(fill, bool) or not isinstance(fill, Real):
         raise TypeError(f"{who}: fill must be a number, got {fill!r}")
     out_dtype = torch.float32 if mode == "linear" else x.dtype
@@ -325,23 +287,13 @@ def affine_resample(x, out_to_in, out_shape, *, spacing=None, origin=None, out_s
         lo, hi = (-32768, 32767) if out_dtype == torch.int16 else ((0, 1) if out_dtype == torch.bool else (0, 255))
         if fillv != math.floor(fillv) or not lo <= fillv <= hi:
             raise ValueError(f"{who}: fill must be an integer in {lo}..{hi} for {out_dtype}, got {fill!r}")
-    lead = tuple(x.shape[:-3])
-    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
-    if n < 1:
-        raise ValueError(f"{who}: the batch is empty, got shape {tuple(x.shape)}")
-    if out is not None:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError(f"{who}: out must be a tensor, got {type(out).__name__}")
-        if tuple(out.shape) != lead + dst or out.dtype != out_dtype or out.device != x.device or not out.is_contiguous():
-            raise ValueError(f"{who}: out must be a contiguous {out_dtype} tensor of shape {lead + dst} on {x.device}, "
-                             f"got {out.dtype} {tuple(out.shape)} on {out.device}"
-                             f"{'' if out.is_contiguous() else ', not contiguous'}")
-    if not x.is_cuda:
-        raise ValueError(f"{who}: the input must live on the GPU; this path has no CPU fallback")
+    lead, n = _lead(x, who)
+    _args.check_out(out, lead + dst, out_dtype, x.device, who, TypeError)
+    _lib.check_device(f"{who}: the input must live on the GPU; this path has no CPU fallback", x)
     m = _check_matrix(out_to_in, x.device, who)
     if out is None:
         out = torch.empty(lead + dst, dtype=out_dtype, device=x.device)
-    with torch.cuda.device(x.device):
+    with torch.cuda.device(x.device.index):                # the index spares torch the parsing of a device
         ops.affine_resample(_lib.as_bytes(x), _lib.as_bytes(out), _MODE_CODE[mode], int(num_classes or 0), n, src, dst, m,
                             sp, org, osp, oorg, fillv)
     return out

@@ -88,8 +88,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
-from .resample import _triple_real
+from . import _args, _lib, ops
 
 SHAPES = ("sphere", "box", "flap")
 _RECORD_FIELDS = ("apply", "count", "k", "cz", "cy", "cx", "size", "shape", "c_diam", "cut", "noise_applied", "nd")
@@ -353,8 +352,13 @@ class SaltAndPepper(_Recorded):
         return sample
 
 
+_REAL = _args.Triple(shape="RandomSpatial: {what} must be a number or a (z, y, x) triple, got {v!r}",
+                     value="RandomSpatial: {what} must be finite, got {v!r}", shape_error=TypeError)
+_REAL_POSITIVE = _REAL._replace(value="RandomSpatial: {what} must be positive and finite, got {v!r}", sign=_args.POSITIVE)
+
+
 def _triple_nonneg(v, what: str) -> Tuple[float, float, float]:
-    t = _triple_real(v, what, "RandomSpatial", False)
+    t = _args.triple(v, _REAL, what=what)
     if t is None or any(s < 0 for s in t):
         raise ValueError(f"RandomSpatial: {what} must be a non-negative number or (z, y, x) triple, got {v!r}")
     return t
@@ -403,7 +407,7 @@ class RandomSpatial:
         if any(2 * locked_borders >= v for v in g):
             raise ValueError(f"RandomSpatial: locked_borders={locked_borders} leaves no free control point of {g}")
         self.locked_borders = int(locked_borders)
-        self.spacing = _triple_real(spacing, "spacing", "RandomSpatial", True)
+        self.spacing = _args.triple(spacing, _REAL_POSITIVE, what="spacing")
         if self.spacing is None:
             raise TypeError("RandomSpatial: spacing must be a number or a (z, y, x) triple")
         self._rng = _DeviceRng(seed)
@@ -449,8 +453,7 @@ class RandomSpatial:
             if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
                 raise ValueError(f"RandomSpatial: out must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on "
                                  f"{x.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        if not x.is_cuda:
-            raise ValueError("RandomSpatial: x must live on the GPU (MI355X); this path has no CPU fallback")
+        _lib.check_device("RandomSpatial: x must live on the GPU (MI355X); this path has no CPU fallback", x)
         x = x.contiguous()
         nbytes = x.numel() * x.element_size()
         if out is not None and out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
