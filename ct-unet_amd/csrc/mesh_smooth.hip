@@ -7,7 +7,7 @@
 //   2. scan     exclusive scan of cnt over V in vertex order -> the cursor of every vertex's segment of `seg`.  Three
 //               launches: the sum of every chunk of SCAN_CHUNK = 1024 threads x 4 vertices, one block that scans the chunk
 //               sums in order (a thread owns ceil(chunks / 1024) consecutive chunks beyond 1024 chunks; int64), and the
-//               chunks again with their bases (block_exclusive_scan of scan.h).
+//               chunks again with their bases (chunked_exclusive_scan of scan.h).
 //   3. fill     a thread per face: seg[cursor[a]++] = b.  The order within a segment depends on arrival; step 4 removes it.
 //               Afterwards cursor[a] is the segment's end, so the segment is [cursor[a] - cnt[a], cursor[a]).
 //   4. sort     a thread per vertex: insertion of the segment's entries into its own sorted duplicate-free prefix, in
@@ -30,10 +30,8 @@
 namespace {
 
 constexpr int FB = 256;                         // block of the per-face and per-vertex kernels
-constexpr int SCB = 1024;                       // scan block
-constexpr int SCI = 4;                          // vertices of a scan thread
-constexpr int SCAN_CHUNK = CTU_MESH_ADJ_SCAN_CHUNK;
-static_assert(SCAN_CHUNK == SCB * SCI, "the header states the scan's single-block capacity");
+constexpr int SCAN_CHUNK = CSCAN_CHUNK;         // scan.h: 1024 threads x 4 vertices
+static_assert(SCAN_CHUNK == CTU_MESH_ADJ_SCAN_CHUNK, "the header states the scan's single-block capacity");
 constexpr int64_t LIMIT = (int64_t)1 << 31;
 
 struct Head { long long E, bad, upper; };      // at the start of the workspace (256 bytes reserved)
@@ -76,61 +74,6 @@ __global__ void __launch_bounds__(FB) adj_pairs_kernel(const int* __restrict__ f
             atomicAdd(cnt + a, 1);
             atomicAdd(cnt + b, 1);
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ scan
-__device__ __forceinline__ void load_items(const int* __restrict__ x, int64_t i0, int64_t n, int (&w)[SCI]) {
-    if (i0 + SCI <= n) {
-        const int4 q = *reinterpret_cast<const int4*>(x + i0);     // x is a 256-byte aligned workspace array, i0 % 4 == 0
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {
-#pragma unroll
-        for (int u = 0; u < SCI; ++u) w[u] = i0 + u < n ? x[i0 + u] : 0;
-    }
-}
-
-__global__ void __launch_bounds__(SCB) adj_scan_sums_kernel(const int* __restrict__ x, int64_t n, long long* __restrict__ bsum) {
-    __shared__ long long lds[SCB / 64];
-    int w[SCI];
-    load_items(x, (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCI, n, w);
-    long long total;
-    block_exclusive_scan((long long)w[0] + w[1] + w[2] + w[3], lds, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// exclusive scan of the chunk sums in place; the total goes to *total and, as an int32, to *end (offsets[V]) if given
-__global__ void __launch_bounds__(SCB) adj_scan_chunks_kernel(long long* __restrict__ bsum, int nb, long long* total, int* end) {
-    __shared__ long long lds[SCB / 64];
-    const int per = (nb + SCB - 1) / SCB;
-    const int r0 = min((int)threadIdx.x * per, nb), r1 = min(r0 + per, nb);
-    long long s = 0;
-    for (int r = r0; r < r1; ++r) s += bsum[r];
-    long long t;
-    long long o = block_exclusive_scan(s, lds, t);
-    for (int r = r0; r < r1; ++r) {
-        const long long b = bsum[r];
-        bsum[r] = o;
-        o += b;
-    }
-    if (threadIdx.x == 0) {
-        *total = t;
-        if (end) *end = (int)t;                                    // below 2^31: the counts sum to at most 6F
-    }
-}
-
-__global__ void __launch_bounds__(SCB) adj_scan_apply_kernel(const int* __restrict__ x, int64_t n, const long long* __restrict__ bsum,
-                                                             int* __restrict__ y) {
-    __shared__ long long lds[SCB / 64];
-    int w[SCI];
-    const int64_t i0 = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCI;
-    load_items(x, i0, n, w);
-    long long total;
-    long long o = bsum[blockIdx.x] + block_exclusive_scan((long long)w[0] + w[1] + w[2] + w[3], lds, total);
-#pragma unroll
-    for (int u = 0; u < SCI; ++u) {
-        if (i0 + u < n) y[i0 + u] = (int)o;
-        o += w[u];
     }
 }
 
@@ -220,14 +163,7 @@ __global__ void __launch_bounds__(FB) smooth_step_kernel(const float4* __restric
 }
 
 int scan(const int* x, int64_t n, long long* bsum, int* y, long long* total, int* end, hipStream_t st) {
-    const int nb = (int)ceil_div64(n, SCAN_CHUNK);
-    adj_scan_sums_kernel<<<nb, SCB, 0, st>>>(x, n, bsum);
-    CTU_CHECK_LAUNCH("mesh adjacency scan sums");
-    adj_scan_chunks_kernel<<<1, SCB, 0, st>>>(bsum, nb, total, end);
-    CTU_CHECK_LAUNCH("mesh adjacency scan chunks");
-    adj_scan_apply_kernel<<<nb, SCB, 0, st>>>(x, n, bsum, y);
-    CTU_CHECK_LAUNCH("mesh adjacency scan apply");
-    return CTU_OK;
+    return chunked_exclusive_scan(x, n, bsum, y, total, end, st, "mesh adjacency scan");
 }
 
 }  // namespace

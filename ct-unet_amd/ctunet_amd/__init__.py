@@ -13,6 +13,7 @@ from . import postprocess  # noqa: F401
 from . import preprocess  # noqa: F401
 from . import resample  # noqa: F401
 from . import registration  # noqa: F401
+from . import simplify  # noqa: F401
 from .inference import Prediction, predict_volume  # noqa: F401
 from .datasets import FlapRec2OTrainDataset, FlapRecWShapePrior2OTrainDataset  # noqa: F401
 from .loss_scale import DynamicLossScale  # noqa: F401
@@ -25,4 +26,4 @@ __all__ = ["UNet", "UNet4b2i3o", "UNet5b2i3o", "UNet4b1i3o", "UNetSP", "UNetSPSm
            "UNet4_2IC", "DynamicLossScale", "predict_volume", "Prediction",
            "SkullRandomHole", "SaltAndPepper", "FlapRecTransform", "flap_rec_transform", "RandomSpatial",
            "cranioplasty_transform", "FlapRecWShapePrior2OTrainDataset", "FlapRec2OTrainDataset", "metrics", "postprocess", "preprocess", "resample", "registration", "mesh", "lr_scheduler",
-           "optim"]
+           "optim", "simplify"]

@@ -169,6 +169,10 @@ SIGNATURES = {
     "ctu_mesh_grid_build": (I, [P, L, P, L, F, L, P, P, P]),
     "ctu_mesh_grid_emit": (I, [P, L, L, L, L, P, P, P, P]),
     "ctu_mesh_distance": (I, [P, L, P, P, L, P, I, I, I, P, L, I, I, I, P, P, F, F, P, P, P, P]),
+    "ctu_mesh_decimate_ws_bytes": (Z, [L, L, L]),
+    "ctu_mesh_decimate_bounds": (I, [P, L, P, L, P, P]),
+    "ctu_mesh_decimate_build": (I, [P, L, P, L, P, P, P, L, I, P, P]),
+    "ctu_mesh_decimate_emit": (I, [P, L, L, L, L, P, P, P, P, P, P, P]),
     "ctu_gaussian_ws_bytes": (Z, [L, I, I, I, I]),
     "ctu_gaussian_filter": (I, [P, I, L, I, I, I, P, P, I, F, P, P, P]),
     "ctu_minmax_ws_bytes": (Z, [L]),

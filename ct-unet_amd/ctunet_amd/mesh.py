@@ -15,6 +15,7 @@ their export and import as binary STL: the last step of the segmentation-to-impl
     moved = mesh.point_distance(mesh.smooth(m).vertices, m).max()      # mm: how far smoothing moved the surface
     sdf = mesh.distance_field(other, scan.shape, spacing=(0.8, 0.45, 0.45), max_distance=5.0, signed=True)   # mm, < 0 inside
     metrics.mesh_surface_metrics(m, other, tolerance=1.0)              # HD, HD95, ASSD, NSD between two meshes, in mm
+    small = simplify.decimate(mesh.smooth(m), 1.0)                     # fewer, larger triangles: see ctunet_amd.simplify
 
 ``volume`` is one ``[D,H,W]`` tensor.  Meshes are ragged (V and F depend on the data), so a batch is a Python loop over its
 items.  bool, uint8 and int64 volumes are masks or label maps: inside = ``v != 0``, or ``v == label`` with ``label=``;

@@ -768,6 +768,40 @@ int ctu_mesh_distance(const float* corners, int64_t F, const int32_t* offsets, c
                       const float* spacing, const float* origin, float max_distance, float far_value, float* dist,
                       int32_t* face, float* closest, void* stream);
 
+/* Decimation of a surface mesh by vertex clustering on a uniform grid (no reference counterpart; rule pinned in
+ * ctunet_amd/simplify.py).  vertices: DEVICE float32 [V][3] in (z, y, x); faces: DEVICE int32 [F][3], F >= 1.  A face with an
+ * index outside [0, V) or a vertex that is not finite is refused: counted, never read through.  A member is a vertex of an
+ * accepted face.  lo, hi, cell_size: HOST float [3] in (z, y, x).
+ *   bounds: the box of the members.  The head of ws then holds, for the caller to read after synchronising (the first of the
+ *          two synchronisations): int64 refused faces, then float32 lo (z, y, x) and hi (z, y, x).  The caller refuses the
+ *          mesh if the count is not 0, and otherwise fixes the grid: n_a = floor((hi_a - lo_a) / cell_a) + 1 cells per axis
+ *          in float64, cells = n_z n_y n_x <= CTU_MESH_DECIMATE_MAX_CELLS.
+ *   build: with lo and hi as bounds gave them and `cells` as above (checked against cell_size): the cell of every member,
+ *          the occupied cells numbered in ascending order, the faces whose corners lie in three different cells bucketed by
+ *          their lowest cell, with cancel != 0 the cancellation of faces with the same three cells and opposite orientation,
+ *          the cells the surviving faces use numbered in ascending order, the surviving faces numbered in input order, and
+ *          the integer sums of the members' quantised positions per used cell.  A face whose bucket holds more than
+ *          CTU_MESH_DECIMATE_MAX_BUCKET faces is not compared and sets the overflow word: no thread loops over more than that
+ *          many items.  The head of ws then holds three int64 for the caller to read after synchronising (the second
+ *          synchronisation): V', F', overflow (refuse the mesh if it is not 0).
+ *   emit:  with the faces and the ws of build, Vp = V' and Fp = F': out_vertices DEVICE float32 [V'][3] (per used cell and axis
+ *          float32(lo + (sum / count) / S), float64), out_faces DEVICE int32 [F'][3] (the surviving faces in input order and
+ *          corner order, renumbered), out_map (NULL: none) DEVICE int32 [V]: the output vertex of every input vertex's cell, -1
+ *          for a vertex in no accepted face or in a cell no surviving face uses.  Every write is bounded by Vp and Fp.
+ *   ws: ctu_mesh_decimate_ws_bytes(V, F, cells) bytes, 0 outside the limits; 16-byte aligned.  cells = 0: the workspace of
+ *       bounds, 256 bytes.  cells >= 1: the workspace of build and emit: 256 + 5 per cell + 49 per vertex + 24 per face + 8 per
+ *       scan chunk of 4096 of the largest of the three, each array rounded up to 256.
+ * Limits: V, F < 2^31, cells <= CTU_MESH_DECIMATE_MAX_CELLS.  Integer atomics only (min, max, counts, fill cursors, sums); float64
+ * with contraction off; two calls are bitwise equal. */
+#define CTU_MESH_DECIMATE_MAX_CELLS 268435456
+#define CTU_MESH_DECIMATE_MAX_BUCKET 4096
+size_t ctu_mesh_decimate_ws_bytes(int64_t V, int64_t F, int64_t cells);
+int ctu_mesh_decimate_bounds(const float* vertices, int64_t V, const int32_t* faces, int64_t F, void* ws, void* stream);
+int ctu_mesh_decimate_build(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
+                            const float* cell_size, int64_t cells, int cancel, void* ws, void* stream);
+int ctu_mesh_decimate_emit(const int32_t* faces, int64_t V, int64_t F, int64_t Vp, int64_t Fp, const float* lo, const float* hi,
+                           float* out_vertices, int32_t* out_faces, int32_t* out_map, void* ws, void* stream);
+
 /* CT preprocessing: from a scanner's volume to a binary skull (no reference counterpart: the reference's datasets load skulls
  * that were thresholded beforehand, ctunet/pytorch/datasets.py:22-45; rules pinned in ctunet_amd/preprocess.py).  Every input
  * `in` is a DEVICE contiguous array of dtype CTU_F32, CTU_I16 or CTU_U8, converted in the kernel.  No entry point allocates
