@@ -148,6 +148,10 @@ SIGNATURES = {
     "ctu_implant_mask": (I, [P, I, P, I, I, I, I, I, C.c_uint32, I, I, I, I, P, P, P]),
     "ctu_distance_ws_bytes": (Z, [I, I, I, I, I, I]),
     "ctu_distance_transform": (I, [P, I, I, I, I, I, I, L, I, I, P, I, P, P, F, P, P]),
+    "ctu_thickness_ws_bytes": (Z, [I, I, I, I, I]),
+    "ctu_local_thickness": (I, [P, I, I, I, I, I, P, P, P, P]),
+    "ctu_thickness_summary_ws_bytes": (Z, [I, L]),
+    "ctu_thickness_summary": (I, [P, I, L, F, P, P, P]),
     "ctu_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P]),
     "ctu_affine_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P, D, P, P]),
     "ctu_registration_ws_bytes": (Z, [L]),

@@ -70,6 +70,28 @@ Distance transform and ball morphology (``distance_transform_edt`` / ``signed_di
   limit), fewer than 2^31 voxels per item, N <= 65535.  Anything larger raises.
 - ``extract_implant(..., opening_radius=r, sampling=s)`` replaces the iterated opening with ``ball_opening(m, r, s)``.
 
+Local thickness (``local_thickness`` / ``thickness_summary``; ``ctu_local_thickness``, ``ctu_thickness_summary`` of
+``csrc/thickness.hip``) is Hildebrand and Rüegsegger's (1997): every foreground voxel gets the diameter of the largest
+inscribed ball that contains it.
+
+- **Foreground** as above.  ``D2`` is ``distance_transform_edt(mask, sampling, squared=True, label=label)``: int32 and exact
+  at unit sampling, float32 otherwise, 0 on background; the outside of the volume is not background, so an object cut by
+  the volume's face reads as continuing.
+- **Offset length** ``dd(p, q)``: at unit sampling the integer ``dz^2 + dy^2 + dx^2``; otherwise float32,
+  ``t_a = float32(k_a) * s_a`` and ``dd = (t_z t_z + t_y t_y) + t_x t_x``, every product and sum rounded on its own.
+- **Covering**: the centre ``q`` covers ``p`` iff both are foreground and ``dd(p, q) < D2(q)``, strictly: the open ball
+  (the closed one holds a background voxel's centre).  ``p`` covers itself.
+- **Result**: ``thickness(p) = 2 sqrt(max {D2(q) : q covers p})``, float32, the correctly rounded root; 0 on background;
+  ``+inf`` everywhere in an item without background.  The units are those of ``sampling``.
+- **Bias**: with voxel centres (ImageJ's convention too) a plate of ``k`` voxels reads ``2 ceil(k / 2)`` voxels: 1 -> 2,
+  2 -> 2, 3 -> 4, 4 -> 4, 5 -> 6.  The result is the true thickness plus 0 to 1 voxel and is not corrected.
+- **Summary**: per item ``(foreground count, min, max, mean, count below min_thickness)`` as float64 on the device;
+  foreground is ``thickness > 0``, below is ``t < float32(min_thickness)``, the mean a float64 sum in a fixed order.  An
+  item without foreground gives ``(0, +inf, 0, NaN, 0)``.
+- The search is exact (its pruning never shows in the result), uses no atomics and no host synchronisation, and two
+  calls are bit-equal.  Limits as the distance transform's.  Not offered: a radius cap, the bias correction, the thickness
+  of the background (pass the inverted mask), per-vertex thickness of meshes, a virtual border.
+
 Each item of a batch is processed on its own.  The morphology calls use no atomics and no host synchronisation, so a
 call can be captured into a graph.  The output and the workspace are ``torch.empty`` tensors, which a capture draws from
 the graph's private pool.  Under capture give ``structure`` as an int or a host array: a structure tensor on the device
@@ -500,3 +522,67 @@ def distance_workspace_bytes(n: int, shape, return_indices: bool = False) -> int
     """Device workspace (bytes) of one ``distance_transform_edt`` call on n items of a (D, H, W) volume: the maps are
     computed inside the result, so only the indices need room (three int16 planes, 6 bytes per voxel)."""
     return int(_lib.load().ctu_distance_ws_bytes(n, *shape, _DIST_EDT, int(bool(return_indices))))
+
+
+# ------------------------------------------------------------------------------------------------ local thickness
+def local_thickness(mask: torch.Tensor, sampling=None, label: Optional[int] = None) -> torch.Tensor:
+    """Local thickness of a bool / uint8 / int64 mask [D,H,W] or [N,D,H,W] (each item on its own, with its own sampling
+    triple where given): every foreground voxel gets the diameter, in the units of ``sampling``, of the largest ball
+    inscribed in the foreground that contains it; background gets 0, an item without background ``+inf`` (module
+    docstring).  float32, of the mask's shape.  With voxel centres a plate of ``k`` voxels reads ``2 ceil(k / 2)``: the
+    result is the true thickness plus 0 to 1 voxel, as ImageJ's, and is not corrected."""
+    n, shape = _volume(mask, "mask", _MASK_DTYPES)
+    _distance_sides(shape)
+    sp = _sampling(sampling, n)
+    has_label, lab = _label_arg(label)
+    _lib.check_device(_ON_GPU, mask)
+    lib = _lib.load()
+    d2 = _distance(mask, n, shape, _DIST_SQUARED, sp, has_label, lab, 0, 0, False)[0]
+    is_float = int(sp is not None)
+    out = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    ws = torch.empty(lib.ctu_thickness_ws_bytes(n, *shape, is_float), dtype=torch.uint8, device=mask.device)
+    with _lib.on(mask.device) as run:
+        run("ctu_local_thickness", d2.data_ptr(), is_float, n, *shape,
+            None if sp is None else _lib.float_array(v for t in sp for v in t), out.data_ptr(), ws.data_ptr())
+    return out
+
+
+def _min_thickness(min_thickness) -> float:
+    if min_thickness is None:
+        return 0.0
+    if isinstance(min_thickness, bool) or not isinstance(min_thickness, Real):
+        raise ValueError(f"postprocess: min_thickness must be a real number or None, got {min_thickness!r}")
+    m = float(min_thickness)
+    if not m >= 0.0:
+        raise ValueError(f"postprocess: min_thickness must be >= 0 and not NaN, got {min_thickness!r}")
+    return m
+
+
+def thickness_summary(thickness: torch.Tensor, min_thickness: Optional[float] = None) -> torch.Tensor:
+    """Summary of a ``local_thickness`` map [D,H,W] or [N,D,H,W]: the float64 device tensor [5] or [N,5] of (foreground
+    count, min, max, mean, count below ``min_thickness``) per item, with no read-back.  Foreground is ``thickness > 0``;
+    ``min_thickness=None`` counts nothing as below; an item without foreground gives (0, +inf, 0, NaN, 0)."""
+    n, shape = _volume(thickness, "thickness", (torch.float32,))
+    mt = _min_thickness(min_thickness)
+    _lib.check_device(_ON_GPU, thickness)
+    lib = _lib.load()
+    src = thickness.contiguous()
+    v = shape[0] * shape[1] * shape[2]
+    out = torch.empty((n, 5) if thickness.dim() == 4 else (5,), dtype=torch.float64, device=thickness.device)
+    ws = torch.empty(lib.ctu_thickness_summary_ws_bytes(n, v), dtype=torch.uint8, device=thickness.device)
+    with _lib.on(thickness.device) as run:
+        run("ctu_thickness_summary", src.data_ptr(), n, v, mt, out.data_ptr(), ws.data_ptr())
+    return out
+
+
+def thickness_workspace_bytes(n: int, shape, sampling=None) -> int:
+    """Temporary device memory (bytes) of one ``local_thickness`` call on n items of a (D, H, W) volume, the result not
+    counted: the squared distance map (4 bytes per voxel), the transform's own workspace and the search's (the pruned
+    candidate map, 4 bytes per voxel, and one maximum per 8x8x8 cell and per item)."""
+    sp = _sampling(sampling, n)
+    lib = _lib.load()
+    own = int(lib.ctu_thickness_ws_bytes(n, *shape, int(sp is not None)))
+    if own == 0:
+        raise ValueError(f"postprocess: local_thickness takes 1..65535 items of sides 1..{MAX_DISTANCE_SIDE} with fewer "
+                         f"than 2^31 voxels, got n={n!r}, shape={tuple(shape)}")
+    return own + 4 * n * shape[0] * shape[1] * shape[2] + int(lib.ctu_distance_ws_bytes(n, *shape, _DIST_SQUARED, 0))

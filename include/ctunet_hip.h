@@ -26,7 +26,8 @@
  *    applies  a = relu(raw*scale + shift)  while loading (`in_scale`,`in_shift`,
  *    `in_relu`; NULL scale = identity).  Raw tensors are what backward re-reads.
  *  - Post-processing (ctu_*_components, ctu_binary_morphology, ctu_distance_transform: exact Euclidean distance, signed
- *    distance and ball morphology in physical units) works on contiguous label maps [N,D,H,W], each item on its own.
+ *    distance and ball morphology in physical units; ctu_local_thickness: the diameter of the largest inscribed ball
+ *    through every voxel) works on contiguous label maps [N,D,H,W], each item on its own.
  */
 #ifndef CTUNET_HIP_H
 #define CTUNET_HIP_H
@@ -584,6 +585,29 @@ size_t ctu_distance_ws_bytes(int N, int D, int H, int W, int out_kind, int want_
 int ctu_distance_transform(const void* in, int dtype, int N, int D, int H, int W, int has_label, int64_t label, int invert,
                            int border_background, const float* spacing, int out_kind, void* out, int32_t* indices,
                            float ball_r2, void* ws, void* stream);
+
+/* Local thickness (Hildebrand and Ruegsegger 1997; no reference counterpart: users would run ImageJ / BoneJ on the host;
+ * rule pinned in ctunet_amd/postprocess.py).  d2: DEVICE [N,D,H,W], the CTU_DIST_SQUARED map of ctu_distance_transform
+ * without the virtual border: int32 (is_float = 0, unit spacing only) or float32 (is_float = 1); 0 marks background, so the
+ * mask is not read again; INT32_MAX / +inf everywhere in an item without background.  spacing: HOST float [N][3] = (z, y, x)
+ * per item, NULL = unit.  The centre q covers p iff dd(p, q) < d2(q), strictly (the open ball; p covers itself), with dd the
+ * integer dz^2 + dy^2 + dx^2 on the int32 path and on the float32 path t_a = float(k_a) s_a, dd = (t_z t_z + t_y t_y) +
+ * t_x t_x, every product and sum rounded on its own.  out: DEVICE float32 [N,D,H,W] = 2 sqrtf(max {d2(q) : q covers p}), the
+ * correctly rounded root as CTU_DIST_EDT's; 0 on background, +inf in an item without background.  Voxel-centre convention: a
+ * plate of k voxels reads 2 ceil(k / 2), i.e. the true thickness plus 0 to 1 voxel; not corrected.
+ * ws: ctu_thickness_ws_bytes() bytes (0 for an invalid shape or is_float): 4 bytes per voxel for the pruned candidate map,
+ * which is its first plane [N,D,H,W] (0 = background or dropped as dominated), plus 4 per 8^3 cell and per item.
+ * Three launches per 64 items (float32) or per call (int32), grids fixed by the shape; no atomics, no host sync,
+ * capture-safe, two calls bit-equal.  Limits: every side <= 1024, D*H*W < 2^31, N <= 65535.
+ * ctu_thickness_summary: thickness DEVICE float32 [N][V] -> out DEVICE float64 [N][5] = (foreground count, min, max, mean,
+ * count below min_thickness); foreground is thickness > 0, below is t < min_thickness in float32 (min_thickness >= 0; 0 counts
+ * nothing); the mean is a float64 sum in a fixed order over the count.  An item without foreground: 0, +inf, 0, NaN, 0.
+ * ws: ctu_thickness_summary_ws_bytes() bytes (0 for N outside 1..65535 or V < 1).  Two launches, deterministic. */
+size_t ctu_thickness_ws_bytes(int N, int D, int H, int W, int is_float);
+int ctu_local_thickness(const void* d2, int is_float, int N, int D, int H, int W, const float* spacing, void* out, void* ws,
+                        void* stream);
+size_t ctu_thickness_summary_ws_bytes(int N, int64_t V);
+int ctu_thickness_summary(const float* thickness, int N, int64_t V, float min_thickness, double* out, void* ws, void* stream);
 
 /* Resampling of volumes between voxel grids (no reference counterpart: the reference resizes on the host in its datasets,
  * ctunet/pytorch/datasets.py:89-112; rule and tables pinned in ctunet_amd/resample.py).  in: DEVICE [N,D,H,W], out: DEVICE
