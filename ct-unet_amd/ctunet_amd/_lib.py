@@ -53,6 +53,13 @@ class WgradJob(C.Structure):
                 ("pairs", C.c_int), ("nmf", C.c_int)]
 
 
+class SegLossCfg(C.Structure):
+    """ctu_seg_loss_cfg of include/ctunet_hip.h."""
+    _fields_ = [("ce_lambda", C.c_float), ("dice_lambda", C.c_float), ("tversky_lambda", C.c_float),
+                ("boundary_lambda", C.c_float), ("w0", C.c_float), ("w1", C.c_float), ("focal_gamma", C.c_float),
+                ("tversky_alpha", C.c_float), ("tversky_beta", C.c_float), ("dice_softmax", C.c_int)]
+
+
 WGRAD_JOBS_MAX = 4       # CTU_WGRAD_JOBS_MAX
 
 # name -> (restype, argtypes); mirrors include/ctunet_hip.h one to one
@@ -114,6 +121,9 @@ SIGNATURES = {
     "ctu_loss_ws_floats": (Z, [I, L]),
     "ctu_loss_fwd": (I, [P, P, I, L, F, F, I, P, P, P]),
     "ctu_loss_bwd": (I, [P, P, I, L, F, F, I, P, P, P, P, I, P]),
+    "ctu_seg_loss_ws_floats": (Z, [I, L]),
+    "ctu_seg_loss_fwd": (I, [P, P, P, I, L, P, P, P, P]),
+    "ctu_seg_loss_bwd": (I, [P, P, P, I, L, P, P, P, P, P, P, P, I, P]),
     "ctu_skip_add": (I, [P, I, P, P, I, P, I, P, P, I, P, I, I, L, P]),
     "ctu_upconv_fused_supported": (I, [I, I, I, I, I, I]),
     "ctu_upconv_fused_packed_floats": (Z, [I, I]),

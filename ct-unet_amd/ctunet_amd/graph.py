@@ -27,7 +27,7 @@ import torch
 
 from . import ops
 from .engine import _tensor_dict, check_input
-from .losses import _check_map, _total, select_terms
+from .losses import LossSpec, _check_map, _total, select_loss_terms
 from .parallel import DEFAULT_BUCKET_BYTES, get_communicator, make_sync
 
 
@@ -74,12 +74,16 @@ class _Segmenter:
 class GraphedTrainStep:
     """model: a ctunet_amd model on the GPU; optimizer: ctunet_amd.optim.Adam/AdamW/SGD/RMSprop (or torch.optim with
     capturable=True).
+    ``loss``: a ``losses.LossSpec`` in place of the two lambdas (class weights, focal, Tversky and boundary terms); with a
+    boundary term ``example_boundary`` holds one signed distance map per target and ``self.boundary`` the static copies the
+    replay reads.
     ``x.grad`` is not filled: the input gradient kernels run (``input_requires_grad``), their result is not kept."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, example_input: torch.Tensor,
                  example_targets: Sequence[torch.Tensor], ce_lambda: float, dice_lambda: float,
                  input_requires_grad: bool = True, warmup: int = 3, distributed: bool = False, process_group=None,
-                 bucket_bytes: Optional[int] = None, scheduler=None):
+                 bucket_bytes: Optional[int] = None, scheduler=None, loss: Optional[LossSpec] = None,
+                 example_boundary: Optional[Sequence[torch.Tensor]] = None):
         self.model, self.opt = model, optimizer
         self.scheduler = scheduler
         if scheduler is not None and getattr(scheduler, "optimizer", optimizer) is not optimizer:
@@ -87,9 +91,18 @@ class GraphedTrainStep:
         # distributed + scheduler: the ranks' mean total loss, so that every rank takes the same decision (one float)
         self._metric = torch.zeros(1, dtype=torch.float32, device=example_input.device) \
             if scheduler is not None and distributed else None
+        if loss is not None:                   # overrides the two lambdas
+            if not any(loss.lambdas):
+                raise ValueError("GraphedTrainStep: every lambda of the LossSpec is 0: there is no loss to train on")
+            ce_lambda, dice_lambda = loss.ce_lambda, loss.dice_lambda
         self.ce, self.dice = float(ce_lambda), float(dice_lambda)
-        if not self.ce and not self.dice:
+        if loss is None and not self.ce and not self.dice:
             raise ValueError("GraphedTrainStep: ce_lambda and dice_lambda are both 0: there is no loss to train on")
+        self.spec = loss if loss is not None else LossSpec(self.ce, self.dice)
+        n_maps = -1 if example_boundary is None else len(example_boundary)
+        if self.spec.boundary_lambda != 0 and n_maps != len(example_targets):
+            raise ValueError("GraphedTrainStep: boundary_lambda != 0 needs example_boundary, one signed distance map per "
+                             "target (losses.boundary_map)")
         scaler = getattr(model, "loss_scaler", None)
         if scaler is not None and not hasattr(optimizer, "guard"):
             raise RuntimeError("GraphedTrainStep: a model with dynamic loss scaling needs an optimizer that reads the device "
@@ -106,6 +119,10 @@ class GraphedTrainStep:
                                "parallel.distribute() on the model (use parallel.broadcast_parameters)")
         self.x = example_input.detach().clone()
         self.targets = [t.detach().clone().contiguous() for t in example_targets]
+        # the boundary term's signed distance maps: static buffers like the targets (``step.boundary[i].copy_(new_map)``)
+        self.boundary: Optional[List[torch.Tensor]] = None
+        if self.spec.boundary_lambda != 0:
+            self.boundary = [b.detach().clone().contiguous() for b in example_boundary]
         self.x_req = input_requires_grad
         self.values: Optional[torch.Tensor] = None
         self.keys: List[str] = []              # set by _step
@@ -154,12 +171,19 @@ class GraphedTrainStep:
                 raise RuntimeError(f"GraphedTrainStep: {len(self.targets)} target(s) for {len(outs)} model output(s)")
             two = out1 is not None
             heads, gouts = [], []
-            for o, t in zip(outs, self.targets):
+            spec = self.spec
+            for i, (o, t) in enumerate(zip(outs, self.targets)):
                 _check_map(o, t)
-                terms, ws = ops.loss_fwd(o, t, self.ce, self.dice, two)
-                gouts.append(ops.loss_bwd(o, t, self.ce, self.dice, two, ws, None, None))
-                heads.append((terms[0], terms[1]))
-            keys, tl = select_terms(heads, self.ce != 0, self.dice != 0)
+                if spec.extended:
+                    phi = None if self.boundary is None else self.boundary[i]
+                    terms, ws = ops.seg_loss_fwd(o, t, spec.lambdas, two, boundary=phi, **spec.kernel_args)
+                    gouts.append(ops.seg_loss_bwd(o, t, spec.lambdas, two, ws, boundary=phi, **spec.kernel_args))
+                    heads.append((terms[0], terms[1], terms[2], terms[3]))
+                else:
+                    terms, ws = ops.loss_fwd(o, t, self.ce, self.dice, two)
+                    gouts.append(ops.loss_bwd(o, t, self.ce, self.dice, two, ws, None, None))
+                    heads.append((terms[0], terms[1], None, None))
+            keys, tl = select_loss_terms(heads, spec)
             values = torch.stack(tl + [_total(tl)])
             if self._metric is not None:
                 self._metric.copy_(values[-1:])            # (before backward: in the first segment of the chain)

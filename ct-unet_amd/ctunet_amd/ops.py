@@ -16,7 +16,7 @@ import gc
 import os
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -917,6 +917,63 @@ def loss_bwd(pred, target, ce_lambda, dice_lambda, dice_softmax, ws, g_ce: Optio
     _lib.check(lib.ctu_loss_bwd(pred.data_ptr(), target.data_ptr(), n, v, ce_lambda, dice_lambda, int(dice_softmax),
                                 ws.data_ptr(), _ptr(g_ce), _ptr(g_dice), g.data_ptr(), int(accumulate), _stream()),
                "loss_bwd")
+    return g
+
+
+def _seg_loss_args(pred, target, lambdas, dice_softmax, class_weight, focal_gamma, tversky_ab, boundary):
+    """(contiguous pred, target, boundary map or None, N, V, ctu_seg_loss_cfg) of one loss-family call."""
+    _need_cuda(pred, "prediction")
+    _need_cuda(target, "target")
+    assert pred.shape == target.shape and pred.dim() == 5 and pred.shape[1] == 2, "loss kernel handles 2-channel maps"
+    pred, target = pred.contiguous(), target.contiguous()
+    n, v = pred.shape[0], pred[0, 0].numel()
+    ce, dice, tv, bd = (float(x) for x in lambdas)
+    if bd != 0.0:
+        if boundary is None:
+            raise ValueError("ctunet_amd: boundary_lambda != 0 needs a boundary (signed distance) map")
+        _need_cuda(boundary, "boundary map")
+        if boundary.dtype != torch.float32 or tuple(boundary.shape) not in ((n,) + tuple(pred.shape[2:]),
+                                                                            (n, 1) + tuple(pred.shape[2:])):
+            raise ValueError(f"ctunet_amd: the boundary map must be float32 [N,D,H,W] or [N,1,D,H,W] of the prediction's "
+                             f"grid, got {boundary.dtype} {tuple(boundary.shape)} for {tuple(pred.shape)}")
+        boundary = boundary.contiguous()
+    else:
+        boundary = None                  # not read
+    cfg = _lib.SegLossCfg(ce, dice, tv, bd, float(class_weight[0]), float(class_weight[1]), float(focal_gamma),
+                          float(tversky_ab[0]), float(tversky_ab[1]), int(bool(dice_softmax)))
+    return pred, target, boundary, n, v, cfg
+
+
+def seg_loss_fwd(pred: torch.Tensor, target: torch.Tensor, lambdas: Sequence[float], dice_softmax: bool,
+                 class_weight: Sequence[float] = (1.0, 1.0), focal_gamma: float = 0.0,
+                 tversky_ab: Sequence[float] = (0.5, 0.5), boundary: Optional[torch.Tensor] = None):
+    """Loss family of csrc/loss_family.hip on one [N,2,D,H,W] map.  lambdas = (ce, dice, tversky, boundary); returns
+    (terms [4] in that order, workspace for ``seg_loss_bwd``)."""
+    pred, target, boundary, n, v, cfg = _seg_loss_args(pred, target, lambdas, dice_softmax, class_weight, focal_gamma,
+                                                      tversky_ab, boundary)
+    lib = _lib.load()
+    ws = torch.empty(lib.ctu_seg_loss_ws_floats(n, v), dtype=torch.float32, device=pred.device)
+    terms = torch.empty(4, dtype=torch.float32, device=pred.device)
+    _lib.check(lib.ctu_seg_loss_fwd(pred.data_ptr(), target.data_ptr(), _ptr(boundary), n, v, ctypes.byref(cfg),
+                                    terms.data_ptr(), ws.data_ptr(), _stream()), "seg_loss_fwd")
+    return terms, ws
+
+
+def seg_loss_bwd(pred, target, lambdas, dice_softmax, ws, upstream: Sequence[Optional[torch.Tensor]] = (None,) * 4,
+                 class_weight: Sequence[float] = (1.0, 1.0), focal_gamma: float = 0.0,
+                 tversky_ab: Sequence[float] = (0.5, 0.5), boundary: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """upstream: the gradients of the four terms (0-d float32 device tensors, read in place; None = 1)."""
+    pred, target, boundary, n, v, cfg = _seg_loss_args(pred, target, lambdas, dice_softmax, class_weight, focal_gamma,
+                                                      tversky_ab, boundary)
+    assert len(upstream) == 4
+    for g_ in upstream:
+        assert g_ is None or (g_.is_cuda and g_.dtype == torch.float32 and g_.numel() == 1)
+    g = out if out is not None else torch.empty_like(pred)
+    lib = _lib.load()
+    _lib.check(lib.ctu_seg_loss_bwd(pred.data_ptr(), target.data_ptr(), _ptr(boundary), n, v, ctypes.byref(cfg),
+                                    ws.data_ptr(), *(_ptr(g_) for g_ in upstream), g.data_ptr(), int(accumulate),
+                                    _stream()), "seg_loss_bwd")
     return g
 
 

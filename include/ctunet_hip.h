@@ -397,6 +397,33 @@ int ctu_loss_bwd(const float* pred, const float* target, int N, int64_t V, float
                  float dice_lambda, int dice_softmax, const float* ws, const float* gscale_ce,
                  const float* gscale_dice, float* gpred, int accumulate, void* stream);
 
+/* Loss family on the same 2-channel map (csrc/loss_family.hip): class-weighted / focal cross-entropy, the Dice term
+ * above, a Tversky term on the foreground channel and a boundary term over a signed distance map.  With c the target
+ * class of a voxel (1 where t1 > t0, else 0), p = softmax(pred), P as above, q = P[:,1], g = target[:,1], eps = 1e-7:
+ *  ce term       = ce_lambda * sum w_c (1 - p_c)^focal_gamma (-log p_c) / sum w_c, over all N*V voxels
+ *  dice term     = as ctu_loss_fwd
+ *  tversky term  = tversky_lambda * (1 - mean_n (TP + eps) / (TP + alpha FP + beta FN + eps)),
+ *                  TP = sum q g, FP = sum q - TP, FN = sum g - TP per item
+ *  boundary term = boundary_lambda * sum q phi / (N V); phi [N,V] float32 (positive outside the object, negative
+ *                  inside), a non-finite entry counts as 0.  phi may be NULL when boundary_lambda == 0 (it is not read then).
+ * terms (device, float[4]) in that order; a term whose lambda is 0 is 0 and gets no gradient.  ws: ctu_seg_loss_ws_floats
+ * floats, 16-byte aligned, kept until ctu_seg_loss_bwd, which writes the sum of the four terms' gradients, each times its
+ * upstream gradient g_* (one device float, read in place; NULL = 1); accumulate != 0: gpred +=.
+ * Refused: N <= 0, V <= 0, w <= 0, focal_gamma < 0, alpha or beta < 0, a missing required pointer. */
+typedef struct ctu_seg_loss_cfg {
+    float ce_lambda, dice_lambda, tversky_lambda, boundary_lambda;
+    float w0, w1;            /* class weights of the cross-entropy */
+    float focal_gamma;
+    float tversky_alpha, tversky_beta;
+    int dice_softmax;
+} ctu_seg_loss_cfg;
+size_t ctu_seg_loss_ws_floats(int N, int64_t V);
+int ctu_seg_loss_fwd(const float* pred, const float* target, const float* phi, int N, int64_t V,
+                     const ctu_seg_loss_cfg* cfg, float* terms, float* ws, void* stream);
+int ctu_seg_loss_bwd(const float* pred, const float* target, const float* phi, int N, int64_t V,
+                     const ctu_seg_loss_cfg* cfg, const float* ws, const float* g_ce, const float* g_dice,
+                     const float* g_tversky, const float* g_boundary, float* gpred, int accumulate, void* stream);
+
 /* -------------------------------------------------------------- utilities ---- */
 /* Additive skip connection, UNet(cat=False): out = act_a(a) + act_b(b) on channels-last tensors, where act_x is the
  * lazy BatchNorm(+ReLU) transform of that operand (scale/shift NULL: identity).  b == NULL: out = act_a(a), which is
