@@ -198,6 +198,9 @@ SIGNATURES = {
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),
     "ctu_window_finalize": (I, [P, P, I, L, P, P, P]),
+    "ctu_extract_patches_flip": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
+    "ctu_window_accumulate_flip": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P, P, P]),
+    "ctu_window_finalize_stats": (I, [P, P, P, P, I, L, P, P, P, P, P, P]),
     "ctu_flap_count": (I, [P, I, I, L, P, P]),
     "ctu_flap_draw": (I, [P, I, I, I, I, I, P, I, P, U, F, I, I, I, P, P, U, F, F, I, P, P]),
     "ctu_flap_apply": (I, [P, I, P, I, I, I, I, P, I, P, P, P, U, I, P, I, P, P, P]),

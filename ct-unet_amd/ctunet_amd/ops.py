@@ -1316,6 +1316,77 @@ def window_finalize(num: torch.Tensor, wsum: torch.Tensor, probs: torch.Tensor,
                                                _stream()), "window_finalize")
 
 
+def _flip_word(flip: torch.Tensor) -> torch.Tensor:
+    if not (flip.is_cuda and flip.dtype == torch.int32 and flip.numel() == 1):
+        raise RuntimeError("ctunet_amd: the flip word must be one int32 on the GPU")
+    return flip
+
+
+def extract_patches_flip(vol: torch.Tensor, coords: torch.Tensor, patch: Tuple[int, int, int],
+                         flip: torch.Tensor) -> torch.Tensor:
+    """extract_patches with every patch mirrored on the axes of the flip word (device int32 [1]: bit 0 = x, 1 = y, 2 = z);
+    the zero padding of an overhanging tile is mirrored with it.  At flip 0 the bits of extract_patches.  16-byte row
+    accesses where the volume row allows; patch[2] a multiple of 4."""
+    _need_cuda(vol, "volume")
+    _need_cuda(coords, "patch coordinates")
+    if vol.dim() != 4 or coords.dim() != 2 or coords.shape[1] != 3 or coords.dtype != torch.int32:
+        raise RuntimeError("ctunet_amd: extract_patches_flip expects vol [C,D,H,W] and int32 coords [P,3]")
+    vol, coords = vol.contiguous(), coords.contiguous()
+    c, d, h, w = vol.shape
+    p = coords.shape[0]
+    out = torch.empty((p, c) + tuple(patch), dtype=torch.float32, device=vol.device)
+    _lib.check(_lib.load().ctu_extract_patches_flip(vol.data_ptr(), coords.data_ptr(), _flip_word(flip).data_ptr(), p, c, d, h,
+                                                    w, patch[0], patch[1], patch[2], out.data_ptr(), _stream()),
+               "extract_patches_flip")
+    return out
+
+
+def window_accumulate_flip(patches: torch.Tensor, coords: torch.Tensor, valid: torch.Tensor, box: torch.Tensor,
+                           flip: torch.Tensor, tables: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], wmin: float,
+                           extent: Tuple[int, int, int], num: torch.Tensor, wsum: Optional[torch.Tensor],
+                           sq: Optional[torch.Tensor] = None, sh: Optional[torch.Tensor] = None) -> None:
+    """window_accumulate for a mirrored pass: the patch predictions are read at the mirrored patch-local index (flip:
+    device int32 [1]), the weights at the un-mirrored one.  sq [K,D,H,W]: also sq += w*y*y; sh [D,H,W]: also
+    sh += w*h(y), the normalised entropy of the contribution (K >= 2)."""
+    for t, nm in ((patches, "patches"), (coords, "coordinates"), (valid, "valid flags"), (box, "box origin"), (num, "num")):
+        _need_cuda(t, nm)
+        assert t.is_contiguous(), nm
+    b, k, pd, ph, pw = patches.shape
+    _, d, h, w = num.shape
+    wz, wy, wx = tables
+    for t, shp in ((wsum, num.shape[1:]), (sq, num.shape), (sh, num.shape[1:])):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == shp), "accumulators"
+    assert num.shape[0] == k, "accumulator shapes"
+    assert coords.shape == (b, 3) and valid.numel() == b and box.numel() == 3 and coords.dtype == torch.int32
+    assert all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+               for t, n in zip(tables, (pd, ph, pw))), "weight tables"
+    _lib.check(_lib.load().ctu_window_accumulate_flip(patches.data_ptr(), coords.data_ptr(), valid.data_ptr(), box.data_ptr(),
+                                                      _flip_word(flip).data_ptr(), b, k, d, h, w, pd, ph, pw, wz.data_ptr(),
+                                                      wy.data_ptr(), wx.data_ptr(), float(wmin), extent[0], extent[1],
+                                                      extent[2], num.data_ptr(), _ptr(wsum), _ptr(sq), _ptr(sh), _stream()),
+               "window_accumulate_flip")
+
+
+def window_finalize_stats(num: torch.Tensor, wsum: torch.Tensor, probs: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                          sq: Optional[torch.Tensor] = None, sh: Optional[torch.Tensor] = None,
+                          var: Optional[torch.Tensor] = None, ent: Optional[torch.Tensor] = None,
+                          mi: Optional[torch.Tensor] = None) -> None:
+    """window_finalize plus var [K,D,H,W] = max(sq/wsum - probs^2, 0) (may be sq), ent [D,H,W] = h(probs) and
+    mi [D,H,W] = max(h(probs) - sh/wsum, 0), each only where given; everything 0 where wsum == 0."""
+    _need_cuda(num, "num")
+    _need_cuda(wsum, "wsum")
+    _need_cuda(probs, "probs")
+    k = num.shape[0]
+    v = wsum.numel()
+    assert num.is_contiguous() and wsum.is_contiguous() and probs.is_contiguous() and num.numel() == k * v == probs.numel()
+    assert labels is None or (labels.is_cuda and labels.dtype == torch.uint8 and labels.numel() == v and labels.is_contiguous())
+    for t, n in ((sq, k * v), (var, k * v), (sh, v), (ent, v), (mi, v)):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n), "statistics"
+    _lib.check(_lib.load().ctu_window_finalize_stats(num.data_ptr(), wsum.data_ptr(), _ptr(sq), _ptr(sh), k, v, probs.data_ptr(),
+                                                     _ptr(labels), _ptr(var), _ptr(ent), _ptr(mi), _stream()),
+               "window_finalize_stats")
+
+
 def _tensor_table(tensors):
     """(pointer array, element-count array, length) over the tensors of a list that are not None: the first three arguments
     of ctu_scale_tensors / ctu_unscale_tensors."""

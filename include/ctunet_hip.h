@@ -922,6 +922,32 @@ int ctu_window_accumulate(const float* patches, const int32_t* coords, const int
 int ctu_window_finalize(const float* num, const float* wsum, int K, int64_t V, float* probs, uint8_t* labels,
                         void* stream);
 
+/* Test-time mirroring, ensembles and uncertainty for sliding-window inference (rule: ctunet_amd/inference.py).  The three
+ * entry points above with a flip word, flip: DEVICE int32 [1], bit 0 = x, bit 1 = y, bit 2 = z (only the low 3 bits are
+ * read; on a mirrored axis a patch-local index a becomes P_a - 1 - a), so one captured launch serves every pass.
+ *   extract_patches_flip: out [P,C,pd,ph,pw] = the zero-padded window of ctu_extract_patches, mirrored; at flip 0 the
+ *     same bits.  16-byte row reads where W % 4 == 0, vol is 16-byte aligned and the source quad starts at a multiple of
+ *     4 inside its row, scalar reads otherwise.  pw a multiple of 4, P * C <= 65535, pd * ph * pw < 2^31; out 16-byte
+ *     aligned, vol at any float address.
+ *   window_accumulate_flip: ctu_window_accumulate reading patches[p][c] at the mirrored local index (the weight tables
+ *     stay indexed by the un-mirrored position), and, per valid patch in order,
+ *       sq [K,D,H,W] += w * (y * y)   if sq is non-NULL
+ *       sh [D,H,W]   += w * h(y)      if sh is non-NULL (K >= 2),  h(y) = -sum_k q_k ln q_k / ln K,
+ *                                     q_k = max(y_k, 0) / sum_j max(y_j, 0), 0 for a zero sum, 0 ln 0 = 0.
+ *     Limits and alignment as ctu_window_accumulate; sq and sh 16-byte aligned.
+ *   window_finalize_stats: probs and labels as ctu_window_finalize, and where the pointer is non-NULL
+ *       var [K,V] = max(sq / wsum - probs^2, 0)  (needs sq; var may be sq itself)
+ *       ent [V]   = h(probs)                     (K >= 2)
+ *       mi  [V]   = max(h(probs) - sh / wsum, 0) (needs sh, K >= 2);   all 0 where wsum == 0. */
+int ctu_extract_patches_flip(const float* vol, const int32_t* coords, const int32_t* flip, int P, int C, int D, int H,
+                             int W, int pd, int ph, int pw, float* out, void* stream);
+int ctu_window_accumulate_flip(const float* patches, const int32_t* coords, const int32_t* valid, const int32_t* box,
+                               const int32_t* flip, int B, int K, int D, int H, int W, int pd, int ph, int pw,
+                               const float* wz, const float* wy, const float* wx, float wmin, int bz, int by, int bx,
+                               float* num, float* wsum, float* sq, float* sh, void* stream);
+int ctu_window_finalize_stats(const float* num, const float* wsum, const float* sq, const float* sh, int K, int64_t V,
+                              float* probs, uint8_t* labels, float* var, float* ent, float* mi, void* stream);
+
 /* Flap-reconstruction augmentation (SkullRandomHole + SaltAndPepper of ctunet/pytorch/transforms.py:13-95,131-134 and
  * ctunet/utilities.py:127-178, on the device; rules pinned in ctunet_amd/transforms.py).  Batch of N skulls
  * [N,1,D,H,W], float32 (u8 = 0) or uint8 (u8 = 1); a voxel's value is its uint8 cast (truncation, float values in
