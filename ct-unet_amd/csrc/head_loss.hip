@@ -16,6 +16,8 @@ constexpr int MAXCO = 4;
 
 struct HeadP {
     const void* in;          // channels-last activations, element type T of the kernel template
+    const void* in_b;        // two-segment kernels: padded channels [CP/2, CP) live here with stride in_cs_b ...
+    int in_cs_b;             // ... and `in` holds [0, CP/2) only (both unused by the one-buffer kernels)
     const float* in_scale;
     const float* in_shift;
     const float* w;
@@ -28,14 +30,16 @@ struct HeadP {
 };
 
 // activated input channels of one voxel -> logits -> y (post softmax/sigmoid)
-template <int CP, class T>
+// S2: the voxel's channels come from two segments (HeadP::in_b); a quad never straddles them
+template <int CP, class T, bool S2>
 __device__ __forceinline__ void head_point(const HeadP& p, const float* sWp, const float* sB, int64_t gv,
                                            float (&a)[CP], float (&lg)[MAXCO], float (&u)[MAXCO],
                                            float (&y)[MAXCO]) {
     const T* src = reinterpret_cast<const T*>(p.in) + (size_t)gv * p.in_cs;
+    const T* src_b = S2 ? reinterpret_cast<const T*>(p.in_b) + (size_t)gv * p.in_cs_b : nullptr;
 #pragma unroll
     for (int qd = 0; qd < CP / 4; ++qd) {
-        float4 v = ld4<T>(src + qd * 4);
+        float4 v = ld4<T>((S2 && qd >= CP / 8) ? src_b + (qd - CP / 8) * 4 : src + qd * 4);
         if (p.in_scale) {
             const float4 sc = *reinterpret_cast<const float4*>(p.in_scale + qd * 4);
             const float4 sh = *reinterpret_cast<const float4*>(p.in_shift + qd * 4);
@@ -89,15 +93,15 @@ __device__ __forceinline__ void softmax2(float a, float b, float& sa, float& sb)
     sa = ea / (ea + eb); sb = eb / (ea + eb);
 }
 
-template <int CP, class T>
-__global__ __launch_bounds__(HB) void head_fwd_kernel(HeadP p, float* __restrict__ out0, float* __restrict__ out1) {
+template <int CP, class T, bool S2>
+__device__ __forceinline__ void head_fwd_body(const HeadP& p, float* __restrict__ out0, float* __restrict__ out1) {
     __shared__ float sWp[MAXCO * CP];
     __shared__ float sB[MAXCO];
     head_load_weights<CP>(p, sWp, sB);
     const int64_t total = (int64_t)p.N * p.V;
     for (int64_t gv = (int64_t)blockIdx.x * HB + threadIdx.x; gv < total; gv += (int64_t)gridDim.x * HB) {
         float a[CP], lg[MAXCO], u[MAXCO], y[MAXCO];
-        head_point<CP, T>(p, sWp, sB, gv, a, lg, u, y);
+        head_point<CP, T, S2>(p, sWp, sB, gv, a, lg, u, y);
         const int64_t n = gv / p.V, v = gv % p.V;
         if (p.head_mode == 0) {
 #pragma unroll
@@ -115,19 +119,30 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(HeadP p, float* __restrict
     }
 }
 
+template <int CP, class T>
+__global__ __launch_bounds__(HB) void head_fwd_kernel(HeadP p, float* __restrict__ out0, float* __restrict__ out1) {
+    head_fwd_body<CP, T, false>(p, out0, out1);
+}
+// the input voxel in two segments of CP/2 channels (HeadP::in / in_b): same loads, same arithmetic
+template <int CP, class T>
+__global__ __launch_bounds__(HB) void head_fwd_seg2_kernel(HeadP p, float* __restrict__ out0, float* __restrict__ out1) {
+    head_fwd_body<CP, T, true>(p, out0, out1);
+}
+
 // partial layout per block: [MAXCO*CP dW][MAXCO db]
 // Backward with CP/4 lanes per voxel: every lane owns one channel quad (16-byte coalesced loads/stores, ~50 VGPRs so
 // the streaming loop is hidden by occupancy instead of being latency-bound at one voxel per 64-accumulator thread).
 // Logits are quad partial sums reduced across the voxel's lanes; block partials keep the layout above.
-template <int CP, class T>
+// S2: lanes with qd >= Q/2 read HeadP::in_b and write gin_b, at channel (qd - Q/2) * 4 of those segments.
+template <int CP, class T, bool S2>
 // bn_partials != NULL: the first bn_cp input channels are relu(BN(raw conv output)) of ONE layer whose activated-output
 // gradient is complete with this kernel's gin (the decoder's last conv feeding the head): the kernel also emits that
 // BatchNorm's backward reduction rows {sum gz, sum gz * xhat} per block (layout of bn_relu_bwd_reduce).
-__global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __restrict__ g0,
-                                                        const float* __restrict__ g1, T* __restrict__ gin,
-                                                        int gin_cs, float* __restrict__ partials,
-                                                        const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
-                                                        int bn_cp, float* __restrict__ bn_partials) {
+__device__ __forceinline__ void head_bwd_q_body(const HeadP& p, const float* __restrict__ g0,
+                                                const float* __restrict__ g1, T* __restrict__ gin, int gin_cs,
+                                                T* __restrict__ gin_b, int gin_cs_b, float* __restrict__ partials,
+                                                const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
+                                                int bn_cp, float* __restrict__ bn_partials) {
     constexpr int Q = CP / 4;
     __shared__ float sWp[MAXCO * CP];
     __shared__ float sB[MAXCO];
@@ -154,10 +169,14 @@ __global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __
         mu = *reinterpret_cast<const float4*>(bn_mean + qd * 4);
         is = *reinterpret_cast<const float4*>(bn_invstd + qd * 4);
     }
+    // this lane's quad: where it is read and where its gradient goes (loop-invariant; per lane with two segments)
+    const bool seg_b = S2 && qd >= Q / 2;
+    const int qoff = (seg_b ? qd - Q / 2 : qd) * 4;
     const int64_t total = (int64_t)p.N * p.V;
     constexpr int VPB = HB / Q;                       // voxels per block and iteration
     for (int64_t gv = (int64_t)blockIdx.x * VPB + threadIdx.x / Q; gv < total; gv += (int64_t)gridDim.x * VPB) {
-        const float4 raw = ld4<T>(reinterpret_cast<const T*>(p.in) + (size_t)gv * p.in_cs + qd * 4);
+        const float4 raw = ld4<T>((seg_b ? reinterpret_cast<const T*>(p.in_b) : reinterpret_cast<const T*>(p.in)) +
+                                  (size_t)gv * (seg_b ? p.in_cs_b : p.in_cs) + qoff);
         const float4 a = xform4(raw, sc, sh, xrelu);
         float lg[MAXCO], u[MAXCO], y[MAXCO], gy[MAXCO];
 #pragma unroll
@@ -229,7 +248,7 @@ __global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __
             for (int j = 0; j < 4; ++j) dw[co][j] = fmaf(gl[co], av[j], dw[co][j]);
         }
         o = rnd4<T>(o);                      // the reduction sees what the BatchNorm-backward apply pass will read back
-        st4<T>(gin + (size_t)gv * gin_cs + qd * 4, o);
+        st4<T>((seg_b ? gin_b : gin) + (size_t)gv * (seg_b ? gin_cs_b : gin_cs) + qoff, o);
         if (bnq) {
             float gz;
             gz = (fmaf(raw.x, sc.x, sh.x) > 0.f) ? o.x : 0.f; r1.x += gz; r2.x += gz * (raw.x - mu.x) * is.x;
@@ -276,6 +295,25 @@ __global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __
             for (int w = 0; w < HB / 64; ++w) s += sRed[w][col];
             bn_partials[(size_t)blockIdx.x * 2 * bn_cp + i] = s;
         }
+}
+
+template <int CP, class T>
+__global__ __launch_bounds__(HB) void head_bwd_q_kernel(HeadP p, const float* __restrict__ g0,
+                                                        const float* __restrict__ g1, T* __restrict__ gin,
+                                                        int gin_cs, float* __restrict__ partials,
+                                                        const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
+                                                        int bn_cp, float* __restrict__ bn_partials) {
+    head_bwd_q_body<CP, T, false>(p, g0, g1, gin, gin_cs, nullptr, 0, partials, bn_mean, bn_invstd, bn_cp, bn_partials);
+}
+// input and input gradient in two segments of CP/2 channels each
+template <int CP, class T>
+__global__ __launch_bounds__(HB) void head_bwd_q_seg2_kernel(HeadP p, const float* __restrict__ g0,
+                                                             const float* __restrict__ g1, T* __restrict__ gin,
+                                                             int gin_cs, T* __restrict__ gin_b, int gin_cs_b,
+                                                             float* __restrict__ partials, const float* __restrict__ bn_mean,
+                                                             const float* __restrict__ bn_invstd, int bn_cp,
+                                                             float* __restrict__ bn_partials) {
+    head_bwd_q_body<CP, T, true>(p, g0, g1, gin, gin_cs, gin_b, gin_cs_b, partials, bn_mean, bn_invstd, bn_cp, bn_partials);
 }
 
 // one block per output (dW element or db element); fixed-order tree over the block partials
@@ -466,17 +504,35 @@ __global__ __launch_bounds__(HB) void loss_bwd_kernel(const float* __restrict__ 
 // =================================================================== C ABI
 static int fill_head(HeadP& p, const void* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                      int in_relu, const float* w, const float* bias, const int32_t* imap, int Ci, int Co, int act,
-                     int head_mode, int N, int64_t V, const char* name) {
+                     int head_mode, int N, int64_t V, const char* name, int buf_cp = 0) {
+    if (buf_cp == 0) buf_cp = cin_p;             // channels the buffer at `in` holds (two segments: half of cin_p)
     CTU_REQUIRE(in && w, "%s: null pointer", name);
     CTU_REQUIRE(cin_p == 8 || cin_p == 16 || cin_p == 32, "%s: cin_p=%d unsupported (8, 16 or 32)", name, cin_p);
     CTU_REQUIRE(Co >= 1 && Co <= MAXCO && Ci >= 1 && Ci <= cin_p, "%s: Co=%d Ci=%d", name, Co, Ci);
     CTU_REQUIRE(head_mode == 0 || Co == 3, "%s: SP re-encoding needs 3 output channels", name);
     CTU_REQUIRE(head_mode >= 0 && head_mode <= 2, "%s: head_mode=%d", name, head_mode);
-    CTU_REQUIRE(in_cs >= cin_p && in_cs % 4 == 0, "%s: bad stride", name);
+    CTU_REQUIRE(in_cs >= buf_cp && in_cs % 4 == 0, "%s: bad stride", name);
     CTU_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "%s: scale/shift must come together", name);
+    p.in_b = nullptr; p.in_cs_b = 0;
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.w = w; p.bias = bias; p.imap = imap;
     p.in_cs = in_cs; p.in_relu = in_relu; p.Ci = Ci; p.Co = Co; p.act = act; p.head_mode = head_mode; p.N = N; p.V = V; p.gscale = 1.f;
     p.gscale_dev = nullptr;
+    return CTU_OK;
+}
+
+// Two-segment input: in_a holds padded channels [0, cp), in_b holds [cp, 2 cp); the kernels see 2 cp channels.
+static int fill_head_seg2(HeadP& p, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp, const float* in_scale,
+                          const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap, int Ci,
+                          int Co, int act, int head_mode, int N, int64_t V, const char* name) {
+    CTU_REQUIRE(in_a && in_b, "%s: null segment", name);
+    CTU_REQUIRE(cp == 4 || cp == 8 || cp == 16, "%s: cp=%d per segment unsupported (4, 8 or 16)", name, cp);
+    CTU_REQUIRE(cs_b >= cp && cs_b % 4 == 0, "%s: bad stride of the second segment", name);
+    CTU_REQUIRE(((reinterpret_cast<uintptr_t>(in_a) | reinterpret_cast<uintptr_t>(in_b)) & 15) == 0,
+                "%s: segments must be 16-byte aligned", name);
+    CTU_REQUIRE(N > 0 && V > 0, "%s: empty volume", name);
+    int rc = fill_head(p, in_a, cs_a, 2 * cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode, N, V, name, cp);
+    if (rc != CTU_OK) return rc;
+    p.in_b = in_b; p.in_cs_b = cs_b;
     return CTU_OK;
 }
 
@@ -501,29 +557,66 @@ int head_fwd_impl(const T* in, int in_cs, int cin_p, const float* in_scale, cons
 }
 
 template <class T>
+int head_fwd_seg2_impl(const T* in_a, int cs_a, const T* in_b, int cs_b, int cp, const float* in_scale, const float* in_shift,
+                       int in_relu, const float* w, const float* bias, const int32_t* imap, int Ci, int Co, int act,
+                       int head_mode, float* out0, float* out1, int N, int64_t nvox_per_item, void* stream) {
+    HeadP p;
+    int rc = fill_head_seg2(p, in_a, cs_a, in_b, cs_b, cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode, N,
+                            nvox_per_item, "head_fwd_seg2");
+    if (rc != CTU_OK) return rc;
+    CTU_REQUIRE(out0 && (head_mode == 0 || out1), "head_fwd_seg2: null output");
+    const int nb = head_blocks((int64_t)N * nvox_per_item);
+    hipStream_t st = (hipStream_t)stream;
+    if (cp == 4) head_fwd_seg2_kernel<8, T><<<nb, HB, 0, st>>>(p, out0, out1);
+    else if (cp == 8) head_fwd_seg2_kernel<16, T><<<nb, HB, 0, st>>>(p, out0, out1);
+    else head_fwd_seg2_kernel<32, T><<<nb, HB, 0, st>>>(p, out0, out1);
+    CTU_CHECK_LAUNCH("head_fwd_seg2");
+    return CTU_OK;
+}
+
+// in_b != NULL: two segments of cin_p / 2 channels (in / in_b, gin / gin_b); one buffer of cin_p channels otherwise
+template <class T>
 int head_bwd_impl(const T* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift, int in_relu, const float* w,
                   const float* bias, const int32_t* imap, int Ci, int Co, int act, int head_mode, const float* g0, const float* g1,
                   T* gin, int gin_cs, float* dw, float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
                   const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream, float gscale = 1.f,
-                  const float* gscale_dev = nullptr) {
+                  const float* gscale_dev = nullptr, const T* in_b = nullptr, int in_cs_b = 0, T* gin_b = nullptr,
+                  int gin_cs_b = 0) {
+    const bool seg2 = in_b != nullptr || gin_b != nullptr;
+    const int seg_cp = seg2 ? cin_p / 2 : cin_p;                 // channels a gin buffer holds
     CTU_REQUIRE(!tail || (bn_partials && tail->gamma && tail->invstd && tail->dgamma && tail->dbeta && tail->coef &&
                           tail->C > 0 && tail->C <= bn_cp && tail->count > 0 && (!tail->running_mean || (tail->mean && tail->running_var))),
                 "head_bwd: incomplete BatchNorm tail");
     HeadP p;
-    int rc = fill_head(p, in, in_cs, cin_p, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode, N,
-                       nvox_per_item, "head_bwd");
+    int rc = seg2 ? fill_head_seg2(p, in, in_cs, in_b, in_cs_b, cin_p / 2, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act,
+                                   head_mode, N, nvox_per_item, "head_bwd_seg2")
+                  : fill_head(p, in, in_cs, cin_p, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode, N,
+                              nvox_per_item, "head_bwd");
     if (rc != CTU_OK) return rc;
     p.gscale = gscale;
     p.gscale_dev = gscale_dev;
     CTU_REQUIRE(g0 && (head_mode == 0 || g1) && gin && dw && db && ws, "head_bwd: null pointer");
-    CTU_REQUIRE(gin_cs >= cin_p && gin_cs % 4 == 0, "head_bwd: bad gin stride");
+    CTU_REQUIRE(gin_cs >= seg_cp && gin_cs % 4 == 0, "head_bwd: bad gin stride");
+    CTU_REQUIRE(!seg2 || (gin_b && gin_cs_b >= seg_cp && gin_cs_b % 4 == 0), "head_bwd_seg2: bad second gradient segment");
+    CTU_REQUIRE(!seg2 || ((reinterpret_cast<uintptr_t>(gin) | reinterpret_cast<uintptr_t>(gin_b)) & 15) == 0,
+                "head_bwd_seg2: gradient segments must be 16-byte aligned");
     CTU_REQUIRE(!bn_partials || (bn_mean && bn_invstd && in_scale && in_relu && bn_cp > 0 && bn_cp % 4 == 0 && bn_cp <= cin_p),
                 "head_bwd: the BatchNorm reduction needs mean/invstd, a BN+ReLU input transform and bn_cp <= cin_p (bn_cp=%d)", bn_cp);
     const int nb = head_blocks((int64_t)N * nvox_per_item);
     hipStream_t st = (hipStream_t)stream;
     const int nfin = Co * Ci + Co + (tail ? 1 : 0);      // + the BatchNorm finalize block
     const ctu_bn_bwd_tail tl = bwd_tail_or_off(tail);
-    if (cin_p == 8) {
+    if (seg2) {
+        if (cin_p == 8)
+            head_bwd_q_seg2_kernel<8, T><<<nb, HB, 0, st>>>(p, g0, g1, gin, gin_cs, gin_b, gin_cs_b, ws, bn_mean, bn_invstd, bn_cp, bn_partials);
+        else if (cin_p == 16)
+            head_bwd_q_seg2_kernel<16, T><<<nb, HB, 0, st>>>(p, g0, g1, gin, gin_cs, gin_b, gin_cs_b, ws, bn_mean, bn_invstd, bn_cp, bn_partials);
+        else
+            head_bwd_q_seg2_kernel<32, T><<<nb, HB, 0, st>>>(p, g0, g1, gin, gin_cs, gin_b, gin_cs_b, ws, bn_mean, bn_invstd, bn_cp, bn_partials);
+        if (cin_p == 8) head_bwd_final_kernel<8><<<nfin, HB, 0, st>>>(ws, nb, Ci, Co, imap, dw, db, bn_partials, bn_cp, tl);
+        else if (cin_p == 16) head_bwd_final_kernel<16><<<nfin, HB, 0, st>>>(ws, nb, Ci, Co, imap, dw, db, bn_partials, bn_cp, tl);
+        else head_bwd_final_kernel<32><<<nfin, HB, 0, st>>>(ws, nb, Ci, Co, imap, dw, db, bn_partials, bn_cp, tl);
+    } else if (cin_p == 8) {
         head_bwd_q_kernel<8, T><<<nb, HB, 0, st>>>(p, g0, g1, gin, gin_cs, ws, bn_mean, bn_invstd, bn_cp, bn_partials);
         head_bwd_final_kernel<8><<<nfin, HB, 0, st>>>(ws, nb, Ci, Co, imap, dw, db, bn_partials, bn_cp, tl);
     } else if (cin_p == 16) {
@@ -598,6 +691,66 @@ extern "C" int ctu_lp_head_bwd_bn_dscale(int dtype, const void* in, int in_cs, i
                                                    head_mode, g0, g1, (T*)gin, gin_cs, dw, db, ws, N, nvox_per_item, bn_mean,
                                                    bn_invstd, bn_cp, bn_partials, tail, stream, 1.f, gscale));
 }
+
+// ---- two-segment forms: (in_a, cs_a) = padded channels [0, cp), (in_b, cs_b) = [cp, 2 cp); vectors, w / imap, ws, dW / db
+// and the BatchNorm rows are those of the one-buffer entries called with cin_p = 2 cp
+extern "C" int ctu_head_fwd_seg2(const float* in_a, int cs_a, const float* in_b, int cs_b, int cp, const float* in_scale,
+                                 const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap,
+                                 int Ci, int Co, int act, int head_mode, float* out0, float* out1, int N,
+                                 int64_t nvox_per_item, void* stream) {
+    return head_fwd_seg2_impl<float>(in_a, cs_a, in_b, cs_b, cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode,
+                                     out0, out1, N, nvox_per_item, stream);
+}
+extern "C" int ctu_lp_head_fwd_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                                    const float* in_scale, const float* in_shift, int in_relu, const float* w, const float* bias,
+                                    const int32_t* imap, int Ci, int Co, int act, int head_mode, float* out0, float* out1, int N,
+                                    int64_t nvox_per_item, void* stream) {
+    CTU_DISPATCH_LP(dtype, return head_fwd_seg2_impl<T>((const T*)in_a, cs_a, (const T*)in_b, cs_b, cp, in_scale, in_shift, in_relu, w,
+                                                        bias, imap, Ci, Co, act, head_mode, out0, out1, N, nvox_per_item, stream));
+}
+
+#define CTU_HEAD_SEG2_CHECK(name)                                                                       \
+    CTU_REQUIRE(in_a && in_b && gin_a && gin_b, name ": null segment");                                 \
+    CTU_REQUIRE(cp == 4 || cp == 8 || cp == 16, name ": cp=%d per segment unsupported (4, 8 or 16)", cp)
+
+extern "C" int ctu_head_bwd_bn_seg2(const float* in_a, int cs_a, const float* in_b, int cs_b, int cp, const float* in_scale,
+                                    const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap,
+                                    int Ci, int Co, int act, int head_mode, const float* g0, const float* g1, float* gin_a,
+                                    int gcs_a, float* gin_b, int gcs_b, float* dw, float* db, float* ws, int N,
+                                    int64_t nvox_per_item, const float* bn_mean, const float* bn_invstd, int bn_cp,
+                                    float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream) {
+    CTU_HEAD_SEG2_CHECK("head_bwd_bn_seg2");
+    return head_bwd_impl<float>(in_a, cs_a, 2 * cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act, head_mode, g0, g1, gin_a,
+                                gcs_a, dw, db, ws, N, nvox_per_item, bn_mean, bn_invstd, bn_cp, bn_partials, tail, stream, 1.f, nullptr,
+                                in_b, cs_b, gin_b, gcs_b);
+}
+extern "C" int ctu_lp_head_bwd_bn_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                                       const float* in_scale, const float* in_shift, int in_relu, const float* w, const float* bias,
+                                       const int32_t* imap, int Ci, int Co, int act, int head_mode, const float* g0,
+                                       const float* g1, void* gin_a, int gcs_a, void* gin_b, int gcs_b, float* dw, float* db,
+                                       float* ws, int N, int64_t nvox_per_item, const float* bn_mean, const float* bn_invstd,
+                                       int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, float gscale, void* stream) {
+    CTU_HEAD_SEG2_CHECK("lp_head_bwd_bn_seg2");
+    CTU_DISPATCH_LP(dtype, return head_bwd_impl<T>((const T*)in_a, cs_a, 2 * cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act,
+                                                   head_mode, g0, g1, (T*)gin_a, gcs_a, dw, db, ws, N, nvox_per_item, bn_mean,
+                                                   bn_invstd, bn_cp, bn_partials, tail, stream, gscale, nullptr, (const T*)in_b,
+                                                   cs_b, (T*)gin_b, gcs_b));
+}
+extern "C" int ctu_lp_head_bwd_bn_dscale_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                                              const float* in_scale, const float* in_shift, int in_relu, const float* w,
+                                              const float* bias, const int32_t* imap, int Ci, int Co, int act, int head_mode,
+                                              const float* g0, const float* g1, void* gin_a, int gcs_a, void* gin_b, int gcs_b,
+                                              float* dw, float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
+                                              const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail,
+                                              const float* gscale, void* stream) {
+    CTU_HEAD_SEG2_CHECK("lp_head_bwd_bn_dscale_seg2");
+    CTU_REQUIRE(gscale, "lp_head_bwd_bn_dscale_seg2: null gscale");
+    CTU_DISPATCH_LP(dtype, return head_bwd_impl<T>((const T*)in_a, cs_a, 2 * cp, in_scale, in_shift, in_relu, w, bias, imap, Ci, Co, act,
+                                                   head_mode, g0, g1, (T*)gin_a, gcs_a, dw, db, ws, N, nvox_per_item, bn_mean,
+                                                   bn_invstd, bn_cp, bn_partials, tail, stream, 1.f, gscale, (const T*)in_b, cs_b,
+                                                   (T*)gin_b, gcs_b));
+}
+#undef CTU_HEAD_SEG2_CHECK
 
 extern "C" size_t ctu_loss_ws_floats(int N, int64_t V) {
     (void)V;

@@ -118,6 +118,8 @@ SIGNATURES = {
     "ctu_head_bwd": (I, [P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P]),
     "ctu_head_bwd_num_blocks": (I, [I, L]),
     "ctu_head_bwd_bn": (I, [P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P, P, I, P, P, P]),
+    "ctu_head_fwd_seg2": (I, [P, I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, I, L, P]),
+    "ctu_head_bwd_bn_seg2": (I, [P, I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, I, P, P, P, I, L, P, P, I, P, P, P]),
     "ctu_loss_ws_floats": (Z, [I, L]),
     "ctu_loss_fwd": (I, [P, P, I, L, F, F, I, P, P, P]),
     "ctu_loss_bwd": (I, [P, P, I, L, F, F, I, P, P, P, P, I, P]),
@@ -254,6 +256,9 @@ SIGNATURES = {
     "ctu_lp_head_fwd": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, I, L, P]),
     "ctu_lp_head_bwd_bn": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P, P, I, P, P, F, P]),
     "ctu_lp_head_bwd_bn_dscale": (I, [I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P, I, L, P, P, I, P, P, P, P]),
+    "ctu_lp_head_fwd_seg2": (I, [I, P, I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, I, L, P]),
+    "ctu_lp_head_bwd_bn_seg2": (I, [I, P, I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, I, P, P, P, I, L, P, P, I, P, P, F, P]),
+    "ctu_lp_head_bwd_bn_dscale_seg2": (I, [I, P, I, P, I, I, P, P, I, P, P, P, I, I, I, I, P, P, P, I, P, I, P, P, P, I, L, P, P, I, P, P, P, P]),
     "ctu_scale_tensors": (I, [P, P, I, F, P, P]),
     "ctu_unscale_tensors": (I, [P, P, I, P, P, P]),
     "ctu_loss_scale_update": (I, [P, P, P, P, F, F, I, P]),

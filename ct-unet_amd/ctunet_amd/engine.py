@@ -12,7 +12,8 @@ Data flow (DESIGN.md has the picture):
     (per-channel scale/shift from ``bn_finalize``), so BN/ReLU never cost an HBM pass forward;
   * the skip concat is free: the decoder's second conv writes channels [0, Cp) and the encoder's
     second conv writes channels [Cp, 2Cp) of one buffer per resolution level
-    (``torch.cat((ubl, d), 1)``, models.py:249 -- upsampled first, skip second);
+    (``torch.cat((ubl, d), 1)``, models.py:249 -- upsampled first, skip second); at the top level the
+    two halves are two dense tensors that the head reads as two segments (SPLIT_CAT0 below);
   * backward re-reads the raw tensors and recomputes activations/pool argmax on the fly; nothing
     but raw conv outputs and per-channel statistics is saved.
 """
@@ -53,6 +54,20 @@ BN_TAIL = os.environ.get("CTUNET_BN_TAIL", "0") != "0"
 # BatchNorm-backward finalize launch (ops.WgradJobs; nothing reads dW before the optimizer or a gradient exchange) -- one
 # dependent launch less per conv layer on the backward chain (CTUNET_DEFER_WGRAD_REDUCE=0: reduce behind each kernel)
 DEFER_WGRAD_REDUCE = os.environ.get("CTUNET_DEFER_WGRAD_REDUCE", "1") != "0"
+# the top level's concat buffer (and its gradient mirror) is two dense [N, D, H, W, Cp] halves instead of one interleaved
+# [N, D, H, W, 2 Cp] tensor: at Cp = 8 a producer's half of a voxel is 32 bytes, so every kernel that streams one half of
+# the interleaved buffer moves whole 128-byte lines for half-used data.  Only the head touches whole voxels; it reads and
+# writes the two halves as two segments (ops.CL2).  Same values bit for bit.  CTUNET_SPLIT_CAT0=0: the interleaved buffer.
+SPLIT_CAT0 = os.environ.get("CTUNET_SPLIT_CAT0", "1") != "0"
+
+
+def _cat_halves(buf: torch.Tensor, cp: int):
+    """(decoder half, encoder half) of a level's concat buffer or of its gradient mirror, as raw slices: channel ranges
+    [0, cp) and [cp, 2 cp) of an interleaved [N, D, H, W, 2 cp] buffer, or the two dense tensors of a split [2, N, D, H, W, cp]
+    one."""
+    if buf.dim() == 6:
+        return CL(buf[0], 0, cp), CL(buf[1], 0, cp)
+    return CL(buf, 0, cp), CL(buf, cp, cp)
 
 
 @dataclass
@@ -357,7 +372,8 @@ class UNetEngine:
         adt = self.dtype
         cur = None if first_direct else ops.ncdhw_to_cl(x, dtype=adt)
         x_cl = cur
-        cat: List[torch.Tensor] = []     # concat buffer per level
+        cat: List[torch.Tensor] = []     # concat buffer per level ([N, D, H, W, 2 Cp]; split level 0: [2, N, D, H, W, Cp])
+        halves = []                      # its (decoder, encoder) halves as raw CL slices
         xf: List[torch.Tensor] = []      # [4, 2Cp] scale/shift/mean/invstd of the concat buffer
         pooled: List[CL] = []
         dskip: List[CL] = []
@@ -369,7 +385,10 @@ class UNetEngine:
         xf_off = 0
         for i, blk in enumerate(plan.enc):
             cp = pad8(blk.cout)
-            cat.append(torch.empty((n, dd, hh, ww, 2 * cp), dtype=adt, device=dev))
+            # (two-segment head kernels: at most 16 channels per segment)
+            split = SPLIT_CAT0 and i == 0 and cp <= 16
+            cat.append(torch.empty((2, n, dd, hh, ww, cp) if split else (n, dd, hh, ww, 2 * cp), dtype=adt, device=dev))
+            halves.append(_cat_halves(cat[i], cp))
             xf.append(xf_all[xf_off:xf_off + 8 * cp].view(4, 2 * cp))
             xf_off += 8 * cp
             t1 = CL(torch.empty((n, dd, hh, ww, cp), dtype=adt, device=dev), 0, cp)
@@ -384,7 +403,7 @@ class UNetEngine:
                                                           f"{blk.prefix}.{blk.first + 1}", blk.cin, blk.cout, imap, t1,
                                                           v1, training, n_upd, save)
             a2, recs[(blk.prefix, 2)] = self._conv_bn(P, a1, f"{blk.prefix}.{blk.first + 3}", f"{blk.prefix}.{blk.first + 4}",
-                                                      blk.cout, blk.cout, None, CL(cat[i], cp, cp), xf[i][:, cp:],
+                                                      blk.cout, blk.cout, None, halves[i][1], xf[i][:, cp:],
                                                       training, n_upd, save)
             dskip.append(a2)
             dd, hh, ww = dd // 2, hh // 2, ww // 2
@@ -439,17 +458,20 @@ class UNetEngine:
                 a1, recs[(blk.prefix, 1)] = self._conv_bn(P, up, f"{blk.prefix}.1", f"{blk.prefix}.2", ct, blk.cout, None,
                                                           t1, v1, training, n_upd, save)
             a2, recs[(blk.prefix, 2)] = self._conv_bn(P, a1, f"{blk.prefix}.4", f"{blk.prefix}.5", blk.cout, blk.cout, None,
-                                                      CL(cat[i], 0, cp), xf[i][:, :cp], training, n_upd, save)
+                                                      halves[i][0], xf[i][:, :cp], training, n_upd, save)
+            h_dec, h_enc = halves[i]
             if plan.skip == "cat":               # free concat: both producers wrote channel slices of cat[i]
-                cur = CL(cat[i], 0, 2 * cp, xf[i][0], xf[i][1], True)
+                if cat[i].dim() == 6:            # split top level: the head reads the two halves as two segments
+                    cur = ops.CL2(h_dec, h_enc, xf[i][0], xf[i][1], True)
+                else:
+                    cur = CL(cat[i], 0, 2 * cp, xf[i][0], xf[i][1], True)
                 cur_segs = ((blk.cout, 0), (blk.cout, cp))
             elif plan.skip == "none":
-                cur = CL(cat[i], 0, cp, xf[i][0][:cp], xf[i][1][:cp], True)
+                cur = h_dec.with_xf(xf[i][0][:cp], xf[i][1][:cp])
                 cur_segs = ((blk.cout, 0),)
             else:                                # "add": the sum of two differently normalised tensors is materialised
                 cur = CL(torch.empty((n, dd, hh, ww, cp), dtype=adt, device=dev), 0, cp)
-                ops.skip_add(CL(cat[i], 0, cp, xf[i][0][:cp], xf[i][1][:cp], True),
-                             CL(cat[i], cp, cp, xf[i][0][cp:], xf[i][1][cp:], True), cur)
+                ops.skip_add(h_dec.with_xf(xf[i][0][:cp], xf[i][1][:cp]), h_enc.with_xf(xf[i][0][cp:], xf[i][1][cp:]), cur)
                 cur_segs = ((blk.cout, 0),)
         # ---- head
         imap_h, _ = self._maps(cur_segs, cur.cp, dev)
@@ -604,28 +626,31 @@ class UNetEngine:
 
         cat, head_in = ctx["cat"], ctx["head_in"]
         gcat = [torch.empty_like(c) for c in cat]
+        ghalves = [_cat_halves(g, g.shape[-1] // (1 if g.dim() == 6 else 2)) for g in gcat]
         wl, bl = P[plan.head + ".weight"], P[plan.head + ".bias"]
         w2 = wl.detach().reshape(wl.shape[0], wl.shape[1])
         gsd = None if dyn is None else dyn.scale
         def g_skip_target(level: int) -> CL:
             """Where the gradient w.r.t. the tensor a decoder level hands on (cat / sum / plain output) is written."""
-            full = gcat[level].shape[-1]
-            return CL(gcat[level], 0, full if plan.skip == "cat" else full // 2)
+            g_dec, g_enc = ghalves[level]
+            if plan.skip != "cat":
+                return g_dec
+            return ops.CL2(g_dec, g_enc) if gcat[level].dim() == 6 else CL(gcat[level], 0, 2 * g_dec.cp)
 
         def g_skip_fanout(level: int):
             """additive skip: d(sum) reaches both addends -- copy it into the encoder half before the decoder's
             BatchNorm backward overwrites the first half in place"""
             if plan.skip == "add":
-                half = gcat[level].shape[-1] // 2
-                ops.skip_add(CL(gcat[level], 0, half), None, CL(gcat[level], half, half))
+                ops.skip_add(ghalves[level][0], None, ghalves[level][1])
 
         # the head's input gradient completes the activated-output gradient of the last decoder conv: its BatchNorm-backward
         # reduction rides on the head backward (as the encoder ones ride on the max-pool backward)
         r_last = recs[(plan.dec[-1].prefix, 2)]
         head_rows, head_fin = None, None
+        head_lo = head_in.a if isinstance(head_in, ops.CL2) else head_in      # where the head's first channels live
         if (POOL_BN and head_in.scale is not None and head_in.relu and head_in.scale.data_ptr() == r_last.vec[0].data_ptr()
-                and head_in.c0 == r_last.y.c0 and head_in.buf is r_last.y.buf):
-            fin = self._bwd_fin(P, r_last, head_in.buf.device)
+                and head_lo.c0 == r_last.y.c0 and head_lo.buf is r_last.y.buf):
+            fin = self._bwd_fin(P, r_last, dev)
             res = ops.head_bwd(head_in, w2, bl.detach(), ctx["imap_h"], plan.act, plan.head_mode, g0.contiguous(),
                                None if g1 is None else g1.contiguous(), g_skip_target(0), (r_last.vec, part), fin, gscale=gs,
                                gscale_dev=gsd)
@@ -645,7 +670,7 @@ class UNetEngine:
             i = nlev - 1 - j
             cp = pad8(blk.cout)
             r1, r2 = recs[(blk.prefix, 1)], recs[(blk.prefix, 2)]
-            g_u2 = CL(gcat[i], 0, cp)
+            g_u2 = ghalves[i][0]
             g_u1 = CL(torch.empty_like(r1.y.buf), 0, cp)
             self._conv_bn_bwd(P, r2, g_u2, g_u1, grads, ws, part, head_rows if j == nlev - 1 else None,
                               head_fin if j == nlev - 1 else None)
@@ -703,7 +728,7 @@ class UNetEngine:
             blk = plan.enc[i]
             cp = pad8(blk.cout)
             r1, r2 = recs[(blk.prefix, 1)], recs[(blk.prefix, 2)]
-            g_d2 = CL(gcat[i], cp, cp)
+            g_d2 = ghalves[i][1]
             # accumulate onto the skip's gradient; g_d2 is then complete, so the pass also carries the reduction of r2's
             # BatchNorm backward (the pooled tensor is that BatchNorm's activated output)
             dsk = ctx["dskip"][i]

@@ -334,6 +334,39 @@ class CL:
         return CL(self.buf, self.c0, self.cp, scale, shift, relu)
 
 
+@dataclass
+class CL2:
+    """A channels-last tensor of 2 * a.cp padded channels kept in two slices of equal width: ``a`` holds channels
+    [0, a.cp), ``b`` holds [a.cp, 2 * a.cp).  Only the head reads or writes a whole voxel of the top-level concat buffer,
+    so its two halves can be two dense tensors (whole 128-byte lines for every kernel that streams one half).
+    scale / shift span all 2 * a.cp channels."""
+    a: CL
+    b: CL
+    scale: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    relu: bool = False
+
+    def __post_init__(self):
+        assert self.a.cp == self.b.cp and self.a.dims == self.b.dims and self.a.dtype == self.b.dtype
+        assert self.a.cp in (8, 16), "the two-segment head kernels take at most 16 channels per segment"
+
+    @property
+    def cp(self) -> int:
+        return 2 * self.a.cp
+
+    @property
+    def lp(self) -> int:
+        return self.a.lp
+
+    @property
+    def dims(self) -> Tuple[int, int, int, int]:
+        return self.a.dims
+
+    def seg_args(self):
+        """(ptr_a, cs_a, ptr_b, cs_b) as the ctu_*_seg2 entries take them."""
+        return self.a.ptr, self.a.cs, self.b.ptr, self.b.cs
+
+
 def new_cl(n, d, h, w, cs, device, zero=False, dtype=torch.float32) -> torch.Tensor:
     f = torch.zeros if zero else torch.empty
     return f((n, d, h, w, cs), dtype=dtype, device=device)
@@ -826,26 +859,30 @@ def convt_wgrad_ws(dims, cin_p, cout_p, dtype=torch.float32) -> int:
 
 
 # ---------------------------------------------------------------------------- head
-def head_fwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int):
+def head_fwd(x, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int):
+    """x: CL, or CL2 (the input voxel in two segments: ctu_head_fwd_seg2, same values bit for bit)."""
     n, d, h, w_ = x.dims
     co, ci = w.shape[0], w.shape[1]
     v = d * h * w_
-    dev = x.buf.device
+    dev = w.device
     if head_mode == 0:
         out0 = torch.empty((n, co, d, h, w_), dtype=torch.float32, device=dev)
         out1 = None
     else:
         out0 = torch.empty((n, 2, d, h, w_), dtype=torch.float32, device=dev)
         out1 = torch.empty((n, 2, d, h, w_), dtype=torch.float32, device=dev)
-    _dual(x.lp, "head_fwd", x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(),
-          _ptr(imap), ci, co, act, head_mode, out0.data_ptr(), _ptr(out1), n, v, _stream())
+    seg2 = isinstance(x, CL2)
+    src = (*x.seg_args(), x.a.cp) if seg2 else (x.ptr, x.cs, x.cp)
+    _dual(x.lp, "head_fwd_seg2" if seg2 else "head_fwd", *src, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(),
+          b.data_ptr(), _ptr(imap), ci, co, act, head_mode, out0.data_ptr(), _ptr(out1), n, v, _stream())
     return out0, out1
 
 
-def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int, g0: torch.Tensor,
-             g1: Optional[torch.Tensor], gin: CL, bn=None, fin=None, gscale: float = 1.0,
+def head_bwd(x, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int, g0: torch.Tensor,
+             g1: Optional[torch.Tensor], gin, bn=None, fin=None, gscale: float = 1.0,
              gscale_dev: Optional[torch.Tensor] = None):
-    """bn = (vec [4, bn_cp] of the BatchNorm whose activated output is x's first bn_cp channels, partials): also emit
+    """x / gin: both CL, or both CL2 (input and input gradient in two segments: the ctu_*_seg2 entries).
+    bn = (vec [4, bn_cp] of the BatchNorm whose activated output is x's first bn_cp channels, partials): also emit
     that BatchNorm's backward reduction rows; returns (dw, db, rows) then (rows -> bn_relu_bwd(pre_reduced=...)).
     fin = (gamma, c, replay) with bn: the launch pair also finalizes that reduction; returns (dw, db, rows, (dgb, coef)).
     gscale (16-bit tensors): g0 / g1 are multiplied by it as they are read (float16 loss scale).
@@ -856,7 +893,9 @@ def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
     n, d, h, w_ = x.dims
     co, ci = w.shape[0], w.shape[1]
     v = d * h * w_
-    dev = x.buf.device
+    dev = w.device
+    seg2 = isinstance(x, CL2)
+    assert seg2 == isinstance(gin, CL2), "head_bwd: input and input gradient are both one buffer or both two segments"
     lib = _lib.load()
     ws = torch.empty(lib.ctu_head_bwd_ws_floats(n, v, x.cp, co), dtype=torch.float32, device=dev)
     dw = torch.empty_like(w)
@@ -875,8 +914,12 @@ def head_bwd(x: CL, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode:
     entry, scale = "head_bwd_bn", ((float(gscale),) if x.lp else ())
     if gscale_dev is not None:
         entry, scale = "head_bwd_bn_dscale", (gscale_dev.data_ptr(),)
-    _dual(x.lp, entry, x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(), _ptr(imap),
-          ci, co, act, head_mode, g0.data_ptr(), _ptr(g1), gin.ptr, gin.cs, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, v,
+    if seg2:
+        entry, src, dst = entry + "_seg2", (*x.seg_args(), x.a.cp), gin.seg_args()
+    else:
+        src, dst = (x.ptr, x.cs, x.cp), (gin.ptr, gin.cs)
+    _dual(x.lp, entry, *src, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(), b.data_ptr(), _ptr(imap),
+          ci, co, act, head_mode, g0.data_ptr(), _ptr(g1), *dst, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, v,
           *bn_args, _tail_arg(tail), *scale, _stream())
     if bn is None:
         return dw, db

@@ -379,6 +379,24 @@ int ctu_head_bwd_bn(const float* in, int in_cs, int cin_p, const float* in_scale
                     const float* g0, const float* g1, float* gin, int gin_cs,
                     float* dw, float* db, float* ws, int N, int64_t nvox_per_item,
                     const float* bn_mean, const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream);
+/* Two-segment forms: the head's 2*cp padded input channels live in two buffers, (in_a, cs_a) holding channels [0, cp) and
+ * (in_b, cs_b) holding [cp, 2*cp); the input gradient is written the same way to (gin_a, gcs_a) / (gin_b, gcs_b).  cp is
+ * 4, 8 or 16.  Everything else -- in_scale / in_shift [2*cp], w, imap (values in [0, 2*cp)), ws (sized for cin_p = 2*cp),
+ * dw, db, the BatchNorm rows and tail -- is what the one-buffer entry takes with cin_p = 2*cp, and every output is bit for
+ * bit what that entry writes for the same values (same loads per lane, same arithmetic, same reduction order).
+ * ctu_head_bwd_bn_seg2 with bn_partials NULL is the plain head backward.
+ * Refused before any launch (CTU_EINVAL): a null segment, a segment that is not 16-byte aligned, a stride below cp or not a
+ * multiple of 4, cp outside {4, 8, 16}, and whatever the one-buffer entries refuse. */
+int ctu_head_fwd_seg2(const float* in_a, int cs_a, const float* in_b, int cs_b, int cp, const float* in_scale,
+                      const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap,
+                      int Ci, int Co, int act, int head_mode, float* out0, float* out1, int N,
+                      int64_t nvox_per_item, void* stream);
+int ctu_head_bwd_bn_seg2(const float* in_a, int cs_a, const float* in_b, int cs_b, int cp, const float* in_scale,
+                         const float* in_shift, int in_relu, const float* w, const float* bias, const int32_t* imap,
+                         int Ci, int Co, int act, int head_mode, const float* g0, const float* g1, float* gin_a,
+                         int gcs_a, float* gin_b, int gcs_b, float* dw, float* db, float* ws, int N,
+                         int64_t nvox_per_item, const float* bn_mean, const float* bn_invstd, int bn_cp,
+                         float* bn_partials, const ctu_bn_bwd_tail* tail, void* stream);
 
 /* ------------------------------------------------------------------- loss ---- */
 /* Fused Dice + cross-entropy on one 2-channel NCDHW map (utilities.py:35-50,
@@ -1150,6 +1168,24 @@ int ctu_lp_head_bwd_bn_dscale(int dtype, const void* in, int in_cs, int cin_p, c
                               float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
                               const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail,
                               const float* gscale, void* stream);
+/* The two-segment forms of the three entries above (see ctu_head_fwd_seg2). */
+int ctu_lp_head_fwd_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                         const float* in_scale, const float* in_shift, int in_relu, const float* w, const float* bias,
+                         const int32_t* imap, int Ci, int Co, int act, int head_mode, float* out0, float* out1, int N,
+                         int64_t nvox_per_item, void* stream);
+int ctu_lp_head_bwd_bn_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                            const float* in_scale, const float* in_shift, int in_relu, const float* w, const float* bias,
+                            const int32_t* imap, int Ci, int Co, int act, int head_mode, const float* g0,
+                            const float* g1, void* gin_a, int gcs_a, void* gin_b, int gcs_b, float* dw, float* db,
+                            float* ws, int N, int64_t nvox_per_item, const float* bn_mean, const float* bn_invstd,
+                            int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail, float gscale, void* stream);
+int ctu_lp_head_bwd_bn_dscale_seg2(int dtype, const void* in_a, int cs_a, const void* in_b, int cs_b, int cp,
+                                   const float* in_scale, const float* in_shift, int in_relu, const float* w,
+                                   const float* bias, const int32_t* imap, int Ci, int Co, int act, int head_mode,
+                                   const float* g0, const float* g1, void* gin_a, int gcs_a, void* gin_b, int gcs_b,
+                                   float* dw, float* db, float* ws, int N, int64_t nvox_per_item, const float* bn_mean,
+                                   const float* bn_invstd, int bn_cp, float* bn_partials, const ctu_bn_bwd_tail* tail,
+                                   const float* gscale, void* stream);
 /* Every tensor of a list scaled in place by s (one launch): un-scaling of loss-scaled fp16 gradients.
  * ptrs: HOST array of n DEVICE float pointers, sizes: HOST int64[n].  nonfinite_flag: NULL or a DEVICE float[1] that is set
  * to 1 when any scaled value is inf / NaN (the fp16 backward overflowed; the caller zeroes it per step and hands it to
