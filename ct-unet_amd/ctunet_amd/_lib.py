@@ -196,6 +196,8 @@ SIGNATURES = {
     "ctu_histogram": (I, [P, I, L, I, P, D, D, P, P]),
     "ctu_threshold_otsu": (I, [P, I, P, D, D, P, P, P]),
     "ctu_binarize": (I, [P, I, L, P, D, P, D, P, P]),
+    "ctu_rank_filter_ws_bytes": (Z, [L, I, I, I, P]),
+    "ctu_rank_filter": (I, [P, I, L, I, I, I, P, I, I, D, P, P, P]),
     "ctu_extract_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_stitch_patches": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "ctu_window_accumulate": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, I, I, I, P, P, P]),

@@ -1,15 +1,19 @@
 """CT preprocessing on the GPU: from a scanner's int16 Hounsfield volume to the binary skull that the networks, the
 registration and the implant extraction take.  Gaussian filter, histogram, Otsu's threshold, a range test and their
-composition (``csrc/preprocess.hip``); no CPU fallback.
+composition (``csrc/preprocess.hip``), and the rank filters: median, percentile, grey minimum and maximum
+(``csrc/rank_filter.hip``); no CPU fallback.
 
     smooth = gaussian_filter(scan, 1.0, spacing=(0.8, 0.45, 0.45))            # float32, sigma in mm
     skull = extract_skull(scan, 300, spacing=(0.8, 0.45, 0.45), sigma=0.5)    # uint8 0 / 1
     t = threshold_otsu(scan, range=(-200, 3000))                              # float64 0-dim DEVICE tensor, no sync
     mask = binarize(scan, t)                                                  # reads t on the device
+    clean = median_filter(scan, 3)                                            # int16 in, int16 out: edges kept
+    skull = extract_skull(scan, 300, median=3)                                # the median first, then the chain above
+    lo, hi = minimum_filter(scan, 3), maximum_filter(scan, (1, 5, 5))         # grey erosion / dilation with a box
 
 Every volume is contiguous ``[..., D, H, W]`` with all leading dimensions a batch; ``histogram`` and ``binarize`` take a
 tensor of any shape.  Inputs are float32, int16 or uint8 and are converted in the kernel.  ``tests/preprocess_ref.py``
-restates each rule in numpy and every device result is bit-equal to it.
+(the rank filters: ``tests/rank_ref.py``) restates each rule in numpy and every device result is bit-equal to it.
 
 **gaussian_filter** (``scipy.ndimage.gaussian_filter`` up to float32 rounding):
 
@@ -51,6 +55,30 @@ tensor (Otsu's result, consumed without a synchronisation); ``upper=None`` is no
 threshold of the filtered volume over ``otsu_range``), ``postprocess.keep_largest_connected_component``
 (``components=0`` skips it), ``postprocess.ball_closing`` when ``closing_radius > 0`` (in the units of ``spacing``).
 
+**rank filters** (``median_filter``, ``percentile_filter``, ``rank_filter``, ``minimum_filter``, ``maximum_filter``;
+``scipy.ndimage``'s functions of those names with a box ``size``), the result in the INPUT's dtype:
+
+- ``size`` is an odd integer or a (z, y, x) triple of odd integers, each in 1..7: a box centred on the voxel.  Even sizes,
+  sizes above 7, footprint arrays and ``origin`` are out of scope and raise.
+- Key: every element maps to an unsigned key that preserves the order and is a bijection on its bits.  uint8: the value;
+  int16: value + 32768; float32 with bits ``b``: ``~b`` if the sign bit is set, else ``b | 0x80000000``.
+- Window: the ``n = sz sy sx`` elements around the output voxel; a position outside the volume is read through ``mode``,
+  per axis, as in ``gaussian_filter`` (``"constant"`` reads ``cval``, which must be representable in the input's dtype: an
+  integer in range for int16 and uint8, finite as a float32 for float32).  The default ``mode`` is ``"nearest"``, as for
+  ``gaussian_filter``; scipy's default is ``"reflect"``.
+- Output: the element whose key is the ``rank``-th smallest (0-based) of that multiset, with its own bits.  Equal keys
+  mean equal bits, so ties cannot matter.
+- float32: the key order is total, negative-sign NaNs < -inf < ... < -0 < +0 < ... < +inf < positive-sign NaNs.  That is the
+  rule; parity with scipy is claimed for NaN-free input only, and by value (``==``), not by bits, where both zeros occur.
+- Rank (scipy's arithmetic): median ``n // 2``; percentile ``p``: ``p += 100`` if ``p < 0``, then ``p`` must lie in
+  [0, 100], ``p == 100`` gives ``n - 1``, otherwise ``int(float(n) * p / 100.0)``; ``rank_filter``: a negative rank counts
+  from the end (``rank + n``), outside ``[-n, n)`` raises; minimum 0; maximum ``n - 1``.
+- Limits: every side ``<= 1024``; ``out=`` may not share memory with the input (every output reads neighbours).
+- Kernels: 3 x 3 x 3 selects in registers by sorting networks; rank 0 and ``n - 1`` run a separable running minimum /
+  maximum; everything else searches the key bit by bit (``path_of``).  A block owns a ``TILE`` of (8, 4, 64) outputs.
+
+**extract_skull** with ``median=m`` (``size`` rules; 0 and 1 skip it) runs ``median_filter(scan, m, mode="nearest")`` first.
+
 No call synchronises with the host, so each can be captured into a graph (outputs and workspaces are ``torch.empty``
 tensors, which a capture draws from the graph's pool); the only atomics add integers, so two calls are bit-equal.  Bad
 arguments raise ``ValueError`` before anything is launched.
@@ -71,6 +99,8 @@ MODES = ("nearest", "reflect", "constant")
 MAX_RADIUS = 32              # CTU_GAUSS_MAX_RADIUS
 MAX_SIDE = 1024
 MAX_BINS = 4096              # CTU_HISTOGRAM_MAX_BINS
+MAX_SIZE = 7                 # CTU_RANK_MAX_SIZE
+TILE = {"fast3": (8, 4, 64), "separable": (8, 4, 64), "generic": (8, 4, 64)}   # CTU_RANK_TILE_Z, _Y, _X: outputs of a block
 _DTYPES = (torch.float32, torch.int16, torch.uint8)
 _NOT_NEGATIVE = _args.Triple(shape="{who}: {what} must be a number or a (z, y, x) triple, got {v!r}",
                              value="{who}: {what} must be finite and not negative, got {v!r}", sign=_args.NOT_NEGATIVE,
@@ -269,12 +299,119 @@ def binarize(x: torch.Tensor, lower, upper=None, out: Optional[torch.Tensor] = N
     return out
 
 
+def _box_size(size, who: str, what: str = "size"):
+    """(sz, sy, sx) of a ``size`` argument: an odd integer or three of them, each in 1..MAX_SIZE."""
+    if isinstance(size, Integral) and not isinstance(size, bool):
+        vals = (size, size, size)
+    else:
+        try:
+            vals = tuple(size)
+        except TypeError:
+            raise ValueError(f"{who}: {what} must be an odd integer or a (z, y, x) triple of them, got {size!r}") from None
+        if len(vals) != 3 or any(isinstance(s, bool) or not isinstance(s, Integral) for s in vals):
+            raise ValueError(f"{who}: {what} must be an odd integer or a (z, y, x) triple of them (no footprint arrays), got "
+                             f"{size!r}")
+    if any(s < 1 or s > MAX_SIZE or s % 2 == 0 for s in vals):
+        raise ValueError(f"{who}: every {what} must be odd and lie in 1..{MAX_SIZE}, got {size!r}")
+    return tuple(int(s) for s in vals)
+
+
+def percentile_rank(percentile, n: int) -> int:
+    """The rank ``scipy.ndimage.percentile_filter`` takes of ``n`` elements (module docstring)."""
+    if isinstance(percentile, bool) or not isinstance(percentile, Real) or math.isnan(percentile):
+        raise ValueError(f"percentile_filter: percentile must be a number, got {percentile!r}")
+    p = percentile
+    if p < 0.0:
+        p += 100
+    if p < 0 or p > 100:
+        raise ValueError(f"percentile_filter: percentile must lie in [-100, 100], got {percentile!r}")
+    return n - 1 if p == 100 else int(float(n) * p / 100.0)
+
+
+def path_of(size, rank: int) -> str:
+    """The kernel a filter of box ``size`` and ``rank`` (0-based, not negative) runs: ``"fast3"``, ``"separable"`` or
+    ``"generic"``; each owns a ``TILE`` of outputs per block."""
+    sz = _box_size(size, "path_of")
+    n = sz[0] * sz[1] * sz[2]
+    if rank in (0, n - 1):
+        return "separable"
+    return "fast3" if sz == (3, 3, 3) else "generic"
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _rank_filter(x, size, rank_of, mode, cval, out, who: str) -> torch.Tensor:
+    """The one call behind the five filters; ``rank_of(n)`` gives the 0-based rank or raises."""
+    _check_input(x, who, True)
+    sz = _box_size(size, who)
+    n = sz[0] * sz[1] * sz[2]
+    rank = rank_of(n)
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"{who}: mode must be one of {', '.join(MODES)}, got {mode!r}")
+    if isinstance(cval, bool) or not isinstance(cval, Real):
+        raise ValueError(f"{who}: cval must be a number, got {cval!r}")
+    if x.dtype == torch.float32:
+        if not math.isfinite(C.c_float(float(cval)).value):
+            raise ValueError(f"{who}: cval must be finite in float32, got {cval!r}")
+    else:
+        lo, hi = (-32768, 32767) if x.dtype == torch.int16 else (0, 255)
+        if not math.isfinite(cval) or cval != int(cval) or not lo <= cval <= hi:
+            raise ValueError(f"{who}: cval must be an integer in {lo}..{hi} for {x.dtype}, got {cval!r}")
+    shape = _args.grid(x.shape[-3:], _GRID, who=who)
+    _args.check_out(out, x.shape, x.dtype, x.device, who)
+    if out is not None and _overlap(x, out):
+        raise ValueError(f"{who}: out shares memory with the input; every output reads its neighbours")
+    _lib.check_device(_ON_GPU.format(who), x)
+    src = x.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    with _lib.on(x.device) as run:
+        run("ctu_rank_filter", src.data_ptr(), _lib.DTYPE_CODE[x.dtype], x.numel() // (shape[0] * shape[1] * shape[2]), *shape,
+            _lib.array(C.c_int, sz), rank, MODES.index(mode), float(cval), out.data_ptr(), None, what=who)
+    return out
+
+
+def median_filter(x: torch.Tensor, size=3, *, mode: str = "nearest", cval=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The median (rank ``n // 2``) of the box ``size`` around every voxel of ``x [..., D, H, W]``, in the dtype of ``x``
+    (module docstring, "rank filters").  ``scipy.ndimage.median_filter``, whose default mode is ``"reflect"``."""
+    return _rank_filter(x, size, lambda n: n // 2, mode, cval, out, "median_filter")
+
+
+def percentile_filter(x: torch.Tensor, percentile, size=3, *, mode: str = "nearest", cval=0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ``percentile`` (-100..100, scipy's rank arithmetic) of the box around every voxel (module docstring)."""
+    return _rank_filter(x, size, lambda n: percentile_rank(percentile, n), mode, cval, out, "percentile_filter")
+
+
+def rank_filter(x: torch.Tensor, rank, size=3, *, mode: str = "nearest", cval=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The element of 0-based ``rank`` (negative: from the end) of the box around every voxel (module docstring)."""
+    def rank_of(n):
+        if isinstance(rank, bool) or not isinstance(rank, Integral) or not -n <= rank < n:
+            raise ValueError(f"rank_filter: rank must be an integer in [-{n}, {n}) for a box of {n} elements, got {rank!r}")
+        return int(rank) + (n if rank < 0 else 0)
+    return _rank_filter(x, size, rank_of, mode, cval, out, "rank_filter")
+
+
+def minimum_filter(x: torch.Tensor, size=3, *, mode: str = "nearest", cval=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Grey erosion with a box: the smallest element of the box around every voxel (module docstring)."""
+    return _rank_filter(x, size, lambda n: 0, mode, cval, out, "minimum_filter")
+
+
+def maximum_filter(x: torch.Tensor, size=3, *, mode: str = "nearest", cval=0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Grey dilation with a box: the largest element of the box around every voxel (module docstring)."""
+    return _rank_filter(x, size, lambda n: n - 1, mode, cval, out, "maximum_filter")
+
+
 def extract_skull(scan: torch.Tensor, threshold, *, spacing=None, sigma=0.0, otsu_range=None, bins: int = 256,
-                  components: int = 1, closing_radius: float = 0.0) -> torch.Tensor:
+                  components: int = 1, closing_radius: float = 0.0, median=0) -> torch.Tensor:
     """The binary skull (uint8 0 / 1) of a CT ``scan [D,H,W]`` or ``[N,D,H,W]``: smoothed by ``sigma`` (units of ``spacing``),
     ``> threshold`` (a number in the scan's units, or ``"otsu"`` over ``otsu_range``), reduced to its ``components`` largest
     components (0: all kept) and closed by a ball of ``closing_radius`` (module docstring).  ``threshold`` has no default:
-    the Hounsfield value that counts as bone is the user's clinical choice."""
+    the Hounsfield value that counts as bone is the user's clinical choice.  ``median`` (an odd size or triple, 1..7; 0 or 1
+    skips it) runs ``median_filter`` on the scan before everything else."""
     from . import postprocess
     who = "extract_skull"
     _check_input(scan, who, True)
@@ -299,7 +436,14 @@ def extract_skull(scan: torch.Tensor, threshold, *, spacing=None, sigma=0.0, ots
         raise ValueError(f"{who}: closing_radius must be a finite number >= 0, got {closing_radius!r}")
     if spacing is not None:
         _args.triple(spacing, _POSITIVE, who=who, what="spacing")
+    med = None
+    if not (isinstance(median, Integral) and not isinstance(median, bool) and median == 0):
+        med = _box_size(median, who, "median")
+        if med == (1, 1, 1):
+            med = None
     v = scan
+    if med is not None:
+        v = scan = median_filter(scan, med, mode="nearest")
     if any(s > 0 for s in sig):
         v = gaussian_filter(scan, sig, spacing=spacing)
     else:

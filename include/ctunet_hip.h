@@ -910,6 +910,27 @@ int ctu_threshold_otsu(const int64_t* hist, int bins, const double* range, doubl
 int ctu_binarize(const void* in, int dtype, int64_t n, const double* lower_dev, double lower, const double* upper_dev,
                  double upper, uint8_t* out, void* stream);
 
+/* Rank filters over a box: median, percentile, grey minimum and maximum (no reference counterpart; rule pinned in
+ * ctunet_amd/preprocess.py, "rank filters").  in: DEVICE contiguous [N,D,H,W] of dtype CTU_F32, CTU_I16 or CTU_U8; out: the
+ * same shape and dtype, a buffer of its own.  size: HOST int [3] = (z, y, x), each odd and in 1..CTU_RANK_MAX_SIZE; the
+ * window of a voxel is the size[0] * size[1] * size[2] = n elements centred on it, a position outside the volume read through
+ * mode per axis (CTU_GAUSS_NEAREST / _REFLECT / _CONSTANT; the constant is cval, which must be representable in the dtype:
+ * an integer in range, or finite as a float32).  Every element maps to an unsigned key that keeps the order and its bits
+ * (uint8: the value; int16: value + 32768; float32 with bits b: ~b if the sign is set, else b | 0x80000000); out is the
+ * element whose key is the rank-th smallest (0-based, 0 <= rank < n) of the window, with its own bits.  The order is
+ * total: NaNs of negative sign < -inf < .. < -0 < +0 < .. < +inf < NaNs of positive sign.
+ * A block owns CTU_RANK_TILE_Z x _Y x _X outputs.  One launch per 65535 items, no workspace (ws_bytes is 0, ws may be
+ * NULL), no atomics, no host sync, capture-safe, bitwise reproducible.  Every side in 1..1024.
+ * Refused before any launch (CTU_EINVAL): null in / out / size, another dtype or mode, a size that is even, < 1 or
+ * > CTU_RANK_MAX_SIZE, rank outside [0, n), a side outside 1..1024, N < 1, a cval the dtype cannot hold. */
+#define CTU_RANK_MAX_SIZE 7
+#define CTU_RANK_TILE_Z 8
+#define CTU_RANK_TILE_Y 4
+#define CTU_RANK_TILE_X 64
+size_t ctu_rank_filter_ws_bytes(int64_t N, int D, int H, int W, const int* size);
+int ctu_rank_filter(const void* in, int dtype, int64_t N, int D, int H, int W, const int* size, int rank, int mode,
+                    double cval, void* out, void* ws, void* stream);
+
 /* Patch tiling of whole volumes (BASELINE config 4: skull volumes tiled to 192^3 patches; the tiles carry the sample
  * schema of ctunet/pytorch/datasets.py:89-112,195-235).  coords: DEVICE int32 [P][3] = (z0, y0, x0) of each patch.
  *   extract: out [P,C,pd,ph,pw] = vol [C,D,H,W] windows, zero-filled outside the volume
