@@ -12,10 +12,11 @@ from . import optim  # noqa: F401
 from . import postprocess  # noqa: F401
 from . import preprocess  # noqa: F401
 from . import resample  # noqa: F401
+from . import sampling  # noqa: F401
 from . import registration  # noqa: F401
 from . import simplify  # noqa: F401
 from .inference import Prediction, predict_volume  # noqa: F401
-from .datasets import FlapRec2OTrainDataset, FlapRecWShapePrior2OTrainDataset  # noqa: F401
+from .datasets import FlapRec2OTrainDataset, FlapRecPatchDataset, FlapRecWShapePrior2OTrainDataset  # noqa: F401
 from .loss_scale import DynamicLossScale  # noqa: F401
 from .losses import LossSpec, boundary_map, seg_loss  # noqa: F401
 from .models import (UNet, UNet4_2IC, UNet4b1i3o, UNet4b2i3o, UNet5b2i3o, UNetDO, UNetSP, UNetSPSmall,  # noqa: F401
@@ -27,4 +28,4 @@ __all__ = ["UNet", "UNet4b2i3o", "UNet5b2i3o", "UNet4b1i3o", "UNetSP", "UNetSPSm
            "UNet4_2IC", "DynamicLossScale", "predict_volume", "Prediction",
            "SkullRandomHole", "SaltAndPepper", "FlapRecTransform", "flap_rec_transform", "RandomSpatial",
            "cranioplasty_transform", "FlapRecWShapePrior2OTrainDataset", "FlapRec2OTrainDataset", "metrics", "postprocess", "preprocess", "resample", "registration", "mesh", "lr_scheduler",
-           "optim", "simplify", "LossSpec", "seg_loss", "boundary_map"]
+           "optim", "simplify", "LossSpec", "seg_loss", "boundary_map", "sampling", "FlapRecPatchDataset"]

@@ -208,6 +208,9 @@ SIGNATURES = {
     "ctu_flap_count": (I, [P, I, I, L, P, P]),
     "ctu_flap_draw": (I, [P, I, I, I, I, I, P, I, P, U, F, I, I, I, P, P, U, F, F, I, P, P]),
     "ctu_flap_apply": (I, [P, I, P, I, I, I, I, P, I, P, P, P, U, I, P, I, P, P, P]),
+    "ctu_patch_index": (I, [P, I, L, I, P, P, P]),
+    "ctu_patch_draw": (I, [P, P, I, I, I, I, I, P, P, I, P, U, P, P, P, P, P, P]),
+    "ctu_patch_crop": (I, [P, I, I, I, I, I, I, P, I, I, I, I, D, P, I, I, I, P]),
     "ctu_spatial_draw": (I, [I, I, I, I, P, P, U, I, D, D, D, P, I, I, I, I, P, P, P]),
     "ctu_spatial_warp": (I, [P, I, I, I, I, I, I, P, I, I, I, P, P, P, P, P]),
     "ctu_lp_upconv_fused_supported": (I, [I, I, I, I, I, I]),

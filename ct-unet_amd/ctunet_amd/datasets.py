@@ -124,6 +124,66 @@ class FlapRec2OTrainDataset(FlapRecWShapePrior2OTrainDataset):
         super().__init__(skulls, None, transform, append_atlas=False, device=device)
 
 
+class FlapRecPatchDataset(Dataset):
+    """Random class-balanced patches of in-memory binary skulls through the flap-reconstruction transform, all on the GPU
+    (BASELINE config 4, "skull volumes tiled to 192^3 patches"; ``sampling`` pins the draw).  Item idx is one patch of
+    skull idx // patches_per_volume, centred on bone with the sampler's class share and jitter, anywhere otherwise:
+
+        {"image":  float32 [2, pd, ph, pw]  broken, noisy skull patch + the atlas window   ([1, ...] without an atlas),
+         "target": (full skull one-hot [2, pd, ph, pw], flap one-hot [2, pd, ph, pw]),
+         "filepath": "memory://<skull>#<patch>",
+         "coords": int32 [4] = (skull, z0, y0, x0) on the device}
+
+    the schema of FlapRecWShapePrior2OTrainDataset at the patch size, plus ``coords``.  skulls: a list of [D,H,W] tensors
+    of one shape or an [M,D,H,W] tensor; they are kept on the device as their uint8 casts (a voxel's value, as the
+    transform reads it) and indexed once.  sampler: a ``sampling.PatchSampler`` with ``classes=None`` (bone = nonzero).
+    atlas: [D,H,W], cropped at the same window as float32.  transform: as FlapRecWShapePrior2OTrainDataset's; it runs on
+    the patch and shares the base transform's state.  Every item advances the sampler's and the transform's counters."""
+
+    def __init__(self, skulls, sampler, atlas=None, transform=None, patches_per_volume: int = 1, device="cuda"):
+        from . import sampling
+        from . import transforms as T
+        if not isinstance(sampler, sampling.PatchSampler) or sampler.classes is not None:
+            raise ValueError("ctunet_amd: sampler must be a sampling.PatchSampler with classes=None (bone = nonzero)")
+        if isinstance(patches_per_volume, bool) or not isinstance(patches_per_volume, int) or patches_per_volume < 1:
+            raise ValueError(f"ctunet_amd: patches_per_volume must be a positive integer, got {patches_per_volume!r}")
+        items = [skulls[i] for i in range(len(skulls))]
+        if not items or any(s.dim() != 3 or s.shape != items[0].shape for s in items):
+            raise ValueError("ctunet_amd: skulls must be a non-empty list of [D,H,W] tensors of one shape or an [M,D,H,W] tensor")
+        base = T.flap_rec_transform if transform is None else transform
+        if not isinstance(base, T.FlapRecTransform) or not base.hole.double_output:
+            raise ValueError("ctunet_amd: transform must be a FlapRecTransform with SkullRandomHole(double_output=True)")
+        self.device = torch.device(device)
+        self.sampler, self.per = sampler, patches_per_volume
+        vols = torch.stack([s.to(self.device) for s in items])
+        self.skulls = vols if vols.dtype == torch.uint8 else vols.to(torch.uint8)    # [M,D,H,W]: the uint8 casts
+        m, d, h, w = self.skulls.shape
+        if atlas is not None and tuple(atlas.shape) != (d, h, w):
+            raise ValueError(f"ctunet_amd: the atlas must be [{d},{h},{w}], got {tuple(atlas.shape)}")
+        self.atlas = None if atlas is None else atlas.to(self.device, torch.float32).contiguous().view(1, 1, d, h, w)
+        self.index = sampler.index(self.skulls)                                      # built once
+        self._item = torch.arange(m, dtype=torch.int32, device=self.device)
+        self._base = base
+
+    def __len__(self):
+        return self.skulls.shape[0] * self.per
+
+    def __getitem__(self, idx: int):
+        from . import sampling
+        from . import transforms as T
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        m = idx // self.per
+        coords = self.sampler.draw(self.index, items=self._item[m:m + 1])
+        vols = self.skulls
+        patch = sampling.crop(vols.view(vols.shape[0], 1, *vols.shape[1:]), coords, self.sampler.patch)
+        ap = None if self.atlas is None else sampling.crop(self.atlas, coords, self.sampler.patch)[0, 0]
+        b = self._base
+        x, (full, flap) = T.FlapRecTransform(b.hole, b.noise, ap, b.spatial).apply(patch)   # shares their state
+        return {"image": x[0], "target": (full[0], flap[0]), "filepath": f"memory://{m}#{idx % self.per}",
+                "coords": coords[0]}
+
+
 class FlapRecTrainDataset(Dataset):
     """Not provided: in the reference (datasets.py:136-149 with 89-112) flap_rec_transform's (full skull, flap) tuple
     target reaches ``sample['target'].long()`` (datasets.py:107-110) and raises, so this class cannot produce a sample."""

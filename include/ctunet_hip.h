@@ -1019,6 +1019,49 @@ int ctu_flap_apply(const void* skull, int u8, const float* atlas, int N, int D, 
                    int mode, int64_t* hole_seq, int64_t* noise_seq, float* noise_nd, uint64_t noise_seed, int decay,
                    float* x, int C, float* full, float* flap, void* stream);
 
+/* Class-balanced random patch sampling for training (no reference counterpart: its datasets feed whole resized volumes;
+ * rule pinned in ctunet_amd/sampling.py).  labels: DEVICE uint8 [M][D][H][W] (bool as its bytes), V = D H W < 2^31,
+ * M <= 65535.  K classes, 1 <= K <= CTU_PATCH_MAX_CLASSES: classes = HOST int [K], class i holds the voxels == classes[i]
+ * (0..255); classes = NULL: K = 1 and the class holds the voxels != 0.  Three entry points, no atomics, no host sync,
+ * capture-safe, bitwise reproducible.
+ *   index: counts [M][K][ceil(V / CTU_PATCH_CHUNK)] int32 = voxels of class i per chunk of CTU_PATCH_CHUNK flat C-order
+ *          indices of item m.  One read of the labels for all K classes, in 16-byte loads on the 16-byte grid of each item's
+ *          own address (an item of odd V starts anywhere); built once for a static dataset.
+ *   draw:  one block per patch j < P, from volume items[j] (DEVICE int32 [P]).  seq = counter[0] + j (counter: DEVICE
+ *          int64 [1]); Philox4x32-10 keyed by seed, stream 0: c0 = 0 -> (r_class, r_k, -, -), c0 = 1 -> (r_z, r_y, r_x, -);
+ *          draw_int(r, lo, span) = lo + ((r span) >> 32).  u = (r_class >> 8) 2^-24 as a double; cum: HOST double [K], the
+ *          rising running sums of the class probabilities, cum[K-1] <= 1; class i is chosen iff cum[i-1] <= u < cum[i],
+ *          otherwise the patch is uniform.  Per axis a (volume side n_a, patch side p_a = patch[a], J_a = jitter[a], HOST
+ *          int [3] each, 0 <= J_a <= (p_a - 1) / 2), hi_a = max(0, n_a - p_a):
+ *            uniform patch: s_a = draw_int(r_a, 0, hi_a + 1)
+ *            class patch:   count = voxels of the class in the item (sum of its counts); count == 0: the uniform rule with
+ *                           the same words, and fallback = 1; else k = draw_int(r_k, 0, count), centre c = the k-th voxel
+ *                           of the class in C order, j_a = draw_int(r_a, -J_a, 2 J_a + 1),
+ *                           s_a = min(max(c_a - p_a / 2 + j_a, 0), hi_a)  -- the centre always lies inside the patch.
+ *          An item outside [0, M) reads nothing: its coords are (-1, 0, 0, 0) and its record is item -1, starts 0, class
+ *          -1, centre -1, the rest 0.  After the draw launch a one-thread launch adds P to counter[0].
+ *          coords:  [P][4] int32 = (item, z0, y0, x0).
+ *          records: [P][CTU_PATCH_RECORD] int32 = 0 item  1-3 start z, y, x  4 class index (-1 = uniform)  5 fallback
+ *                   6 count  7 k  8-10 centre z, y, x (-1 without one)  11 zero.
+ *   crop:  out [P][Ctot][pd][ph][pw], channels [out_channel, out_channel + C) = the window at (z0, y0, x0) of channel c of
+ *          src [Ms][C][D][H][W] item coords[p][0] (Ms == 1: one source shared by every patch with an item >= 0).  dtype
+ *          CTU_U8, CTU_I16 or CTU_F32; the output's is the source's or CTU_F32 (exact conversions).  coords may hold any
+ *          int32: a voxel outside the volume, and every voxel of a patch whose item is negative or (Ms > 1) >= Ms, is
+ *          fill, which the output dtype must hold exactly; no address outside src is formed.  One output row is one span
+ *          of a source row; whole 16-byte chunks of an output row are 16-byte stores at any pw and alignment.  The other
+ *          channels of out are not written.  P C is not bounded by a grid dimension; pd ph pw < 2^31.
+ * Refused before any launch (CTU_EINVAL): null pointers, shapes and sizes outside the above, K outside its range, a class
+ * outside 0..255, cum not rising within [0, 1], a jitter outside its bound, a dtype pair or fill outside the above. */
+#define CTU_PATCH_CHUNK 8192
+#define CTU_PATCH_MAX_CLASSES 4
+#define CTU_PATCH_RECORD 12
+int ctu_patch_index(const uint8_t* labels, int M, int64_t V, int K, const int* classes, int32_t* counts, void* stream);
+int ctu_patch_draw(const uint8_t* labels, const int32_t* counts, int M, int D, int H, int W, int K, const int* classes,
+                   const int32_t* items, int P, int64_t* counter, uint64_t seed, const int* patch, const int* jitter,
+                   const double* cum, int32_t* coords, int32_t* records, void* stream);
+int ctu_patch_crop(const void* src, int src_dtype, int Ms, int C, int D, int H, int W, const int32_t* coords, int P, int pd,
+                   int ph, int pw, double fill, void* out, int out_dtype, int Ctot, int out_channel, void* stream);
+
 /* Random spatial augmentation (flip, cubic B-spline elastic deformation, affine) of a batch in[N][C][D][H][W], uint8
  * (CTU_U8) or float32 (CTU_F32), nearest-neighbour with fill 0; rule, Philox streams and arithmetic order are pinned in
  * ctunet_amd/transforms.py ("RandomSpatial").  Two launches, no atomics, no host sync:
