@@ -170,6 +170,10 @@ SIGNATURES = {
     "ctu_registration_init": (I, [P, L, P, P, P]),
     "ctu_registration_accumulate": (I, [P, L, P, I, I, I, P, P, D, P, P]),
     "ctu_registration_update": (I, [L, I, P, P, P, I, P, P]),
+    "ctu_similarity_ws_bytes": (Z, [L, L]),
+    "ctu_similarity_init": (I, [P, L, P, P, P]),
+    "ctu_similarity_accumulate": (I, [I, P, L, P, I, I, I, P, P, P, L, P, I, I, I, P, P, D, P, P]),
+    "ctu_similarity_update": (I, [I, L, L, I, P, P, P, I, P, P]),
     "ctu_mesh_ws_bytes": (Z, [I, I, I]),
     "ctu_mesh_count": (I, [P, I, I, I, I, I, L, F, P, P]),
     "ctu_mesh_emit": (I, [P, I, I, I, I, F, F, P, P, L, L, P, P, P, P]),

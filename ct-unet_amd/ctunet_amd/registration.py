@@ -41,12 +41,58 @@ in ``0..iterations``: accumulate at ``M_c``; if ``cost_c < cost`` accept (``(M, 
 ``E = [Rod(delta_w), pivot - Rod(delta_w) pivot + delta_t]``.  The step is *refused* -- the candidate stays, the history row
 holds -1 -- when the accepted state has fewer than 6 inliers (fewer than unknowns: only the damping would make the system
 solvable), a pivot of the factorisation is not positive, or the result is not finite; no NaN matrix is ever produced.
-Scale, shear, intensity metrics, pyramids, principal-axis starts, subsampling and random warps are out of scope.
+Shear and affine fits, intensity metrics, pyramids, principal-axis starts, subsampling and random warps are out of scope
+(DESIGN.md); isotropic scale is the similarity model below.
 
 A ``register_points`` call is ``1 + 2 (iterations + 1)`` launches on one stream (the mean of the points and the start
 state; then accumulate and update per iteration): no host synchronisation, no float atomics, no allocation besides the
 result and the workspace (``workspace_bytes(P)``; pass ``workspace=`` to bring your own), so it can be captured into a graph,
 and two calls are bit-equal.  ``RegistrationResult.report()`` is the one read-back.
+
+Similarity registration with the symmetric chamfer cost
+-------------------------------------------------------
+
+    r = register(skull, atlas, moving_spacing=(0.8, 0.45, 0.45), fixed_spacing=1.0, model="similarity", max_distance=4.0)
+
+Heads differ in size by several percent, which six rigid parameters cannot absorb.  ``register(..., model="similarity")``
+fits a seventh, isotropic scale, and by default (``symmetric=True``) adds the reverse distance to the cost: the surface points
+of the fixed mask (``surface_points(fixed_mask)``), pulled back through the inverse matrix, against the distance field of the
+moving mask (``distance_transform_edt(moving == 0, sampling=moving_spacing)``).  With a hole in the moving skull pass a
+``max_distance`` of a few mm: the atlas's points over the hole have no counterpart and must saturate.  The directed cost alone
+(``symmetric=False``) does not collapse but recovers the scale 0.4-0.45 % too small on the analytic skull of the tests; the
+symmetric cost is within 0.06 %.  ``model="rigid", symmetric=True`` runs the same kernels with six unknowns; the defaults
+(``model="rigid"``, ``symmetric=None``) take the rigid path above, bit for bit.  ``register_similarity_points`` is the optimiser
+itself, ``accumulate_similarity`` one accumulation read back (``ctu_similarity_*``; ``tests/similarity_ref.py`` restates the
+rule).  ``history`` has six columns: (cost / (P + Q), inliers of both terms, lambda, flag, backward inliers,
+scale = cbrt(det)), and ``report()`` adds ``scale`` and ``backward_inlier_fraction``.
+
+The pinned rule, all float64, every operation rounded on its own; the sample, the inside test, ``v``, ``g`` and ``lerp`` are the
+rigid rule's.  DOF is 6 (rigid) or 7 (similarity).
+
+Forward term, every moving point ``p`` (float32 ``[P,3]``): ``q = M_c p``; inlier iff ``q`` is inside the fixed field ``F`` and
+``v = F(q) <= max_distance``; ``d = q - pivot`` and the gradient ``g``.  Backward term, every fixed point ``y`` (float32 ``[Q,3]``,
+fixed world; present when Q > 0): ``x = M_c^-1 y``; inlier iff ``x`` is inside the moving field ``G`` (distance in mm to the
+moving object on the moving grid, with its own spacing and origin) and ``w = G(x) <= max_distance``; the residual is ``w``,
+``d = y - pivot``, and the gradient in the fixed frame is ``h_a = -((g_0 Ainv[0][a] + g_1 Ainv[1][a]) + g_2 Ainv[2][a])`` with
+``g`` the gradient of ``G`` at ``x`` and ``Ainv`` the 3x3 of ``M_c^-1`` (``M_c <- E M_c`` gives ``x = M_c^-1 E^-1 y``, hence
+``dw/d delta = (-Ainv^T g) . (generator y)``).  Jacobian row of either term, ``g`` standing for ``g`` or ``h``:
+``J = [d x g, g, (d_0 g_0 + d_1 g_1) + d_2 g_2]`` (the last entry only for DOF 7).  A non-inlier has ``r = max_distance`` (0
+without a bound) and ``J = 0``.  ``cost``, ``H`` and ``b`` run over both terms with equal weight per point, forward points
+first, then backward points; ``pivot = M_c mean(finite moving points)``.
+
+Levenberg-Marquardt as above (``lambda`` from 1e-3, accept iff the cost is lower, ``/ 3`` down to 1e-9 or ``x 10`` up to 1e9,
+damping ``lambda diag(H) + 1e-12 I``) with a Cholesky factorisation of size DOF and the increment
+``E = [L, pivot - L pivot + delta_t]``, ``L = exp(delta_s) Rod(delta_w)`` for DOF 7 and ``Rod(delta_w)`` for DOF 6.
+
+The inverse is formed by the adjugate: cofactors as differences of products
+(``c_ij = a_(i+1)(j+1) a_(i+2)(j+2) - a_(i+1)(j+2) a_(i+2)(j+1)``, indices mod 3), ``det = (a00 c00 + a01 c01) + a02 c02``,
+entries ``c_ji / det``, translation ``-((inv_a0 t_0 + inv_a1 t_1) + inv_a2 t_2)``.  It is written into the state for the
+candidate, so the accumulation reads it, and into ``inverse`` for the accepted matrix.
+
+A step is refused (flag -1, candidate kept, no NaN ever written) with fewer than DOF inliers in total, a Cholesky pivot that is
+not positive, a non-finite candidate, or a candidate whose determinant is non-finite or not positive or whose inverse is not
+finite.  An ``init`` with such a determinant refuses every step: the matrix stays ``init``, the backward points count as
+non-inliers, ``inverse`` reads the identity and the scale column 0.
 """
 from __future__ import annotations
 
@@ -63,23 +109,34 @@ MAX_BLOCKS = 1024                      # CTU_REG_MAX_BLOCKS of ctunet_hip.h
 _HEAD_DOUBLES = 128                    # the workspace head: 1024 bytes
 _PIVOT_C = 62                          # the candidate's pivot in the head (layout: ctunet_hip.h)
 _ROW = 32                              # doubles of a slab row
+_SIM_PIVOT_C = 102                     # the same of the similarity state (layout: ctunet_hip.h)
+_SIM_ROW = 40                          # doubles of a similarity slab row
+_DOF = {"rigid": 6, "similarity": 7}
 
 
 class RegistrationResult(NamedTuple):
     """``matrix`` / ``inverse`` device float64 [4,4] (moving world -> fixed world and back), ``history`` device float64
-    [iterations + 1, 4] = (cost / P, inliers, lambda, 1 accepted / 0 rejected / -1 refused), ``num_points`` P."""
+    [iterations + 1, 4] = (cost / P, inliers, lambda, 1 accepted / 0 rejected / -1 refused), ``num_points`` P.  From the
+    similarity kernels the history has two more columns (backward inliers, scale), the first two count both terms, and
+    ``num_fixed_points`` is Q."""
     matrix: torch.Tensor
     inverse: torch.Tensor
     history: torch.Tensor
     num_points: int = 0
+    num_fixed_points: int = 0
 
     def report(self) -> dict:
         """Reads the history back (one synchronisation): ``rms`` distance in mm of the accepted matrix, ``inlier_fraction``,
-        ``accepted`` steps and ``status`` (0, or -1 when the last step was refused: too few inliers to move at all)."""
+        ``accepted`` steps and ``status`` (0, or -1 when the last step was refused: too few inliers to move at all); with a
+        six-column history also ``scale`` and ``backward_inlier_fraction`` (of the Q fixed points), and ``inlier_fraction``
+        is of P + Q."""
         h = self.history.cpu().numpy()
         last = h[-1]
-        return dict(rms=float(np.sqrt(last[0])), inlier_fraction=float(last[1] / max(self.num_points, 1)),
-                    accepted=int((h[:, 3] == 1).sum()), status=-1 if last[3] < 0 else 0, iterations=int(h.shape[0] - 1))
+        rep = dict(rms=float(np.sqrt(last[0])), inlier_fraction=float(last[1] / max(self.num_points + self.num_fixed_points, 1)),
+                   accepted=int((h[:, 3] == 1).sum()), status=-1 if last[3] < 0 else 0, iterations=int(h.shape[0] - 1))
+        if h.shape[1] >= 6:
+            rep.update(scale=float(last[5]), backward_inlier_fraction=float(last[4] / max(self.num_fixed_points, 1)))
+        return rep
 
 
 _REAL = _args.Triple(shape="registration: {what} must be a number or a (z, y, x) triple, got {v!r}",
@@ -199,6 +256,129 @@ def accumulate(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, 
                 pivot=host[_PIVOT_C:_PIVOT_C + 3].copy(), blocks=int(slab.shape[0]))
 
 
+def similarity_workspace_bytes(P: int, Q: int = 0) -> int:
+    """Device workspace (bytes) of a similarity registration of ``P`` moving and ``Q`` fixed points: the state (1024 bytes) and
+    one slab row of 320 bytes per block of the accumulation over P + Q items, at most 1024 blocks; 0 for P < 1 or Q < 0."""
+    return int(_lib.load().ctu_similarity_ws_bytes(int(P), int(Q)))
+
+
+def _dof(model) -> int:
+    if not isinstance(model, str) or model not in _DOF:
+        raise ValueError(f"registration: model must be 'rigid' or 'similarity', got {model!r}")
+    return _DOF[model]
+
+
+def _check_symmetric_half(fixed_points, moving_field, moving_spacing, moving_origin):
+    """The optional backward term's arguments: both or neither, and a moving frame only with a moving field."""
+    if (fixed_points is None) != (moving_field is None):
+        raise ValueError("registration: fixed_points and moving_field come together or not at all")
+    if fixed_points is None:
+        if moving_spacing is not None or moving_origin is not None:
+            raise ValueError("registration: moving_spacing and moving_origin describe moving_field, which was not given")
+        return
+    if not isinstance(fixed_points, torch.Tensor) or not isinstance(moving_field, torch.Tensor):
+        raise TypeError("registration: fixed_points and moving_field must be tensors")
+    if fixed_points.dtype != torch.float32 or moving_field.dtype != torch.float32:
+        raise TypeError(f"registration: fixed_points and moving_field must be float32, got {fixed_points.dtype} and "
+                        f"{moving_field.dtype}")
+    if fixed_points.dim() != 2 or fixed_points.shape[1] != 3 or fixed_points.shape[0] < 1:
+        raise ValueError(f"registration: fixed_points must be [Q,3] with Q >= 1, got {tuple(fixed_points.shape)}")
+    if moving_field.dim() != 3:
+        raise ValueError(f"registration: moving_field must be one [D,H,W] volume, got {tuple(moving_field.shape)}")
+    if min(moving_field.shape) < 2:
+        raise ValueError(f"registration: a field with a side of 1 has no gradient along it, got {tuple(moving_field.shape)}")
+    if moving_field.numel() >= 1 << 31:
+        raise ValueError(f"registration: the field must hold fewer than 2^31 voxels, got {tuple(moving_field.shape)}")
+
+
+class _SimilarityCall:
+    """The checked arguments of the similarity entry points, shared by the optimiser and the inspection helper."""
+
+    def __init__(self, points, field, fixed_points, moving_field, model, spacing, origin, moving_spacing, moving_origin,
+                 max_distance, iterations=0):
+        _check_inputs(points, field)
+        self.dof = _dof(model)
+        _check_symmetric_half(fixed_points, moving_field, moving_spacing, moving_origin)
+        if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
+            raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+        bound = _bound(max_distance)
+        sp, org = _frame(spacing, origin)
+        msp, morg = _frame(moving_spacing, moving_origin, "moving_")
+        tensors = (points, field) if fixed_points is None else (points, field, fixed_points, moving_field)
+        _lib.check_device(_ON_GPU.format("points and fields"), *tensors)
+        self.dev = points.device
+        for t in tensors:
+            if t.device != self.dev:
+                raise ValueError(f"registration: points live on {self.dev}, another argument on {t.device}")
+        self.keep = [t.contiguous() for t in tensors]                          # alive until the launches are issued
+        pts, fld = self.keep[:2]
+        self.P, self.Q = int(pts.shape[0]), 0 if fixed_points is None else int(fixed_points.shape[0])
+        back = (None, 0, None, 0, 0, 0) if fixed_points is None else \
+            (self.keep[2].data_ptr(), self.Q, self.keep[3].data_ptr(), *self.keep[3].shape)
+        self.points_ptr = pts.data_ptr()
+        self.accumulate_args = (self.dof, pts.data_ptr(), self.P, fld.data_ptr(), *fld.shape, _lib.double_array(sp),
+                                _lib.double_array(org), *back, _lib.double_array(msp), _lib.double_array(morg), bound)
+
+    def workspace(self, workspace):
+        need = similarity_workspace_bytes(self.P, self.Q)
+        if workspace is None:
+            return torch.empty(need, dtype=torch.uint8, device=self.dev)
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != self.dev \
+                or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 8:
+            raise ValueError(f"registration: workspace must be a contiguous, 8-byte aligned uint8 tensor of at least {need} "
+                             f"bytes on {self.dev}")
+        return workspace
+
+
+def register_similarity_points(points: torch.Tensor, field: torch.Tensor, *, fixed_points=None, moving_field=None,
+                               model: str = "similarity", spacing=None, origin=None, moving_spacing=None, moving_origin=None,
+                               init=None, iterations: int = 30, max_distance=None, workspace=None) -> RegistrationResult:
+    """Fit the similarity (``model="similarity"``, 7 unknowns) or rigid (``"rigid"``, 6) matrix that takes ``points`` (float32
+    [P,3], moving world) onto the zero set of ``field`` (float32 distances on the fixed grid of ``spacing`` / ``origin``) and,
+    with ``fixed_points`` (float32 [Q,3], fixed world) and ``moving_field`` (float32 distances to the moving object on the
+    moving grid of ``moving_spacing`` / ``moving_origin``), the fixed points back onto the moving object: the symmetric cost of
+    the module docstring's rule.  The two come together or not at all.  Workspace: ``similarity_workspace_bytes(P, Q)``."""
+    call = _SimilarityCall(points, field, fixed_points, moving_field, model, spacing, origin, moving_spacing, moving_origin,
+                           max_distance, iterations)
+    init = _check_init(init, call.dev)
+    rows = int(iterations) + 1
+    ws = call.workspace(workspace)
+    out = torch.empty((32 + 6 * rows,), dtype=torch.float64, device=call.dev)
+    matrix, inverse, history = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:].view(rows, 6)
+    with _lib.on(call.dev) as run:
+        run("ctu_similarity_init", call.points_ptr, call.P, None if init is None else init.data_ptr(), ws.data_ptr())
+        for it in range(rows):
+            run("ctu_similarity_accumulate", *call.accumulate_args, ws.data_ptr())
+            run("ctu_similarity_update", call.dof, call.P, call.Q, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(),
+                rows, ws.data_ptr())
+    return RegistrationResult(matrix, inverse, history, call.P, call.Q)
+
+
+def accumulate_similarity(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, *, fixed_points=None,
+                          moving_field=None, model: str = "similarity", spacing=None, origin=None, moving_spacing=None,
+                          moving_origin=None, max_distance=None) -> dict:
+    """One accumulation of the similarity kernels at ``matrix`` (device float64 [4,4]; its inverse is the adjugate's), read
+    back for inspection: ``H`` [DOF (DOF + 1) / 2] (upper triangle, row by row), ``b`` [DOF], ``cost``, ``count`` (both terms),
+    ``count_backward`` and the ``pivot`` -- numpy float64, the slab rows summed in block order as the update kernel sums them."""
+    call = _SimilarityCall(points, field, fixed_points, moving_field, model, spacing, origin, moving_spacing, moving_origin,
+                           max_distance)
+    matrix = _check_init(matrix, call.dev)
+    ws = call.workspace(None)
+    with _lib.on(call.dev) as run:
+        run("ctu_similarity_init", call.points_ptr, call.P, None if matrix is None else matrix.data_ptr(), ws.data_ptr())
+        run("ctu_similarity_accumulate", *call.accumulate_args, ws.data_ptr())
+    host = ws.cpu().numpy().view(np.float64)
+    slab = host[_HEAD_DOUBLES:].reshape(-1, _SIM_ROW)
+    nh = call.dof * (call.dof + 1) // 2
+    na = nh + call.dof + 1
+    tot = np.zeros(na)
+    for row in slab:                                                   # block order
+        tot += row[:na]
+    counts = slab[:, na:na + 2].copy().view(np.int64).sum(0)
+    return dict(H=tot[:nh], b=tot[nh:nh + call.dof], cost=float(tot[na - 1]), count=int(counts[0]), count_backward=int(counts[1]),
+                pivot=host[_SIM_PIVOT_C:_SIM_PIVOT_C + 3].copy(), blocks=int(slab.shape[0]))
+
+
 def _mask(t, what: str):
     if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"registration: {what} must be one bool or uint8 [D,H,W] mask")
@@ -223,9 +403,13 @@ def surface_points(mask: torch.Tensor, spacing=None, origin=None) -> torch.Tenso
 
 
 def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spacing=None, moving_origin=None,
-             fixed_spacing=None, fixed_origin=None, iterations: int = 30, max_distance=None, init="centroid") -> RegistrationResult:
+             fixed_spacing=None, fixed_origin=None, iterations: int = 30, max_distance=None, init="centroid",
+             model: str = "rigid", symmetric=None) -> RegistrationResult:
     """Register the binary ``moving_mask`` to ``fixed_mask`` (the atlas), each a bool / uint8 [D,H,W] volume on its own grid:
-    the surface voxels of the moving mask against the exact distance field of the fixed one (module docstring)."""
+    the surface voxels of the moving mask against the exact distance field of the fixed one (module docstring).
+    ``model="similarity"`` also fits an isotropic scale; ``symmetric`` (default: True for the similarity model, False for the
+    rigid one) adds the fixed mask's surface voxels against the distance field of the moving mask.  The defaults are the
+    rigid rule through ``register_points``; every other combination runs ``register_similarity_points``."""
     from . import postprocess
     _mask(moving_mask, "moving_mask")
     _mask(fixed_mask, "fixed_mask")
@@ -235,6 +419,11 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
             raise ValueError(f"registration: init must be 'centroid' or a float64 [4,4] tensor, got {init!r}")
     elif init is not None:
         init = _check_init(init, moving_mask.device)
+    _dof(model)
+    if symmetric is None:
+        symmetric = model == "similarity"
+    elif not isinstance(symmetric, bool):
+        raise ValueError(f"registration: symmetric must be None, True or False, got {symmetric!r}")
     _lib.check_device(_ON_GPU.format("the masks"), moving_mask, fixed_mask)
     if moving_mask.device != fixed_mask.device:
         raise ValueError("registration: the two masks must live on the same device")
@@ -251,5 +440,12 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
         cf = _world(fixed_index, fsp, forg).mean(0)
         init = torch.eye(4, dtype=torch.float64, device=points.device)
         init[:3, 3] = cf - cm
-    return register_points(points, field, spacing=fsp, origin=forg, init=init, iterations=iterations,
-                           max_distance=max_distance)
+    if model == "rigid" and not symmetric:
+        return register_points(points, field, spacing=fsp, origin=forg, init=init, iterations=iterations,
+                               max_distance=max_distance)
+    half = {}
+    if symmetric:
+        half = dict(fixed_points=surface_points(fixed, fsp, forg), moving_spacing=msp, moving_origin=morg,
+                    moving_field=postprocess.distance_transform_edt(moving_mask == 0, sampling=msp))
+    return register_similarity_points(points, field, model=model, spacing=fsp, origin=forg, init=init, iterations=iterations,
+                                      max_distance=max_distance, **half)

@@ -728,6 +728,33 @@ int ctu_registration_accumulate(const float* points, int64_t P, const float* fie
 int ctu_registration_update(int64_t P, int it, double* matrix, double* inverse, double* history, int history_rows, void* ws,
                             void* stream);
 
+/* Similarity (dof = 7: rotation, translation, isotropic scale) or rigid (dof = 6) registration with the symmetric chamfer
+ * cost (rule pinned in ctunet_amd/registration.py): the forward term is the one above; the backward term takes the fixed
+ * object's surface points (fixed_points: DEVICE float32 [Q][3], fixed world) through the candidate's inverse into the
+ * distance field of the moving object (moving_field: DEVICE float32 [d][h][w] on the moving grid of moving_spacing /
+ * moving_origin).  Q = 0: the forward term alone (fixed_points, moving_field and its frame are then ignored).  The calls and
+ * their order are those above with the same dof, P and Q throughout; ws holds ctu_similarity_ws_bytes(P, Q) bytes (0 for
+ * P < 1 or Q < 0): a head of 1024 bytes -- M [16], M_c [16], their inverses [16] [16], H [28], b [7], pivot [3], candidate
+ * pivot [3], mean [3], cost, lambda, det, candidate det, inliers and backward inliers (int64), alive (int64) -- then one slab
+ * row of 40 doubles per block: min(ceil((P + Q) / 256), CTU_REG_MAX_BLOCKS) rows of (H [dof (dof + 1) / 2], b [dof], cost,
+ * inliers (int64), backward inliers (int64), padding).
+ *   init:       the mean of the finite moving points, the start state and the adjugate inverse of init; an init whose
+ *               determinant is not finite and positive (or whose inverse is not finite) leaves alive = 0: backward points
+ *               are non-inliers, every step is refused, inverse reads the identity and the scale column 0.
+ *   accumulate: one launch over P + Q items (forward, then backward) into the slab; no float atomics.
+ *   update:     as above with a Cholesky of size dof and the increment [L, pivot - L pivot + delta_t], L = exp(delta_s)
+ *               Rod(delta_w) (dof 6: Rod(delta_w)); the step is also refused when the candidate's determinant is not finite
+ *               and positive or its inverse not finite.  Writes matrix, inverse (adjugate) and history[it] = (cost / (P + Q),
+ *               inliers, lambda, flag, backward inliers, cbrt(det)), history DEVICE double [history_rows][6]. */
+size_t ctu_similarity_ws_bytes(int64_t P, int64_t Q);
+int ctu_similarity_init(const float* points, int64_t P, const double* init, void* ws, void* stream);
+int ctu_similarity_accumulate(int dof, const float* points, int64_t P, const float* field, int D, int H, int W,
+                              const double* spacing, const double* origin, const float* fixed_points, int64_t Q,
+                              const float* moving_field, int d, int h, int w, const double* moving_spacing,
+                              const double* moving_origin, double max_distance, void* ws, void* stream);
+int ctu_similarity_update(int dof, int64_t P, int64_t Q, int it, double* matrix, double* inverse, double* history,
+                          int history_rows, void* ws, void* stream);
+
 /* Surface meshes of label volumes and scalar fields (no reference counterpart: the reference writes NIfTI volumes only;
  * rule pinned in ctunet_amd/mesh.py): marching tetrahedra on the Kuhn split of the cells of the grid padded by one layer of
  * outside points, welded (shared vertex indices) and closed.  volume: DEVICE contiguous [D,H,W] of dtype CTU_U8 or CTU_I64
