@@ -174,6 +174,13 @@ SIGNATURES = {
     "ctu_similarity_init": (I, [P, L, P, P, P]),
     "ctu_similarity_accumulate": (I, [I, P, L, P, I, I, I, P, P, P, L, P, I, I, I, P, P, D, P, P]),
     "ctu_similarity_update": (I, [I, L, L, I, P, P, P, I, P, P]),
+    "ctu_ffd_ws_bytes": (Z, [P, L]),
+    "ctu_ffd_cells": (I, [P, L, P, P, P, P, P, P]),
+    "ctu_ffd_init": (I, [P, L, P, D, P, P, P]),
+    "ctu_ffd_accumulate": (I, [P, L, P, P, I, I, I, P, P, P, P, P, D, P, P, P, P, L, P, P]),
+    "ctu_ffd_update": (I, [L, P, P, P, P, L, I, P, P, I, P, P]),
+    "ctu_ffd_transform_points": (I, [P, L, P, P, P, P, P, P, P, P]),
+    "ctu_ffd_resample": (I, [P, I, I, I, L, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, D, P, P]),
     "ctu_mesh_ws_bytes": (Z, [I, I, I]),
     "ctu_mesh_count": (I, [P, I, I, I, I, I, L, F, P, P]),
     "ctu_mesh_emit": (I, [P, I, I, I, I, F, F, P, P, L, L, P, P, P, P]),

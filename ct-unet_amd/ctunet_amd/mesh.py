@@ -720,11 +720,15 @@ def distance_field(m: Mesh, shape, spacing=None, origin=None, max_distance=_REQU
     return out
 
 
-def transform(m: Mesh, matrix: torch.Tensor) -> Mesh:
+def transform(m: Mesh, matrix) -> Mesh:
     """The mesh with every vertex moved through ``matrix`` (float64 [3,4] or [4,4] on the mesh's device, acting on (z, y, x)
     column vectors: ``registration``'s ``matrix`` / ``inverse``): ``R v + t`` in float64, rounded to float32 once.  The faces
-    are shared, not copied; a matrix with a negative determinant flips the surface's orientation and is not corrected."""
+    are shared, not copied; a matrix with a negative determinant flips the surface's orientation and is not corrected.
+    A ``registration.DeformableResult`` in place of the matrix pushes the vertices through ``registration.transform_points``."""
     v, f = _check_mesh(m, "transform")
+    from . import registration
+    if isinstance(matrix, registration.DeformableResult):
+        return Mesh(registration.transform_points(v, matrix), f)
     if not isinstance(matrix, torch.Tensor) or matrix.dtype != torch.float64 or tuple(matrix.shape) not in ((3, 4), (4, 4)):
         raise ValueError("mesh: transform takes a float64 matrix [3,4] or [4,4]")
     if matrix.device != v.device:

@@ -93,6 +93,49 @@ A step is refused (flag -1, candidate kept, no NaN ever written) with fewer than
 not positive, a non-finite candidate, or a candidate whose determinant is non-finite or not positive or whose inverse is not
 finite.  An ``init`` with such a determinant refuses every step: the matrix stays ``init``, the backward points count as
 non-inliers, ``inverse`` reads the identity and the scale column 0.
+
+B-spline deformable registration (free-form deformation)
+--------------------------------------------------------
+
+    d = register_deformable(skull, atlas, moving_spacing=(0.8, 0.45, 0.45), fixed_spacing=1.0, max_distance=6.0)
+    prior = resample.deformable_resample(atlas, d, skull.shape, spacing=1.0, out_spacing=(0.8, 0.45, 0.45),
+                                         mode="label_linear", num_classes=2)               # the atlas on the patient's grid
+    in_atlas = mesh.transform(patient_mesh, d)                                             # points and meshes go forward
+    d.report()                                                                             # the one read-back
+
+A matrix cannot take the atlas onto one particular head.  ``register_deformable`` runs ``register`` (or takes ``affine=``) and
+then fits a displacement field on top of the frozen matrix; ``register_ffd_points`` is that optimiser itself, ``FFDPlan`` its
+two halves (the binning, which synchronises once, and ``run()``, which does not and can be captured into a graph),
+``accumulate_ffd`` one accumulation read back, ``transform_points`` the transform of points (``ctu_ffd_*`` of
+``csrc/ffd.hip``; ``tests/ffd_ref.py`` restates the rule).
+
+The transform, all float64, every operation rounded on its own: ``T(p) = q0 + u(q0)``, ``q0 = M p`` as above.  ``T`` maps
+moving world to fixed world, so it PULLS a fixed-frame volume onto a moving-frame grid and PUSHES moving-frame points into
+the fixed frame; the inverse field is out of scope.  ``u`` is a uniform cubic B-spline over control displacements ``c``
+``[3,Gz,Gy,Gx]`` (mm, fixed frame) on a lattice over the fixed field's box ``[origin, origin + (n - 1) spacing]``: with
+``control_spacing`` ``h`` (a number or a triple, mm), ``ncell_a = max(1, ceil(extent_a / h_a))``, ``G_a = ncell_a + 3`` (at most
+64) and control index ``i`` at ``origin_a + (i - 1) h_a``.  ``t_a = (q0_a - origin_a) / h_a`` clamped into ``[0, ncell_a]`` (a
+non-finite ``t_a`` takes 0), ``cell_a = min(floor(t_a), ncell_a - 1)``, ``f_a = t_a - cell_a``: the clamp extends ``u``
+continuously beyond the box.  The weights ``B(f)`` are ``RandomSpatial``'s (``tests/spatial_ref.py::bspline``) and
+``u_a = sum_lmn ((Bz_l By_m) Bx_n) c_a[cell_z + l, cell_y + m, cell_x + n]``, 64 terms added in the order l, m, n (x innermost)
+from 0.  Derivative weights: ``dB = (-(1 - f)^2 / 2, (3 f^2 - 4 f) / 2, ((-3 f^2 + 2 f) + 1) / 2, f^2 / 2)``, taken as zero on an
+axis whose ``t_a`` was clamped; ``D_ab = sum ((dBz_l By_m) Bx_n | (Bz_l dBy_m) Bx_n | (Bz_l By_m) dBx_n)_b c_a``,
+``J = I + D_ab / h_b`` and ``det`` by the first row's cofactors, ``(J00 m0 - J01 m1) + J02 m2``.
+
+The fit.  For every point ``q = T(p)``; the sample ``v``, the inside test, the gradient ``g`` and the inlier test
+(``v <= max_distance``) are the rigid rule's at ``q``.  Data cost ``1/2 sum r^2`` (``r = v`` for an inlier, ``max_distance`` or 0
+otherwise); regulariser ``1/2 w sum_edges |c_i - c_j|^2`` over the 6-neighbour lattice edges, ``w = stiffness P / (Gz Gy Gx)``.
+With ``B_c = (Bz_l By_m) Bx_n`` the weight of control ``c`` at a point: ``grad_c = sum_inliers (v g) B_c + w (deg_c c - sum_nbrs c_j)``
+(neighbours in the order -z, +z, -y, +y, -x, +x) and the majorising diagonal ``d_c = sum_inliers |g|^2 B_c + 2 w deg_c`` (the
+weights are non-negative and sum to 1, so ``(g g^T) x (B B^T) <= |g|^2 I x diag(B)``).  State: controls ``c`` (``init_control`` or
+0), ``cost = +inf``, ``lambda = 1e-3``, candidate ``c_c = c``.  For ``it`` in ``0..iterations``: accumulate at ``c_c``; accept iff the
+total cost is lower (``lambda <- max(lambda / 3, 1e-9)``, else ``lambda <- min(10 lambda, 1e9)``); the next candidate is
+``c - grad / ((1 + lambda) d + 1e-12)`` from the accepted state.  The step is refused (flag -1, the candidate stays) when the
+accepted state has no inlier or an entry of the candidate is not finite; no NaN is ever written.  History row:
+(total cost / P, data rms ``sqrt(sum r^2 / P)``, regulariser energy, inliers, lambda, flag).  The device sums a cell's points in
+sorted order segment by segment, and a control's cells by a fixed tree, so two calls are bit-equal; only the order of the
+sums differs from the restatement's.  Multi-resolution lattices, the inverse field, a symmetric FFD cost, intensity metrics
+and bending energy are out of scope.
 """
 from __future__ import annotations
 
@@ -102,6 +145,8 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
+
+import ctypes as C
 
 from . import _args, _lib
 
@@ -449,3 +494,235 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
                     moving_field=postprocess.distance_transform_edt(moving_mask == 0, sampling=msp))
     return register_similarity_points(points, field, model=model, spacing=fsp, origin=forg, init=init, iterations=iterations,
                                       max_distance=max_distance, **half)
+
+
+# ---- B-spline deformable registration -----------------------------------------------------------------------------------
+FFD_SEGMENT = 256                      # CTU_FFD_SEGMENT of ctunet_hip.h
+FFD_MAX_G = 64                         # CTU_FFD_MAX_G
+
+
+class DeformableResult(NamedTuple):
+    """``T(p) = M p + u(M p)``: ``matrix`` device float64 [4,4] (moving world -> fixed world), ``control`` device float64
+    [3,Gz,Gy,Gx] (mm) on the lattice of ``control_spacing`` over the box ``box_origin`` .. ``box_origin + box_extent`` (host
+    triples), ``history`` device float64 [iterations + 1, 6] = (total cost / P, data rms, regulariser energy, inliers, lambda,
+    1 accepted / 0 rejected / -1 refused), ``num_points`` P and ``jacobian`` device float64 [P]: ``det(I + du/dq0)`` at the
+    fitted points (None for a result put together by hand)."""
+    matrix: torch.Tensor
+    control: torch.Tensor
+    control_spacing: tuple
+    box_origin: tuple
+    box_extent: tuple
+    history: Optional[torch.Tensor] = None
+    num_points: int = 0
+    jacobian: Optional[torch.Tensor] = None
+
+    def report(self) -> dict:
+        """Reads history, controls and determinants back (the one synchronisation): ``rms_before`` / ``rms`` in mm (first and
+        last history row), ``inlier_fraction``, ``accepted`` steps, ``status`` (-1 when the last step was refused),
+        ``max_displacement`` (the longest control displacement, mm), ``min_jacobian`` and ``folded`` (points with
+        ``det <= 0``)."""
+        c = self.control.cpu().numpy()
+        rep = dict(max_displacement=float(np.sqrt((c * c).sum(0)).max()))
+        if self.history is not None:
+            h = self.history.cpu().numpy()
+            last = h[-1]
+            rep.update(rms_before=float(h[0, 1]), rms=float(last[1]), inlier_fraction=float(last[3] / max(self.num_points, 1)),
+                       accepted=int((h[:, 5] == 1).sum()), status=-1 if last[5] < 0 else 0, iterations=int(h.shape[0] - 1))
+        if self.jacobian is not None:
+            j = self.jacobian.cpu().numpy()
+            rep.update(min_jacobian=float(j.min()), folded=int((j <= 0).sum()))
+        return rep
+
+
+def ffd_lattice(shape, spacing, origin, control_spacing):
+    """(G, h, box_origin, box_extent) of the control lattice over the grid ``shape`` / ``spacing`` / ``origin`` (module
+    docstring); refuses a ``G`` above 64."""
+    sp, org = _frame(spacing, origin)
+    sp, org = sp or (1.0, 1.0, 1.0), org or (0.0, 0.0, 0.0)
+    h = _args.triple(control_spacing, _REAL_POSITIVE, what="control_spacing")
+    if h is None:
+        raise ValueError("registration: control_spacing must be positive and finite, got None")
+    extent = tuple((int(n) - 1) * s for n, s in zip(shape, sp))
+    G = tuple(max(1, math.ceil(e / ha)) + 3 for e, ha in zip(extent, h))
+    if max(G) > FFD_MAX_G:
+        raise ValueError(f"registration: control_spacing {h} gives a lattice of {G} control points, more than {FFD_MAX_G} "
+                         "along an axis")
+    return G, tuple(h), tuple(org), extent
+
+
+def _lattice_args(G, h, box_origin):
+    return _lib.array(C.c_int, G), _lib.double_array(h), _lib.double_array(box_origin)
+
+
+def _check_control(control, G, device, what: str):
+    if not isinstance(control, torch.Tensor) or control.dtype != torch.float64 or tuple(control.shape) != (3, *G):
+        raise ValueError(f"registration: {what} must be a float64 [3,{G[0]},{G[1]},{G[2]}] tensor")
+    if control.device != device:
+        raise ValueError(f"registration: {what} lives on {control.device}, the points on {device}")
+    return control.contiguous()
+
+
+class FFDPlan:
+    """The binning of a free-form fit, done once: the lattice cell of every point under the frozen ``matrix``, the points
+    sorted by cell and cut into segments of at most 256, workspace and outputs.  Building it synchronises once (the number
+    of segments); ``run()`` launches the fit without a synchronisation or an allocation and can be captured into a graph.
+    Every ``run()`` writes the same output tensors."""
+
+    def __init__(self, points, field, matrix, *, spacing=None, origin=None, control_spacing=10.0, stiffness=0.1,
+                 iterations: int = 60, max_distance=None):
+        _check_inputs(points, field)
+        if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
+            raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+        if isinstance(stiffness, bool) or not isinstance(stiffness, Real) or not math.isfinite(stiffness) or stiffness < 0:
+            raise ValueError(f"registration: stiffness must be a finite number >= 0, got {stiffness!r}")
+        if not isinstance(matrix, torch.Tensor) or matrix.dtype != torch.float64 or tuple(matrix.shape) != (4, 4):
+            raise ValueError("registration: the matrix must be a float64 [4,4] tensor (moving world -> fixed world)")
+        self.bound = _bound(max_distance)
+        self.sp, self.org = _frame(spacing, origin)
+        self.G, self.h, self.box_origin, self.box_extent = ffd_lattice(field.shape, self.sp, self.org, control_spacing)
+        _lib.check_device(_ON_GPU.format("points and field"), points, field)
+        if points.device != field.device:
+            raise ValueError(f"registration: points live on {points.device}, the field on {field.device}")
+        dev = self.dev = points.device
+        self.matrix = _check_init(matrix, dev)
+        self.pts, self.fld = points.contiguous(), field.contiguous()
+        P = self.P = int(self.pts.shape[0])
+        g3 = self.G[0] * self.G[1] * self.G[2]
+        self.weight = float(stiffness) * P / g3
+        self.rows = int(iterations) + 1
+        self.lat = _lattice_args(self.G, self.h, self.box_origin)
+        cells = torch.empty(P, dtype=torch.int32, device=dev)
+        with _lib.on(dev) as run:
+            run("ctu_ffd_cells", self.pts.data_ptr(), P, self.matrix.data_ptr(), *self.lat, cells.data_ptr())
+        ncells = (self.G[0] - 3) * (self.G[1] - 3) * (self.G[2] - 3)
+        cells = cells.to(torch.int64)
+        perm = torch.sort(cells, stable=True)[1]
+        counts = torch.bincount(cells, minlength=ncells)
+        cell_seg = torch.zeros(ncells + 1, dtype=torch.int64, device=dev)
+        cell_seg[1:] = torch.cumsum((counts + (FFD_SEGMENT - 1)) // FFD_SEGMENT, 0)
+        S = self.S = int(cell_seg[-1])                                         # the one synchronisation
+        seg = torch.arange(S, device=dev)
+        seg_cell = torch.searchsorted(cell_seg[1:].contiguous(), seg, right=True)
+        first = FFD_SEGMENT * (seg - cell_seg[seg_cell])                        # of the segment within its cell's run
+        seg_begin = (torch.cumsum(counts, 0) - counts)[seg_cell] + first
+        seg_count = torch.clamp(counts[seg_cell] - first, max=FFD_SEGMENT)
+        self.tables = tuple(t.to(torch.int32).contiguous() for t in (perm, seg_cell, seg_begin, seg_count, cell_seg))
+        self.ws = torch.empty(int(_lib.load().ctu_ffd_ws_bytes(self.lat[0], S)), dtype=torch.uint8, device=dev)
+        self.control = torch.empty((3, *self.G), dtype=torch.float64, device=dev)
+        self.history = torch.empty((self.rows, 6), dtype=torch.float64, device=dev)
+        self.jacobian = torch.empty(P, dtype=torch.float64, device=dev)
+
+    def _accumulate(self, run):
+        perm, seg_cell, seg_begin, seg_count, _ = self.tables
+        run("ctu_ffd_accumulate", self.pts.data_ptr(), self.P, self.matrix.data_ptr(), self.fld.data_ptr(), *self.fld.shape,
+            _lib.double_array(self.sp), _lib.double_array(self.org), *self.lat, self.bound, perm.data_ptr(), seg_cell.data_ptr(),
+            seg_begin.data_ptr(), seg_count.data_ptr(), self.S, self.ws.data_ptr())
+
+    def run(self, init_control=None) -> "DeformableResult":
+        if init_control is not None:
+            init_control = _check_control(init_control, self.G, self.dev, "init_control")
+        with _lib.on(self.dev) as run:
+            run("ctu_ffd_init", self.lat[0], self.S, None if init_control is None else init_control.data_ptr(), self.weight,
+                self.ws.data_ptr(), self.control.data_ptr())
+            for it in range(self.rows):
+                self._accumulate(run)
+                run("ctu_ffd_update", self.P, *self.lat, self.tables[4].data_ptr(), self.S, it, self.control.data_ptr(),
+                    self.history.data_ptr(), self.rows, self.ws.data_ptr())
+            run("ctu_ffd_transform_points", self.pts.data_ptr(), self.P, self.matrix.data_ptr(), self.control.data_ptr(),
+                *self.lat, None, self.jacobian.data_ptr())
+        return DeformableResult(self.matrix, self.control, self.h, self.box_origin, self.box_extent, self.history, self.P,
+                                self.jacobian)
+
+
+def register_ffd_points(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, *, spacing=None, origin=None,
+                        control_spacing=10.0, stiffness=0.1, iterations: int = 60, max_distance=None,
+                        init_control=None) -> DeformableResult:
+    """Fit the B-spline displacement that, behind the frozen ``matrix`` (float64 [4,4], moving world -> fixed world), takes
+    ``points`` (float32 [P,3], moving world) onto the zero set of ``field`` (float32 distances on the fixed grid of ``spacing``
+    / ``origin``) by the module docstring's rule.  ``init_control`` warm-starts at the same lattice."""
+    return FFDPlan(points, field, matrix, spacing=spacing, origin=origin, control_spacing=control_spacing, stiffness=stiffness,
+                   iterations=iterations, max_distance=max_distance).run(init_control)
+
+
+def accumulate_ffd(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, control: torch.Tensor, *, spacing=None,
+                   origin=None, control_spacing=10.0, stiffness=0.1, max_distance=None) -> dict:
+    """One accumulation of the free-form kernels at ``control``, read back for inspection: ``grad`` [3,Gz,Gy,Gx] and ``diag``
+    [Gz,Gy,Gx] (regulariser included), ``cost`` (total), ``sum2`` (sum of r^2), ``regulariser``, ``count`` and ``segments`` --
+    numpy float64, summed as the kernels sum them.  A cost that is not finite leaves ``grad`` and ``diag`` zero."""
+    plan = FFDPlan(points, field, matrix, spacing=spacing, origin=origin, control_spacing=control_spacing, stiffness=stiffness,
+                   iterations=0, max_distance=max_distance)
+    plan.run(control)
+    host = plan.ws.cpu().numpy()
+    head = host[:48].view(np.float64)
+    body = host[_HEAD_DOUBLES * 8:].view(np.float64)
+    g3 = plan.G[0] * plan.G[1] * plan.G[2]
+    return dict(grad=body[9 * g3:12 * g3].reshape(3, *plan.G).copy(), diag=body[12 * g3:13 * g3].reshape(plan.G).copy(),
+                cost=float(head[0]), sum2=float(head[1]), regulariser=float(head[2]), count=int(head[5:6].view(np.int64)[0]),
+                segments=plan.S)
+
+
+def _check_result(result) -> DeformableResult:
+    if not isinstance(result, DeformableResult):
+        raise TypeError(f"registration: expected a DeformableResult, got {type(result).__name__}")
+    m, c = result.matrix, result.control
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or tuple(m.shape) != (4, 4):
+        raise ValueError("registration: a DeformableResult's matrix must be a float64 [4,4] tensor")
+    if not isinstance(c, torch.Tensor) or c.dtype != torch.float64 or c.dim() != 4 or c.shape[0] != 3 \
+            or min(c.shape[1:]) < 4 or max(c.shape[1:]) > FFD_MAX_G:
+        raise ValueError(f"registration: a DeformableResult's control must be a float64 [3,Gz,Gy,Gx] tensor with every G in "
+                         f"4..{FFD_MAX_G}")
+    if c.device != m.device:
+        raise ValueError(f"registration: the matrix lives on {m.device}, the control on {c.device}")
+    h = _args.triple(result.control_spacing, _REAL_POSITIVE, what="control_spacing")
+    org = _args.triple(result.box_origin, _REAL, what="box_origin")
+    if h is None or org is None:
+        raise ValueError("registration: a DeformableResult needs control_spacing and box_origin")
+    return result._replace(matrix=m.contiguous(), control=c.contiguous(), control_spacing=tuple(h), box_origin=tuple(org))
+
+
+def transform_points(points: torch.Tensor, result: DeformableResult, return_jacobian: bool = False):
+    """``T(p)`` of float32 ``points`` [P,3] (moving world) in the fixed frame: float64 inside, rounded to float32 once; with
+    ``return_jacobian`` also ``det(I + du/dq0)`` per point (float64 [P])."""
+    r = _check_result(result)
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("registration: points must be a float32 [P,3] tensor")
+    _lib.check_device(_ON_GPU.format("points"), points)
+    if points.device != r.matrix.device:
+        raise ValueError(f"registration: points live on {points.device}, the result on {r.matrix.device}")
+    pts = points.contiguous()
+    P = int(pts.shape[0])
+    out = torch.empty_like(pts)
+    jac = torch.empty(P, dtype=torch.float64, device=pts.device) if return_jacobian else None
+    if P:
+        with _lib.on(pts.device) as run:
+            run("ctu_ffd_transform_points", pts.data_ptr(), P, r.matrix.data_ptr(), r.control.data_ptr(),
+                *_lattice_args(tuple(r.control.shape[1:]), r.control_spacing, r.box_origin), out.data_ptr(),
+                None if jac is None else jac.data_ptr())
+    return (out, jac) if return_jacobian else out
+
+
+def register_deformable(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spacing=None, moving_origin=None,
+                        fixed_spacing=None, fixed_origin=None, affine=None, model: str = "similarity", control_spacing=10.0,
+                        stiffness=0.1, iterations: int = 60, max_distance=None) -> DeformableResult:
+    """``register(..., model=model, max_distance=max_distance)`` unless ``affine`` (a float64 [4,4] tensor or a
+    ``RegistrationResult``) is given, then the free-form fit of the moving mask's surface voxels against the fixed mask's
+    distance field behind that matrix."""
+    from . import postprocess
+    _mask(moving_mask, "moving_mask")
+    _mask(fixed_mask, "fixed_mask")
+    (msp, morg), (fsp, forg) = _frame(moving_spacing, moving_origin, "moving_"), _frame(fixed_spacing, fixed_origin, "fixed_")
+    ffd_lattice(fixed_mask.shape, fsp, forg, control_spacing)
+    _lib.check_device(_ON_GPU.format("the masks"), moving_mask, fixed_mask)
+    if isinstance(affine, RegistrationResult):
+        affine = affine.matrix
+    if affine is None:
+        affine = register(moving_mask, fixed_mask, moving_spacing=msp, moving_origin=morg, fixed_spacing=fsp, fixed_origin=forg,
+                          model=model, max_distance=max_distance).matrix
+    else:
+        affine = _check_init(affine, moving_mask.device)
+    points = surface_points(moving_mask, msp, morg)
+    if points.shape[0] < 1:
+        raise ValueError("registration: the moving mask is empty")
+    field = postprocess.distance_transform_edt(fixed_mask == 0, sampling=fsp)
+    return register_ffd_points(points, field, affine, spacing=fsp, origin=forg, control_spacing=control_spacing,
+                               stiffness=stiffness, iterations=iterations, max_distance=max_distance)

@@ -297,3 +297,48 @@ def affine_resample(x, out_to_in, out_shape, *, spacing=None, origin=None, out_s
         ops.affine_resample(_lib.as_bytes(x), _lib.as_bytes(out), _MODE_CODE[mode], int(num_classes or 0), n, src, dst, m,
                             sp, org, osp, oorg, fillv)
     return out
+
+
+def deformable_resample(x, result, out_shape, *, spacing=None, origin=None, out_spacing=None, out_origin=None,
+                        mode: str = "linear", num_classes: Optional[int] = None, fill=0, out=None) -> torch.Tensor:
+    """``x [..., D, H, W]`` (fixed frame, grid ``spacing`` / ``origin``) pulled onto the moving-frame grid ``out_shape`` /
+    ``out_spacing`` / ``out_origin`` through ``result`` (a ``registration.DeformableResult``): per output voxel the world
+    coordinate ``w``, ``s = T(w) = M w + u(M w)``, then ``affine_resample``'s rule per mode from ``u_a = (s_a - origin_a) /
+    spacing_a`` on; same dtypes, limits and fill.  With zero controls it is ``affine_resample(x, result.matrix, ...)`` bit
+    for bit."""
+    from . import registration
+    who = "deformable_resample"
+    _check_call(x, mode, num_classes, who, _AFFINE_DTYPES)
+    src = _args.grid(tuple(int(s) for s in x.shape[-3:]), _GRID, who=who, what="the input grid")
+    dst = _args.grid(out_shape, _GRID, who=who, what="out_shape")
+    sp = _args.triple(spacing, _REAL_POSITIVE, who=who, what="spacing")
+    org = _args.triple(origin, _REAL, who=who, what="origin")
+    osp = _args.triple(out_spacing, _REAL_POSITIVE, who=who, what="out_spacing")
+    oorg = _args.triple(out_origin, _REAL, who=who, what="out_origin")
+    if isinstance(fill, bool) or not isinstance(fill, Real):
+        raise TypeError(f"{who}: fill must be a number, got {fill!r}")
+    out_dtype = torch.float32 if mode == "linear" else x.dtype
+    fillv = float(fill) + 0.0                                            # -0.0 -> 0.0
+    if out_dtype == torch.float32:
+        if not math.isfinite(fillv) or not math.isfinite(C.c_float(fillv).value):
+            raise ValueError(f"{who}: fill must be finite in float32, got {fill!r}")
+    else:
+        lo, hi = (-32768, 32767) if out_dtype == torch.int16 else ((0, 1) if out_dtype == torch.bool else (0, 255))
+        if fillv != math.floor(fillv) or not lo <= fillv <= hi:
+            raise ValueError(f"{who}: fill must be an integer in {lo}..{hi} for {out_dtype}, got {fill!r}")
+    r = registration._check_result(result)
+    lead, n = _lead(x, who)
+    _args.check_out(out, lead + dst, out_dtype, x.device, who, TypeError)
+    _lib.check_device(f"{who}: the input must live on the GPU; this path has no CPU fallback", x)
+    if r.matrix.device != x.device:
+        raise ValueError(f"{who}: the result lives on {r.matrix.device}, the volume on {x.device}: the kernel reads it from "
+                         "device memory")
+    if out is None:
+        out = torch.empty(lead + dst, dtype=out_dtype, device=x.device)
+    xin, xout = _lib.as_bytes(x), _lib.as_bytes(out)
+    with _lib.on(x.device) as run:
+        run("ctu_ffd_resample", xin.data_ptr(), ops.RESAMPLE_CODE[xin.dtype], _MODE_CODE[mode], int(num_classes or 0), n, *src,
+            *dst, r.matrix.data_ptr(), r.control.data_ptr(),
+            *registration._lattice_args(tuple(r.control.shape[1:]), r.control_spacing, r.box_origin), _lib.double_array(sp),
+            _lib.double_array(org), _lib.double_array(osp), _lib.double_array(oorg), fillv, xout.data_ptr())
+    return out

@@ -755,6 +755,54 @@ int ctu_similarity_accumulate(int dof, const float* points, int64_t P, const flo
 int ctu_similarity_update(int dof, int64_t P, int64_t Q, int it, double* matrix, double* inverse, double* history,
                           int history_rows, void* ws, void* stream);
 
+/* B-spline free-form deformation behind a frozen affine matrix (rule pinned in ctunet_amd/registration.py):
+ * T(p) = q0 + u(q0), q0 = matrix p (DEVICE double, the first 12 entries of a row-major [3][4] / [4][4]); u the uniform cubic
+ * B-spline over control: DEVICE double [3][Gz][Gy][Gx] (mm, fixed frame).  G: HOST int [3], each in 4..CTU_FFD_MAX_G;
+ * control_spacing, box_origin: HOST double [3]; control index i sits at box_origin + (i - 1) control_spacing and the lattice
+ * has G - 3 cells per axis.  A knot is clamped into the lattice (NaN -> 0) before it indexes a control.
+ *   cells:      cells[i] = the lattice cell (cz * ncy + cy) * ncx + cx of point i (DEVICE int32 [P]); the caller sorts the
+ *               points by it (stably) and cuts each cell's run into segments of at most CTU_FFD_SEGMENT points:
+ *               perm [P] (sorted position -> point), seg_cell / seg_begin / seg_count [S] (begin: a sorted position) and
+ *               cell_seg [cells + 1] (the first segment of every cell, ascending), all DEVICE int32.  Every index read from
+ *               them is checked against its range; a bad one counts as an absent point.
+ *   ws:         ctu_ffd_ws_bytes(G, S) bytes (0 for a bad G or S < 1), 8-byte aligned: a head of 1024 bytes, the accepted
+ *               controls, two candidate buffers, gradient and diagonal of the accepted controls, one cost and one inlier
+ *               count per segment, and one slab row of 256 doubles (64 controls x gradient z, y, x, diagonal) per segment.
+ *   init:       the start state (controls = init_control, DEVICE double [3][Gz][Gy][Gx] or NULL = 0; cost = +inf,
+ *               lambda = 1e-3, regulariser weight `weight`), and control = the start controls.
+ *   accumulate: one block per segment at the current candidate; no float atomics.
+ *   update:     iteration `it`: reduces cost and regulariser, accepts iff the total cost is lower (lambda / 3, at least 1e-9;
+ *               otherwise lambda * 10, at most 1e9), then a wave per control point gathers gradient and diagonal (on an
+ *               accept), stores the accepted controls into `control` and writes the next candidate
+ *               c - grad / ((1 + lambda) d + 1e-12).  history[it] = (total cost / P, data rms, regulariser energy, inliers,
+ *               lambda, 1 accepted / 0 rejected / -1 refused), history DEVICE double [history_rows][6]; a step is refused
+ *               without an inlier or with a candidate entry that is not finite (that entry is never written).
+ * A fit is cells, init, then (accumulate, update) for it = 0 .. history_rows - 1: no host sync after the tables are built,
+ * capture-safe, two runs bitwise equal.
+ *   transform_points: out (DEVICE float32 [P][3] or NULL) = float32(T(p)); jacobian (DEVICE double [P] or NULL) =
+ *               det(I + du/dq0); at least one of the two.
+ *   resample:   ctu_affine_resample with s = T(w) in place of s = out_to_in w: per output voxel w is its world coordinate,
+ *               u_a = (s_a - origin_a) / spacing_a, then that entry point's rule per mode; same dtypes, limits and fill. */
+#define CTU_FFD_SEGMENT 256
+#define CTU_FFD_MAX_G 64
+size_t ctu_ffd_ws_bytes(const int* G, int64_t S);
+int ctu_ffd_cells(const float* points, int64_t P, const double* matrix, const int* G, const double* control_spacing,
+                  const double* box_origin, int* cells, void* stream);
+int ctu_ffd_init(const int* G, int64_t S, const double* init_control, double weight, void* ws, double* control, void* stream);
+int ctu_ffd_accumulate(const float* points, int64_t P, const double* matrix, const float* field, int D, int H, int W,
+                       const double* spacing, const double* origin, const int* G, const double* control_spacing,
+                       const double* box_origin, double max_distance, const int* perm, const int* seg_cell,
+                       const int* seg_begin, const int* seg_count, int64_t S, void* ws, void* stream);
+int ctu_ffd_update(int64_t P, const int* G, const double* control_spacing, const double* box_origin, const int* cell_seg,
+                   int64_t S, int it, double* control, double* history, int history_rows, void* ws, void* stream);
+int ctu_ffd_transform_points(const float* points, int64_t P, const double* matrix, const double* control, const int* G,
+                             const double* control_spacing, const double* box_origin, float* out, double* jacobian,
+                             void* stream);
+int ctu_ffd_resample(const void* in, int dtype, int mode, int num_classes, int64_t N, int D, int H, int W, int d, int h, int w,
+                     const double* matrix, const double* control, const int* G, const double* control_spacing,
+                     const double* box_origin, const double* spacing, const double* origin, const double* out_spacing,
+                     const double* out_origin, double fill, void* out, void* stream);
+
 /* Surface meshes of label volumes and scalar fields (no reference counterpart: the reference writes NIfTI volumes only;
  * rule pinned in ctunet_amd/mesh.py): marching tetrahedra on the Kuhn split of the cells of the grid padded by one layer of
  * outside points, welded (shared vertex indices) and closed.  volume: DEVICE contiguous [D,H,W] of dtype CTU_U8 or CTU_I64
