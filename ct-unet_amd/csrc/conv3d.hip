@@ -1148,6 +1148,11 @@ struct WgP {
     const float* lz_coef;
     int lz_cp;
 };
+// the fused up-convolution's coarse activations in two segments: `in` holds channels [0, seg_c), in1 those from seg_c on
+struct WgP2 : WgP {
+    const float* in1;
+    int seg_c;
+};
 
 // One block: one (ci-tile of 16, co-tile of 16) pair, KDS kd-planes of taps, a strided set of
 // spatial tiles.  MFMA view: M = 16 input channels, N = 16 output channels, K = voxels.
@@ -1343,9 +1348,15 @@ inline int wgrad_gx(int ntiles, int pairs_z) {
 // so the separate apply pass over the layer (read g, read y, write g) disappears.  Every staged item stores the value of the
 // address it fetched (volume-face items fetch the box origin and store that voxel's value again; blocks that share a
 // gradient tile store identical values), so the stores need no predicate.  Full boxes and channel tiles only (host check).
-template <int SM, int SN, int UP = 0, bool LZ = false>
-__global__ __launch_bounds__(256, CTU_K3S_OCC) void conv3d_wgrad_k3s_kernel(WgP p, int tiles_per_block) {
+// S2 (UP only): the coarse activations' channels live in two segments of the same voxel stride -- channels [0, seg_c) behind
+// p.in, [seg_c, cin_p) behind p.in1 (WgP2), seg_c a multiple of 16: the block's 16-channel input tile lies in one segment,
+// chosen from the scalar arguments; the per-thread offsets, the transform vectors and the slabs are the one-buffer kernel's.
+// The parameter struct depends on S2, so the one-buffer instantiations are the code they were before S2 existed.
+template <int SM, int SN, int UP = 0, bool LZ = false, bool S2 = false>
+__global__ __launch_bounds__(256, CTU_K3S_OCC) void conv3d_wgrad_k3s_kernel(typename std::conditional<S2, WgP2, WgP>::type p,
+                                                                            int tiles_per_block) {
     static_assert(!UP || (SM == 1 && SN == 1), "the fused up-convolution uses the full 16 x 16 channel tile");
+    static_assert(!S2 || UP, "two input segments: the fused up-convolution only");
     // box: 4 x 4 x 16 voxels; 4 x 4 x 8 for the full 16 x 16 channel tile, whose 27 accumulators leave fewer staging registers
     constexpr int TD = 4, TH = 4, TW = (SM == 2 && SN == 2) ? 16 : 8, HD = 6, HH = 6, HW = TW + 2, HV = HD * HH * HW;
     constexpr int KPR = TW / 4, NKS = TH * KPR;       // K-steps (4 voxels) per row / per plane
@@ -1462,7 +1473,11 @@ __global__ __launch_bounds__(256, CTU_K3S_OCC) void conv3d_wgrad_k3s_kernel(WgP 
     auto prep = [&](Box b) -> bool {
         const int d0 = b.tz * TD, h0 = b.ty * TH, w0 = b.tx * TW;
         const long long org = (((long long)b.n * p.D + d0) * p.H + h0) * p.W + w0;
-        pf_abase = reinterpret_cast<const char*>(p.in + (org - ((long long)p.H * p.W + p.W + 1)) * p.in_cs);
+        const float* src = p.in;
+        if constexpr (S2) {
+            if (ci0 >= p.seg_c) src = p.in1 - p.seg_c;     // uniform: this block's segment
+        }
+        pf_abase = reinterpret_cast<const char*>(src + (org - ((long long)p.H * p.W + p.W + 1)) * p.in_cs);
         if (UP) {
             const long long gorg = (((long long)b.n * 2 * p.D + 2 * d0 + pz) * gH + 2 * h0 + py) * gW + 2 * w0 + px;
             pf_gbase = reinterpret_cast<const char*>(p.g + gorg * p.g_cs);
@@ -2506,15 +2521,16 @@ extern "C" size_t ctu_upconv_fused_wgrad_ws_floats(int N, int D, int H, int W, i
     return na > nb ? na : nb;                            // either tiling (the w-parity tile needs nout_p = 8 = g_cs)
 }
 
-static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
-                                   int in_relu, const float* gout, int g_cs, int nout_p, float* dweff, float* ws,
-                                   int N, int D, int H, int W, const LazyBn* lz, void* stream);
+// in1 / seg_c: the coarse activations in two segments (seg_c == 0: one buffer, in1 unused)
+static int upconv_fused_wgrad_impl(const float* in, const float* in1, int seg_c, int in_cs, int cin_p, const float* in_scale,
+                                   const float* in_shift, int in_relu, const float* gout, int g_cs, int nout_p, float* dweff,
+                                   float* ws, int N, int D, int H, int W, const LazyBn* lz, void* stream);
 
 extern "C" int ctu_upconv_fused_wgrad(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                                       int in_relu, const float* gout, int g_cs, int nout_p, float* dweff, float* ws,
                                       int N, int D, int H, int W, void* stream) {
-    return upconv_fused_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, nout_p, dweff, ws, N, D, H, W,
-                                   nullptr, stream);
+    return upconv_fused_wgrad_impl(in, nullptr, 0, in_cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, nout_p, dweff, ws,
+                                   N, D, H, W, nullptr, stream);
 }
 
 // full coarse boxes (4 x 4 x 8) and full 16-channel input tiles
@@ -2522,23 +2538,57 @@ extern "C" int ctu_upconv_fused_wgrad_bn_supported(int N, int D, int H, int W, i
     return (N > 0 && D % 4 == 0 && H % 4 == 0 && W % 8 == 0 && cin_p % 16 == 0 && nout_p % 8 == 0) ? 1 : 0;
 }
 
+#define CTU_UPWG_BN_CHECK(name)                                                                                              \
+    CTU_REQUIRE(y && bn_scale && bn_shift && coef && gy_out, name ": null pointer");                                         \
+    CTU_REQUIRE(ctu_upconv_fused_wgrad_bn_supported(N, D, H, W, cin_p, nout_p), name ": geometry not supported");            \
+    CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0 && gy_out != ga,                                   \
+                name ": y / gy_out alignment, gy_out must not alias ga")
+
 extern "C" int ctu_upconv_fused_wgrad_bn(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
                                          int in_relu, const float* ga, int g_cs, int nout_p, const float* y,
                                          const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
                                          float* dweff, float* ws, int N, int D, int H, int W, void* stream) {
-    CTU_REQUIRE(y && bn_scale && bn_shift && coef && gy_out, "upconv_fused_wgrad_bn: null pointer");
-    CTU_REQUIRE(ctu_upconv_fused_wgrad_bn_supported(N, D, H, W, cin_p, nout_p), "upconv_fused_wgrad_bn: geometry not supported");
-    CTU_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)gy_out & 15) == 0 && gy_out != ga, "upconv_fused_wgrad_bn: y / gy_out alignment, gy_out must not alias ga");
+    CTU_UPWG_BN_CHECK("upconv_fused_wgrad_bn");
     const LazyBn lz = {y, bn_scale, bn_shift, coef, gy_out, nout_p};
-    return upconv_fused_wgrad_impl(in, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, nout_p, dweff, ws, N, D, H, W, &lz, stream);
+    return upconv_fused_wgrad_impl(in, nullptr, 0, in_cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, nout_p, dweff, ws,
+                                   N, D, H, W, &lz, stream);
 }
 
-static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
-                                   int in_relu, const float* gout, int g_cs, int nout_p, float* dweff, float* ws,
-                                   int N, int D, int H, int W, const LazyBn* lz, void* stream) {
+// the two-segment forms: the block's 16-channel input tile must lie in one segment
+#define CTU_UPWG_SEG2_CHECK(name)                                                                                            \
+    CTU_REQUIRE(in0 && in1, name ": null segment");                                                                          \
+    CTU_REQUIRE(seg_c > 0 && seg_c % 16 == 0 && 2 * seg_c == cin_p,                                                          \
+                name ": seg_c=%d must be a multiple of 16 and half of cin_p=%d", seg_c, cin_p);                              \
+    CTU_REQUIRE(((uintptr_t)in1 & 15) == 0, name ": 16-byte alignment")
+
+extern "C" int ctu_upconv_fused_wgrad_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p, const float* in_scale,
+                                           const float* in_shift, int in_relu, const float* gout, int g_cs, int nout_p,
+                                           float* dweff, float* ws, int N, int D, int H, int W, void* stream) {
+    CTU_UPWG_SEG2_CHECK("upconv_fused_wgrad_seg2");
+    return upconv_fused_wgrad_impl(in0, in1, seg_c, cs, cin_p, in_scale, in_shift, in_relu, gout, g_cs, nout_p, dweff, ws,
+                                   N, D, H, W, nullptr, stream);
+}
+
+extern "C" int ctu_upconv_fused_wgrad_bn_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p,
+                                              const float* in_scale, const float* in_shift, int in_relu, const float* ga, int g_cs,
+                                              int nout_p, const float* y, const float* bn_scale, const float* bn_shift,
+                                              const float* coef, float* gy_out, float* dweff, float* ws, int N, int D, int H,
+                                              int W, void* stream) {
+    CTU_UPWG_SEG2_CHECK("upconv_fused_wgrad_bn_seg2");
+    CTU_UPWG_BN_CHECK("upconv_fused_wgrad_bn_seg2");
+    const LazyBn lz = {y, bn_scale, bn_shift, coef, gy_out, nout_p};
+    return upconv_fused_wgrad_impl(in0, in1, seg_c, cs, cin_p, in_scale, in_shift, in_relu, ga, g_cs, nout_p, dweff, ws,
+                                   N, D, H, W, &lz, stream);
+}
+#undef CTU_UPWG_SEG2_CHECK
+#undef CTU_UPWG_BN_CHECK
+
+static int upconv_fused_wgrad_impl(const float* in, const float* in1, int seg_c, int in_cs, int cin_p, const float* in_scale,
+                                   const float* in_shift, int in_relu, const float* gout, int g_cs, int nout_p, float* dweff,
+                                   float* ws, int N, int D, int H, int W, const LazyBn* lz, void* stream) {
     CTU_REQUIRE(in && gout && dweff && ws, "upconv_fused_wgrad: null pointer");
     CTU_REQUIRE(cin_p % 8 == 0 && nout_p % 8 == 0 && cin_p > 0 && nout_p > 0 && nout_p <= 64, "upconv_fused_wgrad: padded channels");
-    CTU_REQUIRE(in_cs >= cin_p && in_cs % 4 == 0 && g_cs >= nout_p && g_cs % 4 == 0, "upconv_fused_wgrad: bad stride");
+    CTU_REQUIRE(in_cs >= (seg_c ? seg_c : cin_p) && in_cs % 4 == 0 && g_cs >= nout_p && g_cs % 4 == 0, "upconv_fused_wgrad: bad stride");
     CTU_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)gout & 15) == 0, "upconv_fused_wgrad: 16-byte alignment");
     CTU_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "upconv_fused_wgrad: scale/shift must come together");
     CTU_REQUIRE((int64_t)(2 * H * W + 2 * W + 2) * in_cs * 4 < (int64_t)1 << 31 && (int64_t)(8 * 2 * H + 8) * 2 * W * g_cs * 4 < (int64_t)1 << 31,
@@ -2546,7 +2596,8 @@ static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const 
     hipStream_t st = (hipStream_t)stream;
     const bool pw = nout_p == 8 && g_cs == 8;             // (w-parity, c_out) tile: the two fine voxels are 16 contiguous floats
     const UpWgPlan g = upwg_plan(N, D, H, W, cin_p, nout_p, pw);
-    WgP p;
+    WgP2 p;                                              // (the one-buffer kernels take its WgP part)
+    p.in1 = in1; p.seg_c = seg_c;
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.g = gout; p.ws = ws;
     p.in_cs = in_cs; p.cin_p = cin_p; p.in_relu = in_relu; p.g_cs = g_cs; p.cout_p = nout_p;
     p.N = N; p.D = D; p.H = H; p.W = W;
@@ -2554,17 +2605,26 @@ static int upconv_fused_wgrad_impl(const float* in, int in_cs, int cin_p, const 
     p.ntiles = g.ntiles; p.n_ci_t = g.n_ci_g; p.n_co_t = g.n_co_g;
     p.lz_y = nullptr; p.lz_out = nullptr; p.lz_scale = nullptr; p.lz_shift = nullptr; p.lz_coef = nullptr; p.lz_cp = 0;
     if (lz) { p.lz_y = lz->y; p.lz_out = lz->out; p.lz_scale = lz->scale; p.lz_shift = lz->shift; p.lz_coef = lz->coef; p.lz_cp = lz->cp; }
+    const dim3 grid(g.grid.gx, g.pairs);
+    // one launch of the tiling UP (1: channel tile, 2: w-parity tile), with or without the lazy BatchNorm backward, one-buffer
+    // or two-segment form
+#define CTU_UPWG_LAUNCH(UP)                                                                                              \
+    do {                                                                                                                 \
+        if (seg_c && lz) conv3d_wgrad_k3s_kernel<1, 1, UP, true, true><<<grid, 256, 0, st>>>(p, g.grid.tpb);              \
+        else if (seg_c) conv3d_wgrad_k3s_kernel<1, 1, UP, false, true><<<grid, 256, 0, st>>>(p, g.grid.tpb);              \
+        else if (lz) conv3d_wgrad_k3s_kernel<1, 1, UP, true><<<grid, 256, 0, st>>>(p, g.grid.tpb);                        \
+        else conv3d_wgrad_k3s_kernel<1, 1, UP><<<grid, 256, 0, st>>>(p, g.grid.tpb);                                      \
+    } while (0)
     if (pw) {
         p.cout_p = 16;                                   // all 4 channel quads of the (w-parity, c_out) tile are real
-        if (lz) conv3d_wgrad_k3s_kernel<1, 1, 2, true><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
-        else conv3d_wgrad_k3s_kernel<1, 1, 2><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
+        CTU_UPWG_LAUNCH(2);
         CTU_CHECK_LAUNCH("upconv_fused_wgrad(pw)");
         upconv_wgrad_reduce_pw_kernel<<<dim3(12 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, g.n_ci_g, g.grid.gx);
         CTU_CHECK_LAUNCH("upconv_fused_wgrad_reduce(pw)");
         return CTU_OK;
     }
-    if (lz) conv3d_wgrad_k3s_kernel<1, 1, 1, true><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
-    else conv3d_wgrad_k3s_kernel<1, 1, 1><<<dim3(g.grid.gx, g.pairs), 256, 0, st>>>(p, g.grid.tpb);
+    CTU_UPWG_LAUNCH(1);
+#undef CTU_UPWG_LAUNCH
     CTU_CHECK_LAUNCH("upconv_fused_wgrad");
     upconv_wgrad_reduce_kernel<<<dim3(8 * 256 / 64, g.pairs), 64 * RPARTS, 0, st>>>(ws, dweff, cin_p, nout_p, g.n_ci_g, g.n_co_g, g.grid.gx);
     CTU_CHECK_LAUNCH("upconv_fused_wgrad_reduce");

@@ -39,11 +39,24 @@ struct UpP {
     ctu_bn_tail tail;         // counter != NULL: the last block of the launch finalizes the BatchNorm (bn_tail.h)
 };
 
+// Parameters of a kernel's two-segment form: the coarse tensor behind P's pointer (UpP::in, UpDP::out) holds channels
+// [0, seg_c) only, seg1 holds the channels from seg_c on, both at P's voxel stride.
+template <class P>
+struct UpSeg2 : P {
+    float* seg1;
+    int seg_c;
+};
+
 // PW (8 padded output channels): a 16-wide tile would be half empty, so the w-parity moves into the tile instead --
 // columns = (p_w, c_out), 4 (p_d, p_h) parities per block, 2 x 2 x 3 taps (w offsets 0..2; offset 0 only feeds the
 // p_w = 0 half, offset 2 only the p_w = 1 half, zeros elsewhere): 48 tile-taps instead of 64.
-template <int PB, int NTP, bool PW = false>
-__global__ __launch_bounds__(256, 2) void upconv_fused_fwd_kernel(UpP p, int ntiles, int tiles_per_block) {
+// S2: the coarse input's channels live in two segments of the same voxel stride -- channels [0, seg_c) behind p.in,
+// [seg_c, rin_p) behind p.seg1 (UpSeg2<UpP>; seg_c a multiple of 8, so a staged 8-channel chunk lies in one segment: the
+// choice is uniform for the block and made from the scalar arguments per load_a; the per-thread offsets are the one-buffer
+// kernel's).  The parameter struct depends on S2, so the one-buffer instantiations are the code they were before S2 existed.
+template <int PB, int NTP, bool PW = false, bool S2 = false>
+__global__ __launch_bounds__(256, 2) void upconv_fused_fwd_kernel(typename std::conditional<S2, UpSeg2<UpP>, UpP>::type p, int ntiles,
+                                                                   int tiles_per_block) {
     static_assert(PW ? (PB == 4 && NTP == 1) : ((PB * NTP == 8 || (PB == 4 && NTP == 1)) && (PB == 8 || PB == 4 || PB == 2)), "tile-parities per block");
     constexpr int NTW = PW ? 3 : 2, TAPS = 4 * NTW;      // taps along w / per parity
     constexpr int MT = 4, TD = 4, TH = 4, TW = 16;
@@ -135,7 +148,11 @@ __global__ __launch_bounds__(256, 2) void upconv_fused_fwd_kernel(UpP p, int nti
             sh = *reinterpret_cast<const float4*>(p.in_shift + cc * 8 + half * 4);
         }
         const long long org = (((long long)b.n * p.D + d0) * p.H + h0) * p.W + w0 - ((long long)p.H * p.W + p.W + 1);
-        const char* base = reinterpret_cast<const char*>(p.in + org * p.in_cs + cc * 8);
+        const float* src = p.in;
+        if constexpr (S2) {
+            if (cc * 8 >= p.seg_c) src = p.seg1 - p.seg_c;                  // uniform: this chunk's segment
+        }
+        const char* base = reinterpret_cast<const char*>(src + org * p.in_cs + cc * 8);
         a_interior = d0 >= 1 && h0 >= 1 && w0 >= 1 && d0 + TD < p.D && h0 + TH < p.H && w0 + TW < p.W;
         if (a_interior) {
 #pragma unroll
@@ -358,8 +375,12 @@ struct UpDP {
     int tiles_d, tiles_h, tiles_w, n16;
 };
 
-template <int NT>
-__global__ __launch_bounds__(256, 2) void upconv_fused_bwd_data_kernel(UpDP p, int ntiles, int tiles_per_block) {
+// S2: the coarse input gradient is written as two segments of the same voxel stride -- channels [0, seg_c) to p.out,
+// [seg_c, cin_p) to p.seg1 (UpSeg2<UpDP>; seg_c a multiple of 16: an output N-tile lies in one segment, chosen from the scalar
+// arguments).
+template <int NT, bool S2 = false>
+__global__ __launch_bounds__(256, 2) void upconv_fused_bwd_data_kernel(typename std::conditional<S2, UpSeg2<UpDP>, UpDP>::type p,
+                                                                        int ntiles, int tiles_per_block) {
     constexpr int MT = 4, TD = 4, TH = 4, TW = 16;
     constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2, HV = HD * HH * HW;
     constexpr int NTHR = 256;
@@ -567,17 +588,22 @@ __global__ __launch_bounds__(256, 2) void upconv_fused_bwd_data_kernel(UpDP p, i
         if (c == nchunk - 1) {
             const int d0 = box.tz * TD, h0 = box.ty * TH, w0 = box.tx * TW;
             const int gw = w0 + m;
-            float* obase = p.out + ((((size_t)box.n * p.D + d0 + wave) * p.H + h0) * p.W + gw) * p.out_cs;
+            const size_t ovox = (((size_t)box.n * p.D + d0 + wave) * p.H + h0) * p.W + gw;
+            float* obase = p.out + ovox * p.out_cs;
             const int orow = p.W * p.out_cs;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int co = (by * NT + nt) * 16 + kq * 4;
+                float* otile = obase;
+                if constexpr (S2) {
+                    if ((by * NT + nt) * 16 >= p.seg_c) otile = p.seg1 - p.seg_c + ovox * p.out_cs;     // uniform: this tile's segment
+                }
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     if (co < p.cin_p && d0 + wave < p.D && h0 + mt < p.H && gw < p.W) {
                         float4 o;
                         o.x = acc[mt][nt][0]; o.y = acc[mt][nt][1]; o.z = acc[mt][nt][2]; o.w = acc[mt][nt][3];
-                        *reinterpret_cast<float4*>(obase + mt * orow + co) = o;
+                        *reinterpret_cast<float4*>(otile + mt * orow + co) = o;
                     }
                     acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
@@ -1048,19 +1074,30 @@ extern "C" int ctu_upconv_fused_pack(const float* wt, const float* bt, const flo
     return ctu_upconv_fused_pack_all(wt, bt, w3, C, Co, cinv, cin_p, nout_p, wp, beff, ws, nullptr, stream);
 }
 
-extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
-                                    int in_relu, const float* wp, const float* beff, float* out, int out_cs, int nout_p,
-                                    float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail, void* stream) {
+// The two-segment forms (ctu_upconv_fused_*_seg2): the coarse tensor's cin_p channels in two buffers of the same voxel
+// stride, seg_c = cin_p / 2 channels each.  The forward stages 8-channel chunks, the weight and data gradients work on
+// 16-channel tiles: a chunk / tile must lie in one segment (mult = 8 / 16).
+static bool up_seg2_ok(int cin_p, int seg_c, int mult) { return seg_c > 0 && seg_c % mult == 0 && 2 * seg_c == cin_p; }
+
+extern "C" int ctu_upconv_fused_seg2_supported(int k, int D, int H, int W, int cin_p, int nout_p, int seg_c) {
+    return ctu_upconv_fused_supported(k, D, H, W, cin_p, nout_p) && up_seg2_ok(cin_p, seg_c, 16);
+}
+
+// seg_c == 0: the one-buffer entry (in1 unused, in_cs >= cin_p); else in / in1 hold seg_c channels each at stride in_cs
+static int upconv_fused_fwd_impl(const float* in, const float* in1, int seg_c, int in_cs, int cin_p, const float* in_scale,
+                                 const float* in_shift, int in_relu, const float* wp, const float* beff, float* out, int out_cs,
+                                 int nout_p, float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail, void* stream) {
     CTU_REQUIRE(in && wp && beff && out, "upconv_fused_fwd: null pointer");
     CTU_REQUIRE(ctu_upconv_fused_supported(3, D, H, W, cin_p, nout_p), "upconv_fused_fwd: unsupported geometry (W=%d cin_p=%d nout_p=%d)",
                 W, cin_p, nout_p);
-    CTU_REQUIRE(in_cs >= cin_p && in_cs % 4 == 0 && out_cs >= nout_p && out_cs % 4 == 0, "upconv_fused_fwd: bad stride");
+    CTU_REQUIRE(in_cs >= (seg_c ? seg_c : cin_p) && in_cs % 4 == 0 && out_cs >= nout_p && out_cs % 4 == 0, "upconv_fused_fwd: bad stride");
     CTU_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "upconv_fused_fwd: scale/shift must come together");
     CTU_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)wp & 15) == 0 && ((uintptr_t)beff & 15) == 0,
                 "upconv_fused_fwd: 16-byte alignment");
     CTU_REQUIRE((int64_t)N * D * H * W * 8 < (int64_t)1 << 31 && (int64_t)(2 * H * W + 2 * W + 2) * in_cs * 4 < (int64_t)1 << 31,
                 "upconv_fused_fwd: volume too large for 32-bit offsets");
-    UpP p;
+    UpSeg2<UpP> p;                                      // (the one-buffer kernels take its UpP part)
+    p.seg1 = const_cast<float*>(in1); p.seg_c = seg_c;
     p.in = in; p.in_scale = in_scale; p.in_shift = in_shift; p.wp = wp; p.beff = beff; p.out = out; p.stats = stats;
     CTU_REQUIRE(!tail || (stats && tail->counter && tail->gamma && tail->beta && tail->scale && tail->shift && tail->mean &&
                           tail->invstd && tail->C > 0 && tail->C <= nout_p && tail->count > 0),
@@ -1072,16 +1109,41 @@ extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const
     p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     const int ny = r.ny, gx = r.grid.gx, tpb = r.grid.tpb, ntiles = r.ntiles;
     hipStream_t st = (hipStream_t)stream;
+    // one launch of the variant <PB, NTP, PW> on ny parity groups, one-buffer or two-segment form
+#define CTU_UP_FWD(NY, ...)                                                                                            \
+    do {                                                                                                               \
+        if (seg_c) upconv_fused_fwd_kernel<__VA_ARGS__, true><<<dim3(gx, NY), 256, 0, st>>>(p, ntiles, tpb);            \
+        else upconv_fused_fwd_kernel<__VA_ARGS__, false><<<dim3(gx, NY), 256, 0, st>>>(p, ntiles, tpb);                 \
+    } while (0)
     if (nout_p == 16 && ny == 2) {
-        upconv_fused_fwd_kernel<4, 1><<<dim3(gx, 2), 256, 0, st>>>(p, ntiles, tpb);
+        CTU_UP_FWD(2, 4, 1, false);
     } else if (nout_p == 8) {
         p.wp = wp + up_std_packed(cin_p, nout_p);                 // w-parity-in-tile packing
-        upconv_fused_fwd_kernel<4, 1, true><<<dim3(gx, 1), 256, 0, st>>>(p, ntiles, tpb);
-    } else if (ny == 1) upconv_fused_fwd_kernel<8, 1><<<dim3(gx, 1), 256, 0, st>>>(p, ntiles, tpb);
-    else if (ny == 2) upconv_fused_fwd_kernel<4, 2><<<dim3(gx, 2), 256, 0, st>>>(p, ntiles, tpb);
-    else upconv_fused_fwd_kernel<2, 4><<<dim3(gx, 4), 256, 0, st>>>(p, ntiles, tpb);
+        CTU_UP_FWD(1, 4, 1, true);
+    } else if (ny == 1) CTU_UP_FWD(1, 8, 1, false);
+    else if (ny == 2) CTU_UP_FWD(2, 4, 2, false);
+    else CTU_UP_FWD(4, 2, 4, false);
+#undef CTU_UP_FWD
     CTU_CHECK_LAUNCH("upconv_fused_fwd");
     return CTU_OK;
+}
+
+extern "C" int ctu_upconv_fused_fwd(const float* in, int in_cs, int cin_p, const float* in_scale, const float* in_shift,
+                                    int in_relu, const float* wp, const float* beff, float* out, int out_cs, int nout_p,
+                                    float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail, void* stream) {
+    return upconv_fused_fwd_impl(in, nullptr, 0, in_cs, cin_p, in_scale, in_shift, in_relu, wp, beff, out, out_cs, nout_p, stats,
+                                 N, D, H, W, tail, stream);
+}
+
+extern "C" int ctu_upconv_fused_fwd_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p, const float* in_scale,
+                                         const float* in_shift, int in_relu, const float* wp, const float* beff, float* out,
+                                         int out_cs, int nout_p, float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail,
+                                         void* stream) {
+    CTU_REQUIRE(in0 && in1, "upconv_fused_fwd_seg2: null segment");
+    CTU_REQUIRE(up_seg2_ok(cin_p, seg_c, 8), "upconv_fused_fwd_seg2: seg_c=%d must be a multiple of 8 and half of cin_p=%d", seg_c, cin_p);
+    CTU_REQUIRE(((uintptr_t)in1 & 15) == 0, "upconv_fused_fwd_seg2: 16-byte alignment");
+    return upconv_fused_fwd_impl(in0, in1, seg_c, cs, cin_p, in_scale, in_shift, in_relu, wp, beff, out, out_cs, nout_p, stats,
+                                 N, D, H, W, tail, stream);
 }
 
 extern "C" int ctu_channel_sum_num_blocks(int64_t nvox);
@@ -1150,14 +1212,16 @@ extern "C" int ctu_upconv_fused_pack_bwd(const float* wp, int cin_p, int nout_p,
     return upconv_pack_gather(wp, cin_p, nout_p, nullptr, wpd, (hipStream_t)stream);
 }
 
-extern "C" int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin, int gin_cs,
-                                         int cin_p, int N, int D, int H, int W, void* stream) {
+// seg_c == 0: the one-buffer entry (gin1 unused, gin_cs >= cin_p); else gin / gin1 take seg_c channels each at stride gin_cs
+static int upconv_fused_bwd_data_impl(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin, float* gin1, int seg_c,
+                                      int gin_cs, int cin_p, int N, int D, int H, int W, void* stream) {
     CTU_REQUIRE(gout && wpd && gin, "upconv_fused_bwd_data: null pointer");
     CTU_REQUIRE(ctu_upconv_fused_supported(3, D, H, W, cin_p, nout_p), "upconv_fused_bwd_data: unsupported geometry");
-    CTU_REQUIRE(g_cs >= nout_p && g_cs % 4 == 0 && gin_cs >= cin_p && gin_cs % 4 == 0, "upconv_fused_bwd_data: bad stride");
+    CTU_REQUIRE(g_cs >= nout_p && g_cs % 4 == 0 && gin_cs >= (seg_c ? seg_c : cin_p) && gin_cs % 4 == 0, "upconv_fused_bwd_data: bad stride");
     CTU_REQUIRE(((uintptr_t)gout & 15) == 0 && ((uintptr_t)gin & 15) == 0 && ((uintptr_t)wpd & 15) == 0, "upconv_fused_bwd_data: alignment");
     CTU_REQUIRE((int64_t)(12 * 2 * H + 12) * 2 * W * g_cs * 4 + 64 < (int64_t)1 << 31, "upconv_fused_bwd_data: volume too large for 32-bit offsets");
-    UpDP p;
+    UpSeg2<UpDP> p;                                     // (the one-buffer kernels take its UpDP part)
+    p.seg1 = gin1; p.seg_c = seg_c;
     p.g = gout; p.wp = wpd; p.out = gin; p.g_cs = g_cs; p.nout_p = nout_p; p.out_cs = gin_cs; p.cin_p = cin_p;
     p.N = N; p.D = D; p.H = H; p.W = W;
     p.n16 = ceil_div(cin_p, 16);
@@ -1165,9 +1229,26 @@ extern "C" int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p
     p.tiles_d = r.tiles_d; p.tiles_h = r.tiles_h; p.tiles_w = r.tiles_w;
     const int NT = r.nt, ny = r.ny, gx = r.grid.gx, tpb = r.grid.tpb, ntiles = r.ntiles;
     hipStream_t st = (hipStream_t)stream;
-    if (NT == 4) upconv_fused_bwd_data_kernel<4><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
+    if (seg_c) {
+        if (NT == 4) upconv_fused_bwd_data_kernel<4, true><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
+        else if (NT == 2) upconv_fused_bwd_data_kernel<2, true><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
+        else upconv_fused_bwd_data_kernel<1, true><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
+    } else if (NT == 4) upconv_fused_bwd_data_kernel<4><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
     else if (NT == 2) upconv_fused_bwd_data_kernel<2><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
     else upconv_fused_bwd_data_kernel<1><<<dim3(gx, ny), 256, 0, st>>>(p, ntiles, tpb);
     CTU_CHECK_LAUNCH("upconv_fused_bwd_data");
     return CTU_OK;
+}
+
+extern "C" int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin, int gin_cs,
+                                         int cin_p, int N, int D, int H, int W, void* stream) {
+    return upconv_fused_bwd_data_impl(gout, g_cs, nout_p, wpd, gin, nullptr, 0, gin_cs, cin_p, N, D, H, W, stream);
+}
+
+extern "C" int ctu_upconv_fused_bwd_data_seg2(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin0, float* gin1,
+                                              int seg_c, int cs, int cin_p, int N, int D, int H, int W, void* stream) {
+    CTU_REQUIRE(gin0 && gin1, "upconv_fused_bwd_data_seg2: null segment");
+    CTU_REQUIRE(up_seg2_ok(cin_p, seg_c, 16), "upconv_fused_bwd_data_seg2: seg_c=%d must be a multiple of 16 and half of cin_p=%d", seg_c, cin_p);
+    CTU_REQUIRE(((uintptr_t)gin1 & 15) == 0, "upconv_fused_bwd_data_seg2: alignment");
+    return upconv_fused_bwd_data_impl(gout, g_cs, nout_p, wpd, gin0, gin1, seg_c, cs, cin_p, N, D, H, W, stream);
 }

@@ -13,7 +13,8 @@ Data flow (DESIGN.md has the picture):
   * the skip concat is free: the decoder's second conv writes channels [0, Cp) and the encoder's
     second conv writes channels [Cp, 2Cp) of one buffer per resolution level
     (``torch.cat((ubl, d), 1)``, models.py:249 -- upsampled first, skip second); at the top level the
-    two halves are two dense tensors that the head reads as two segments (SPLIT_CAT0 below);
+    two halves are two dense tensors that the head reads as two segments (SPLIT_CAT0 below), at the level
+    below it two dense tensors that the fused up-convolution reads as two segments (SPLIT_CAT1);
   * backward re-reads the raw tensors and recomputes activations/pool argmax on the fly; nothing
     but raw conv outputs and per-channel statistics is saved.
 """
@@ -21,6 +22,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -59,15 +61,24 @@ DEFER_WGRAD_REDUCE = os.environ.get("CTUNET_DEFER_WGRAD_REDUCE", "1") != "0"
 # the interleaved buffer moves whole 128-byte lines for half-used data.  Only the head touches whole voxels; it reads and
 # writes the two halves as two segments (ops.CL2).  Same values bit for bit.  CTUNET_SPLIT_CAT0=0: the interleaved buffer.
 SPLIT_CAT0 = os.environ.get("CTUNET_SPLIT_CAT0", "1") != "0"
+# the same for level 1 (fp32, Cp = 16: 64-byte halves of a 128-byte voxel): its whole-voxel consumer is the fused
+# up-convolution of the top decoder block, whose forward, weight-gradient and data-gradient kernels take the coarse tensor as
+# two segments (the ctu_upconv_fused_*_seg2 entries).  Split only where that block runs fused and those entries take the
+# geometry; the unfused ConvTranspose3d kernels and the 16-bit fused ones read one buffer, so there the level stays
+# interleaved.  Levels >= 2 have halves of a whole line or more.  CTUNET_SPLIT_CAT1=0: the interleaved buffer.
+SPLIT_CAT1 = os.environ.get("CTUNET_SPLIT_CAT1", "1") != "0"
 
 
-def _cat_halves(buf: torch.Tensor, cp: int):
+def _cat_halves(buf: torch.Tensor, cp: int, split: bool):
     """(decoder half, encoder half) of a level's concat buffer or of its gradient mirror, as raw slices: channel ranges
-    [0, cp) and [cp, 2 cp) of an interleaved [N, D, H, W, 2 cp] buffer, or the two dense tensors of a split [2, N, D, H, W, cp]
-    one."""
+    [0, cp) and [cp, 2 cp) of an interleaved [N, D, H, W, 2 cp] buffer, or the two dense tensors of a split one
+    ([2, N, D, H, W, cp] at the top level, [2 N, D, H, W, cp] -- the same memory -- below it)."""
+    if not split:
+        return CL(buf, 0, cp), CL(buf, cp, cp)
     if buf.dim() == 6:
         return CL(buf[0], 0, cp), CL(buf[1], 0, cp)
-    return CL(buf, 0, cp), CL(buf, cp, cp)
+    n = buf.shape[0] // 2
+    return CL(buf[:n], 0, cp), CL(buf[n:], 0, cp)
 
 
 @dataclass
@@ -298,14 +309,28 @@ class UNetEngine:
         rec = _ConvRec(x, out.raw(), vec4, stats, nblk, conv, bn, cin, cout, imap, bias is not None) if save else None
         return y, rec
 
-    def _fuse_up(self, x: CL, nout_p: int) -> bool:
-        """Run ConvTranspose3d -> Conv3d of a decoder block as one coarse-grid kernel (ops.upconv_fused_fwd)?
+    def _fuse_up(self, x, nout_p: int) -> bool:
+        """Run ConvTranspose3d -> Conv3d of a decoder block as one coarse-grid kernel (ops.upconv_fused_fwd)?  x: the coarse
+        input (a CL / CL2, or anything with its dims and cp: the question is asked before the tensor exists, _split_cat).
         Levels whose first conv has at most 16 (padded) output channels: they hold the FLOPs and have enough boxes."""
         if not (self.plan.k == 3 and not self.plan.conv_bias and nout_p <= FUSE_UP_MAX_CO and FUSE_UP):
             return False
         if self.dtype == torch.float32:
             return ops.upconv_fused_supported(x.dims, 3, x.cp, nout_p)
         return LP_FUSE_UP and ops.lp_upconv_fused_supported(x.dims, 3, x.cp, nout_p)
+
+    def _split_cat(self, level: int, dims, cp: int) -> bool:
+        """Keep this level's concat buffer (dims, 2 * cp padded channels) as two dense halves (SPLIT_CAT0 / SPLIT_CAT1)?
+        Only where what reads whole voxels of it takes two segments: the head at level 0, at level 1 the decoder block above
+        it when it runs fused in fp32 on a geometry the two-segment kernels take -- decided here, at allocation time."""
+        if level == 0:
+            return SPLIT_CAT0 and cp <= 16           # (two-segment head kernels: at most 16 channels per segment)
+        plan = self.plan
+        if not (SPLIT_CAT1 and level == 1 and plan.skip == "cat" and self.dtype == torch.float32 and cp * 4 < 128):
+            return False
+        nout_p = pad8(plan.dec[len(plan.enc) - level].cout)      # the block that consumes this level's concat
+        whole = SimpleNamespace(dims=dims, cp=2 * cp)
+        return self._fuse_up(whole, nout_p) and ops.upconv_fused_seg2_supported(dims, 3, 2 * cp, nout_p, cp)
 
     def _upconv_bn(self, P, x: CL, prefix: str, ct: int, cout: int, cinv, out: CL, vec4: torch.Tensor, training: bool,
                    n_upd: int, save: bool) -> Tuple[CL, Optional[_ConvRec]]:
@@ -372,7 +397,8 @@ class UNetEngine:
         adt = self.dtype
         cur = None if first_direct else ops.ncdhw_to_cl(x, dtype=adt)
         x_cl = cur
-        cat: List[torch.Tensor] = []     # concat buffer per level ([N, D, H, W, 2 Cp]; split level 0: [2, N, D, H, W, Cp])
+        cat: List[torch.Tensor] = []     # concat buffer per level ([N, D, H, W, 2 Cp]; split: see _cat_halves)
+        cat_split: List[bool] = []
         halves = []                      # its (decoder, encoder) halves as raw CL slices
         xf: List[torch.Tensor] = []      # [4, 2Cp] scale/shift/mean/invstd of the concat buffer
         pooled: List[CL] = []
@@ -385,10 +411,11 @@ class UNetEngine:
         xf_off = 0
         for i, blk in enumerate(plan.enc):
             cp = pad8(blk.cout)
-            # (two-segment head kernels: at most 16 channels per segment)
-            split = SPLIT_CAT0 and i == 0 and cp <= 16
-            cat.append(torch.empty((2, n, dd, hh, ww, cp) if split else (n, dd, hh, ww, 2 * cp), dtype=adt, device=dev))
-            halves.append(_cat_halves(cat[i], cp))
+            split = self._split_cat(i, (n, dd, hh, ww), cp)
+            shape = (n, dd, hh, ww, 2 * cp) if not split else ((2, n, dd, hh, ww, cp) if i == 0 else (2 * n, dd, hh, ww, cp))
+            cat.append(torch.empty(shape, dtype=adt, device=dev))
+            cat_split.append(split)
+            halves.append(_cat_halves(cat[i], cp, split))
             xf.append(xf_all[xf_off:xf_off + 8 * cp].view(4, 2 * cp))
             xf_off += 8 * cp
             t1 = CL(torch.empty((n, dd, hh, ww, cp), dtype=adt, device=dev), 0, cp)
@@ -451,6 +478,7 @@ class UNetEngine:
                 a1, recs[(blk.prefix, 1)] = self._upconv_bn(P, cur, blk.prefix, ct, blk.cout, cinv_t, t1, v1, training,
                                                             n_upd, save)
             else:
+                assert isinstance(cur, CL), "a split concat level feeds a fused up-convolution only"
                 up = CL(torch.empty((n, dd, hh, ww, ctp), dtype=adt, device=dev), 0, ctp)
                 wpt = self._packed(f"{blk.prefix}.0", wt, "convt", cinv_t, cur.cp, ctp, 0)
                 ops.convt_fwd(cur, wpt, P[f"{blk.prefix}.0.bias"].detach(), up)
@@ -461,7 +489,7 @@ class UNetEngine:
                                                       halves[i][0], xf[i][:, :cp], training, n_upd, save)
             h_dec, h_enc = halves[i]
             if plan.skip == "cat":               # free concat: both producers wrote channel slices of cat[i]
-                if cat[i].dim() == 6:            # split top level: the head reads the two halves as two segments
+                if cat_split[i]:                 # split level: its consumer (head / fused up-convolution) reads two segments
                     cur = ops.CL2(h_dec, h_enc, xf[i][0], xf[i][1], True)
                 else:
                     cur = CL(cat[i], 0, 2 * cp, xf[i][0], xf[i][1], True)
@@ -479,8 +507,8 @@ class UNetEngine:
         w2 = wl.detach().reshape(wl.shape[0], wl.shape[1])
         out0, out1 = ops.head_fwd(cur, w2, bl.detach(), imap_h, plan.act, plan.head_mode)
         if save:
-            ctx.update(recs=recs, x_cl=x_cl, cat=cat, xf=xf, pooled=pooled, dskip=dskip, dec_in=dec_in, ups=ups,
-                       head_in=cur, imap_h=imap_h, center_out=center_out, dims=(n, d, h, w))
+            ctx.update(recs=recs, x_cl=x_cl, cat=cat, cat_split=cat_split, xf=xf, pooled=pooled, dskip=dskip, dec_in=dec_in,
+                       ups=ups, head_in=cur, imap_h=imap_h, center_out=center_out, dims=(n, d, h, w))
         return out0, out1, ctx
 
     # ------------------------------------------------------------------ backward pieces
@@ -624,9 +652,9 @@ class UNetEngine:
         # never recomputed and has no backward.
         self._replay_stats = bool(ctx["training"] and ctx["chk"])
 
-        cat, head_in = ctx["cat"], ctx["head_in"]
+        cat, cat_split, head_in = ctx["cat"], ctx["cat_split"], ctx["head_in"]
         gcat = [torch.empty_like(c) for c in cat]
-        ghalves = [_cat_halves(g, g.shape[-1] // (1 if g.dim() == 6 else 2)) for g in gcat]
+        ghalves = [_cat_halves(g, g.shape[-1] // (1 if sp else 2), sp) for g, sp in zip(gcat, cat_split)]
         wl, bl = P[plan.head + ".weight"], P[plan.head + ".bias"]
         w2 = wl.detach().reshape(wl.shape[0], wl.shape[1])
         gsd = None if dyn is None else dyn.scale
@@ -635,7 +663,7 @@ class UNetEngine:
             g_dec, g_enc = ghalves[level]
             if plan.skip != "cat":
                 return g_dec
-            return ops.CL2(g_dec, g_enc) if gcat[level].dim() == 6 else CL(gcat[level], 0, 2 * g_dec.cp)
+            return ops.CL2(g_dec, g_enc) if cat_split[level] else CL(gcat[level], 0, 2 * g_dec.cp)
 
         def g_skip_fanout(level: int):
             """additive skip: d(sum) reaches both addends -- copy it into the encoder half before the decoder's

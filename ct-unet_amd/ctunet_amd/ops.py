@@ -337,9 +337,9 @@ class CL:
 @dataclass
 class CL2:
     """A channels-last tensor of 2 * a.cp padded channels kept in two slices of equal width: ``a`` holds channels
-    [0, a.cp), ``b`` holds [a.cp, 2 * a.cp).  Only the head reads or writes a whole voxel of the top-level concat buffer,
-    so its two halves can be two dense tensors (whole 128-byte lines for every kernel that streams one half).
-    scale / shift span all 2 * a.cp channels."""
+    [0, a.cp), ``b`` holds [a.cp, 2 * a.cp).  Only the head reads or writes a whole voxel of the top-level concat buffer and
+    only the fused up-convolution one of the level below, so their halves can be two dense tensors (whole 128-byte lines
+    for every kernel that streams one half).  scale / shift span all 2 * a.cp channels."""
     a: CL
     b: CL
     scale: Optional[torch.Tensor] = None
@@ -348,11 +348,18 @@ class CL2:
 
     def __post_init__(self):
         assert self.a.cp == self.b.cp and self.a.dims == self.b.dims and self.a.dtype == self.b.dtype
-        assert self.a.cp in (8, 16), "the two-segment head kernels take at most 16 channels per segment"
 
     @property
     def cp(self) -> int:
         return 2 * self.a.cp
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.a.dtype
+
+    @property
+    def nvox(self) -> int:
+        return self.a.nvox
 
     @property
     def lp(self) -> int:
@@ -363,8 +370,13 @@ class CL2:
         return self.a.dims
 
     def seg_args(self):
-        """(ptr_a, cs_a, ptr_b, cs_b) as the ctu_*_seg2 entries take them."""
+        """(ptr_a, cs_a, ptr_b, cs_b) as the ctu_head_*_seg2 entries take them."""
         return self.a.ptr, self.a.cs, self.b.ptr, self.b.cs
+
+    def up_args(self):
+        """(ptr_a, ptr_b, seg_c, cs, cp) as the ctu_upconv_fused_*_seg2 entries take them (one stride for both segments)."""
+        assert self.a.cs == self.b.cs, "the two-segment up-convolution kernels take segments of equal voxel stride"
+        return self.a.ptr, self.b.ptr, self.a.cp, self.a.cs, self.cp
 
 
 def new_cl(n, d, h, w, cs, device, zero=False, dtype=torch.float32) -> torch.Tensor:
@@ -872,6 +884,7 @@ def head_fwd(x, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int
         out0 = torch.empty((n, 2, d, h, w_), dtype=torch.float32, device=dev)
         out1 = torch.empty((n, 2, d, h, w_), dtype=torch.float32, device=dev)
     seg2 = isinstance(x, CL2)
+    assert not seg2 or x.a.cp in (8, 16), "the two-segment head kernels take at most 16 channels per segment"
     src = (*x.seg_args(), x.a.cp) if seg2 else (x.ptr, x.cs, x.cp)
     _dual(x.lp, "head_fwd_seg2" if seg2 else "head_fwd", *src, _ptr(x.scale), _ptr(x.shift), int(x.relu), w.data_ptr(),
           b.data_ptr(), _ptr(imap), ci, co, act, head_mode, out0.data_ptr(), _ptr(out1), n, v, _stream())
@@ -896,6 +909,7 @@ def head_bwd(x, w: torch.Tensor, b: torch.Tensor, imap, act: int, head_mode: int
     dev = w.device
     seg2 = isinstance(x, CL2)
     assert seg2 == isinstance(gin, CL2), "head_bwd: input and input gradient are both one buffer or both two segments"
+    assert not seg2 or x.a.cp in (8, 16), "the two-segment head kernels take at most 16 channels per segment"
     lib = _lib.load()
     ws = torch.empty(lib.ctu_head_bwd_ws_floats(n, v, x.cp, co), dtype=torch.float32, device=dev)
     dw = torch.empty_like(w)
@@ -1046,6 +1060,12 @@ def upconv_fused_supported(dims, k: int, cin_p: int, nout_p: int) -> bool:
     return bool(_lib.load().ctu_upconv_fused_supported(k, d, h, w, cin_p, nout_p))
 
 
+def upconv_fused_seg2_supported(dims, k: int, cin_p: int, nout_p: int, seg_c: int) -> bool:
+    """Do the two-segment forms of the fused forward / weight gradient / data gradient (a CL2 coarse tensor) take this geometry?"""
+    n, d, h, w = dims
+    return bool(_lib.load().ctu_upconv_fused_seg2_supported(k, d, h, w, cin_p, nout_p, seg_c))
+
+
 def upconv_fused_pack(wt: torch.Tensor, bt: torch.Tensor, w3: torch.Tensor, cinv, cin_p: int, nout_p: int,
                       into=None):
     """Composite weights (fragment order) and the 27 border-class biases of ConvTranspose3d(C,C,2,2) -> Conv3d(C,Co,3).
@@ -1086,9 +1106,10 @@ def upconv_fused_num_blocks(dims, nout_p: int) -> int:
     return _lib.load().ctu_upconv_fused_num_blocks(n, d, h, w, nout_p)
 
 
-def upconv_fused_fwd(x: CL, wp: torch.Tensor, beff: torch.Tensor, out: CL, stats: Optional[torch.Tensor],
+def upconv_fused_fwd(x, wp: torch.Tensor, beff: torch.Tensor, out: CL, stats: Optional[torch.Tensor],
                      algo_ch: Optional[Tuple[int, int]] = None, tail=None) -> None:
-    """out (fine grid, raw) = conv3(convT(act(x))) in one kernel; x is the COARSE input."""
+    """out (fine grid, raw) = conv3(convT(act(x))) in one kernel; x is the COARSE input: a CL, or a CL2 (its channels in two
+    segments: ctu_upconv_fused_fwd_seg2, same values bit for bit)."""
     n, d, h, w = x.dims
     assert out.dims == (n, 2 * d, 2 * h, 2 * w)
     ci, co = algo_ch if algo_ch is not None else (x.cp, out.cp)
@@ -1096,9 +1117,11 @@ def upconv_fused_fwd(x: CL, wp: torch.Tensor, beff: torch.Tensor, out: CL, stats
     # algorithmic work of the two layers it replaces: convT 2*ci*ci*8 per coarse voxel + conv 2*27*ci*co per fine voxel
     with _timed(lambda: (f"upconv_fused_fwd_kernel<{out.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
                          4.0 * vox * (ci + 8 * co), (w, x.cp, out.cp))):
-        _lib.check(_lib.load().ctu_upconv_fused_fwd(x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu),
-                                                    wp.data_ptr(), beff.data_ptr(), out.ptr, out.cs, out.cp, _ptr(stats),
-                                                    n, d, h, w, _tail_arg(tail), _stream()), "upconv_fused_fwd")
+        seg2 = isinstance(x, CL2)
+        entry = getattr(_lib.load(), "ctu_upconv_fused_fwd_seg2" if seg2 else "ctu_upconv_fused_fwd")
+        _lib.check(entry(*(x.up_args() if seg2 else (x.ptr, x.cs, x.cp)), _ptr(x.scale), _ptr(x.shift), int(x.relu),
+                         wp.data_ptr(), beff.data_ptr(), out.ptr, out.cs, out.cp, _ptr(stats),
+                         n, d, h, w, _tail_arg(tail), _stream()), "upconv_fused_fwd")
 
 
 def upconv_fused_wgrad_bn_supported(dims, cin_p: int, nout_p: int, dtype=torch.float32) -> bool:
@@ -1106,9 +1129,9 @@ def upconv_fused_wgrad_bn_supported(dims, cin_p: int, nout_p: int, dtype=torch.f
     return dtype == torch.float32 and bool(_lib.load().ctu_upconv_fused_wgrad_bn_supported(n, d, h, w, cin_p, nout_p))
 
 
-def upconv_fused_wgrad(x: CL, g: CL, c: int, co: int, bt: torch.Tensor, pack_ws: torch.Tensor, imap, lazy=None):
+def upconv_fused_wgrad(x, g: CL, c: int, co: int, bt: torch.Tensor, pack_ws: torch.Tensor, imap, lazy=None):
     """(dWT [C,C,2,2,2], dbT [C], dW3 [Co,C,3,3,3]) of the fused ConvTranspose3d -> Conv3d pair: x = COARSE input of the
-    transposed conv, g = fine-grid gradient w.r.t. the conv's raw output, pack_ws = scratch of this step's
+    transposed conv (CL, or CL2: the ctu_upconv_fused_wgrad*_seg2 entries), g = fine-grid gradient w.r.t. the conv's raw output, pack_ws = scratch of this step's
     upconv_fused_pack (transposed weights).
     lazy = (y, vec, coef, gy): g is the gradient w.r.t. the ACTIVATED output; the BatchNorm + ReLU backward is applied while
     the weight-gradient kernel stages it and the raw-output gradient lands in gy (read by the projections here and by
@@ -1119,16 +1142,19 @@ def upconv_fused_wgrad(x: CL, g: CL, c: int, co: int, bt: torch.Tensor, pack_ws:
                          lambda: (f"upconv_fused_wgrad_kernel<{g.cp}> (+slab reduce)", 4.0 * (n * d * h * w) * (c + 8 * co)))
 
 
-def _upconv_wgrad(x: CL, g: CL, c: int, co: int, bt, pack_ws, imap, lazy, tag_bytes):
+def _upconv_wgrad(x, g: CL, c: int, co: int, bt, pack_ws, imap, lazy, tag_bytes):
     """Body of upconv_fused_wgrad / lp_upconv_fused_wgrad: composite-weight gradient (with the lazy BatchNorm backward or
     without), then its projection onto the two layers' parameters.  The 16-bit weight-gradient entries carry no g.cp (it is 8).
     tag_bytes() -> (tag, algorithmic bytes) of the timer record."""
     n, d, h, w = x.dims
-    dev = x.buf.device
+    dev = g.buf.device
+    seg2 = isinstance(x, CL2)                            # (fp32 only: the 16-bit entries take one buffer)
+    assert not (seg2 and x.lp)
+    sfx = "_seg2" if seg2 else ""
     gcp = () if x.lp else (g.cp,)
     dweff = torch.empty((8, 8, x.cp, g.cp), dtype=torch.float32, device=dev)
     ws = torch.empty(_query(x.lp, "upconv_fused_wgrad_ws_floats", n, d, h, w, x.cp, *gcp), dtype=torch.float32, device=dev)
-    act = (x.ptr, x.cs, x.cp, _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, *gcp)
+    act = (*(x.up_args() if seg2 else (x.ptr, x.cs, x.cp)), _ptr(x.scale), _ptr(x.shift), int(x.relu), g.ptr, g.cs, *gcp)
     detail = (w, x.cp, g.cp)
 
     def record():
@@ -1139,11 +1165,11 @@ def _upconv_wgrad(x: CL, g: CL, c: int, co: int, bt, pack_ws, imap, lazy, tag_by
             y, vec, coef, gy = lazy
             assert y.dims == g.dims and gy.dims == g.dims and y.cs == g.cs == gy.cs and y.cp == g.cp == gy.cp
             assert gy.buf.data_ptr() != g.buf.data_ptr()
-            _dual(x.lp, "upconv_fused_wgrad_bn", *act, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
+            _dual(x.lp, "upconv_fused_wgrad_bn" + sfx, *act, y.ptr, vec[0].data_ptr(), vec[1].data_ptr(), coef.data_ptr(), gy.ptr,
                   dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream())
             g = gy
         else:
-            _dual(x.lp, "upconv_fused_wgrad", *act, dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream())
+            _dual(x.lp, "upconv_fused_wgrad" + sfx, *act, dweff.data_ptr(), ws.data_ptr(), n, d, h, w, _stream())
     dwt = torch.empty((c, c, 2, 2, 2), dtype=torch.float32, device=dev)
     dbt = torch.empty(c, dtype=torch.float32, device=dev)
     dw3 = torch.empty((co, c, 3, 3, 3), dtype=torch.float32, device=dev)
@@ -1222,16 +1248,19 @@ def upconv_fused_pack_bwd(wp: torch.Tensor, cin_p: int, nout_p: int, into: Optio
     return wpd
 
 
-def upconv_fused_bwd_data(g: CL, wpd: torch.Tensor, gin: CL, algo_ch: Optional[Tuple[int, int]] = None) -> None:
-    """gin (coarse) <- gradient of the fused ConvTranspose3d -> Conv3d pair w.r.t. its (activated) input."""
+def upconv_fused_bwd_data(g: CL, wpd: torch.Tensor, gin, algo_ch: Optional[Tuple[int, int]] = None) -> None:
+    """gin (coarse; CL, or CL2: written as two segments, ctu_upconv_fused_bwd_data_seg2) <- gradient of the fused
+    ConvTranspose3d -> Conv3d pair w.r.t. its (activated) input."""
     n, d, h, w = gin.dims
     assert g.dims == (n, 2 * d, 2 * h, 2 * w)
     ci, co = algo_ch if algo_ch is not None else (gin.cp, g.cp)
     vox = n * d * h * w
     with _timed(lambda: (f"upconv_fused_bwd_data_kernel<{g.cp}>", vox * (16.0 * ci * ci + 8 * 54.0 * ci * co),
                          4.0 * vox * (ci + 8 * co), (w, gin.cp, g.cp))):
-        _lib.check(_lib.load().ctu_upconv_fused_bwd_data(g.ptr, g.cs, g.cp, wpd.data_ptr(), gin.ptr, gin.cs, gin.cp,
-                                                         n, d, h, w, _stream()), "upconv_fused_bwd_data")
+        seg2 = isinstance(gin, CL2)
+        entry = getattr(_lib.load(), "ctu_upconv_fused_bwd_data_seg2" if seg2 else "ctu_upconv_fused_bwd_data")
+        _lib.check(entry(g.ptr, g.cs, g.cp, wpd.data_ptr(), *(gin.up_args() if seg2 else (gin.ptr, gin.cs, gin.cp)),
+                         n, d, h, w, _stream()), "upconv_fused_bwd_data")
 
 
 # ---------------------------------------------------------------------------- inference tail / sample schema

@@ -505,6 +505,30 @@ int ctu_upconv_fused_pack_bwd(const float* wp, int cin_p, int nout_p, float* wpd
 int ctu_upconv_fused_bwd_data(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin, int gin_cs,
                               int cin_p, int N, int D, int H, int W, void* stream);
 
+/* Two-segment forms of the four entries that touch a whole COARSE voxel: its cin_p padded channels live in two buffers of
+ * the same voxel stride cs, (in0, cs) holding channels [0, seg_c) and (in1, cs) holding [seg_c, cin_p), seg_c = cin_p / 2
+ * (the two dense halves of a concat level); ctu_upconv_fused_bwd_data_seg2 writes the coarse gradient the same way.
+ * Everything else -- in_scale / in_shift [cin_p], the packed weights, channel maps, partial rows, workspaces, dweff, gy_out --
+ * is what the one-buffer entry takes, and every output is bit for bit what that entry writes for the same values: an
+ * 8-channel chunk of the forward and a 16-channel tile of the two gradients lie in one segment, so the kernels only pick a
+ * base pointer per chunk / tile; loads, arithmetic and summation order are unchanged.
+ * Refused before any launch (CTU_EINVAL): a null segment, a segment that is not 16-byte aligned, cs < seg_c or not a
+ * multiple of 4, 2 * seg_c != cin_p, seg_c not a multiple of 8 (forward) or 16 (weight and data gradient), and whatever
+ * the one-buffer entries refuse.  ctu_upconv_fused_seg2_supported: all four entries take this geometry. */
+int ctu_upconv_fused_seg2_supported(int k, int D, int H, int W, int cin_p, int nout_p, int seg_c);
+int ctu_upconv_fused_fwd_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p, const float* in_scale,
+                              const float* in_shift, int in_relu, const float* wp, const float* beff, float* out, int out_cs,
+                              int nout_p, float* stats, int N, int D, int H, int W, const ctu_bn_tail* tail, void* stream);
+int ctu_upconv_fused_wgrad_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p, const float* in_scale,
+                                const float* in_shift, int in_relu, const float* gout, int g_cs, int nout_p, float* dweff,
+                                float* ws, int N, int D, int H, int W, void* stream);
+int ctu_upconv_fused_wgrad_bn_seg2(const float* in0, const float* in1, int seg_c, int cs, int cin_p, const float* in_scale,
+                                   const float* in_shift, int in_relu, const float* ga, int g_cs, int nout_p, const float* y,
+                                   const float* bn_scale, const float* bn_shift, const float* coef, float* gy_out,
+                                   float* dweff, float* ws, int N, int D, int H, int W, void* stream);
+int ctu_upconv_fused_bwd_data_seg2(const float* gout, int g_cs, int nout_p, const float* wpd, float* gin0, float* gin1,
+                                   int seg_c, int cs, int cin_p, int N, int D, int H, int W, void* stream);
+
 /* -------------------------------------------------- inference tail / sample schema ---- */
 /* hard_segm_from_tensor (/root/reference/ctunet/utilities.py:103-124): seg[n,v] = (float)argmax_c prob[n,c,v] over an
  * NCDHW map; the first maximum wins (torch.argmax). */
