@@ -59,10 +59,12 @@ CLASS_INPUT = {  # name -> (in_ch, size) as in make_golden.class_checksums
 }
 
 
-def fp64_rule_misses(checks, g64, full_size, report=None):
+def fp64_rule_misses(checks, g64, full_size, report=None, floor=None):
     """The fp64 rule for gradients (test_models_gpu.oracle_train_check and the module-lifecycle tests share it).
     checks: [(name, got, ATen-CPU fp32 gradient, fp64 oracle gradient)]; g64: the fp64 oracle's gradients by parameter
-    name; full_size: patch of at least 128^3.  Returns the list of misses (empty = pass)."""
+    name; full_size: patch of at least 128^3; floor: the rule's floor as a fraction of the tensor's largest fp64 entry in place of
+    the one full_size selects (tests/test_mask_stable_gpu.py: 1e-4, on states whose ReLU masks cannot flip).  Returns the list
+    of misses (empty = pass)."""
     def err(a, b):
         return (a.detach().cpu().double() - b).abs().max().item()
     # One ReLU mask (or pooling arg-max) that flips on fp32 rounding noise changes a weight-gradient entry -- a sum of N
@@ -73,7 +75,8 @@ def fp64_rule_misses(checks, g64, full_size, report=None):
     # floor of the rule is 2e-3 of scale where one flip stays below it (>= 128^3, the full-size tests); on the small
     # patches of the per-class runs it is a loose 6e-2, backed by the DIRECTION of every gradient tensor against the fp64
     # oracle (a handful of flips moves the cosine by ~1e-3; a wrong tap, stride or missing term moves it by far more).
-    floor = 2e-3 if full_size else 6e-2
+    if floor is None:
+        floor = 2e-3 if full_size else 6e-2
     misses = []
     for n_, got, c32, r64 in checks:
         scale = r64.abs().max().item()
