@@ -204,19 +204,27 @@ def _bound(max_distance) -> float:
     return float(max_distance)
 
 
-def _check_inputs(points, field):
+def _check_inputs(points, field, names=("points", "field"), count: str = "P"):
+    """A point set and the distance field it is sampled against: (points, field), or (fixed_points, moving_field)."""
+    pn, fn = names
     if not isinstance(points, torch.Tensor) or not isinstance(field, torch.Tensor):
-        raise TypeError("registration: points and field must be tensors")
+        raise TypeError(f"registration: {pn} and {fn} must be tensors")
     if points.dtype != torch.float32 or field.dtype != torch.float32:
-        raise TypeError(f"registration: points and field must be float32, got {points.dtype} and {field.dtype}")
+        raise TypeError(f"registration: {pn} and {fn} must be float32, got {points.dtype} and {field.dtype}")
     if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
-        raise ValueError(f"registration: points must be [P,3] with P >= 1, got {tuple(points.shape)}")
+        raise ValueError(f"registration: {pn} must be [{count},3] with {count} >= 1, got {tuple(points.shape)}")
     if field.dim() != 3:
-        raise ValueError(f"registration: field must be one [D,H,W] volume, got {tuple(field.shape)}")
+        raise ValueError(f"registration: {fn} must be one [D,H,W] volume, got {tuple(field.shape)}")
     if min(field.shape) < 2:
         raise ValueError(f"registration: a field with a side of 1 has no gradient along it, got {tuple(field.shape)}")
     if field.numel() >= 1 << 31:
         raise ValueError(f"registration: the field must hold fewer than 2^31 voxels, got {tuple(field.shape)}")
+
+
+def _iterations(iterations) -> int:
+    if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
+        raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+    return int(iterations)
 
 
 def _check_init(init, device):
@@ -235,8 +243,7 @@ def workspace_bytes(P: int) -> int:
     return int(_lib.load().ctu_registration_ws_bytes(int(P)))
 
 
-def _workspace(P: int, device, workspace):
-    need = workspace_bytes(P)
+def _workspace(need: int, device, workspace):
     if workspace is None:
         return torch.empty(need, dtype=torch.uint8, device=device)
     if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != device \
@@ -246,13 +253,43 @@ def _workspace(P: int, device, workspace):
     return workspace
 
 
+def _optimise(family: str, dev, points_ptr, P: int, init, accumulate_args, update_head, iterations: int, columns: int, ws):
+    """The launch loop of both optimisers -- ``ctu_<family>_init``, then accumulate and update per iteration -- into fresh
+    (matrix, inverse, history) with ``columns`` history columns; ``update_head`` is what the update takes ahead of ``it``."""
+    rows = iterations + 1
+    out = torch.empty((32 + columns * rows,), dtype=torch.float64, device=dev)
+    matrix, inverse, history = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:].view(rows, columns)
+    with _lib.on(dev) as run:
+        run(f"ctu_{family}_init", points_ptr, P, None if init is None else init.data_ptr(), ws.data_ptr())
+        for it in range(rows):
+            run(f"ctu_{family}_accumulate", *accumulate_args, ws.data_ptr())
+            run(f"ctu_{family}_update", *update_head, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(), rows,
+                ws.data_ptr())
+    return matrix, inverse, history
+
+
+def _accumulate_once(family: str, dev, points_ptr, P: int, matrix, accumulate_args, ws, row: int, sums: int, counts: int,
+                     pivot_at: int):
+    """``ctu_<family>_init`` at ``matrix`` and one accumulation, read back: the first ``sums`` doubles of the slab rows (``row``
+    doubles each) added in block order, the ``counts`` int64 counts behind them, the candidate's pivot (at ``pivot_at`` in the
+    head) and the number of blocks."""
+    with _lib.on(dev) as run:
+        run(f"ctu_{family}_init", points_ptr, P, None if matrix is None else matrix.data_ptr(), ws.data_ptr())
+        run(f"ctu_{family}_accumulate", *accumulate_args, ws.data_ptr())
+    host = ws.cpu().numpy().view(np.float64)
+    slab = host[_HEAD_DOUBLES:].reshape(-1, row)
+    tot = np.zeros(sums)
+    for r in slab:                                                     # block order
+        tot += r[:sums]
+    return tot, slab[:, sums:sums + counts].copy().view(np.int64).sum(0), host[pivot_at:pivot_at + 3].copy(), int(slab.shape[0])
+
+
 def register_points(points: torch.Tensor, field: torch.Tensor, *, spacing=None, origin=None, init=None, iterations: int = 30,
                     max_distance=None, workspace=None) -> RegistrationResult:
     """Fit the rigid matrix that takes ``points`` (float32 [P,3], moving world) onto the zero set of ``field`` (float32
     [D,H,W] distances on the fixed grid of ``spacing`` / ``origin``) by the module docstring's rule."""
     _check_inputs(points, field)
-    if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
-        raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+    iterations = _iterations(iterations)
     bound = _bound(max_distance)
     sp, org = _frame(spacing, origin)
     _lib.check_device(_ON_GPU.format("points and field"), points, field)
@@ -261,17 +298,10 @@ def register_points(points: torch.Tensor, field: torch.Tensor, *, spacing=None, 
     dev = points.device
     init = _check_init(init, dev)
     pts, fld = points.contiguous(), field.contiguous()
-    P, rows = int(pts.shape[0]), int(iterations) + 1
-    ws = _workspace(P, dev, workspace)
-    out = torch.empty((32 + 4 * rows,), dtype=torch.float64, device=dev)
-    matrix, inverse, history = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:].view(rows, 4)
-    c_sp, c_org = _lib.double_array(sp), _lib.double_array(org)
-    with _lib.on(dev) as run:
-        run("ctu_registration_init", pts.data_ptr(), P, None if init is None else init.data_ptr(), ws.data_ptr())
-        for it in range(rows):
-            run("ctu_registration_accumulate", pts.data_ptr(), P, fld.data_ptr(), *fld.shape, c_sp, c_org, bound, ws.data_ptr())
-            run("ctu_registration_update", P, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(), rows, ws.data_ptr())
-    return RegistrationResult(matrix, inverse, history, P)
+    P = int(pts.shape[0])
+    ws = _workspace(workspace_bytes(P), dev, workspace)
+    args = (pts.data_ptr(), P, fld.data_ptr(), *fld.shape, _lib.double_array(sp), _lib.double_array(org), bound)
+    return RegistrationResult(*_optimise("registration", dev, pts.data_ptr(), P, init, args, (P,), iterations, 4, ws), P)
 
 
 def accumulate(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, *, spacing=None, origin=None,
@@ -287,18 +317,10 @@ def accumulate(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, 
     matrix = _check_init(matrix, dev)
     pts, fld = points.contiguous(), field.contiguous()
     P = int(pts.shape[0])
-    ws = _workspace(P, dev, None)
-    with _lib.on(dev) as run:
-        run("ctu_registration_init", pts.data_ptr(), P, None if matrix is None else matrix.data_ptr(), ws.data_ptr())
-        run("ctu_registration_accumulate", pts.data_ptr(), P, fld.data_ptr(), *fld.shape, _lib.double_array(sp),
-            _lib.double_array(org), bound, ws.data_ptr())
-    host = ws.cpu().numpy().view(np.float64)
-    slab = host[_HEAD_DOUBLES:].reshape(-1, _ROW)
-    tot = np.zeros(28)
-    for row in slab:                                                   # block order
-        tot += row[:28]
-    return dict(H=tot[:21], b=tot[21:27], cost=float(tot[27]), count=int(slab[:, 28].copy().view(np.int64).sum()),
-                pivot=host[_PIVOT_C:_PIVOT_C + 3].copy(), blocks=int(slab.shape[0]))
+    args = (pts.data_ptr(), P, fld.data_ptr(), *fld.shape, _lib.double_array(sp), _lib.double_array(org), bound)
+    tot, counts, pivot, blocks = _accumulate_once("registration", dev, pts.data_ptr(), P, matrix, args,
+                                                  _workspace(workspace_bytes(P), dev, None), _ROW, 28, 1, _PIVOT_C)
+    return dict(H=tot[:21], b=tot[21:27], cost=float(tot[27]), count=int(counts[0]), pivot=pivot, blocks=blocks)
 
 
 def similarity_workspace_bytes(P: int, Q: int = 0) -> int:
@@ -313,29 +335,6 @@ def _dof(model) -> int:
     return _DOF[model]
 
 
-def _check_symmetric_half(fixed_points, moving_field, moving_spacing, moving_origin):
-    """The optional backward term's arguments: both or neither, and a moving frame only with a moving field."""
-    if (fixed_points is None) != (moving_field is None):
-        raise ValueError("registration: fixed_points and moving_field come together or not at all")
-    if fixed_points is None:
-        if moving_spacing is not None or moving_origin is not None:
-            raise ValueError("registration: moving_spacing and moving_origin describe moving_field, which was not given")
-        return
-    if not isinstance(fixed_points, torch.Tensor) or not isinstance(moving_field, torch.Tensor):
-        raise TypeError("registration: fixed_points and moving_field must be tensors")
-    if fixed_points.dtype != torch.float32 or moving_field.dtype != torch.float32:
-        raise TypeError(f"registration: fixed_points and moving_field must be float32, got {fixed_points.dtype} and "
-                        f"{moving_field.dtype}")
-    if fixed_points.dim() != 2 or fixed_points.shape[1] != 3 or fixed_points.shape[0] < 1:
-        raise ValueError(f"registration: fixed_points must be [Q,3] with Q >= 1, got {tuple(fixed_points.shape)}")
-    if moving_field.dim() != 3:
-        raise ValueError(f"registration: moving_field must be one [D,H,W] volume, got {tuple(moving_field.shape)}")
-    if min(moving_field.shape) < 2:
-        raise ValueError(f"registration: a field with a side of 1 has no gradient along it, got {tuple(moving_field.shape)}")
-    if moving_field.numel() >= 1 << 31:
-        raise ValueError(f"registration: the field must hold fewer than 2^31 voxels, got {tuple(moving_field.shape)}")
-
-
 class _SimilarityCall:
     """The checked arguments of the similarity entry points, shared by the optimiser and the inspection helper."""
 
@@ -343,9 +342,14 @@ class _SimilarityCall:
                  max_distance, iterations=0):
         _check_inputs(points, field)
         self.dof = _dof(model)
-        _check_symmetric_half(fixed_points, moving_field, moving_spacing, moving_origin)
-        if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
-            raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+        # the optional backward term: both or neither, and a moving frame only with a moving field
+        if (fixed_points is None) != (moving_field is None):
+            raise ValueError("registration: fixed_points and moving_field come together or not at all")
+        if fixed_points is not None:
+            _check_inputs(fixed_points, moving_field, ("fixed_points", "moving_field"), "Q")
+        elif moving_spacing is not None or moving_origin is not None:
+            raise ValueError("registration: moving_spacing and moving_origin describe moving_field, which was not given")
+        self.iterations = _iterations(iterations)
         bound = _bound(max_distance)
         sp, org = _frame(spacing, origin)
         msp, morg = _frame(moving_spacing, moving_origin, "moving_")
@@ -365,14 +369,7 @@ class _SimilarityCall:
                                 _lib.double_array(org), *back, _lib.double_array(msp), _lib.double_array(morg), bound)
 
     def workspace(self, workspace):
-        need = similarity_workspace_bytes(self.P, self.Q)
-        if workspace is None:
-            return torch.empty(need, dtype=torch.uint8, device=self.dev)
-        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != self.dev \
-                or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 8:
-            raise ValueError(f"registration: workspace must be a contiguous, 8-byte aligned uint8 tensor of at least {need} "
-                             f"bytes on {self.dev}")
-        return workspace
+        return _workspace(similarity_workspace_bytes(self.P, self.Q), self.dev, workspace)
 
 
 def register_similarity_points(points: torch.Tensor, field: torch.Tensor, *, fixed_points=None, moving_field=None,
@@ -386,17 +383,9 @@ def register_similarity_points(points: torch.Tensor, field: torch.Tensor, *, fix
     call = _SimilarityCall(points, field, fixed_points, moving_field, model, spacing, origin, moving_spacing, moving_origin,
                            max_distance, iterations)
     init = _check_init(init, call.dev)
-    rows = int(iterations) + 1
     ws = call.workspace(workspace)
-    out = torch.empty((32 + 6 * rows,), dtype=torch.float64, device=call.dev)
-    matrix, inverse, history = out[:16].view(4, 4), out[16:32].view(4, 4), out[32:].view(rows, 6)
-    with _lib.on(call.dev) as run:
-        run("ctu_similarity_init", call.points_ptr, call.P, None if init is None else init.data_ptr(), ws.data_ptr())
-        for it in range(rows):
-            run("ctu_similarity_accumulate", *call.accumulate_args, ws.data_ptr())
-            run("ctu_similarity_update", call.dof, call.P, call.Q, it, matrix.data_ptr(), inverse.data_ptr(), history.data_ptr(),
-                rows, ws.data_ptr())
-    return RegistrationResult(matrix, inverse, history, call.P, call.Q)
+    return RegistrationResult(*_optimise("similarity", call.dev, call.points_ptr, call.P, init, call.accumulate_args,
+                                         (call.dof, call.P, call.Q), call.iterations, 6, ws), call.P, call.Q)
 
 
 def accumulate_similarity(points: torch.Tensor, field: torch.Tensor, matrix: torch.Tensor, *, fixed_points=None,
@@ -408,20 +397,12 @@ def accumulate_similarity(points: torch.Tensor, field: torch.Tensor, matrix: tor
     call = _SimilarityCall(points, field, fixed_points, moving_field, model, spacing, origin, moving_spacing, moving_origin,
                            max_distance)
     matrix = _check_init(matrix, call.dev)
-    ws = call.workspace(None)
-    with _lib.on(call.dev) as run:
-        run("ctu_similarity_init", call.points_ptr, call.P, None if matrix is None else matrix.data_ptr(), ws.data_ptr())
-        run("ctu_similarity_accumulate", *call.accumulate_args, ws.data_ptr())
-    host = ws.cpu().numpy().view(np.float64)
-    slab = host[_HEAD_DOUBLES:].reshape(-1, _SIM_ROW)
     nh = call.dof * (call.dof + 1) // 2
     na = nh + call.dof + 1
-    tot = np.zeros(na)
-    for row in slab:                                                   # block order
-        tot += row[:na]
-    counts = slab[:, na:na + 2].copy().view(np.int64).sum(0)
+    tot, counts, pivot, blocks = _accumulate_once("similarity", call.dev, call.points_ptr, call.P, matrix, call.accumulate_args,
+                                                  call.workspace(None), _SIM_ROW, na, 2, _SIM_PIVOT_C)
     return dict(H=tot[:nh], b=tot[nh:nh + call.dof], cost=float(tot[na - 1]), count=int(counts[0]), count_backward=int(counts[1]),
-                pivot=host[_SIM_PIVOT_C:_SIM_PIVOT_C + 3].copy(), blocks=int(slab.shape[0]))
+                pivot=pivot, blocks=blocks)
 
 
 def _mask(t, what: str):
@@ -571,8 +552,7 @@ class FFDPlan:
     def __init__(self, points, field, matrix, *, spacing=None, origin=None, control_spacing=10.0, stiffness=0.1,
                  iterations: int = 60, max_distance=None):
         _check_inputs(points, field)
-        if isinstance(iterations, bool) or not isinstance(iterations, Integral) or not 0 <= iterations <= 10000:
-            raise ValueError(f"registration: iterations must be an integer in 0..10000, got {iterations!r}")
+        self.rows = _iterations(iterations) + 1
         if isinstance(stiffness, bool) or not isinstance(stiffness, Real) or not math.isfinite(stiffness) or stiffness < 0:
             raise ValueError(f"registration: stiffness must be a finite number >= 0, got {stiffness!r}")
         if not isinstance(matrix, torch.Tensor) or matrix.dtype != torch.float64 or tuple(matrix.shape) != (4, 4):
@@ -589,7 +569,6 @@ class FFDPlan:
         P = self.P = int(self.pts.shape[0])
         g3 = self.G[0] * self.G[1] * self.G[2]
         self.weight = float(stiffness) * P / g3
-        self.rows = int(iterations) + 1
         self.lat = _lattice_args(self.G, self.h, self.box_origin)
         cells = torch.empty(P, dtype=torch.int32, device=dev)
         with _lib.on(dev) as run:
