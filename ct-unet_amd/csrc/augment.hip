@@ -8,24 +8,11 @@
 //
 // Replaces: ctunet/pytorch/transforms.py:13-95 (SaltAndPepper, SkullRandomHole) and ctunet/utilities.py:127-178 (shape_3d),
 //           ctunet/pytorch/transforms.py:241-300 (random_blank_patch), run per sample in NumPy on the host there.
-#include "common.h"
-#include "philox.h"
+#include "flap_pass.h"
 
 namespace {
 
-using namespace ctu_rng;
-
-constexpr int AB = 256;
-constexpr int REC = CTU_FLAP_RECORD;
-
-// lo + floor(r (hi - lo) / 2^32): uniform integer in [lo, hi) for hi - lo <= 2^32
-__device__ __forceinline__ int64_t draw_int(uint32_t r, int64_t lo, uint64_t span) {
-    return lo + (int64_t)(((uint64_t)r * span) >> 32);
-}
-
-__device__ __forceinline__ bool bone_at(const void* skull, int u8, int64_t i) {
-    return u8 ? static_cast<const uint8_t*>(skull)[i] != 0 : static_cast<const float*>(skull)[i] >= 1.0f;
-}
+using namespace ctu_flap;
 
 // --------------------------------------------------------------------------------------------------------------- count
 // grid (nchunks, N): block (c, n) counts the bone voxels of flat indices [c CH, min(V, (c+1) CH)) of sample n.
@@ -88,28 +75,15 @@ __global__ void __launch_bounds__(AB) flap_draw_kernel(DrawArgs a) {
     if (a.mode & CTU_FLAP_HOLE) {
         const int64_t seq = a.hole_seq[0] + n;
         const int32_t* cn = a.counts + (int64_t)n * a.nchunks;
-        const int per = (a.nchunks + AB - 1) / AB;
-        const int c0 = threadIdx.x * per, c1 = min(a.nchunks, c0 + per);
-        int64_t s = 0;
-        for (int c = c0; c < c1; ++c) s += cn[c];
-        tsum[threadIdx.x] = s;
+        segment_counts(cn, a.nchunks, tsum);
         __syncthreads();
         if (threadIdx.x == 0) {
             const uint4 r = philox_seq(0, 0, seq, a.hk0, a.hk1);
             const uint4 r2 = philox_seq(1, 0, seq, a.hk0, a.hk1);
-            int64_t total = 0;
-            for (int t = 0; t < AB; ++t) total += tsum[t];
+            const int64_t total = bone_total(tsum);
             const int64_t k = total > 0 ? draw_int(r.y, 0, (uint64_t)total) : 0;
             int64_t chunk = -1, kloc = 0;
-            if (total > 0) {                          // the thread segment, then the chunk, that holds the k-th bone voxel
-                int64_t acc = 0;
-                int t = 0;
-                while (acc + tsum[t] <= k) acc += tsum[t++];
-                for (int c = t * per;; ++c) {
-                    if (acc + cn[c] > k) { chunk = c; kloc = k - acc; break; }
-                    acc += cn[c];
-                }
-            }
+            if (total > 0) find_chunk(cn, a.nchunks, tsum, k, chunk, kloc);
             sh_chunk = chunk;
             sh_kloc = kloc;
             sh_idx = -1;
@@ -127,22 +101,7 @@ __global__ void __launch_bounds__(AB) flap_draw_kernel(DrawArgs a) {
             rec[9] = rec[0] && total > 0;
         }
         __syncthreads();
-        if (threadIdx.x < 64 && sh_chunk >= 0) {     // wave 0 rescans the chunk: 64 voxels per ballot
-            const int lane = threadIdx.x;
-            int64_t kl = sh_kloc;
-            const int64_t e = min(V, (sh_chunk + 1) * CTU_FLAP_CHUNK);
-            for (int64_t b = sh_chunk * CTU_FLAP_CHUNK; b < e; b += 64) {
-                const int64_t i = b + lane;
-                const bool bone = i < e && bone_at(a.skull, a.u8, (int64_t)n * V + i);
-                const uint64_t m = __ballot(bone);
-                const int pc = __popcll(m);
-                if (kl < pc) {
-                    if (bone && __popcll(m & ((1ull << lane) - 1ull)) == kl) sh_idx = i;
-                    break;
-                }
-                kl -= pc;
-            }
-        }
+        if (threadIdx.x < 64 && sh_chunk >= 0) scan_chunk(a.skull, a.u8, (int64_t)n * V, V, sh_chunk, sh_kloc, &sh_idx);
         __syncthreads();
         if (threadIdx.x == 0) {
             const int64_t i = sh_idx;
@@ -206,13 +165,7 @@ __device__ __forceinline__ bool inside(int shape, int size, float cd2, int dz, i
 }
 
 __global__ void __launch_bounds__(AB) flap_apply_kernel(ApplyArgs a) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {       // advance the instances' device state (nothing else reads it here)
-        if (a.mode & CTU_FLAP_HOLE) a.hole_seq[0] += a.N;
-        if (a.mode & CTU_FLAP_NOISE) {
-            a.noise_seq[0] += a.N;
-            if (a.decay) a.noise_nd[0] = __int_as_float(a.params[(int64_t)(a.N - 1) * REC + 11]);
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) advance_state(a.mode, a.decay, a.N, a.params, a.hole_seq, a.noise_seq, a.noise_nd);
     const int Wq = (a.W + 3) >> 2;
     const int64_t V = (int64_t)a.D * a.H * a.W;
     const int64_t total = (int64_t)a.N * a.D * a.H * Wq;
@@ -226,27 +179,8 @@ __global__ void __launch_bounds__(AB) flap_apply_kernel(ApplyArgs a) {
         const int64_t zyx = ((int64_t)z * a.H + y) * a.W + x;
         const int64_t src = (int64_t)n * V + zyx;
         const int32_t* rec = a.params + (int64_t)n * REC;
-        // the skull's 4 voxels: value = its uint8 cast (truncation on [0, 256)), bone = value != 0
         float val[4];
-        if (a.vec) {
-            if (a.u8) {
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.skull) + src);
-#pragma unroll
-                for (int l = 0; l < 4; ++l) val[l] = (float)((w >> (8 * l)) & 0xFFu);
-            } else {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.skull) + src);
-#pragma unroll
-                for (int l = 0; l < 4; ++l) val[l] = truncf(v[l]);
-            }
-        } else {
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                val[l] = 0.f;
-                if (x + l < a.W)
-                    val[l] = a.u8 ? (float)static_cast<const uint8_t*>(a.skull)[src + l]
-                                  : truncf(static_cast<const float*>(a.skull)[src + l]);
-            }
-        }
+        read_quad(a.skull, a.u8, a.vec, src, x, a.W, val);
         float img[4], bone[4], fl[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
@@ -267,50 +201,12 @@ __global__ void __launch_bounds__(AB) flap_apply_kernel(ApplyArgs a) {
                 fl[l] = b && in ? 1.f : 0.f;
             }
         }
-        if ((a.mode & CTU_FLAP_NOISE) && rec[10]) {
-            const int64_t seq = (int64_t)(((uint64_t)(uint32_t)rec[15] << 32) | (uint32_t)rec[14]);
-            const uint32_t c0 = (uint32_t)(((int64_t)z * a.H + y) * Wq + xq);
-            const uint4 r1 = philox_seq(c0, 1, seq, a.nk0, a.nk1);
-            const uint4 r2 = philox_seq(c0, 2, seq, a.nk0, a.nk1);
-            const float t0 = __int_as_float(rec[12]), t1 = __int_as_float(rec[13]);
-            const uint32_t w1[4] = {r1.x, r1.y, r1.z, r1.w}, w2[4] = {r2.x, r2.y, r2.z, r2.w};
-#pragma unroll
-            for (int l = 0; l < 4; ++l) img[l] = (img[l] != 0.f && !(unif_f32(w1[l]) <= t0)) || unif_f32(w2[l]) <= t1 ? 1.f : 0.f;
-        }
+        if ((a.mode & CTU_FLAP_NOISE) && rec[10])
+            salt_pepper(rec, (uint32_t)(((int64_t)z * a.H + y) * Wq + xq), a.nk0, a.nk1, img);
         float* xo = a.x + (int64_t)n * a.C * V + zyx;
-        float* fo = a.full ? a.full + (int64_t)n * 2 * V + zyx : nullptr;
-        float* po = a.flap ? a.flap + (int64_t)n * 2 * V + zyx : nullptr;
-        if (a.vec) {
-            *reinterpret_cast<f32x4*>(xo) = f32x4{img[0], img[1], img[2], img[3]};
-            if (a.atlas && a.C > 1) *reinterpret_cast<f32x4*>(xo + V) = *reinterpret_cast<const f32x4*>(a.atlas + zyx);
-            if (fo) {
-                *reinterpret_cast<f32x4*>(fo) = f32x4{1.f - bone[0], 1.f - bone[1], 1.f - bone[2], 1.f - bone[3]};
-                *reinterpret_cast<f32x4*>(fo + V) = f32x4{bone[0], bone[1], bone[2], bone[3]};
-            }
-            if (po) {
-                *reinterpret_cast<f32x4*>(po) = f32x4{1.f - fl[0], 1.f - fl[1], 1.f - fl[2], 1.f - fl[3]};
-                *reinterpret_cast<f32x4*>(po + V) = f32x4{fl[0], fl[1], fl[2], fl[3]};
-            }
-        } else {
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                if (x + l >= a.W) break;
-                xo[l] = img[l];
-                if (a.atlas && a.C > 1) xo[V + l] = a.atlas[zyx + l];
-                if (fo) { fo[l] = 1.f - bone[l]; fo[V + l] = bone[l]; }
-                if (po) { po[l] = 1.f - fl[l]; po[V + l] = fl[l]; }
-            }
-        }
+        write_quad(xo, a.atlas && a.C > 1 ? a.atlas + zyx : nullptr, a.full ? a.full + (int64_t)n * 2 * V + zyx : nullptr,
+                   a.flap ? a.flap + (int64_t)n * 2 * V + zyx : nullptr, V, a.vec, x, a.W, img, bone, fl);
     }
-}
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-int check_shape(int N, int D, int H, int W) {
-    CTU_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "flap: bad shape %dx%dx%dx%d", N, D, H, W);
-    CTU_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "flap: %dx%dx%d voxels per sample (< 2^31 supported)", D, H, W);
-    CTU_REQUIRE((int64_t)D * H * ((W + 3) / 4) < ((int64_t)1 << 32), "flap: noise counter overflow");
-    return CTU_OK;
 }
 
 }  // namespace
@@ -374,8 +270,7 @@ extern "C" int ctu_flap_apply(const void* skull, int u8, const float* atlas, int
     a.u8 = u8 ? 1 : 0;
     a.N = N; a.D = D; a.H = H; a.W = W; a.C = C;
     a.mode = mode; a.decay = decay ? 1 : 0;
-    a.vec = W % 4 == 0 && aligned(skull, u8 ? 4 : 16) && aligned(x, 16) && (!atlas || aligned(atlas, 16)) &&
-            (!full || aligned(full, 16)) && (!flap || aligned(flap, 16));
+    a.vec = quad_vec(skull, a.u8, atlas, W, x, full, flap);
     a.nk0 = (uint32_t)noise_seed; a.nk1 = (uint32_t)(noise_seed >> 32);
     const int64_t quads = (int64_t)N * D * H * ((W + 3) / 4);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(quads, AB), 2048));

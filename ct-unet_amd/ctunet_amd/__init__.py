@@ -21,11 +21,11 @@ from .loss_scale import DynamicLossScale  # noqa: F401
 from .losses import LossSpec, boundary_map, seg_loss  # noqa: F401
 from .models import (UNet, UNet4_2IC, UNet4b1i3o, UNet4b2i3o, UNet5b2i3o, UNetDO, UNetSP, UNetSPSmall,  # noqa: F401
                      recAE_v2_fixed)
-from .transforms import (FlapRecTransform, RandomSpatial, SaltAndPepper, SkullRandomHole,  # noqa: F401
-                         cranioplasty_transform, flap_rec_transform)
+from .transforms import (FlapRecTransform, RandomDilate, RandomSpatial, SaltAndPepper, SkullRandomDefect,  # noqa: F401
+                         SkullRandomHole, cranioplasty_transform, flap_rec_transform, realistic_cranioplasty_transform)
 
 __all__ = ["UNet", "UNet4b2i3o", "UNet5b2i3o", "UNet4b1i3o", "UNetSP", "UNetSPSmall", "UNetDO", "recAE_v2_fixed",
            "UNet4_2IC", "DynamicLossScale", "predict_volume", "Prediction",
            "SkullRandomHole", "SaltAndPepper", "FlapRecTransform", "flap_rec_transform", "RandomSpatial",
-           "cranioplasty_transform", "FlapRecWShapePrior2OTrainDataset", "FlapRec2OTrainDataset", "metrics", "postprocess", "preprocess", "resample", "registration", "mesh", "lr_scheduler",
+           "cranioplasty_transform", "SkullRandomDefect", "RandomDilate", "realistic_cranioplasty_transform", "FlapRecWShapePrior2OTrainDataset", "FlapRec2OTrainDataset", "metrics", "postprocess", "preprocess", "resample", "registration", "mesh", "lr_scheduler",
            "optim", "simplify", "LossSpec", "seg_loss", "boundary_map", "sampling", "FlapRecPatchDataset"]

@@ -229,6 +229,9 @@ SIGNATURES = {
     "ctu_patch_crop": (I, [P, I, I, I, I, I, I, P, I, I, I, I, D, P, I, I, I, P]),
     "ctu_spatial_draw": (I, [I, I, I, I, P, P, U, I, D, D, D, P, I, I, I, I, P, P, P]),
     "ctu_spatial_warp": (I, [P, I, I, I, I, I, I, P, I, I, I, P, P, P, P, P]),
+    "ctu_defect_draw": (I, [P, I, I, I, I, I, P, P, P, U, D, P, I, I, I, I, I, P, P, P]),
+    "ctu_defect_apply": (I, [P, I, P, I, I, I, I, P, P, P, I, I, I, D, D, P, I, P, P, P, U, I, P, I, P, P, P]),
+    "ctu_random_dilate": (I, [P, I, I, I, I, I, I, P, U, D, P, P]),
     "ctu_lp_upconv_fused_supported": (I, [I, I, I, I, I, I]),
     "ctu_lp_upconv_fused_packed_elems": (Z, [I]),
     "ctu_lp_upconv_fused_num_blocks": (I, [I, I, I, I]),

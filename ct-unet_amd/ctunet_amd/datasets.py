@@ -85,8 +85,9 @@ class FlapRecWShapePrior2OTrainDataset(Dataset):
     skulls: a list of [D,H,W] tensors or one [M,D,H,W] tensor, float32 or uint8, on the host or the device (host items
     are copied to the device per item); atlas: [D,H,W].  transform: a ``transforms.FlapRecTransform`` (default: the
     module's ``flap_rec_transform``, with the reference's decaying noise density); its hole must be double-output.
-    The transform runs as ONE fused pass per item (after the warp of its ``spatial`` step, when it has one, as
-    ``transforms.cranioplasty_transform`` does); every call advances its device sample counters."""
+    The transform runs as ONE fused pass per item (after the warp of its ``spatial`` step and the thickening of its
+    ``dilate`` step, when it has them, as ``transforms.realistic_cranioplasty_transform`` does); every call advances its
+    device sample counters."""
 
     def __init__(self, skulls, atlas=None, transform=None, append_atlas: bool = True, device="cuda"):
         from . import transforms as T
@@ -96,12 +97,12 @@ class FlapRecWShapePrior2OTrainDataset(Dataset):
         self.device = torch.device(device)
         base = T.flap_rec_transform if transform is None else transform
         if not isinstance(base, T.FlapRecTransform) or not base.hole.double_output:
-            raise ValueError("ctunet_amd: transform must be a FlapRecTransform with SkullRandomHole(double_output=True)")
+            raise ValueError("ctunet_amd: transform must be a FlapRecTransform whose hole has double_output=True")
         self.append_atlas = bool(append_atlas)
         if self.append_atlas and atlas is None:
             raise ValueError("ctunet_amd: append_atlas needs an atlas [D,H,W]")
         self.atlas = atlas.to(self.device, torch.float32).contiguous() if self.append_atlas else None
-        self.transform = T.FlapRecTransform(base.hole, base.noise, self.atlas, base.spatial)   # shares their state
+        self.transform = T.FlapRecTransform(base.hole, base.noise, self.atlas, base.spatial, base.dilate)   # shares their state
 
     def __len__(self):
         return len(self.skulls)
@@ -152,7 +153,7 @@ class FlapRecPatchDataset(Dataset):
             raise ValueError("ctunet_amd: skulls must be a non-empty list of [D,H,W] tensors of one shape or an [M,D,H,W] tensor")
         base = T.flap_rec_transform if transform is None else transform
         if not isinstance(base, T.FlapRecTransform) or not base.hole.double_output:
-            raise ValueError("ctunet_amd: transform must be a FlapRecTransform with SkullRandomHole(double_output=True)")
+            raise ValueError("ctunet_amd: transform must be a FlapRecTransform whose hole has double_output=True")
         self.device = torch.device(device)
         self.sampler, self.per = sampler, patches_per_volume
         vols = torch.stack([s.to(self.device) for s in items])
@@ -179,7 +180,7 @@ class FlapRecPatchDataset(Dataset):
         patch = sampling.crop(vols.view(vols.shape[0], 1, *vols.shape[1:]), coords, self.sampler.patch)
         ap = None if self.atlas is None else sampling.crop(self.atlas, coords, self.sampler.patch)[0, 0]
         b = self._base
-        x, (full, flap) = T.FlapRecTransform(b.hole, b.noise, ap, b.spatial).apply(patch)   # shares their state
+        x, (full, flap) = T.FlapRecTransform(b.hole, b.noise, ap, b.spatial, b.dilate).apply(patch)   # shares their state
         return {"image": x[0], "target": (full[0], flap[0]), "filepath": f"memory://{m}#{idx % self.per}",
                 "coords": coords[0]}
 

@@ -1549,6 +1549,71 @@ def flap_apply(skulls: torch.Tensor, atlas: Optional[torch.Tensor], params: torc
                                           x.data_ptr(), x.shape[1], _ptr(full), _ptr(flap), _stream()), "flap_apply")
 
 
+DEFECT_RECORD = 64                               # CTU_DEFECT_RECORD of ctunet_hip.h
+DEFECT_MAX_BALLS, DEFECT_MAX_LATTICE = 12, 64    # CTU_DEFECT_MAX_BALLS / CTU_DEFECT_MAX_LATTICE
+DILATE_MAX_ITERATIONS = 3                        # CTU_DILATE_MAX_ITERATIONS
+
+
+def _defect_buffers(n: int, grid: Tuple[int, int, int], record: torch.Tensor, lattice: torch.Tensor) -> None:
+    for t, nm, numel in ((record, "record", n * DEFECT_RECORD), (lattice, "lattice", n * grid[0] * grid[1] * grid[2])):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == numel, f"defect {nm}"
+
+
+def defect_draw(skulls: torch.Tensor, counts: torch.Tensor, spacing, seq: torch.Tensor, seed: int, p: float, ranges,
+                balls: Tuple[int, int], grid: Tuple[int, int, int], record: torch.Tensor, lattice: torch.Tensor) -> None:
+    """record float64 [N, DEFECT_RECORD] and lattice float64 [N, Gz, Gy, Gx] of the N skulls, drawn from the device counter
+    seq behind flap_count's counts (layout and rule: ctunet_hip.h, transforms.py).  ranges: the 6 host doubles of
+    ctu_defect_draw.  One launch."""
+    u8 = _skull_kind(skulls, "skulls")
+    n, _, d, h, w = skulls.shape
+    _defect_buffers(n, grid, record, lattice)
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == n * -(-d * h * w // FLAP_CHUNK)
+    assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1 and len(ranges) == 6
+    _lib.check(_lib.load().ctu_defect_draw(skulls.data_ptr(), u8, n, d, h, w, _lib.double_array(spacing), counts.data_ptr(),
+                                           seq.data_ptr(), seed, float(p), _lib.double_array(ranges), balls[0], balls[1],
+                                           grid[0], grid[1], grid[2], record.data_ptr(), lattice.data_ptr(), _stream()),
+               "defect_draw")
+
+
+def defect_apply(skulls: torch.Tensor, atlas: Optional[torch.Tensor], spacing, record: torch.Tensor, lattice: torch.Tensor,
+                 grid: Tuple[int, int, int], scale: float, amp: float, params: Optional[torch.Tensor], mode: int,
+                 hole_seq: torch.Tensor, noise_seq: Optional[torch.Tensor], noise_nd: Optional[torch.Tensor],
+                 noise_seed: int, decay: bool, x: torch.Tensor, full: Optional[torch.Tensor],
+                 flap: Optional[torch.Tensor]) -> None:
+    """flap_apply's pass with the records' defects as the holes (params: flap_draw's noise records, or None); advances the
+    device counters (and the density with decay)."""
+    u8 = _skull_kind(skulls, "skulls")
+    n, _, d, h, w = skulls.shape
+    _defect_buffers(n, grid, record, lattice)
+    for t, nm, c in ((x, "x", x.shape[1]), (full, "full-skull target", 2), (flap, "flap target", 2)):
+        if t is None:
+            continue
+        _need_cuda(t, nm)
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, c, d, h, w), nm
+    if atlas is not None:
+        _need_cuda(atlas, "atlas")
+        assert atlas.is_contiguous() and atlas.numel() == d * h * w, "atlas [D,H,W]"
+    if params is not None:
+        assert params.is_cuda and params.dtype == torch.int32 and params.numel() == n * FLAP_RECORD
+    _lib.check(_lib.load().ctu_defect_apply(skulls.data_ptr(), u8, _ptr(atlas), n, d, h, w, _lib.double_array(spacing),
+                                            record.data_ptr(), lattice.data_ptr(), grid[0], grid[1], grid[2], float(scale),
+                                            float(amp), _ptr(params), mode, hole_seq.data_ptr(), _ptr(noise_seq),
+                                            _ptr(noise_nd), noise_seed, int(decay), x.data_ptr(), x.shape[1], _ptr(full),
+                                            _ptr(flap), _stream()), "defect_apply")
+
+
+def random_dilate(x: torch.Tensor, out: torch.Tensor, iterations: int, seq: torch.Tensor, seed: int, p: float) -> None:
+    """out uint8 [N,1,D,H,W] = the bone of x (uint8 / float32) dilated by `iterations` steps of the 6-neighbour cross for
+    the samples drawn with probability p from the device counter seq, which advances by N.  One gather launch."""
+    _skull_kind(x, "x")
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == x.shape, "random_dilate out"
+    assert x.dim() == 5 and x.shape[1] == 1, "random_dilate x"
+    assert seq.is_cuda and seq.dtype == torch.int64 and seq.numel() == 1
+    n, _, d, h, w = x.shape
+    _lib.check(_lib.load().ctu_random_dilate(x.data_ptr(), _lib.DTYPE_CODE[x.dtype], n, d, h, w, int(iterations),
+                                             seq.data_ptr(), seed, float(p), out.data_ptr(), _stream()), "random_dilate")
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_LABEL_LINEAR = 0, 1, 2          # CTU_RESAMPLE_* of ctunet_hip.h
 RESAMPLE_CODE = _lib.DTYPE_CODE              # the dtype codes of ctu_resample
 

@@ -78,6 +78,40 @@ phi_c = (2 u - 1) max_displacement_c; the ``locked_borders`` outer layers on eve
 The draw kernel records, per sample, float64 [26]: 0-2 flip flags, 3 affine applied, 4 elastic applied, 5-7 scales, 8-10
 angles, 11-13 translations, 14-25 M row-major -- and the control grid [N, 3, Gz, Gy, Gx]; M uses the device's sin / cos, so
 the restatement takes the recorded M for the voxel rule and tests bound M against NumPy's separately.
+
+SkullRandomDefect (csrc/defect.hip; tests/defect_ref.py restates it): the "complex craniectomy defects" that the same
+docstring lists, as a union of at most MAX_BALLS = 12 balls with a rough surface, in millimetres.  The rule is this
+package's own.  All arithmetic is float64, every operation rounded on its own (no contraction); sp is the spacing, n the
+grid (D, H, W), axes are (z, y, x).
+Host, per call shape: (lo, hi) = size_range(n), s = min(sp); ``radius=None`` -> ((0.75 lo) s, (0.75 hi) s) mm;
+``roughness=None`` (the amplitude amp, mm) -> 0.15 radius[0]; ``roughness_scale=None`` (the lattice pitch scale, mm) ->
+1.5 radius[0]; lattice points per axis G_a = floor((n_a sp_a) / scale) + 2.  ValueError for G_a > 64, balls outside
+1 <= lo <= hi <= 12, spread < 0, shrink outside 0 < lo <= hi <= 1, amp < 0, radius outside 0 < lo <= hi, scale <= 0.
+Draws: Philox as above, key = the instance's seed, seq = its device sample counter + n, u = (r >> 8) 2^-24 as a double,
+integers by draw_int.  All draws are consumed whether or not the defect is cut.  Stream 0, (c0 -> words):
+  0        -> (u_apply, k over the bone count, u_r0, K = balls_lo + draw over (balls_hi - balls_lo + 1))
+  16 + 2 j -> (parent i uniform in [0, j), u_shrink, -, -)          j = 1 .. K - 1
+  17 + 2 j -> (u_z, u_y, u_x, -)
+The centre voxel is the k-th bone voxel in C order (SkullRandomHole's rule and search).  Ball 0: c_0,a = float64(centre_a)
+sp_a, r_0 = radius_lo + u_r0 (radius_hi - radius_lo).  Ball j: r_j = (shrink_lo + u_shrink (shrink_hi - shrink_lo)) r_i,
+c_j,a = c_i,a + (((2 u_a) - 1) spread) r_i.  No transcendental is involved.
+Stream 1 is the roughness lattice: c0 = the lattice point's flat index (iz Gy + iy) Gx + ix, word 0 -> nu = 2 u - 1, stored
+as float64 [N, Gz, Gy, Gx].
+Box (inclusive, per axis; the apply kernel may skip the shape test outside it):
+  lo_a = max(0, min_j floor((c_j,a - (r_j + amp)) / sp_a) - 1),  hi_a = min(n_a - 1, max_j ceil((c_j,a + (r_j + amp)) / sp_a) + 1)
+Voxel o: w_a = float64(o_a) sp_a;  g_a = w_a / scale, i_a = floor(g_a) (<= G_a - 2 by the choice of G), f_a = g_a - i_a;
+nu(o) = the trilinear interpolation of the lattice, x first, then y, then z, each lerp a + f (b - a);  rho_j = r_j + amp nu;
+the voxel is inside iff some j < K has rho_j > 0 and ((d_z d_z + d_y d_y) + d_x d_x) <= rho_j rho_j with d_a = w_a - c_j,a.
+Outputs as for the hole: image = bone and not inside, flap = bone and inside, full = bone; not drawn (u_apply >= p) or no
+bone: image unchanged (its uint8 cast), flap zero.  Without bone the record holds no chain: centre -1, balls zero, box
+lo 0 and hi -1.
+The draw kernel records, per sample, float64 [64]: 0 drawn, 1 bone count, 2 k, 3-5 centre, 6 K, 7 cut, 8-10 box lo, 11-13
+box hi, 14-15 zero, 16 + 4 j .. 19 + 4 j ball j = (c_z, c_y, c_x, r).
+
+RandomDilate (csrc/defect.hip): the "dilations prior to the craniectomy generation" of that docstring (the reference draws
+only dilation, 119-120).  Sample n is dilated iff u < p, u = word 0 of stream 0, c0 = 0 of its own seed and counter + n; a
+dilated sample equals ``scipy.ndimage.binary_dilation(bone, generate_binary_structure(3, 1), iterations, border_value=0)``
+(``iterations`` steps of the 6-neighbour cross = the L1 ball of that radius, one gather pass), any other sample is ``bone``.
 """
 from __future__ import annotations
 
@@ -204,8 +238,9 @@ def _out(t: Optional[torch.Tensor], shape, device, name) -> torch.Tensor:
     return t
 
 
-def _run(hole: Optional["SkullRandomHole"], noise: Optional["SaltAndPepper"], skulls: torch.Tensor,
+def _run(hole, noise: Optional["SaltAndPepper"], skulls: torch.Tensor,
          atlas: Optional[torch.Tensor], x: Optional[torch.Tensor], targets: Optional[Sequence[torch.Tensor]]):
+    """The fused pass of ``hole`` (a SkullRandomHole, a SkullRandomDefect or None) and ``noise`` (or None) on a batch."""
     skulls = _batch(skulls, "skulls")
     dev = skulls.device
     n, _, d, h, w = skulls.shape
@@ -232,6 +267,21 @@ def _run(hole: Optional["SkullRandomHole"], noise: Optional["SaltAndPepper"], sk
         ops.flap_count(skulls, counts)
     hs = hole._rng if hole is not None else None
     ns = noise._rng if noise is not None else None
+    if isinstance(hole, SkullRandomDefect):
+        geo = hole.geometry((d, h, w))
+        record, lattice = hole._buffers(n, geo["lattice"], dev)
+        ops.defect_draw(skulls, counts, hole.spacing, hs.counter, hs.seed, hole.p,
+                        geo["radius"] + (hole.spread,) + hole.shrink + (geo["roughness"],), hole.balls, geo["lattice"],
+                        record, lattice)
+        if noise is not None:                       # the noise scalars: the hole's draw kernel in noise-only mode
+            ops.flap_draw(skulls, None, ops.FLAP_NOISE, None, 0, 0.0, (0, 1), 0, ns.counter, ns.density, ns.seed, noise.p,
+                          noise.salt_ratio, noise.decay, params)
+            noise._params = params
+        ops.defect_apply(skulls, atlas, hole.spacing, record, lattice, geo["lattice"], geo["roughness_scale"],
+                         geo["roughness"], params if noise is not None else None, mode, hs.counter, ns and ns.counter,
+                         ns and ns.density, ns.seed if ns else 0, bool(noise and noise.decay), x, full, flap)
+        hole._params = params if noise is not None else None
+        return x, [full, flap] if full is not None else [flap]
     ops.flap_draw(skulls, counts, mode, hs and hs.counter, hs.seed if hs else 0, hole.p if hole else 0.0,
                   size_range((d, h, w)) if hole else (0, 1), hole._shape_code if hole else 0,
                   ns and ns.counter, ns and ns.density, ns.seed if ns else 0, noise.p if noise else 0.0,
@@ -509,21 +559,220 @@ class RandomSpatial:
         return sample
 
 
+MAX_BALLS = ops.DEFECT_MAX_BALLS
+
+
+def _pair(v, what: str) -> Tuple[float, float]:
+    try:
+        lo, hi = v
+    except (TypeError, ValueError):
+        raise TypeError(f"SkullRandomDefect: {what} must be a (low, high) pair, got {v!r}") from None
+    if any(isinstance(t, bool) or not isinstance(t, Real) or not math.isfinite(t) for t in (lo, hi)):
+        raise TypeError(f"SkullRandomDefect: {what} must be a (low, high) pair of finite numbers, got {v!r}")
+    return float(lo), float(hi)
+
+
+def _scalar(v, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v):
+        raise TypeError(f"SkullRandomDefect: {what} must be a finite number, got {v!r}")
+    return float(v)
+
+
+class SkullRandomDefect:
+    """Cut an irregular craniectomy defect -- a union of ``balls`` rough balls around a random bone voxel, sized in
+    millimetres -- out of binary skulls (module docstring, the "SkullRandomDefect" rule).  A sibling of SkullRandomHole with
+    the same calling forms: ``apply`` on device batches, ``sample`` dicts as the reference's.  Three launches per call (four
+    with noise fused in by FlapRecTransform), no host sync: it can be captured in a graph after one warm call."""
+
+    def __init__(self, p=1, double_output=False, spacing=(1, 1, 1), radius=None, balls=(3, 8), spread=0.9,
+                 shrink=(0.5, 0.9), roughness=None, roughness_scale=None, seed: Optional[int] = None):
+        self.p = _check_p(p, "p")
+        self.double_output = bool(double_output)
+        self.spacing = _args.triple(spacing, _REAL_POSITIVE._replace(
+            shape="SkullRandomDefect: {what} must be a number or a (z, y, x) triple, got {v!r}",
+            value="SkullRandomDefect: {what} must be positive and finite, got {v!r}"), what="spacing")
+        if self.spacing is None:
+            raise TypeError("SkullRandomDefect: spacing must be a number or a (z, y, x) triple")
+        self.radius = None if radius is None else _pair(radius, "radius")
+        if self.radius is not None and not 0 < self.radius[0] <= self.radius[1]:
+            raise ValueError(f"SkullRandomDefect: radius must satisfy 0 < low <= high (mm), got {radius!r}")
+        try:
+            blo, bhi = balls
+        except (TypeError, ValueError):
+            raise TypeError(f"SkullRandomDefect: balls must be a (low, high) pair of ints, got {balls!r}") from None
+        if any(isinstance(b, bool) or not isinstance(b, int) for b in (blo, bhi)):
+            raise TypeError(f"SkullRandomDefect: balls must be a (low, high) pair of ints, got {balls!r}")
+        if not 1 <= blo <= bhi <= MAX_BALLS:
+            raise ValueError(f"SkullRandomDefect: balls must satisfy 1 <= low <= high <= {MAX_BALLS}, got {balls!r}")
+        self.balls = (blo, bhi)
+        self.spread = _scalar(spread, "spread")
+        if self.spread < 0:
+            raise ValueError(f"SkullRandomDefect: spread must not be negative, got {spread!r}")
+        self.shrink = _pair(shrink, "shrink")
+        if not 0 < self.shrink[0] <= self.shrink[1] <= 1:
+            raise ValueError(f"SkullRandomDefect: shrink must satisfy 0 < low <= high <= 1, got {shrink!r}")
+        self.roughness = None if roughness is None else _scalar(roughness, "roughness")
+        if self.roughness is not None and self.roughness < 0:
+            raise ValueError(f"SkullRandomDefect: roughness must not be negative, got {roughness!r}")
+        self.roughness_scale = None if roughness_scale is None else _scalar(roughness_scale, "roughness_scale")
+        if self.roughness_scale is not None and self.roughness_scale <= 0:
+            raise ValueError(f"SkullRandomDefect: roughness_scale must be positive, got {roughness_scale!r}")
+        self._rng = _DeviceRng(seed)
+        self._params: Optional[torch.Tensor] = None            # the fused noise's records of the last call
+        self._record: Optional[torch.Tensor] = None
+        self._lattice: Optional[torch.Tensor] = None
+
+    @property
+    def seed(self) -> int:
+        return self._rng.seed
+
+    def to(self, device) -> "SkullRandomDefect":
+        self._rng.to(device)
+        return self
+
+    def state_dict(self) -> Dict:
+        c, _ = self._rng.state()
+        return {"seed": self._rng.seed, "counter": c}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        self._rng.seed = _seed(sd["seed"])
+        self._rng.load(sd["counter"], None)
+
+    def geometry(self, shape: Sequence[int]) -> Dict:
+        """What a volume of ``shape`` = (D, H, W) resolves the defaults to, on the host: radius (lo, hi), roughness and
+        roughness_scale in mm and the lattice size (Gz, Gy, Gx); ValueError where the rule refuses them."""
+        lo, hi = size_range(shape)
+        s = min(self.spacing)
+        radius = self.radius if self.radius is not None else ((0.75 * lo) * s, (0.75 * hi) * s)
+        if not 0 < radius[0] <= radius[1]:
+            raise ValueError(f"SkullRandomDefect: a {tuple(shape)} volume gives the radius range {radius}; it must satisfy "
+                             "0 < low <= high")
+        amp = self.roughness if self.roughness is not None else 0.15 * radius[0]
+        scale = self.roughness_scale if self.roughness_scale is not None else 1.5 * radius[0]
+        lattice = tuple(math.floor((n * sp) / scale) + 2 for n, sp in zip(shape, self.spacing))
+        if any(g > ops.DEFECT_MAX_LATTICE for g in lattice):
+            raise ValueError(f"SkullRandomDefect: roughness_scale {scale} mm needs a {lattice} lattice on a {tuple(shape)} "
+                             f"volume (at most {ops.DEFECT_MAX_LATTICE} points per axis)")
+        return {"radius": radius, "roughness": amp, "roughness_scale": scale, "lattice": lattice}
+
+    def _buffers(self, n: int, lattice: Tuple[int, int, int], device: torch.device):
+        """The record and the lattice of a batch of n: kept between calls, so a steady call allocates neither."""
+        if self._record is None or self._record.shape[0] != n or self._record.device != device \
+                or tuple(self._lattice.shape[1:]) != lattice:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd: call the transform once with this batch shape before capturing it in a graph")
+            self._record = torch.empty((n, ops.DEFECT_RECORD), dtype=torch.float64, device=device)
+            self._lattice = torch.empty((n,) + lattice, dtype=torch.float64, device=device)
+        return self._record, self._lattice
+
+    def apply(self, skulls: torch.Tensor, x: Optional[torch.Tensor] = None,
+              targets: Optional[Sequence[torch.Tensor]] = None):
+        """skulls [N,1,D,H,W] float32 / uint8 on the GPU -> (x [N,1,D,H,W], [full, flap] or [flap] one-hot
+        [N,2,D,H,W]), float32; x / targets: caller-supplied outputs."""
+        return _run(self, None, skulls, None, x, targets)
+
+    __call__ = SkullRandomHole.__call__        # the sample-dict form needs only ``apply`` and ``double_output``
+
+    @property
+    def last_params(self) -> List[Dict]:
+        """Per-sample records of the last call (one read-back): apply, cut (drawn and bone present), count, k, centre,
+        n_balls, balls (n_balls tuples (cz, cy, cx, r) in mm; none without bone), box ((lo_z, lo_y, lo_x), (hi_z, hi_y,
+        hi_x)), and the fused noise's noise_applied, nd, thresholds and noise_seq (False / 0 without noise)."""
+        if self._record is None:
+            raise RuntimeError("ctunet_amd: the transform has not been called yet")
+        noise = _decode(self._params) if self._params is not None else [None] * self._record.shape[0]
+        out = []
+        for r, nz in zip(self._record.cpu().tolist(), noise):
+            k = int(r[6])
+            d = {"noise_applied": False, "nd": 0.0, "thresholds": (0.0, 0.0), "noise_seq": 0} if nz is None else \
+                {f: nz[f] for f in ("noise_applied", "nd", "thresholds", "noise_seq")}
+            d.update(apply=bool(r[0]), cut=bool(r[7]), count=int(r[1]), k=int(r[2]), centre=tuple(int(v) for v in r[3:6]),
+                     n_balls=k, balls=[tuple(r[16 + 4 * j:20 + 4 * j]) for j in range(k if r[1] > 0 else 0)],
+                     box=(tuple(int(v) for v in r[8:11]), tuple(int(v) for v in r[11:14])))
+            out.append(d)
+        return out
+
+    @property
+    def last_lattice(self) -> torch.Tensor:
+        """The roughness lattice of the last call, float64 [N, Gz, Gy, Gx] on the host (one read-back)."""
+        if self._lattice is None:
+            raise RuntimeError("ctunet_amd: the transform has not been called yet")
+        return self._lattice.cpu()
+
+
+class RandomDilate:
+    """Thicken a random share ``p`` of a batch of binary skulls by ``iterations`` steps of the 6-neighbour cross (module
+    docstring, the "RandomDilate" rule): one gather launch, the per-sample choice drawn on the device, so a replayed graph
+    draws afresh."""
+
+    def __init__(self, p=0.3, iterations=1, seed: Optional[int] = None):
+        self.p = _check_p(p, "p")
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= ops.DILATE_MAX_ITERATIONS:
+            raise ValueError(f"RandomDilate: iterations must be an int in 1..{ops.DILATE_MAX_ITERATIONS}, got {iterations!r}")
+        self.iterations = iterations
+        self._rng = _DeviceRng(seed)
+
+    @property
+    def seed(self) -> int:
+        return self._rng.seed
+
+    def to(self, device) -> "RandomDilate":
+        self._rng.to(device)
+        return self
+
+    def state_dict(self) -> Dict:
+        c, _ = self._rng.state()
+        return {"seed": self._rng.seed, "counter": c}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        self._rng.seed = _seed(sd["seed"])
+        self._rng.load(sd["counter"], None)
+
+    def apply(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [N,1,D,H,W] uint8 / float32 on the GPU -> uint8 0 / 1, the same shape (out: caller-supplied, not x)."""
+        x = _batch(x, "x")
+        if out is None:
+            out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != x.shape or out.device != x.device \
+                or not out.is_contiguous():
+            raise ValueError(f"RandomDilate: out must be a contiguous uint8 tensor of shape {tuple(x.shape)} on {x.device}")
+        nbytes = x.numel() * x.element_size()
+        if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + out.numel():
+            raise ValueError("RandomDilate: out overlaps x; the gather cannot run in place")
+        self._rng.to(x.device)
+        with torch.cuda.device(x.device):
+            ops.random_dilate(x, out, self.iterations, self._rng.counter, self._rng.seed, self.p)
+        return out
+
+    def __call__(self, sample: Dict) -> Dict:
+        img = sample["image"]
+        if not isinstance(img, torch.Tensor):
+            raise TypeError(f"Expected 'torch.Tensor'. Got {type(img)}.")
+        is_batch = img.dim() == 4
+        b = (img if is_batch else img.unsqueeze(0)).unsqueeze(1).to("cuda")
+        out = self.apply(b if b.dtype in (torch.float32, torch.uint8) else b.float())[:, 0]
+        sample["image"] = out if is_batch else out[0]
+        return sample
+
+
 class FlapRecTransform(_Recorded):
     """``hole`` then ``noise`` in ONE fused pass, bit-equal to applying them in sequence (each keeps its own seed, counter
-    and density); ``atlas`` [D,H,W] float32 becomes channel 1 of the network input, as the shape-prior datasets append it."""
+    and density); ``atlas`` [D,H,W] float32 becomes channel 1 of the network input, as the shape-prior datasets append it.
+    ``hole`` is a SkullRandomHole or a SkullRandomDefect; ``spatial`` warps and then ``dilate`` thickens the skulls first."""
 
-    def __init__(self, hole: SkullRandomHole, noise: Optional[SaltAndPepper] = None, atlas: Optional[torch.Tensor] = None,
-                 spatial: Optional[RandomSpatial] = None):
-        if not isinstance(hole, SkullRandomHole) or not (noise is None or isinstance(noise, SaltAndPepper)) \
-                or not (spatial is None or isinstance(spatial, RandomSpatial)):
-            raise TypeError("FlapRecTransform(hole: SkullRandomHole, noise: SaltAndPepper | None, atlas=None, "
-                            "spatial: RandomSpatial | None)")
+    def __init__(self, hole, noise: Optional[SaltAndPepper] = None, atlas: Optional[torch.Tensor] = None,
+                 spatial: Optional[RandomSpatial] = None, dilate: Optional[RandomDilate] = None):
+        if not isinstance(hole, (SkullRandomHole, SkullRandomDefect)) or not (noise is None or isinstance(noise, SaltAndPepper)) \
+                or not (spatial is None or isinstance(spatial, RandomSpatial)) \
+                or not (dilate is None or isinstance(dilate, RandomDilate)):
+            raise TypeError("FlapRecTransform(hole: SkullRandomHole | SkullRandomDefect, noise: SaltAndPepper | None, "
+                            "atlas=None, spatial: RandomSpatial | None, dilate: RandomDilate | None)")
         if noise is not None and (noise.keyws[:1] != ("image",) or noise.apply_to != (True,) + (False,) * (len(noise.apply_to) - 1)):
             raise ValueError("FlapRecTransform: the fused noise applies to the image only (apply_to=(True, False))")
-        self.hole, self.noise, self.spatial = hole, noise, spatial
+        self.hole, self.noise, self.spatial, self.dilate = hole, noise, spatial, dilate
         self.atlas = None if atlas is None else atlas.float().contiguous()
         self._warped: Optional[torch.Tensor] = None
+        self._dilated: Optional[torch.Tensor] = None
 
     def to(self, device) -> "FlapRecTransform":
         self.hole.to(device)
@@ -533,12 +782,16 @@ class FlapRecTransform(_Recorded):
             self.atlas = self.atlas.to(device)
         if self.spatial is not None:
             self.spatial.to(device)
+        if self.dilate is not None:
+            self.dilate.to(device)
         return self
 
     def state_dict(self) -> Dict:
         sd = {"hole": self.hole.state_dict(), "noise": None if self.noise is None else self.noise.state_dict()}
         if self.spatial is not None:
             sd["spatial"] = self.spatial.state_dict()
+        if self.dilate is not None:
+            sd["dilate"] = self.dilate.state_dict()
         return sd
 
     def load_state_dict(self, sd: Dict) -> None:
@@ -547,6 +800,8 @@ class FlapRecTransform(_Recorded):
             self.noise.load_state_dict(sd["noise"])
         if self.spatial is not None and sd.get("spatial") is not None:
             self.spatial.load_state_dict(sd["spatial"])
+        if self.dilate is not None and sd.get("dilate") is not None:
+            self.dilate.load_state_dict(sd["dilate"])
 
     def _warp(self, skulls: torch.Tensor) -> torch.Tensor:
         """The skulls' uint8 casts warped by ``spatial`` into a uint8 buffer kept between calls."""
@@ -559,13 +814,24 @@ class FlapRecTransform(_Recorded):
             self._warped = torch.empty_like(skulls)
         return self.spatial.apply(skulls, out=self._warped)
 
+    def _thicken(self, skulls: torch.Tensor) -> torch.Tensor:
+        """The skulls' bone dilated by ``dilate`` into a uint8 buffer kept between calls."""
+        skulls = _batch(skulls, "skulls")
+        if self._dilated is None or self._dilated.shape != skulls.shape or self._dilated.device != skulls.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctunet_amd: call the transform once with this shape before capturing it in a graph")
+            self._dilated = torch.empty(skulls.shape, dtype=torch.uint8, device=skulls.device)
+        return self.dilate.apply(skulls, out=self._dilated)
+
     def apply(self, skulls: torch.Tensor, x: Optional[torch.Tensor] = None,
               targets: Optional[Sequence[torch.Tensor]] = None):
         """skulls [N,1,D,H,W] -> (x [N,C,D,H,W], one-hot targets), float32, written into x / targets when given (e.g.
-        ``GraphedTrainStep.x`` / ``.targets``).  With ``spatial`` the skulls are warped first; the full-skull target is the
-        warped skull and the atlas channel is not warped."""
+        ``GraphedTrainStep.x`` / ``.targets``).  With ``spatial`` the skulls are warped first, with ``dilate`` then
+        thickened; the full-skull target is the warped, dilated skull and the atlas channel is not warped."""
         if self.spatial is not None:
             skulls = self._warp(skulls)
+        if self.dilate is not None:
+            skulls = self._thicken(skulls)
         if self.atlas is not None and self.atlas.device != skulls.device:
             self.atlas = self.atlas.to(skulls.device)
         return _run(self.hole, self.noise, skulls, self.atlas, x, targets)
@@ -574,11 +840,18 @@ class FlapRecTransform(_Recorded):
     def _params(self) -> Optional[torch.Tensor]:
         return self.hole._params            # the records of the last call of its hole (fused or not)
 
+    @property
+    def last_params(self) -> List[Dict]:
+        """The records of the last call of its hole (fused or not): ``hole.last_params``."""
+        return self.hole.last_params
+
     def __call__(self, sample: Dict) -> Dict:
         """The reference's Compose([hole, noise]) on a sample dict: float32 image, uint8 target(s); no atlas.  With
-        ``spatial`` the image is warped first."""
+        ``spatial`` the image is warped first, with ``dilate`` then thickened."""
         if self.spatial is not None:
             sample = dict(sample, image=self.spatial({"image": sample["image"]})["image"])
+        if self.dilate is not None:
+            sample = dict(sample, image=self.dilate({"image": sample["image"]})["image"])
         sample = self.hole(sample)
         img = sample["image"]
         if self.noise is not None:
@@ -595,7 +868,16 @@ cranioplasty_transform = FlapRecTransform(SkullRandomHole(p=0.9, double_output=T
 """The pipeline the docstring of the reference's ``cranioplasty_transform`` (ctunet/pytorch/transforms.py:173-228)
 describes, with its numbers: flip of axis 0 (p = .5), elastic deformation (7 control points, 7.5 mm, 2 locked layers,
 p = .5), affine (scales .9-1.1, 15 degrees, translation (10, 10, 15) mm, p = .5), the flap extraction (p = .9) and salt and
-pepper noise (p = 1, density .05).  Differences: no erode / dilate step; the warp follows this module's RandomSpatial rule,
+pepper noise (p = 1, density .05).  Differences: no erode / dilate step (``realistic_cranioplasty_transform`` has the
+dilation); the warp follows this module's RandomSpatial rule,
 not torchio's; voxel spacing is (1, 1, 1) mm unless a RandomSpatial with another ``spacing`` is used; and the reference's
 function itself cannot run (it calls ``erode_dilate`` and ``skull_random_hole``, which do not exist, and uses the
 ``SaltAndPepper`` class as a function), so there is no behaviour to match, only this described pipeline."""
+
+realistic_cranioplasty_transform = FlapRecTransform(SkullRandomDefect(p=0.9, double_output=True),
+                                                    SaltAndPepper(p=1, noise_density=.05),
+                                                    spatial=RandomSpatial(flip_axes=(0,)), dilate=RandomDilate(p=0.3))
+"""``cranioplasty_transform`` with the two augmentations that docstring lists besides: the skull is thickened by one step of
+the 6-neighbour cross with p = .3 after the warp, and the hole is an irregular defect (SkullRandomDefect: 3-8 rough balls,
+radii from the hole's size range in mm) instead of a sphere, box or idealised flap.  Spacing (1, 1, 1) mm unless the
+members are built with another."""

@@ -1182,6 +1182,38 @@ int ctu_spatial_draw(int N, int D, int H, int W, const double* spacing, const in
 int ctu_spatial_warp(const void* in, int dtype, int N, int C, int D, int H, int W, const double* spacing, int gz, int gy,
                      int gx, const double* record, const double* control, int64_t* seq, void* out, void* stream);
 
+/* Irregular craniectomy defects (a union of rough balls, in millimetres) and random dilation of binary skulls; rules,
+ * Philox streams and arithmetic order are pinned in ctunet_amd/transforms.py ("SkullRandomDefect", "RandomDilate").  Skulls
+ * as for the flap entry points above: [N,1,D,H,W] float32 (u8 = 0) or uint8 (u8 = 1), bone = nonzero uint8 cast.
+ *   draw:  after ctu_flap_count (counts).  One block per sample writes record [N][CTU_DEFECT_RECORD] and lattice
+ *          [N][gz][gy][gx] (float64, DEVICE) from the DEVICE sample counter seq (int64 [1], read only); sample n uses
+ *          sequence number seq + n.  spacing: HOST (z, y, x) mm.  ranges: HOST double [6] = radius lo, hi (mm), spread,
+ *          shrink lo, hi, roughness amplitude (mm).  balls_lo .. balls_hi (inclusive) within 1..CTU_DEFECT_MAX_BALLS;
+ *          2 <= g <= CTU_DEFECT_MAX_LATTICE per axis.
+ *   apply: ctu_flap_apply's pass (same x / atlas / full / flap / counters / density contract) with the record's defect as
+ *          the hole.  mode: CTU_FLAP_HOLE, or CTU_FLAP_HOLE | CTU_FLAP_NOISE with params = ctu_flap_draw's records in
+ *          CTU_FLAP_NOISE mode.  scale: the lattice pitch (mm), amp: the roughness amplitude (mm).  Advances hole_seq
+ *          (the defect's counter) and the noise state.
+ * record (float64): 0 drawn (u < p)  1 bone count  2 k  3-5 centre z, y, x (-1 without bone)  6 balls K  7 cut (drawn
+ *         and count > 0)  8-10 box lo z, y, x  11-13 box hi z, y, x (inclusive; lo 0, hi -1 without bone)  14-15 zero
+ *         16 + 4 j .. 19 + 4 j: ball j < K = centre z, y, x and radius (mm), zero for j >= K and without bone
+ *   dilate: out [N,1,D,H,W] uint8 = bone dilated by `iterations` (1..CTU_DILATE_MAX_ITERATIONS) steps of the 6-neighbour
+ *          cross (the L1 ball of that radius, border 0) for the samples whose draw u < p, bone itself for the others.  in:
+ *          CTU_U8 or CTU_F32, not out.  One gather launch, then a one-thread launch that advances seq by N. */
+#define CTU_DEFECT_RECORD 64
+#define CTU_DEFECT_MAX_BALLS 12
+#define CTU_DEFECT_MAX_LATTICE 64
+#define CTU_DILATE_MAX_ITERATIONS 3
+int ctu_defect_draw(const void* skull, int u8, int N, int D, int H, int W, const double* spacing, const int32_t* counts,
+                    const int64_t* seq, uint64_t seed, double p, const double* ranges, int balls_lo, int balls_hi, int gz,
+                    int gy, int gx, double* record, double* lattice, void* stream);
+int ctu_defect_apply(const void* skull, int u8, const float* atlas, int N, int D, int H, int W, const double* spacing,
+                     const double* record, const double* lattice, int gz, int gy, int gx, double scale, double amp,
+                     const int32_t* params, int mode, int64_t* hole_seq, int64_t* noise_seq, float* noise_nd,
+                     uint64_t noise_seed, int decay, float* x, int C, float* full, float* flap, void* stream);
+int ctu_random_dilate(const void* in, int dtype, int N, int D, int H, int W, int iterations, int64_t* seq, uint64_t seed,
+                      double p, uint8_t* out, void* stream);
+
 /* ------------------------------------------------ reduced precision (bf16 / fp16 activations) ---- */
 /* BASELINE configs 4 ("bf16, 192^3 patches") and 5 ("fp16 MFMA conv path, 256^3 patches").  Same operations, call sites
  * and argument meaning as the fp32 entry points above, with
