@@ -1,7 +1,7 @@
-// The front end of the volume kernels (morphology, distance, surface, mesh, fill holes): a lane reads 16 x-consecutive
-// voxels of a uint8 / int64 / float32 map and turns them into a 16-bit membership mask.  One routine, mask16, and one small
-// functor per membership rule; with them store_mask16, the way back from a mask to 16 bytes of 0 / 1, and the constants
-// every one of these kernels shares.
+// The front end of the volume kernels (morphology, distance, surface, mesh, fill holes, region properties): a lane reads 16
+// x-consecutive voxels of a uint8 / int32 / int64 / float32 map and turns them into a 16-bit membership mask.  One routine,
+// mask16, and one small functor per membership rule; with them each16 (the values themselves), store_mask16, the way back
+// from a mask to 16 bytes of 0 / 1, and the constants every one of these kernels shares.
 #pragma once
 #include "common.h"
 
@@ -67,6 +67,33 @@ __device__ __forceinline__ uint32_t mask16(const T* p, int nv, Pred pred) {
         for (int u = 0; u < nv; ++u) b |= (uint32_t)pred(p[u]) << u;
     }
     return b;
+}
+
+// the values themselves, for the kernels that need more than membership (regionprops.hip): f(u, p[u]) for u < nv <= 16,
+// with mask16's loads (int32 takes four).  Fully unrolled, so an f that fills a register array keeps it in registers.
+template <class T, class F>
+__device__ __forceinline__ void each16(const T* p, int nv, F f) {
+    constexpr int PER = 16 / (int)sizeof(T);
+    typedef T Vec __attribute__((ext_vector_type(PER)));
+    if (nv == 16 && ((uintptr_t)p & 15) == 0) {
+        if constexpr (sizeof(T) == 1) {
+            const uint4 v = *reinterpret_cast<const uint4*>(p);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int u = 0; u < 16; ++u) f(u, (T)(w[u >> 2] >> (8 * (u & 3))));
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16 / PER; ++q) {
+                const Vec v = reinterpret_cast<const Vec*>(p)[q];
+#pragma unroll
+                for (int u = 0; u < PER; ++u) f(q * PER + u, v[u]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+            if (u < nv) f(u, p[u]);
+    }
 }
 
 // the way back: bit u of m as the byte p[u] = 0 / 1 for u < nv <= 16, one 16-byte store where all 16 go to an aligned p

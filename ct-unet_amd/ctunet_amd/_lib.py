@@ -159,6 +159,9 @@ SIGNATURES = {
     "ctu_components_ws_bytes": (Z, [I, I, I, I]),
     "ctu_label_components": (I, [P, I, I, I, I, I, I, P, I, P, P, P, P]),
     "ctu_filter_components": (I, [P, I, I, I, I, I, I, P, I, I, I, P, P, P]),
+    "ctu_region_moments_ws_bytes": (Z, [I, I]),
+    "ctu_region_moments": (I, [P, I, I, I, I, I, I, P, P, P, P, P]),
+    "ctu_region_derive": (I, [P, I, I, P, P, P, P, P, P]),
     "ctu_morphology_ws_bytes": (Z, [I, I, I, I, I]),
     "ctu_binary_morphology": (I, [P, I, I, I, I, I, I, C.c_uint32, I, I, I, L, P, P, P]),
     "ctu_fill_holes": (I, [P, I, I, I, I, I, I, I, L, P, P, P]),

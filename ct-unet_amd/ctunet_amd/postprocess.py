@@ -92,6 +92,41 @@ inscribed ball that contains it.
   calls are bit-equal.  Limits as the distance transform's.  Not offered: a radius cap, the bias correction, the thickness
   of the background (pass the inverted mask), per-vertex thickness of meshes, a virtual border.
 
+Region properties (``region_properties`` / ``bounding_box`` / ``crop_to_box``; ``ctu_region_moments``, ``ctu_region_derive`` of
+``csrc/regionprops.hip``; ``tests/regionprops_ref.py`` restates the rule in numpy) are what ``scipy.ndimage.sum_labels`` /
+``find_objects`` / ``center_of_mass`` give on the host, from one pass over a label map on the device:
+
+- **Regions**: ``labels`` is bool, uint8, int32 (what ``label`` returns) or int64, [D,H,W] or [N,D,H,W]; region ``r``
+  (1 <= r <= R = ``num_regions``, at most 65536) is the set of voxels whose value is ``r`` (a bool mask is region 1), 0 is
+  background, and a voxel whose value is negative or above R belongs to no region and is counted in ``overflow``.  R is a
+  capacity the caller chooses: nothing is read back to size the result.
+- **Limits**: every side at most 1024, fewer than 2^31 voxels per item, N <= 65535.  With sides up to 1024 every sum below
+  stays under 2^31 * 2^20 = 2^51 < 2^53, so each converts to float64 exactly.
+- ``moments`` int64 [N,R,10]: (count, Sz, Sy, Sx, Szz, Szy, Szx, Syy, Syx, Sxx), sums over the voxel indices (z, y, x) of the
+  region.  Exact integers, summed with integer atomics: independent of any order of arrival.
+- ``boxes`` int32 [N,R,6]: (z0, y0, x0, z1, y1, x1), half open, the slices of ``scipy.ndimage.find_objects``; six zeros for an
+  empty region.  ``overflow`` int64 [N].
+- ``centroid`` float64 [N,R,3], world units: with ``n = count`` and ``m_a = S_a / n``, ``origin_a + sampling_a * m_a``; NaN for
+  an empty region.  ``sampling`` and ``origin`` are a scalar, a (z, y, x) triple or one triple per item (``None``: 1 and 0).
+- ``covariance`` float64 [N,R,3,3], world units squared: ``c_ab = S_ab / n - m_a * m_b``, then
+  ``(c_ab * sampling_min(a,b)) * sampling_max(a,b)`` (the population covariance of the voxel centres); float64, every
+  operation rounded on its own; NaN for an empty region.
+- ``extent`` float64 [N,R,3] and ``axes`` float64 [N,R,3,3]: the eigenvalues of the covariance in descending order and the
+  unit eigenvectors as columns (``axes[..., :, j]`` belongs to ``extent[..., j]``), by 8 cyclic Jacobi sweeps over the pairs
+  (0,1), (0,2), (1,2) from ``E = I``: a pair with ``a_pq != 0`` takes ``theta = (a_qq - a_pp) / (2 a_pq)``,
+  ``t = sign(theta) / (|theta| + sqrt(theta theta + 1))``, ``c = 1 / sqrt(t t + 1)``, ``s = t c``; ``a_pp -= t a_pq``,
+  ``a_qq += t a_pq``, ``a_pq = 0``, with ``r`` the third index ``(a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq)`` and the
+  same for the columns p, q of every row of ``E``.  Equal eigenvalues keep their index order.  Each of the first two axes is
+  signed so that its component of largest magnitude (the first one of equals) is positive; the third axis is the cross
+  product of the first two, so the frame is right-handed in (z, y, x) index order.  A region of fewer than 2 voxels gives NaN
+  axes (one voxel: extent 0; none: NaN).  A region with nearly equal extents has ill-defined axes.
+- No host synchronisation and no allocation besides the result and the workspace (24 bytes per region): a call can be
+  captured into a graph, and two calls are bit-equal.
+- **Boxes as regions of interest** (``bounding_box``): per axis of size ``S``, from the region's ``(lo, hi)``: ``lo -= margin``,
+  ``hi += margin``; ``side = ceil((hi - lo) / multiple_of) * multiple_of``, ``lo -= (side - (hi - lo)) // 2``; if ``side <= S``
+  the box is shifted inside, ``lo = max(min(lo, S - side), 0)``, ``hi = lo + side``; otherwise it is clipped to ``(0, S)``.  An
+  empty region gives the whole volume.  Integer arithmetic on the device.
+
 Each item of a batch is processed on its own.  The morphology calls use no atomics and no host synchronisation, so a
 call can be captured into a graph.  The output and the workspace are ``torch.empty`` tensors, which a capture draws from
 the graph's private pool.  Under capture give ``structure`` as an int or a host array: a structure tensor on the device
@@ -102,7 +137,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from numbers import Integral, Real
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -586,3 +621,160 @@ def thickness_workspace_bytes(n: int, shape, sampling=None) -> int:
         raise ValueError(f"postprocess: local_thickness takes 1..65535 items of sides 1..{MAX_DISTANCE_SIDE} with fewer "
                          f"than 2^31 voxels, got n={n!r}, shape={tuple(shape)}")
     return own + 4 * n * shape[0] * shape[1] * shape[2] + int(lib.ctu_distance_ws_bytes(n, *shape, _DIST_SQUARED, 0))
+
+
+# ------------------------------------------------------------------------------------------------ region properties
+MAX_REGIONS = 65536                    # CTU_REGION_MAX
+MAX_REGION_SIDE = 1024                 # the volume kernels' MAX_SIDE: keeps every moment below 2^53, exact in float64
+_LABEL_DTYPES = (torch.bool, torch.uint8, torch.int32, torch.int64)
+
+
+class RegionProperties(NamedTuple):
+    """Device tensors of ``region_properties`` (module docstring): ``moments`` int64 [N,R,10], ``boxes`` int32 [N,R,6],
+    ``overflow`` int64 [N], ``centroid`` float64 [N,R,3], ``covariance`` float64 [N,R,3,3], ``extent`` float64 [N,R,3],
+    ``axes`` float64 [N,R,3,3]."""
+    moments: torch.Tensor
+    boxes: torch.Tensor
+    overflow: torch.Tensor
+    centroid: torch.Tensor
+    covariance: torch.Tensor
+    extent: torch.Tensor
+    axes: torch.Tensor
+
+
+def _num_regions(num_regions) -> int:
+    if isinstance(num_regions, bool) or not isinstance(num_regions, Integral) or not 1 <= num_regions <= MAX_REGIONS:
+        raise ValueError(f"postprocess: num_regions must be an integer in 1..{MAX_REGIONS}, got {num_regions!r}")
+    return int(num_regions)
+
+
+def _region_sides(shape) -> None:
+    if any(s > MAX_REGION_SIDE for s in shape):
+        raise ValueError(f"postprocess: region properties take sides up to {MAX_REGION_SIDE} (the sums stay exact in float64), "
+                         f"got {tuple(shape)}")
+
+
+def _origin(origin, n: int):
+    """None (origin 0), else N (z, y, x) triples of finite floats: a scalar, a triple or one triple per item."""
+    def finite(v):
+        if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v):
+            raise ValueError(f"postprocess: origin must hold finite numbers, got {v!r}")
+        return float(v)
+    if origin is None:
+        return None
+    if isinstance(origin, torch.Tensor):
+        origin = origin.tolist()
+    if isinstance(origin, Real) and not isinstance(origin, bool):
+        return [[finite(origin)] * 3 for _ in range(n)]
+    if not hasattr(origin, "__len__"):
+        raise ValueError(f"postprocess: origin must be a number, a (z, y, x) triple or {n} such triples, got {origin!r}")
+    items = list(origin)
+    if len(items) == 3 and all(isinstance(v, Real) for v in items):
+        return [[finite(v) for v in items] for _ in range(n)]
+    if len(items) == n and all(hasattr(v, "__len__") and len(v) == 3 for v in items):
+        return [[finite(v) for v in t] for t in items]
+    raise ValueError(f"postprocess: origin must be a number, a (z, y, x) triple or {n} such triples, got {origin!r}")
+
+
+def region_properties(labels: torch.Tensor, num_regions: int, sampling=None, origin=None) -> RegionProperties:
+    """Voxel count, first and second moments, bounding box, centroid, covariance and principal axes of the regions
+    1..``num_regions`` of a bool / uint8 / int32 / int64 label map [D,H,W] or [N,D,H,W] (module docstring, "Region
+    properties").  Every result keeps the leading N (1 for a [D,H,W] map).  One pass over the map, no read-back."""
+    n, shape = _volume(labels, "labels", _LABEL_DTYPES)
+    _region_sides(shape)
+    R = _num_regions(num_regions)
+    sp = parse_spacing(sampling, n, "postprocess: sampling")
+    org = _origin(origin, n)
+    _lib.check_device(_ON_GPU, labels)
+    lib = _lib.load()
+    src = _lib.as_bytes(labels)
+    dev = labels.device
+    moments = torch.empty((n, R, 10), dtype=torch.int64, device=dev)
+    boxes = torch.empty((n, R, 6), dtype=torch.int32, device=dev)
+    overflow = torch.empty((n,), dtype=torch.int64, device=dev)
+    centroid = torch.empty((n, R, 3), dtype=torch.float64, device=dev)
+    covariance = torch.empty((n, R, 3, 3), dtype=torch.float64, device=dev)
+    extent = torch.empty((n, R, 3), dtype=torch.float64, device=dev)
+    axes = torch.empty((n, R, 3, 3), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.ctu_region_moments_ws_bytes(n, R), dtype=torch.uint8, device=dev)
+    frame = None
+    if sp is not None or org is not None:
+        frame = _lib.double_array(v for i in range(n) for v in ((sp[i] if sp else [1.0] * 3) + (org[i] if org else [0.0] * 3)))
+    with _lib.on(dev) as run:
+        run("ctu_region_moments", src.data_ptr(), _lib.DTYPE_CODE[src.dtype], n, *shape, R, moments.data_ptr(), boxes.data_ptr(),
+            overflow.data_ptr(), ws.data_ptr())
+        run("ctu_region_derive", moments.data_ptr(), n, R, frame, centroid.data_ptr(), covariance.data_ptr(), extent.data_ptr(),
+            axes.data_ptr())
+    return RegionProperties(moments, boxes, overflow, centroid, covariance, extent, axes)
+
+
+def region_workspace_bytes(n: int, num_regions: int) -> int:
+    """Device workspace (bytes) of one ``region_properties`` call: the box accumulators, 24 bytes per (item, region)."""
+    return int(_lib.load().ctu_region_moments_ws_bytes(int(n), _num_regions(num_regions)))
+
+
+def _margin(margin):
+    if isinstance(margin, Integral) and not isinstance(margin, bool):
+        margin = (margin,) * 3
+    try:
+        m = tuple(margin)
+    except TypeError:
+        m = ()
+    if len(m) != 3 or any(isinstance(v, bool) or not isinstance(v, Integral) or not 0 <= v <= MAX_REGION_SIDE for v in m):
+        raise ValueError(f"postprocess: margin must be an integer or a (z, y, x) triple of integers in 0..{MAX_REGION_SIDE}, "
+                         f"got {margin!r}")
+    return tuple(int(v) for v in m)
+
+
+def bounding_box(labels: torch.Tensor, region: int = 1, margin=0, multiple_of: int = 1,
+                 num_regions: Optional[int] = None) -> torch.Tensor:
+    """The box of region ``region`` of a label map [D,H,W] or [N,D,H,W] as a region of interest: device int32 [N,6] =
+    (z0, y0, x0, z1, y1, x1), half open, grown by ``margin`` voxels (an int or a (z, y, x) triple), then to sides that are
+    multiples of ``multiple_of``, shifted back inside the volume where that fits and clipped where it does not (module
+    docstring); the whole volume for an empty region.  ``num_regions`` (default ``region``) is the capacity handed to
+    ``region_properties``.  Integer arithmetic on the device, no read-back."""
+    n, shape = _volume(labels, "labels", _LABEL_DTYPES)
+    _region_sides(shape)
+    R = _num_regions(region if num_regions is None else num_regions)
+    if isinstance(region, bool) or not isinstance(region, Integral) or not 1 <= region <= R:
+        raise ValueError(f"postprocess: region must be an integer in 1..num_regions = {R}, got {region!r}")
+    mg = _margin(margin)
+    if isinstance(multiple_of, bool) or not isinstance(multiple_of, Integral) or not 1 <= multiple_of <= MAX_REGION_SIDE:
+        raise ValueError(f"postprocess: multiple_of must be an integer in 1..{MAX_REGION_SIDE}, got {multiple_of!r}")
+    m = int(multiple_of)
+    p = region_properties(labels, R)
+    return _grow_boxes(p.boxes[:, region - 1], p.moments[:, region - 1, 0] != 0, shape, mg, m)
+
+
+def _grow_boxes(boxes: torch.Tensor, some: torch.Tensor, shape, mg, m: int) -> torch.Tensor:
+    """The arithmetic of ``bounding_box`` on one region's boxes [N,6] and its "not empty" flags [N], on their device."""
+    box = boxes.to(torch.int64)
+    cols = [None] * 6
+    for a in range(3):
+        S = shape[a]
+        lo, hi = box[:, a] - mg[a], box[:, 3 + a] + mg[a]
+        side = (hi - lo + (m - 1)) // m * m
+        lo = lo - (side - (hi - lo)) // 2
+        lo = torch.clamp(torch.minimum(lo, S - side), min=0)
+        fits = (side <= S) & some
+        zero = torch.zeros_like(lo)
+        cols[a] = torch.where(fits, lo, zero)
+        cols[3 + a] = torch.where(fits, lo + side, zero + S)
+    return torch.stack(cols, dim=1).to(torch.int32)
+
+
+def crop_to_box(x: torch.Tensor, box) -> Tuple[torch.Tensor, tuple]:
+    """``(view, slices)``: the part of ``x`` [..., D, H, W] inside ``box`` = (z0, y0, x0, z1, y1, x1) (a [6] or [1,6] tensor, as
+    ``bounding_box`` returns for one item, or six integers).  The shape of the result depends on the data, so the six
+    integers of a device box are read back: the one synchronisation.  ``view`` is ``x[(..., *slices)]``, a view, never a
+    copy; a result computed on it goes back with ``out[(..., *slices)] = result``."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 3:
+        raise ValueError("postprocess: x must be a tensor whose last three dimensions are (D, H, W)")
+    vals = box.flatten().tolist() if isinstance(box, torch.Tensor) else list(box)
+    if len(vals) != 6 or any(isinstance(v, bool) or not isinstance(v, Integral) for v in vals):
+        raise ValueError(f"postprocess: box must hold the six integers (z0, y0, x0, z1, y1, x1) of one item, got {box!r}")
+    for a in range(3):
+        if not 0 <= vals[a] < vals[3 + a] <= x.shape[-3 + a]:
+            raise ValueError(f"postprocess: box {vals} does not lie inside a volume of shape {tuple(x.shape[-3:])}")
+    slices = tuple(slice(int(vals[a]), int(vals[3 + a])) for a in range(3))
+    return x[(..., *slices)], slices

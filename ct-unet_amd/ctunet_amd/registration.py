@@ -41,13 +41,33 @@ in ``0..iterations``: accumulate at ``M_c``; if ``cost_c < cost`` accept (``(M, 
 ``E = [Rod(delta_w), pivot - Rod(delta_w) pivot + delta_t]``.  The step is *refused* -- the candidate stays, the history row
 holds -1 -- when the accepted state has fewer than 6 inliers (fewer than unknowns: only the damping would make the system
 solvable), a pivot of the factorisation is not positive, or the result is not finite; no NaN matrix is ever produced.
-Shear and affine fits, intensity metrics, pyramids, principal-axis starts, subsampling and random warps are out of scope
+Shear and affine fits, intensity metrics, pyramids, subsampling and random warps are out of scope
 (DESIGN.md); isotropic scale is the similarity model below.
 
 A ``register_points`` call is ``1 + 2 (iterations + 1)`` launches on one stream (the mean of the points and the start
 state; then accumulate and update per iteration): no host synchronisation, no float atomics, no allocation besides the
 result and the workspace (``workspace_bytes(P)``; pass ``workspace=`` to bring your own), so it can be captured into a graph,
 and two calls are bit-equal.  ``RegistrationResult.report()`` is the one read-back.
+
+Principal-axes starts
+---------------------
+
+    r = register(skull, atlas, moving_spacing=(0.8, 0.45, 0.45), fixed_spacing=1.0, init="moments")
+
+A scan that arrives turned (prone, feet first, a swapped axis, a strongly tilted gantry) sends the iteration from the centroid
+start into a wrong basin, and the rms it reports there looks plausible.  ``init="moments"`` runs the chosen optimiser (rigid or
+similarity, symmetric or not, unchanged) from five starts and keeps the best; the surface points and the distance fields are
+computed once.  ``principal_frame(mask, spacing, origin)`` gives ``(centroid [3], axes [3,3], extent [3])``, float64 on the
+device, from ``postprocess.region_properties`` of the binary mask (one pass of ``ctu_region_moments``; the rule of the axes, their
+signs and their right-handedness is pinned there).  With ``A_m`` / ``A_f`` the frames and ``c_m`` / ``c_f`` the centroids of the
+moving and the fixed mask, start ``k < 4`` is the proper rotation ``R = A_f diag(s_k) A_m^T``, ``s`` = (+,+,+), (+,-,-), (-,+,-),
+(-,-,+), with the translation ``c_f - R c_m``; start 4 is the identity rotation with ``c_f - c_m``: the centroid start, its
+centroids taken from the moments.  Selection, on the device and without a synchronisation, from the last history row of
+every start: among the starts whose final inlier count is at least half the largest final inlier count, the lowest final
+cost / P; the lowest index wins a tie.  The inlier condition matters: with ``max_distance=None`` a point thrown outside the
+fixed field costs nothing.  ``RegistrationResult.candidate`` holds the chosen index.  A region with nearly equal extents has
+ill-defined axes: nothing is promised then beyond the centroid start, and thanks to the fifth start nothing is lost.
+Reflections are not tried.  The cost is five optimiser runs and two passes over the masks.
 
 Similarity registration with the symmetric chamfer cost
 -------------------------------------------------------
@@ -163,12 +183,14 @@ class RegistrationResult(NamedTuple):
     """``matrix`` / ``inverse`` device float64 [4,4] (moving world -> fixed world and back), ``history`` device float64
     [iterations + 1, 4] = (cost / P, inliers, lambda, 1 accepted / 0 rejected / -1 refused), ``num_points`` P.  From the
     similarity kernels the history has two more columns (backward inliers, scale), the first two count both terms, and
-    ``num_fixed_points`` is Q."""
+    ``num_fixed_points`` is Q.  ``candidate``: from ``register(init="moments")`` the device int64 scalar that holds the index
+    of the chosen start (0..3 the principal-axes starts, 4 the centroid start), otherwise None."""
     matrix: torch.Tensor
     inverse: torch.Tensor
     history: torch.Tensor
     num_points: int = 0
     num_fixed_points: int = 0
+    candidate: Optional[torch.Tensor] = None
 
     def report(self) -> dict:
         """Reads the history back (one synchronisation): ``rms`` distance in mm of the accepted matrix, ``inlier_fraction``,
@@ -428,6 +450,52 @@ def surface_points(mask: torch.Tensor, spacing=None, origin=None) -> torch.Tenso
     return _world(torch.nonzero(surf), sp, org).to(torch.float32)
 
 
+def principal_frame(mask: torch.Tensor, spacing=None, origin=None):
+    """``(centroid [3], axes [3,3], extent [3])`` of the foreground of one bool / uint8 [D,H,W] mask, float64 on the device:
+    the centroid in world units (z, y, x), the unit principal axes as columns (right-handed, signs as
+    ``postprocess.region_properties`` pins them) and the variances along them in descending order.  A mask with nearly
+    equal extents has ill-defined axes; fewer than 2 voxels give NaN."""
+    from . import postprocess
+    _mask(mask, "mask")
+    sp, org = _frame(spacing, origin)
+    _lib.check_device(_ON_GPU.format("the mask"), mask)
+    p = postprocess.region_properties(mask if mask.dtype == torch.bool else mask != 0, 1, sampling=sp, origin=org)
+    return p.centroid[0, 0], p.axes[0, 0], p.extent[0, 0]
+
+
+_MOMENT_SIGNS = ((1, 1, 1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1))
+
+
+def _moment_starts(moving_frame, fixed_frame):
+    """The five float64 [4,4] starts of ``init="moments"`` (module docstring), built on the device."""
+    (cm, Am, _), (cf, Af, _) = moving_frame, fixed_frame
+    starts = []
+    for s in _MOMENT_SIGNS + (None,):
+        M = torch.eye(4, dtype=torch.float64, device=cm.device)
+        if s is not None:
+            B = Af.clone()
+            for j in range(3):
+                if s[j] < 0:
+                    B[:, j] = -B[:, j]
+            M[:3, :3] = (B.unsqueeze(1) * Am.unsqueeze(0)).sum(-1)                # B Am^T
+        M[:3, 3] = cf - (M[:3, :3] * cm).sum(-1)
+        starts.append(M)
+    return starts
+
+
+def _best_of(results) -> RegistrationResult:
+    """The selection rule of ``init="moments"`` over the last history rows, on the device."""
+    last = torch.stack([r.history[-1] for r in results])
+    cost, inliers = last[:, 0], last[:, 1]
+    ok = (inliers >= 0.5 * inliers.max()) & ~torch.isnan(cost)
+    k = torch.argmin(torch.where(ok, cost, torch.full_like(cost, math.inf)))       # the first of equal minima
+
+    def pick(tensors):
+        return torch.stack(tensors).index_select(0, k.reshape(1))[0]
+    return results[0]._replace(matrix=pick([r.matrix for r in results]), inverse=pick([r.inverse for r in results]),
+                          history=pick([r.history for r in results]), candidate=k)
+
+
 def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spacing=None, moving_origin=None,
              fixed_spacing=None, fixed_origin=None, iterations: int = 30, max_distance=None, init="centroid",
              model: str = "rigid", symmetric=None) -> RegistrationResult:
@@ -441,8 +509,8 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
     _mask(fixed_mask, "fixed_mask")
     (msp, morg), (fsp, forg) = _frame(moving_spacing, moving_origin, "moving_"), _frame(fixed_spacing, fixed_origin, "fixed_")
     if isinstance(init, str):
-        if init != "centroid":
-            raise ValueError(f"registration: init must be 'centroid' or a float64 [4,4] tensor, got {init!r}")
+        if init not in ("centroid", "moments"):
+            raise ValueError(f"registration: init must be 'centroid', 'moments' or a float64 [4,4] tensor, got {init!r}")
     elif init is not None:
         init = _check_init(init, moving_mask.device)
     _dof(model)
@@ -461,20 +529,30 @@ def register(moving_mask: torch.Tensor, fixed_mask: torch.Tensor, *, moving_spac
     if fixed_index.shape[0] < 1:
         raise ValueError("registration: the fixed mask is empty")
     field = postprocess.distance_transform_edt(~fixed, sampling=fsp)
-    if isinstance(init, str):
+    starts = None
+    if isinstance(init, str) and init == "moments":
+        starts = _moment_starts(principal_frame(moving_mask, msp, morg), principal_frame(fixed, fsp, forg))
+    elif isinstance(init, str):
         cm = _world(torch.nonzero(moving_mask != 0), msp, morg).mean(0)
         cf = _world(fixed_index, fsp, forg).mean(0)
         init = torch.eye(4, dtype=torch.float64, device=points.device)
         init[:3, 3] = cf - cm
     if model == "rigid" and not symmetric:
-        return register_points(points, field, spacing=fsp, origin=forg, init=init, iterations=iterations,
-                               max_distance=max_distance)
-    half = {}
-    if symmetric:
-        half = dict(fixed_points=surface_points(fixed, fsp, forg), moving_spacing=msp, moving_origin=morg,
-                    moving_field=postprocess.distance_transform_edt(moving_mask == 0, sampling=msp))
-    return register_similarity_points(points, field, model=model, spacing=fsp, origin=forg, init=init, iterations=iterations,
-                                      max_distance=max_distance, **half)
+        def run(start):
+            return register_points(points, field, spacing=fsp, origin=forg, init=start, iterations=iterations,
+                                   max_distance=max_distance)
+    else:
+        half = {}
+        if symmetric:
+            half = dict(fixed_points=surface_points(fixed, fsp, forg), moving_spacing=msp, moving_origin=morg,
+                        moving_field=postprocess.distance_transform_edt(moving_mask == 0, sampling=msp))
+
+        def run(start):
+            return register_similarity_points(points, field, model=model, spacing=fsp, origin=forg, init=start,
+                                              iterations=iterations, max_distance=max_distance, **half)
+    if starts is None:
+        return run(init)
+    return _best_of([run(start) for start in starts])
 
 
 # ---- B-spline deformable registration -----------------------------------------------------------------------------------

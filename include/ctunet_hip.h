@@ -594,6 +594,33 @@ int ctu_label_components(const void* in, int dtype, int N, int D, int H, int W, 
 int ctu_filter_components(const void* in, int dtype, int N, int D, int H, int W, int connectivity,
                           const int64_t* applied, int n_applied, int mode, int param, void* out, void* ws, void* stream);
 
+/* Region properties of label maps (no reference counterpart: users would copy the label map to the host for scipy.ndimage;
+ * rule pinned in ctunet_amd/postprocess.py, "Region properties").  labels: DEVICE contiguous [N,D,H,W] of dtype CTU_U8,
+ * CTU_I32 (what ctu_label_components writes) or CTU_I64.  Region r (1 <= r <= R) of an item is the set of voxels whose value
+ * is r; 0 is background; a negative value or one above R belongs to no region and is counted in overflow.
+ *   moments:  DEVICE int64 [N][R][10] = (count, Sz, Sy, Sx, Szz, Szy, Szx, Syy, Syx, Sxx) over the voxel indices, exact.
+ *   boxes:    DEVICE int32 [N][R][6] = (z0, y0, x0, z1, y1, x1), half open; six zeros for an empty region.
+ *   overflow: DEVICE int64 [N].
+ * Every side <= 1024 and D*H*W < 2^31, so every sum stays below 2^51 and converts to float64 exactly; N <= 65535,
+ * R <= CTU_REGION_MAX.  ws: ctu_region_moments_ws_bytes() bytes (the box accumulators, 24 per region; 0 for N or R out of
+ * range).  Three memsets, one pass over the map (64-bit integer atomics only: the result does not depend on the order of
+ * arrival and two calls are bit-equal), one launch that decodes the boxes.  No host sync, capture-safe.
+ * ctu_region_derive: the float64 fields of moments, one lane per region, every operation rounded on its own.  frame: HOST
+ * [N][6] = (sampling z, y, x, origin z, y, x) per item, or NULL for sampling 1 and origin 0.  With n = count, m_a = S_a / n:
+ *   centroid [N][R][3]      origin_a + sampling_a * m_a
+ *   covariance [N][R][3][3] ((S_ab / n - m_a * m_b) * sampling_min(a,b)) * sampling_max(a,b)
+ *   extent [N][R][3], axes [N][R][3][3]: eigenvalues in descending order and unit eigenvectors as columns, by
+ *     CTU_REGION_SWEEPS cyclic Jacobi sweeps; the first two axes are signed so that their component of largest magnitude
+ *     (the first one of equals) is positive, the third is their cross product.
+ * An empty region gives NaN everywhere; a region of one voxel NaN axes.  One launch per 64 items. */
+#define CTU_REGION_MAX 65536
+#define CTU_REGION_SWEEPS 8
+size_t ctu_region_moments_ws_bytes(int N, int R);
+int ctu_region_moments(const void* labels, int dtype, int N, int D, int H, int W, int R, int64_t* moments, int32_t* boxes,
+                       int64_t* overflow, void* ws, void* stream);
+int ctu_region_derive(const int64_t* moments, int N, int R, const double* frame, double* centroid, double* covariance,
+                      double* extent, double* axes, void* stream);
+
 /* Binary morphology of masks on bit images, hole filling and the implant mask (reference: erode / dilate / ErodeDilate of
  * ctunet/pytorch/transforms.py:97-127,356-377 through SimpleITK; pinned here on scipy.ndimage, definitions in
  * ctunet_amd/postprocess.py).  in: DEVICE [N,D,H,W] of dtype CTU_U8 or CTU_I64; a voxel is foreground if it is nonzero or,
